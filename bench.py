@@ -13,10 +13,17 @@ HBM before the timed region; the framebuffer stays in device memory (the referen
 Frames in flight (--inflight, default 4 = one slot per hardware queue of the process): a frame's critical path is the serial octree walk of its dearest pixel,
 which leaves most of the GPU idle for most of one frame; consecutive frames are therefore submitted on separate
 streams (one context per slot) and overlap on the device.  Every frame is still refreshed, rendered completely
-and kept in its slot's framebuffer; `value` is frames/second x pixels over the K timed steps.  The same frames
-one at a time (the reference's blocking runKernel) are timed right after and reported as `one_frame_at_a_time`.
+and kept in its slot's framebuffer; `value` is frames/second x pixels over the K timed steps.  With --full, the same
+frames one at a time (the reference's blocking runKernel) are timed right after and reported as `one_frame_at_a_time`.
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  --full adds everything else the
+line can carry (see below); --dump-outputs DIR writes what the last timed step computed (dump_outputs()).  The warm-up
+of a plain single-GPU run is the W steps of --warmup and then max(10, min(K, 50)) + frames-in-flight more untimed
+still frames: as many as --full's animated leg and the re-warm after it render before the timed region, so that both
+forms time the K steps on an equally warm device (the line's `warmup` stays W).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full --dump-outputs bench_outputs/
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (bare: starts the N ranks itself as child processes through the same launcher,
@@ -25,11 +32,13 @@ one at a time (the reference's blocking runKernel) are timed right after and rep
                                          line's keys — over gloo without touching a device: runs on a box with no GPU)
 
 Rank 0 prints ONE JSON line.  Beside the contract's keys: `kernel_ms` (mean HIP-event duration of a render launch in
-the timed region), `one_frame_at_a_time` (the same frames submitted and waited for one by one: latency), `roofline`
-(`achieved` from the launch duration and the number of launches sharing the device, `single_launch` without overlap,
-`traffic` from the committed rocprofv3 PMC passes), `cpu_baseline` (the oracle on this host's cores), `total_rays`
-(primary + shadow rays), `config.sharding` / `config.split_calibration` (N > 1: the arrangement chosen and the
-measurements it was chosen from), `check` (with --check: rank 0's framebuffer against the oracle).
+the timed region), `roofline` (`achieved` from the launch duration and the number of launches sharing the device),
+`config.sharding` / `config.split_calibration` (N > 1: the arrangement chosen and the measurements it was chosen from),
+`check` (with --check: rank 0's framebuffer against the oracle).  Only with --full, each from runs of its own after the
+timed steps: `animated` (the same workload with the camera clock running), `one_frame_at_a_time` (the same frames
+submitted and waited for one by one: latency) and the kernel-alone `roofline` figures, `roofline.traffic` / `valu`
+(from the committed rocprofv3 PMC passes), `cpu_baseline` (the oracle on this host's cores), `total_rays` (primary +
+shadow rays) and, with N > 1, `comm.config5`.
 """
 from __future__ import annotations
 
@@ -247,6 +256,37 @@ def spread(values):
     return {"mean": round(sum(v) / len(v), 4), "median": round(med, 4), "min": round(v[0], 4), "max": round(v[-1], 4), "frames": len(v)}
 
 
+DUMP_MAX_PIXELS = 1 << 20      # larger frames are dumped at this many pixels, a fixed seeded sample
+DUMP_SEED = 12345
+
+
+def dump_outputs(fb, width, height, out_dir):
+    """--dump-outputs: what a caller of the timed path receives from its last step, rank 0's framebuffer (16 B/pixel:
+    x and y as float32, the packed colour's four bytes, a word left unspecified), as .npy files two builds can be compared by:
+      pixel_index.npy    float64 (k,)    which pixels (row-major y * width + x): all of them, or DUMP_MAX_PIXELS of them drawn
+                                         without replacement by a generator seeded with DUMP_SEED, in increasing order
+      xy.npy             float32 (k, 2)  the x, y floats of those pixels
+      rgba.npy           float32 (k, 4)  their colour bytes r, g, b, a (0..255)
+      rgba_row_sums.npy  float64 (H, 4)  every row's sum of each colour byte over ALL pixels of the frame
+    At 3840x2160 about 32 MB in all.  `fb`: the int32 tensor of the frame on the device, complete (after flush + sync)."""
+    import numpy as np
+    import torch
+    n = width * height
+    px = fb[:n * 4].view(n, 4)
+    if n <= DUMP_MAX_PIXELS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_MAX_PIXELS, replace=False))
+    sample = px[torch.from_numpy(idx).to(px.device)].cpu().numpy()           # (k, 4) int32
+    colour = px[:, 2].contiguous().view(torch.uint8).view(height, width, 4)
+    row_sums = colour.sum(dim=1, dtype=torch.int64).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "xy.npy"), np.ascontiguousarray(sample[:, :2]).view(np.float32))
+    np.save(os.path.join(out_dir, "rgba.npy"), np.ascontiguousarray(sample[:, 2]).view(np.uint8).reshape(-1, 4).astype(np.float32))
+    np.save(os.path.join(out_dir, "rgba_row_sums.npy"), row_sums.astype(np.float64))
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks as CHILD processes through
     torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) and pass rank 0's output through.  Nothing in
@@ -288,8 +328,8 @@ def dry_run(args):
                           "config": {"workload": f"Scenes/{args.workload}.txt {args.width}x{args.height}"},
                           "comm": {"backend": "gloo" if world > 1 else None, "world_size": world,
                                    "ranks_in_group": td.get_world_size() if world > 1 else 1,
-                                   # a real N > 1 run also times BASELINE config 5 in the three arrangements (main(): config5)
-                                   "config5": None if world == 1 else {"workload": "Scenes/bunny.txt 7680x4320 (BASELINE config 5)", "ms_per_frame": None,
+                                   # a real N > 1 run with --full also times BASELINE config 5 in the three arrangements (main(): config5)
+                                   "config5": None if (world == 1 or not args.full) else {"workload": "Scenes/bunny.txt 7680x4320 (BASELINE config 5)", "ms_per_frame": None,
                                                                        "chosen": None, "dry_run": True}}}), flush=True)
     if world > 1:
         td.destroy_process_group()
@@ -299,7 +339,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5,
+                    help="untimed steps before the timed ones; one GPU adds max(10, min(steps, 50)) + frames in flight more (module docstring)")
     ap.add_argument("--workload", default="bunny", choices=sorted(WORKLOADS))
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
@@ -315,7 +356,14 @@ def main():
                     help="what is gathered with N>1: the colour plane at 3 B/pixel (constant alpha byte dropped), at 4 B/pixel as rendered, "
                          "or the naive exchange of whole 16-byte pixels (SURVEY.md 8e: kept to measure against)")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (gloo, no device work): see the module docstring")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the animated and one-at-a-time "
+                         "legs, the kernel-alone roofline, committed counter figures, the CPU baseline and (N > 1) BASELINE config 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's framebuffer) to DIR/<name>.npy: see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))     # bare `python bench.py --gpus N`: this process only launches and relays
@@ -473,10 +521,15 @@ def main():
     # The headline workload is a still scene: its Object[] is byte-identical from frame to frame, and rpt_set_objects then reuses
     # the per-object screen bounds instead of recomputing them (a memcmp per object).  An animated scene pays for them on the
     # submitting thread — 1-13 us per object and frame, which for dozens of moving objects is as much as the device needs for the
-    # frame (profiles/r02_host_cost.txt).  So the same workload is also timed with the camera clock running (every frame differs),
-    # and that figure stands next to the headline one.
+    # frame (profiles/r02_host_cost.txt).  So with --full the same workload is also timed with the camera clock running (every frame
+    # differs), and that figure stands next to the headline one.
     animated = None
-    if n == 1 and not force_dist and not animate:
+    if not args.full and n == 1 and not force_dist and not animate:
+        # without that leg, as many still frames (untimed) as it and the re-warm after it render: the headline is measured on a
+        # device as warm as with --full (with only the W warm-up steps, 200 timed steps came out 3-4 % slower on an MI355X)
+        for _ in range(max(10, min(args.steps, 50)) + frame.depth):
+            step()
+    if args.full and n == 1 and not force_dist and not animate:
         a_steps = max(10, min(args.steps, 50))
         barrier()
         t0 = time.perf_counter()
@@ -498,12 +551,14 @@ def main():
     kernel_ms = sum(launches) / max(len(launches), 1)
     kernel_sum_ms = sum(launches)
     kernel_name = kernel_label(frame.slots[0].r.last_variant())        # what the timed launches were made with
+    if args.dump_outputs and rank == 0:
+        dump_outputs(frame.framebuffer, W, H, args.dump_outputs)      # before the --full legs below render into the slots again
 
-    # the same frames one at a time (submit, wait, submit ...: what the reference's blocking runKernel() does) — the
+    # --full: the same frames one at a time (submit, wait, submit ...: what the reference's blocking runKernel() does) — the
     # frame LATENCY, and the launch duration without other launches sharing the device
     blocking_ms = blocking_kernel_ms = None
     blocking_frames, blocking_launches = [], []
-    if n == 1 and not force_dist:
+    if args.full and n == 1 and not force_dist:
         nb = max(1, min(args.steps, 50))
         for _ in range(min(max(args.warmup, 0), 3)):     # untimed: the blocking call launches another kernel (43) than the frames in flight
             frame.slots[0].r.set_objects(scene)          # above 3 Mpx did (41), and its first launch in a process is a cold one (0.3-0.4 ms)
@@ -526,12 +581,12 @@ def main():
         frame.slots[0].frames += nb
 
     # N > 1: the one shipped workload where sharding can pay — BASELINE config 5, Scenes/bunny.txt at 7680x4320 (0.28 ms per frame on one
-    # GPU; the 4K headline frame is shorter than one gather, so its curve is expected to be flat: README.md) — timed in the three
-    # arrangements after the headline.  Every rank runs the same collectives.  RPT_BENCH_CONFIG5=0 skips it, =WxH changes its size
+    # GPU; the 4K headline frame is shorter than one gather, so its curve is expected to be flat: README.md) — timed with --full in the
+    # three arrangements after the headline.  Every rank runs the same collectives.  RPT_BENCH_CONFIG5=0 skips it, =WxH changes its size
     # (rehearsals on one GPU over gloo use a smaller frame).
     config5 = None
     c5 = os.environ.get("RPT_BENCH_CONFIG5", "7680x4320")
-    if (n > 1 or force_dist) and c5 != "0" and args.workload == "bunny" and not animate:
+    if args.full and (n > 1 or force_dist) and c5 != "0" and args.workload == "bunny" and not animate:
         W5, H5 = (int(x) for x in c5.split("x"))
         if (W5, H5) != (W, H):
             barrier()
@@ -647,10 +702,11 @@ def main():
             rf["frac_blocking"] = rf["frac"]          # (round 2's name for the same number)
         else:
             rf["frac_kernel_alone"] = None
-            rf["note_regime"] = "N > 1: no kernel-alone measurement in this run; frac is the device-level figure"
-        # HBM traffic: rocprofv3 PMC passes of this command, quoted only when taken on THIS build, per kernel — the block of the
-        # kernel each figure names
-        if n == 1 and not force_dist and args.variant == 0:
+            rf["note_regime"] = ("N > 1: no kernel-alone measurement in this run; frac is the device-level figure" if n > 1 or force_dist else
+                                 "no kernel-alone measurement without --full; frac is the device-level figure")
+        # --full: HBM traffic from rocprofv3 PMC passes of this command, quoted only when taken on THIS build, per kernel — the block of
+        # the kernel each figure names
+        if args.full and n == 1 and not force_dist and args.variant == 0:
             traffic, source = measured_traffic(args.workload, W, H, short(rf["kernel"]))
             rf["traffic"] = traffic
             rf["traffic_source"] = (f"{source}, block {short(rf['kernel'])} (rocprofv3 --pmc of this command on this build of librpt_hip.so: recorded hash matches)"
@@ -667,7 +723,7 @@ def main():
                            "split_timings_ms_per_frame": split_timings,
                            "config5": config5,
                            "note": "every N > 1 figure before an 8-GPU node has run this line is a rehearsal on one GPU or a model: none is a measurement of xGMI"}
-        if not args.no_cpu_baseline and n == 1:
+        if args.full and not args.no_cpu_baseline and n == 1:
             out["cpu_baseline"] = cpu_baseline(scene, W, H)
             # second column of SURVEY.md §8(d): primary + shadow rays, the shadow rays counted by the oracle
             shadow = out["cpu_baseline"]["shadow_rays_per_frame"]

@@ -615,14 +615,15 @@ def test_shadow_ray_culls_on_the_shipped_meshes(renderer):
 
 
 def test_bench_n_gt_1_line_carries_config_5():
-    """With N > 1 the line also times BASELINE config 5 (bunny 7680x4320; here a smaller stand-in, two ranks on one GPU over gloo)
+    """With N > 1 and --full the line also times BASELINE config 5 (bunny 7680x4320; here a smaller stand-in, two ranks on one GPU over gloo)
     in the three arrangements — the one shipped workload where sharding can pay."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {**os.environ, "RPT_BENCH_BACKEND": "gloo", "RPT_SPLIT": "equal", "RPT_BENCH_CONFIG5": "1920x1080"}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--width", "1280", "--height", "720", "--no-cpu-baseline", "--check"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--width", "1280", "--height", "720", "--full",
+           "--no-cpu-baseline", "--check"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""After `gpurun … bash tools/profile.sh r02_<workload>_<W>x<H> …` has left its output under gpurun_out/prof_<tag>/: copy the two
+"""After `bash tools/profile.sh r02_<workload>_<W>x<H> …` has left its output under $RESULTS/prof_<tag>/ (default bench_outputs/): copy the two
 condensed files of every tag into profiles/ and print one table row per workload (DESIGN.md §6.2's counters table).
 
     python tools/collect_profiles.py r02_bunny_3840x2160 r02_shadows_3840x2160 …
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main(tags):
     for t in tags:
-        src = os.path.join(ROOT, "gpurun_out", f"prof_{t}")
+        src = os.path.join(ROOT, os.environ.get("RESULTS", "bench_outputs"), f"prof_{t}")
         for suf in ("_pmc_summary.json", "_kernel_stats.csv"):
             shutil.copy(os.path.join(src, t + suf), os.path.join(ROOT, "profiles", t + suf))
         d = json.load(open(os.path.join(ROOT, "profiles", t + "_pmc_summary.json")))

@@ -1,19 +1,19 @@
 #!/bin/bash
 # Profiles bench.py on the GPU box with rocprofv3; run through gpurun from the repo root:
 #   gpurun --timeout 900 -- 'bash tools/profile.sh r02_bunny4k [bench.py arguments, e.g. --workload shadows]'
-# Writes raw output under gpurun_out/prof_<tag>/ and the two condensed files the judge reads into profiles/:
+# Writes raw output under $RESULTS/prof_<tag>/ (default bench_outputs/, relative to the repository root) and the two condensed files into profiles/:
 #   profiles/<tag>_kernel_stats.csv   (rocprofv3 --kernel-trace --stats)
 #   profiles/<tag>_pmc_summary.json   (tools/pmc_summary.py over the PMC passes; carries the git revision and the
 #                                      hash of librpt_hip.so, which bench.py checks before quoting roofline.traffic)
-# (gpurun merges gpurun_out/ back; profiles/ on the box does not travel, so both are also left in gpurun_out/prof_<tag>/.)
+# (both are also left in $RESULTS/prof_<tag>/, for a GPU machine whose profiles/ does not come back.)
 set -o pipefail
 TAG=${1:-r02}
 shift
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$ROOT/gpurun_out/prof_$TAG
+OUT=$ROOT/${RESULTS:-bench_outputs}/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline $*"
+BENCH="python3 $ROOT/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline $*"
 echo "$BENCH" > "$OUT/command.txt"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $BENCH > "$OUT/trace.log" 2>&1 || { tail -20 "$OUT/trace.log"; exit 1; }
 # counters: separate passes, --kernel-trace only (never combined with sys/hip/hsa tracing)

@@ -23,7 +23,7 @@ def bench(lib, workload, w, h, inflight, steps):
     if lib:
         env["RPT_HIP_LIB"] = os.path.join(ROOT, "relativitypathtracer_amd", lib)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "10", "--workload", workload, "--width", str(w), "--height", str(h),
-                        "--inflight", str(inflight), "--no-cpu-baseline", "--check"], capture_output=True, text=True, env=env, timeout=600)
+                        "--inflight", str(inflight), "--full", "--no-cpu-baseline", "--check"], capture_output=True, text=True, env=env, timeout=600)
     if p.returncode != 0:
         return None, p.stderr[-400:]
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]), None

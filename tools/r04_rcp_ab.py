@@ -42,7 +42,7 @@ def bench(lib, workload, w, h, steps=60):
     if lib:
         env["RPT_HIP_LIB"] = os.path.join(ROOT, "relativitypathtracer_amd", lib)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "10", "--workload", workload, "--width", str(w), "--height", str(h),
-                        "--no-cpu-baseline", "--check"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-cpu-baseline", "--check"], capture_output=True, text=True, env=env, timeout=600)
     if p.returncode != 0:
         return None, p.stderr[-400:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
