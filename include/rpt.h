@@ -125,6 +125,9 @@ int rpt_set_debug_rgb(rpt_ctx *ctx, void *device_ptr_or_null_or_1);
  *       (a second copy of it, addressable by node index): what the blocking rpt_render launches
  *   44  41 without the octree walk compiled in (61 VGPRs, no scratch, 8 waves per SIMD): what frames without a mesh object
  *       get; asked for explicitly while Object[] holds a mesh, 41 is launched instead
+ *   48, 49      41 / 43 with the triangle test's 1 / det as the IEEE division sequence whatever the scene.  41 and 43 themselves
+ *               take it through the exact reciprocal (csrc/rpt_device_math.hip.h rcp_exact: the same float) when every triangle
+ *               of the scene is in its domain (rpt_scene_exact_rcp), and launch 48's / 49's code otherwise
  *   50, 51      NOT bit-exact, opt-in only: 41 compiled with the arithmetic OpenCL C allows by default (fma contraction,
  *               2.5-ulp division, 3-ulp sqrt; csrc/rpt_relaxed.hip), 5 / 6 waves per SIMD.  Never chosen by variant 0.
  * Everything else — instrumented kernels (7 loop counters, 8 primary rays only, 11 per-wave timeline) and the measurement arms
@@ -141,6 +144,11 @@ int rpt_set_msaa(rpt_ctx *ctx, int samples_per_axis);
 /* The kernel (a number of the list above) this context's last launch was made with; 0 before the first launch.  What
  * variant 0 resolved to: tests and bench.py name the kernel they measured from this, not from a copy of the rule. */
 int rpt_last_variant(const rpt_ctx *ctx);
+/* 1 if this context's last launch tested triangles with the exact reciprocal (41 / 43 on a scene inside its domain), else 0. */
+int rpt_last_exact_rcp(const rpt_ctx *ctx);
+/* Host code, no device: 1 if every triangle the octrees' lists name has |e1| |e2| <= 2^60 (e1 = B - A, e2 = C - A in float, finite
+ * vertices), the domain on which kernels 41 / 43 use the exact reciprocal; 0 if not; -RPT_ERR_ARG / -RPT_ERR_SCENE for a bad desc. */
+int rpt_scene_exact_rcp(const rpt_scene_desc *s);
 
 /* A culled-vs-un-culled self-check on the device.  The default kernels drop objects per wavefront from conservatively
  * sampled screen bounds and shadow rays per wavefront from segment-vs-box tests; a wrong bound would make an object vanish from
@@ -276,6 +284,11 @@ int rpt_probe_object(rpt_ctx *ctx, int which, int object_index, const float *hos
  * {sets inside the fast path's domain, mismatching quotients with one residual correction, with two, mismatches of the guarded
  * form over ALL sets, mismatching sets seen}; the first max_samples mismatching sets (4 floats each) go to samples_out. */
 int rpt_probe_division(rpt_ctx *ctx, int mode, unsigned int seed, int blocks, int per_thread, unsigned long long counts_out[5], float *samples_out, int max_samples);
+/* Test hook (csrc/rpt_device_math.hip.h rcp_newton / rcp_exact): every float s with lo <= |s| <= hi (0 < lo <= hi <= 2^127), both signs,
+ * through the three reciprocal forms on the device, compared bit for bit with IEEE 1.0f / s.  counts_out = {values compared,
+ * mismatches of form 1, 2, 3, mismatching values seen}; the first max_samples mismatches go to samples_out as {s, mask of the forms
+ * that missed: 1, 2, 4}. */
+int rpt_probe_reciprocal(rpt_ctx *ctx, float lo, float hi, unsigned long long counts_out[5], float *samples_out, int max_samples);
 /* Test hook, the octree walk at ray level: n rays {origin.xyz, dir.xyz} in the object space of mesh object `object_index` of the
  * current Object[] go through the three walks of the product library — the reference's layouts (opencl_kernel.cl:200-308 as
  * written), the throughput walk of kernel 41 and the latency walk of kernel 43 — and host_out receives 3 x 8 floats per ray:

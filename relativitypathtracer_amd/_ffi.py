@@ -138,6 +138,9 @@ HIP_SYMBOLS = {
     "rpt_certify_screen_bounds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "rpt_verify_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_last_variant": (C.c_int, [C.c_void_p]),
+    "rpt_last_exact_rcp": (C.c_int, [C.c_void_p]),
+    "rpt_scene_exact_rcp": (C.c_int, [C.c_void_p]),
+    "rpt_probe_reciprocal": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_uint64), C.c_void_p, C.c_int]),
     "rpt_set_msaa": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_probe_walk": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "rpt_timing_end_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),

@@ -59,6 +59,7 @@ struct Geometry {
     DeviceBuffer dgrids;                      // 16^3 cells per octree root: where four child steps from the root end (descend_from_root)
     int grid_roots = 0;
     bool compact_ok = false;                  // derived octree layout usable (children consecutive)
+    bool exact_rcp_ok = false;                // every triangle a walk tests lies in the exact reciprocal's domain (rpt_scene_exact_rcp)
     unsigned long long generation = 0;        // unique per upload (the rectangle cache of a context names its geometry by this, not by address)
     std::vector<int> node_new_index;          // reference node index -> index in the derived, breadth-first numbering
     int top_count = 0;                        // derived nodes [0, top_count) are the forest's top levels (<= RPT_TOP_MAX)
@@ -119,6 +120,7 @@ struct rpt_ctx {
     bool colour_plane = false;
     int variant = 0;
     int last_variant = 0;                             // the kernel the last launch was made with (rpt_last_variant)
+    bool last_exact_rcp = false;                      // ... and whether its walk took 1 / det through rcp_exact (rpt_last_exact_rcp)
     int msaa = 1;                                     // MSAASAMPLES (rpt_set_msaa)
     int serial = 0;                                   // creation index of this context in the process (diagnostics output)
 #ifdef RPT_DIAGNOSTICS
@@ -784,6 +786,9 @@ int launch(rpt_ctx *ctx) {
     // Frames in flight that are too small to fill the chip with walks wait for latency as well (profiles/r03_latency_walk_ab.txt:
     // 43 ahead of 41 up to 1920x1080 — bunny -6 %, shadows -19 % — level at 2560x1440, behind from 3200x1800): 43 for those too.
     const bool small_frame = (size_t)tiles * RPT_TILE_ROWS * (size_t)ctx->width <= (size_t)RPT_LATENCY_KERNEL_MAX_PIXELS;
+    // Kernels 41 and 43 take the triangle test's 1 / det through rcp_exact when the scene's triangles allow it (exact_rcp_ok,
+    // rpt_scene_exact_rcp: the same floats as the IEEE division there) and the IEEE division otherwise; 48 / 49 are 41 / 43 with the
+    // IEEE division whatever the scene (the A/B arm).  rpt_last_variant reports 41 / 43 either way, rpt_last_exact_rcp which ran.
     int v = ctx->variant == 0 ? (!ctx->has_mesh ? 44 : (ctx->latency_call || small_frame ? 43 : 41)) : ctx->variant;
     if (v == 44 && ctx->has_mesh) v = 41;          // (asked for explicitly on a scene with meshes: the full kernel)
     if (!ctx->geo->compact_ok && v != 44) v = 1;
@@ -791,8 +796,8 @@ int launch(rpt_ctx *ctx) {
     // pixels outside it, and beyond 2^20 pixels a side a tile's 1.5-pixel skirt is no longer large against float rounding — such
     // frames are rendered by the un-culled kernel (same pixels, every object tested everywhere).
     const bool window_holds_frame = 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U && ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
-    if (!window_holds_frame && (v == 41 || v == 43 || v == 44)) v = 3;
-    const bool band_first = v == 43
+    if (!window_holds_frame && (v == 41 || v == 43 || v == 44 || v == 48 || v == 49)) v = 3;
+    const bool band_first = v == 43 || v == 49
 #ifdef RPT_DIAGNOSTICS
                             || v == 143 || v == 2573 || (v >= 256 && v < 1000 && (v & 8))
 #endif
@@ -812,8 +817,16 @@ int launch(rpt_ctx *ctx) {
     case 47: hipLaunchKernelGGL(rptd::rpt_render_kernel_msaa_unculled_w5, grid1, dim3(64), 0, ctx->stream, a); break;
     case 1: hipLaunchKernelGGL(rptd::rpt_render_kernel_v0, grid1, dim3(64), 0, ctx->stream, a); break;
     case 3: hipLaunchKernelGGL(rptd::rpt_render_kernel_unculled_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 41: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 43: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_w5, grid1, dim3(64), 0, ctx->stream, a); break;
+    case 41:
+        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_w5, grid1, dim3(64), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_w5, grid1, dim3(64), 0, ctx->stream, a);
+        break;
+    case 43:
+        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_w5, grid1, dim3(64), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_w5, grid1, dim3(64), 0, ctx->stream, a);
+        break;
+    case 48: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_w5, grid1, dim3(64), 0, ctx->stream, a); break;
+    case 49: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_w5, grid1, dim3(64), 0, ctx->stream, a); break;
     case 44: hipLaunchKernelGGL(rptd::rpt_render_kernel_analytic_w8, grid1, dim3(64), 0, ctx->stream, a); break;
     case 50:
     case 51:
@@ -829,6 +842,7 @@ int launch(rpt_ctx *ctx) {
     }
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = v;
+    ctx->last_exact_rcp = (v == 41 || v == 43) && ctx->geo->exact_rcp_ok;
     return RPT_OK;
 }
 
@@ -942,6 +956,7 @@ int rpt_upload_scene(rpt_ctx *ctx, const rpt_scene_desc *s) {
     ctx->geo->octree_count = s->octree_count;
     ctx->geo->octree_tri_count = s->octree_tri_count;
     if (int rc = build_derived_geometry(ctx, *s)) return rc;
+    ctx->geo->exact_rcp_ok = rpt_scene_exact_rcp(s) == 1;
     ctx->geo->host_node_bounds.resize(s->octree_count * 6);
     for (size_t i = 0; i < s->octree_count; i++) {
         float *b = &ctx->geo->host_node_bounds[6 * i];
@@ -1156,7 +1171,7 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
 int rpt_set_variant(rpt_ctx *ctx, int variant) {
     if (!ctx) return RPT_ERR_ARG;
     switch (variant) {
-    case 0: case 1: case 3: case 41: case 43: case 44: case 50: case 51: break;
+    case 0: case 1: case 3: case 41: case 43: case 44: case 48: case 49: case 50: case 51: break;
     default:
 #ifdef RPT_DIAGNOSTICS
         break;       // the diagnostics library knows many more (rpt_diag_kernels.hip.h); an unknown number fails at the launch
@@ -1169,6 +1184,32 @@ int rpt_set_variant(rpt_ctx *ctx, int variant) {
 }
 
 int rpt_last_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_variant : 0; }
+int rpt_last_exact_rcp(const rpt_ctx *ctx) { return ctx && ctx->last_exact_rcp ? 1 : 0; }
+
+// The domain of the triangle test's exact reciprocal (rcp_exact, intersect_triangle_edges<true>): |det| <= |e1| |e2| (1 + 2^-20) for
+// a normalised direction, and rcp_exact equals 1 / det for 1e-7 <= |det| <= 2^125.  Asked here: |e1| |e2| <= 2^60 for every triangle a
+// walk tests (those the octrees' lists name), e1 = fl(B - A) and e2 = fl(C - A) as the derived records hold them; a non-finite
+// vertex fails.  The margin (2^60 against 2^125) makes the double-precision product's rounding irrelevant.
+int rpt_scene_exact_rcp(const rpt_scene_desc *s) {
+    if (!s || (s->vertex_count && !s->vertices) || (s->triangle_words && !s->triangles) || (s->octree_tri_count && !s->octreeTris)) return -RPT_ERR_ARG;
+    const size_t n_tris = s->triangle_words / RPT_TRI_STRIDE;
+    const double limit = 0x1p60;
+    for (size_t i = 0; i < s->octree_tri_count; i++) {
+        const int t = s->octreeTris[i];
+        if (t < 0 || (size_t)t >= n_tris) return -RPT_ERR_SCENE;
+        const rpt_float3 *vv[3];
+        for (int c = 0; c < 3; c++) {
+            const uint32_t w = s->triangles[9 * (size_t)t + 3 * c];
+            if (w >= s->vertex_count) return -RPT_ERR_SCENE;
+            vv[c] = &s->vertices[w];
+        }
+        const float e1[3] = {vv[1]->x - vv[0]->x, vv[1]->y - vv[0]->y, vv[1]->z - vv[0]->z}, e2[3] = {vv[2]->x - vv[0]->x, vv[2]->y - vv[0]->y, vv[2]->z - vv[0]->z};
+        const double l1 = std::sqrt((double)e1[0] * e1[0] + (double)e1[1] * e1[1] + (double)e1[2] * e1[2]);
+        const double l2 = std::sqrt((double)e2[0] * e2[0] + (double)e2[1] * e2[1] + (double)e2[2] * e2[2]);
+        if (!(l1 * l2 <= limit)) return 0;      // (NaN and inf fail too)
+    }
+    return 1;
+}
 
 int rpt_set_msaa(rpt_ctx *ctx, int samples_per_axis) {
     if (!ctx) return RPT_ERR_ARG;
@@ -1529,7 +1570,8 @@ int rpt_probe_walk(rpt_ctx *ctx, int object_index, const float *host_rays, float
     int rc = RPT_OK;
     if (hipMemcpy(d_in, host_rays, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) rc = RPT_ERR_DEVICE;
     if (!rc) {
-        hipLaunchKernelGGL(rptd::rpt_probe_walk_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a, object_index, d_in, d_out, n);
+        hipLaunchKernelGGL(rptd::rpt_probe_walk_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a, object_index, d_in, d_out, n,
+                           ctx->geo->exact_rcp_ok ? 1 : 0);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
             hipMemcpy(host_out, d_out, sizeof(float) * 24 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(ctx, RPT_ERR_DEVICE, "rpt_probe_walk: device error");
@@ -1558,6 +1600,37 @@ int rpt_probe_division(rpt_ctx *ctx, int mode, unsigned int seed, int blocks, in
             hipMemcpy(counts_out, d_counts, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess ||
             (d_samples && hipMemcpy(samples_out, d_samples, sizeof(float) * 4 * (size_t)max_samples, hipMemcpyDeviceToHost) != hipSuccess))
             rc = fail(ctx, RPT_ERR_DEVICE, "rpt_probe_division: device error");
+    }
+    (void)hipFree(d_counts);
+    if (d_samples) (void)hipFree(d_samples);
+    return rc;
+}
+
+int rpt_probe_reciprocal(rpt_ctx *ctx, float lo, float hi, unsigned long long counts_out[5], float *samples_out, int max_samples) {
+    if (!ctx || !counts_out || !(lo > 0.0f) || !(hi >= lo) || !(hi <= 0x1p127f) || max_samples < 0) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    uint32_t lo_bits, hi_bits;
+    std::memcpy(&lo_bits, &lo, 4);
+    std::memcpy(&hi_bits, &hi, 4);
+    const unsigned long long per_sign = (unsigned long long)(hi_bits - lo_bits) + 1ull;
+    unsigned long long *d_counts = nullptr;
+    float *d_samples = nullptr;
+    RPT_HIP(ctx, hipMalloc((void **)&d_counts, 5 * sizeof(unsigned long long)));
+    if (max_samples > 0 && samples_out && hipMalloc((void **)&d_samples, sizeof(float) * 2 * (size_t)max_samples) != hipSuccess) {
+        (void)hipFree(d_counts);
+        return fail(ctx, RPT_ERR_NOMEM, "rpt_probe_reciprocal: hipMalloc");
+    }
+    int rc = RPT_OK;
+    if (hipMemsetAsync(d_counts, 0, 5 * sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = RPT_ERR_DEVICE;
+    if (!rc && d_samples && hipMemsetAsync(d_samples, 0, sizeof(float) * 2 * (size_t)max_samples, ctx->stream) != hipSuccess) rc = RPT_ERR_DEVICE;
+    if (!rc) {
+        // every bit pattern of [lo, hi], both signs: 2^30 lanes at most (hi_bits - lo_bits < 2^31), a fixed grid striding over them
+        const unsigned int blocks = 16384;
+        hipLaunchKernelGGL(rptd::rpt_probe_reciprocal_kernel, dim3(blocks), dim3(256), 0, ctx->stream, lo_bits, per_sign, d_counts, d_samples, max_samples);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+            hipMemcpy(counts_out, d_counts, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess ||
+            (d_samples && hipMemcpy(samples_out, d_samples, sizeof(float) * 2 * (size_t)max_samples, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = fail(ctx, RPT_ERR_DEVICE, "rpt_probe_reciprocal: device error");
     }
     (void)hipFree(d_counts);
     if (d_samples) (void)hipFree(d_samples);

@@ -69,6 +69,38 @@ RPT_DEV f3 operator/(f3 a, float s) { return div3_shared<RPT_SHARED_RCP>(a, s); 
 #else
 RPT_DEV f3 operator/(f3 a, float s) { return mk3(a.x / s, a.y / s, a.z / s); }
 #endif
+// ---- the correctly rounded reciprocal on a STATIC domain (the triangle test's 1 / det: DESIGN.md §4 item 6) ------------------------
+// rcp_exact(s) == 1.0f / s bit for bit for every s with 2^-125 <= |s| <= 2^125, and NaN for a NaN s — without the scaling and
+// fix-up of the IEEE sequence, which exist for the operands outside that range (the walk's caller guarantees the range per mesh,
+// so no per-lane guard is needed).  Form RCP_FORM:
+//   y0 = v_rcp_f32(s)                       (within 1 ulp of 1/s)
+//   y1 = y0 + y0 (1 - s y0)                 one Newton step, both fmas exact in their residual: RN(1/s) for every s whose
+//                                           significand is not all ones (Markstein), within 1 ulp for those
+//   y2 = y1 + y1 e1,  e1 = 1 - s y1         a second step.  y1 (1 + e1) = (1/s)(1 - e1^2) lies just inside 1/s, and no midpoint
+//                                           between two floats lies that close to 1/s unless e1^2 = 2^-48 exactly, i.e. y1 = 2^k and
+//                                           s = 2^-k (1 - 2^-24) (all-ones significand, y1 one ulp low): then y1 (1 + e1) IS the
+//                                           midpoint and ties-to-even returns y1.  The true 1/s lies beyond it, so that one case
+//                                           takes y1 (1 + 2^-23), the float above (e1 == 2^-24 identifies it; no other s has it).
+// Why the range: s y and the residual stay normal and exact (no overflow, no subnormal reciprocal); 1 / +-inf = 0 and 1 / 0 = inf
+// are outside it (the fmas would give NaN).  Form 3 is correct by the argument above for any seed within 1 ulp; forms 1 and 2 are
+// correct exactly where v_rcp_f32's seed for an all-ones significand does not lead to the tie.  On gfx950 it never does: all three
+// forms equal 1.0f / s on EVERY float of [2^-125, 2^125], both signs (4 194 304 002 values; rpt_probe_reciprocal,
+// tests/test_gpu_exact_division.py, which re-checks it on every run of the suite), so the product takes form 1: 3 instructions
+// instead of the division's 11.
+template <int FORM>
+RPT_DEV float rcp_newton(float s) {
+    const float y0 = __builtin_amdgcn_rcpf(s);
+    const float y1 = __builtin_fmaf(__builtin_fmaf(-s, y0, 1.0f), y0, y0);
+    if (FORM == 1) return y1;
+    const float e1 = __builtin_fmaf(-s, y1, 1.0f);
+    if (FORM == 2) return __builtin_fmaf(e1, y1, y1);
+    return __builtin_fmaf(e1 == 0x1p-24f ? 0x1p-23f : e1, y1, y1);
+}
+#ifndef RPT_RCP_FORM
+#define RPT_RCP_FORM 1
+#endif
+RPT_DEV float rcp_exact(float s) { return rcp_newton<RPT_RCP_FORM>(s); }
+
 RPT_DEV f3 operator-(f3 a) { return mk3(-a.x, -a.y, -a.z); }
 RPT_DEV f4 operator+(f4 a, f4 b) { return mk4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 RPT_DEV f4 operator*(f4 a, float s) { return mk4(a.x * s, a.y * s, a.z * s, a.w * s); }

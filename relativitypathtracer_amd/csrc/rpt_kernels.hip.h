@@ -321,12 +321,19 @@ template <> struct NodeRef<0> {
         v0v2 = C - A;
     }
 };
-// opencl_kernel.cl:106-126 with the two edge vectors supplied
+// opencl_kernel.cl:106-126 with the two edge vectors supplied.  EXACT_RCP: 1 / det through rcp_exact (rpt_device_math.hip.h), the
+// same float on the domain 2^-125 <= |det| <= 2^125.  The line above it leaves |det| >= 1e-7 > 2^-24; the ray's direction is
+// normalised (intersect_object / intersect_object_primary), so |det| <= |e1| |e2| (1 + 2^-20) with e1, e2 the record's edges, and
+// the host instantiates this form only for scenes whose triangles all have |e1| |e2| <= 2^60 (rpt_upload_scene: exact_rcp_ok).
+// A NaN det (a NaN vertex or direction) passes the line above as before; both forms then give a NaN invDet, a NaN dist, and
+// test_tri_rec's 0 <= dist rejects the triangle either way (uv's NaN never leaves this function).  So on every mesh that selects
+// it the observable result is the IEEE form's.
+template <bool EXACT_RCP = false>
 RPT_DEV bool intersect_triangle_edges(f3 A, f3 v0v1, f3 v0v2, const Ray &ray, float &dist, f2 &uv) {
     const f3 pvec = cross(ray.dir, v0v2);
     const float det = dot(v0v1, pvec);
     if (det < RPT_EPSILON && -RPT_EPSILON < det) return false;
-    const float invDet = 1 / det;
+    const float invDet = EXACT_RCP ? rcp_exact(det) : 1 / det;
     const f3 tvec = ray.origin - A;
     uv.x = dot(tvec, pvec) * invDet;
     if (uv.x < 0 || uv.x > 1) return false;
@@ -505,10 +512,11 @@ RPT_DEV TriRec load_first_tri(const KernelArgs &a, int node) {
     }
     return r;
 }
+template <bool EXACT_RCP = false>
 RPT_DEV void test_tri_rec(const TriRec &r, const Ray &ray, Hit &hit, int &hitTri, bool &didHit) {
     float dist;
     f2 triUV;
-    if (intersect_triangle_edges(mk3(r.t0.x, r.t0.y, r.t0.z), mk3(r.t0.w, r.t1.x, r.t1.y), mk3(r.t1.z, r.t1.w, r.e2z), ray, dist, triUV)) {
+    if (intersect_triangle_edges<EXACT_RCP>(mk3(r.t0.x, r.t0.y, r.t0.z), mk3(r.t0.w, r.t1.x, r.t1.y), mk3(r.t1.z, r.t1.w, r.e2z), ray, dist, triUV)) {
         if (0 <= dist && dist < hit.dist) {
             hitTri = r.tri;
             hit.dist = dist;
@@ -629,7 +637,9 @@ RPT_DEV TriRec load_tri_rec_leader(const KernelArgs &a, int k) {
 // leaf it came from — an integer compare, nothing geometric is assumed — and every entry of that leaf's list was either tested
 // in the previous step or skipped there for the same reason (induction over the steps).  The record's address is known with
 // the node's: its load travels with the node record and does not lengthen the chain.
-template <bool PIPELINE, bool FIRST, bool PACKED_COUNT = true, bool ROOT_GRID = false, bool LATE_ID = false, int UNIFORM = 0, bool DEDUP = false>
+// EXACT_RCP: the triangle test's 1 / det without the IEEE scaling (intersect_triangle_edges); the host selects it per scene.
+template <bool PIPELINE, bool FIRST, bool PACKED_COUNT = true, bool ROOT_GRID = false, bool LATE_ID = false, int UNIFORM = 0, bool DEDUP = false,
+          bool EXACT_RCP = false>
 RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, const Ray &newRay, f3 world_origin,
                          float world_dirlen, Hit &hit) {
     int curr = root;
@@ -682,7 +692,7 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
         if (UNIFORM && uni) {          // one list for the whole wave: records through the scalar cache
             const int ue = __builtin_amdgcn_readfirstlane(trisEnd);
             for (int k = __builtin_amdgcn_readfirstlane(i); k < ue; k++)
-                test_tri_rec(UNIFORM == 2 ? load_tri_rec_leader<LATE_ID>(a, k) : load_tri_rec<LATE_ID>(a, k), newRay, hit, hitTri, didHit);
+                test_tri_rec<EXACT_RCP>(UNIFORM == 2 ? load_tri_rec_leader<LATE_ID>(a, k) : load_tri_rec<LATE_ID>(a, k), newRay, hit, hitTri, didHit);
         } else if (PIPELINE) {
             if (i < trisEnd) {
                 TriRec cur = FIRST ? first : load_tri_rec<LATE_ID>(a, i);
@@ -690,17 +700,17 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
                     TriRec nxt = cur;
                     if (i + 1 < trisEnd) nxt = load_tri_rec<LATE_ID>(a, i + 1);
                     if (LATE_ID) cur.tri = i;
-                    if (!(DEDUP && i - listBegin < 32 && ((seen >> (i - listBegin)) & 1u))) test_tri_rec(cur, newRay, hit, hitTri, didHit);     // (the record was asked for an iteration ago: only the arithmetic is saved here)
+                    if (!(DEDUP && i - listBegin < 32 && ((seen >> (i - listBegin)) & 1u))) test_tri_rec<EXACT_RCP>(cur, newRay, hit, hitTri, didHit);     // (the record was asked for an iteration ago: only the arithmetic is saved here)
                     cur = nxt;
                 }
             }
         } else if (DEDUP) {
             for (; i < trisEnd; i++) {
                 if (i - listBegin < 32 && ((seen >> (i - listBegin)) & 1u)) continue;                    // tested in the previous leaf: neither loaded nor tested
-                test_tri_rec(load_tri_rec<LATE_ID>(a, i), newRay, hit, hitTri, didHit);
+                test_tri_rec<EXACT_RCP>(load_tri_rec<LATE_ID>(a, i), newRay, hit, hitTri, didHit);
             }
         } else {
-            for (; i < trisEnd; i++) test_tri_rec(load_tri_rec<LATE_ID>(a, i), newRay, hit, hitTri, didHit);
+            for (; i < trisEnd; i++) test_tri_rec<EXACT_RCP>(load_tri_rec<LATE_ID>(a, i), newRay, hit, hitTri, didHit);
         }
         uv = nmin + uv * (nmax - nmin);
         if (exit_is_past_hit(uv - newRay.origin, hit.dist, didHit) || next == -1) break;
@@ -723,6 +733,9 @@ namespace rptd {
 
 // Which walk a kernel variant uses.  V = 0: the reference's layouts; V = 23 (kernel 43: the blocking call, and frames in flight
 // too small to fill the chip with walks): the latency form — records an iteration ahead, a leaf's first record with its node.
+// V = 21 / 25: the walks of 20 / 23 with the triangle test's exact reciprocal (EXACT_RCP), for scenes inside its domain.
+template <int V> RPT_DEV constexpr bool latency_walk() { return V == 23 || V == 25; }
+template <int V> RPT_DEV constexpr bool exact_rcp_walk() { return V == 21 || V == 25; }
 template <int V>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
 #ifdef RPT_DIAGNOSTICS
@@ -731,7 +744,8 @@ RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const 
     if (V == 0) return octree_core_ref(a, obj, newRay, world_origin, world_dirlen, hit);
     // (the packed leaf count pays in the throughput walk — one instruction less per node visit, -0.5...-1 % — and costs the latency
     // walk 2-4.5 %, whose count then sits behind a shift and a compare instead of arriving beside the box: profiles/r03_packed_count_ab.txt)
-    return octree_walk<V == 23, V == 23, V != 23, false, true>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
+    return octree_walk<latency_walk<V>(), latency_walk<V>(), !latency_walk<V>(), false, true, 0, false, exact_rcp_walk<V>()>(a, obj, a.dobjs[i].root, newRay, world_origin,
+                                                                                                                      world_dirlen, hit);
 }
 
 RPT_DEV float max3(f3 v) { return cl_max(cl_max(v.x, v.y), v.z); }   // opencl_kernel.cl:310
@@ -1153,8 +1167,8 @@ RPT_DEV unsigned long long wave_object_mask(const KernelArgs &a, int tile_x0, in
 
 template <int V> RPT_DEV constexpr bool culled_variant() { return V >= 20; }
 template <int V> RPT_DEV constexpr bool zorder_lanes() { return V == 641 || V == 653; }
-template <int V> RPT_DEV constexpr bool one_wave_workgroups() { return V == 0 || V == 1 || V == 20 || V == 23 || V == 24 || V == 657 || V == 669 || V == 673 || V == 705 || V == 717; }     // the product kernels (+ three arms re-measured that way)
-template <int V> RPT_DEV constexpr bool band_first_variant() { return V == 23 || V == 123 || (V >= 256 && V < 1000 && (V & 8)); }
+template <int V> RPT_DEV constexpr bool one_wave_workgroups() { return V == 0 || V == 1 || V == 20 || V == 21 || V == 23 || V == 24 || V == 25 || V == 657 || V == 669 || V == 673 || V == 705 || V == 717; }     // the product kernels (+ three arms re-measured that way)
+template <int V> RPT_DEV constexpr bool band_first_variant() { return V == 23 || V == 25 || V == 123 || (V >= 256 && V < 1000 && (V & 8)); }
 
 // ---------------------------------------------------------------------------------------------
 // One thread per pixel, wave = 8x8 tile, workgroup = 32x8 strip.
@@ -1288,9 +1302,13 @@ RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
 __global__ __launch_bounds__(64) void rpt_render_kernel_v0(const KernelArgs a) { render_pixel_body<0>(a); }                                                              // 1: any valid octree
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_w5(const KernelArgs a) { render_pixel_body<1>(a); }         // 3: no cull (rpt_verify_frame; the escape hatch)
 // the wave's object mask from the per-object screen rectangles by lane-parallel test + __ballot, 5 waves per SIMD (96 VGPRs, 8 B of scratch outside the loops)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_w5(const KernelArgs a) { render_pixel_body<20>(a); }          // 41 = rpt_render_async
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_w5(const KernelArgs a) { render_pixel_body<21>(a); }          // 41 = rpt_render_async
 // the same with the tile rows that hold the meshes dispatched first and the latency walk (44 B of scratch): latency, not throughput
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_w5(const KernelArgs a) { render_pixel_body<23>(a); }    // 43 = the blocking rpt_render; rpt_render_async below RPT_LATENCY_KERNEL_MAX_PIXELS
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_w5(const KernelArgs a) { render_pixel_body<25>(a); }    // 43 = the blocking rpt_render; rpt_render_async below RPT_LATENCY_KERNEL_MAX_PIXELS
+// 41 and 43 above take the triangle test's 1 / det through rcp_exact (V = 21 / 25); these two keep the IEEE division, for scenes
+// outside rcp_exact's domain (rpt_scene_exact_rcp) and as variants 48 / 49
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_w5(const KernelArgs a) { render_pixel_body<20>(a); }        // 48 (and 41 outside the domain)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_w5(const KernelArgs a) { render_pixel_body<23>(a); }  // 49 (and 43 outside the domain)
 // without the octree walk compiled in, for frames whose Object[] holds no mesh: 61 VGPRs, no scratch, EIGHT waves per SIMD
 // (arch 1080p 0.0370 -> 0.0301 ms per frame in flight, cubes.txt 4K 0.0898 -> 0.0725)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_w8(const KernelArgs a) { render_pixel_body<24>(a); }        // 44
@@ -1494,6 +1512,30 @@ __global__ __launch_bounds__(256) void rpt_probe_division_kernel(int mode, uint3
     atomicAdd(&counts[0], n_cmp); atomicAdd(&counts[1], bad1); atomicAdd(&counts[2], bad2); atomicAdd(&counts[3], badg);
 }
 
+// The exact reciprocal against IEEE 1 / s (rpt_probe_reciprocal): every float s whose bit pattern lies in [lo_bits, lo_bits + per_sign),
+// with both signs.  counts = {values compared, mismatches of rcp_newton<1>, <2>, <3> (rpt_device_math.hip.h), samples written}; the
+// first max_samples mismatching s go to samples as {s, bit mask of the forms that missed (1, 2, 4)}.
+__global__ __launch_bounds__(256) void rpt_probe_reciprocal_kernel(uint32_t lo_bits, unsigned long long per_sign, unsigned long long *counts, float *samples, int max_samples) {
+    unsigned long long n_cmp = 0, bad1 = 0, bad2 = 0, bad3 = 0;
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < 2ull * per_sign; i += stride) {
+        const uint32_t sign = i < per_sign ? 0u : 0x80000000u;
+        const float s = __uint_as_float(sign | (lo_bits + (uint32_t)(i < per_sign ? i : i - per_sign)));
+        const uint32_t ref = __float_as_uint(1.0f / s);
+        const int miss = (__float_as_uint(rcp_newton<1>(s)) != ref ? 1 : 0) | (__float_as_uint(rcp_newton<2>(s)) != ref ? 2 : 0) |
+                         (__float_as_uint(rcp_newton<3>(s)) != ref ? 4 : 0);
+        n_cmp++;
+        bad1 += miss & 1;
+        bad2 += (miss >> 1) & 1;
+        bad3 += (miss >> 2) & 1;
+        if (miss && samples) {
+            const unsigned long long slot = atomicAdd(&counts[4], 1ull);
+            if (slot < (unsigned long long)max_samples) { samples[2 * slot] = s; samples[2 * slot + 1] = (float)miss; }
+        }
+    }
+    atomicAdd(&counts[0], n_cmp); atomicAdd(&counts[1], bad1); atomicAdd(&counts[2], bad2); atomicAdd(&counts[3], bad3);
+}
+
 // Known-answer probes at OBJECT level (rpt_probe_object; the oracle's counterpart is rpt_oracle_object_rays): which =
 //   0: one 4-D ray {origin4, dir4} in the rest frame of object `object` through intersect_object, the general form every shadow ray
 //      and the V = 0 kernel's primary rays take: out 8 = {hit, dist, normal.xyz, uv.xy, 0}   (opencl_kernel.cl:312-359, 200-308)
@@ -1555,7 +1597,8 @@ __global__ __launch_bounds__(64) void rpt_probe_object_kernel(const KernelArgs a
 // product library holds — the reference's layouts (octree_core_ref), the throughput walk (octree_walk<false, false>) and the latency
 // walk (octree_walk<true, true>) — with the hit re-measured from the origin (0, 0, 0) at unit direction length.  8 floats per walk
 // and ray: hit flag, dist, normal.xyz, uv.xy, 0.
-__global__ __launch_bounds__(256) void rpt_probe_walk_kernel(const KernelArgs a, int object, const float *rays, float *out, int n) {
+// exact = 1: the two derived-layout walks in the EXACT_RCP form kernels 41 / 43 launch on this scene (its triangles are in the domain)
+__global__ __launch_bounds__(256) void rpt_probe_walk_kernel(const KernelArgs a, int object, const float *rays, float *out, int n, int exact) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Ray r;
@@ -1569,9 +1612,12 @@ __global__ __launch_bounds__(256) void rpt_probe_walk_kernel(const KernelArgs a,
         hit.normal = mk3(0.0f, 0.0f, 0.0f);
         hit.uv.x = hit.uv.y = 0.0f;
         hit.object = -1;
-        const bool h = w == 0 ? octree_core_ref(a, obj, r, mk3(0.0f, 0.0f, 0.0f), 1.0f, hit)
-                     : w == 1 ? octree_walk<false, false, true, false, true>(a, obj, root, r, mk3(0.0f, 0.0f, 0.0f), 1.0f, hit)
-                              : octree_walk<true, true, false, false, true>(a, obj, root, r, mk3(0.0f, 0.0f, 0.0f), 1.0f, hit);
+        const f3 o0 = mk3(0.0f, 0.0f, 0.0f);
+        const bool h = w == 0 ? octree_core_ref(a, obj, r, o0, 1.0f, hit)
+                     : w == 1 ? (exact ? octree_walk<false, false, true, false, true, 0, false, true>(a, obj, root, r, o0, 1.0f, hit)
+                                       : octree_walk<false, false, true, false, true>(a, obj, root, r, o0, 1.0f, hit))
+                              : (exact ? octree_walk<true, true, false, false, true, 0, false, true>(a, obj, root, r, o0, 1.0f, hit)
+                                       : octree_walk<true, true, false, false, true>(a, obj, root, r, o0, 1.0f, hit));
         float *o = out + ((size_t)i * 3 + w) * 8;
         o[0] = h ? 1.0f : 0.0f;
         o[1] = h ? hit.dist : 0.0f;

@@ -113,6 +113,10 @@ class Renderer:
         """The kernel variant (include/rpt.h) the last launch of this context was made with: what variant 0 resolved to."""
         return int(self._lib.rpt_last_variant(self._h))
 
+    def last_exact_rcp(self) -> bool:
+        """Whether the last launch's triangle test took 1 / det through the exact reciprocal (kernels 41 / 43 on a scene in its domain)."""
+        return bool(self._lib.rpt_last_exact_rcp(self._h))
+
     def verify_frame(self) -> int:
         """Pixels whose packed colour differs between the kernel a frame would get and the un-culled kernel (0 = the culls changed nothing)."""
         n = C.c_uint64(0)
@@ -229,6 +233,13 @@ class Renderer:
         counts = (C.c_uint64 * 5)()
         samples = np.zeros((max_samples, 4), dtype=np.float32)
         self._check(self._lib.rpt_probe_division(self._h, int(mode), int(seed) & 0xffffffff, int(blocks), int(per_thread), counts, samples.ctypes.data, max_samples), "rpt_probe_division")
+        return [int(c) for c in counts], samples
+
+    def probe_reciprocal(self, lo: float, hi: float, max_samples: int = 16):
+        """rpt_probe_reciprocal (include/rpt.h): (counts[5], samples[max_samples, 2])."""
+        counts = (C.c_uint64 * 5)()
+        samples = np.zeros((max_samples, 2), dtype=np.float32)
+        self._check(self._lib.rpt_probe_reciprocal(self._h, float(lo), float(hi), counts, samples.ctypes.data, max_samples), "rpt_probe_reciprocal")
         return [int(c) for c in counts], samples
 
     def probe_object(self, which: int, object_index: int, inputs: np.ndarray) -> np.ndarray:
