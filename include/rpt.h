@@ -24,7 +24,9 @@
  * rpt_set_tile_pattern (pixel-row tiles for multi-GPU sharding), rpt_pack_/rpt_scatter_* (the exchange's two kernels),
  * rpt_build_octree (GPU counterpart of Mesh::GenerateOctree) and the test hooks rpt_probe, rpt_probe_walk, rpt_probe_object,
  * rpt_probe_division, rpt_set_debug_rgb, rpt_verify_frame, rpt_object_screen_rect / _bounds / _bounds_proposed,
- * rpt_certify_screen_bounds and rpt_mesh_segment_cull_record (the last five are host code: no device needed).
+ * rpt_certify_screen_bounds and rpt_mesh_segment_cull_record (the last five are host code: no device needed), and the opt-in
+ * relativistic Doppler shift and searchlight beaming, which the reference does not render: rpt_set_doppler with its test hooks
+ * rpt_set_debug_doppler / rpt_read_debug_doppler and rpt_probe which = 6 ("Doppler and beaming").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -110,6 +112,26 @@ int rpt_set_stream(rpt_ctx *ctx, void *hip_stream);
  * width*height*12 B) to this device pointer; NULL disables. 1 = library-owned buffer. */
 int rpt_set_debug_rgb(rpt_ctx *ctx, void *device_ptr_or_null_or_1);
 
+/* Relativistic Doppler shift and searchlight beaming (not in the reference; DESIGN.md "Doppler and beaming"), per context, off by
+ * default, not shared by rpt_share_scene.  flags: 0 (the reference), or RPT_DOPPLER_SHIFT and / or RPT_DOPPLER_BEAMING; anything
+ * else is RPT_ERR_ARG.  With flags != 0 every kernel a frame would get is replaced by its Doppler twin — 3, 41, 43, 44, 48, 49 by
+ * 203, 241, 243, 244, 248, 249 (rpt_last_variant reports these) — and the light colours and the surface colour seen by the camera
+ * are shifted by the frequency ratios the Lorentz matrices imply.  Kernels without a twin (variants 1, 50, 51, and MSAA > 1, also
+ * variant 0 on an octree whose children are not consecutive) make rpt_render / rpt_render_async / rpt_verify_frame return
+ * RPT_ERR_ARG at the LAUNCH; the call itself accepts any valid flags.  With light propagation off (interval 0) or a scene at
+ * rest the frame equals the reference's. */
+#define RPT_DOPPLER_SHIFT 1
+#define RPT_DOPPLER_BEAMING 2
+int rpt_set_doppler(rpt_ctx *ctx, int flags);
+/* Test hook, the shape of rpt_set_debug_rgb: while it is set and Doppler is on, frames are rendered by the un-culled Doppler
+ * debug kernel (rpt_last_variant 240), which also writes 11 floats per pixel (row-major, width*height*44 B) to this device
+ * pointer (1 = a library-owned buffer; NULL disables): {D_cam, D of the first light that contributed (1 if none), the reference's
+ * linear colour (no Doppler) rgb, the colour after the light factors rgb, the final linear colour after S(D_cam) rgb}; a miss
+ * pixel's record is all zero.  The product twins carry none of it.  rpt_read_debug_doppler copies the library-owned record of
+ * the last frame (RPT_ERR_STATE if the last frame was not rendered by the debug kernel). */
+int rpt_set_debug_doppler(rpt_ctx *ctx, void *device_ptr_or_null_or_1);
+int rpt_read_debug_doppler(rpt_ctx *ctx, void *host_dst, size_t bytes);
+
 /* Kernel variant: 0 = default (fastest validated); the others select alternative implementations of the same path for
  * A/B measurement.  All produce identical results.
  *   0   default: 44 when the current Object[] holds no mesh; else 43 for the blocking rpt_render and for contexts of at
@@ -150,7 +172,7 @@ int rpt_last_exact_rcp(const rpt_ctx *ctx);
  * vertices), the domain on which kernels 41 / 43 use the exact reciprocal; 0 if not; -RPT_ERR_ARG / -RPT_ERR_SCENE for a bad desc. */
 int rpt_scene_exact_rcp(const rpt_scene_desc *s);
 
-/* A culled-vs-un-culled self-check on the device.  The default kernels drop objects per wavefront from conservatively
+/* A culled-vs-un-culled self-check on the device (with Doppler on: the twin a frame would get against the un-culled twin, 203).  The default kernels drop objects per wavefront from conservatively
  * sampled screen bounds and shadow rays per wavefront from segment-vs-box tests; a wrong bound would make an object vanish from
  * a tile without any error.  rpt_verify_frame renders the context's CURRENT state (objects, parameters, rows) once with the
  * kernel a frame would get (rpt_render_async's choice, or the variant set) and once with the un-culled kernel (3) into scratch
@@ -268,7 +290,8 @@ void rpt_free_host(void *p);
 
 /* Known-answer probes of individual device functions (tests): which = 0 intersect_triangle
  * (in 15 floats -> out 4), 1 intersect_AABB (12 -> 5), 2 createCamRay (4 -> 3), 3 hable (3 -> 3), 4 asin / atan2 of the
- * textured-sphere (u,v) (3 -> 2), 5 the walk's pure steps: exit face of a leaf and child selection, general and fast (6 -> 12). */
+ * textured-sphere (u,v) (3 -> 2), 5 the walk's pure steps: exit face of a leaf and child selection, general and fast (6 -> 12),
+ * 6 the Doppler kernels' colour operator S_f (5 -> 3: {D, r, g, b, flags as a float} -> the operated r, g, b). */
 int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int n);
 /* Test hook, one object's functions at ray level (the oracle's counterpart: rpt_oracle_object_rays): which = 0 n 4-D rays
  * {origin4, dir4} of object `object_index`'s rest frame through its intersector in the general form of opencl_kernel.cl:312-359 /

@@ -172,6 +172,9 @@ HIP_SYMBOLS = {
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rpt_free_host": (None, [C.c_void_p]),
     "rpt_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "rpt_set_doppler": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_set_debug_doppler": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_read_debug_doppler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -132,6 +132,12 @@ struct rpt_ctx {
     bool frame_rendered = false;
     bool latency_call = false;                        // the launch in progress comes from the blocking rpt_render()
     bool has_mesh = true;                             // the current Object[] holds a mesh object (rpt_set_objects); picks the kernel
+    // rpt_set_doppler (not in the reference): RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING, 0 = off; per context, never shared
+    int doppler = 0;
+    void *external_doppler = nullptr;                 // rpt_set_debug_doppler: the record's buffer (or the library's, want_owned_doppler)
+    bool want_owned_doppler = false;
+    bool doppler_recorded = false;                    // the last launch was the Doppler debug kernel (the record is the last frame's)
+    DeviceBuffer owned_doppler;
 };
 
 namespace {
@@ -588,6 +594,9 @@ int ensure_outputs(rpt_ctx *ctx) {
     if (ctx->want_owned_rgb) {
         if (int rc = reserve(ctx, ctx->owned_rgb, px * 12)) return rc;
     }
+    if (ctx->want_owned_doppler && ctx->doppler) {
+        if (int rc = reserve(ctx, ctx->owned_doppler, px * RPT_DOPPLER_RECORD * sizeof(float))) return rc;
+    }
     return RPT_OK;
 }
 
@@ -812,7 +821,35 @@ int launch(rpt_ctx *ctx) {
         if (v != 3 && v != 41 && v != 43 && v != 44) return fail(ctx, RPT_ERR_ARG, "rpt_set_msaa > 1 is implemented for the default kernels and variant 3 (derived octree layouts)");
         v = v == 3 ? 47 : 46;
     }
+    // Doppler on (rpt_set_doppler): every kernel chosen above goes to its twin (its number + 200), or to the debug kernel (240, un-culled)
+    // while the record hook is set.  The kernels without a twin refuse here, at the launch: the setting may precede rpt_set_variant.
+    float *const record = ctx->doppler ? (float *)(ctx->external_doppler ? ctx->external_doppler : (ctx->want_owned_doppler ? ctx->owned_doppler.ptr : nullptr)) : nullptr;
+    if (ctx->doppler) {
+        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_doppler: MSAA > 1 has no Doppler kernel");
+        if (v != 3 && v != 41 && v != 43 && v != 44 && v != 48 && v != 49)
+            return fail(ctx, RPT_ERR_ARG, v == 1 ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
+                                                  : "rpt_set_doppler: this kernel variant has no Doppler twin");
+        v = record ? 240 : v + 200;
+    }
+    rptd::DopplerArgs da;         // (the twins' arguments: this frame's KernelArgs + the two Doppler fields)
+    static_cast<rptd::KernelArgs &>(da) = a;
+    da.doppler = ctx->doppler;
+    da.debug_doppler = record;
+    ctx->doppler_recorded = false;
     switch (v) {
+    case 203: hipLaunchKernelGGL(rptd::rpt_render_kernel_unculled_doppler_w5, grid1, dim3(64), 0, ctx->stream, da); break;
+    case 240: hipLaunchKernelGGL(rptd::rpt_render_kernel_doppler_record_w5, grid1, dim3(64), 0, ctx->stream, da); ctx->doppler_recorded = true; break;
+    case 241:
+        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
+        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
+        break;
+    case 243:
+        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
+        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
+        break;
+    case 244: hipLaunchKernelGGL(rptd::rpt_render_kernel_analytic_doppler_w8, grid1, dim3(64), 0, ctx->stream, da); break;
+    case 248: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da); break;
+    case 249: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da); break;
     case 46: hipLaunchKernelGGL(rptd::rpt_render_kernel_msaa_w5, grid1, dim3(64), 0, ctx->stream, a); break;
     case 47: hipLaunchKernelGGL(rptd::rpt_render_kernel_msaa_unculled_w5, grid1, dim3(64), 0, ctx->stream, a); break;
     case 1: hipLaunchKernelGGL(rptd::rpt_render_kernel_v0, grid1, dim3(64), 0, ctx->stream, a); break;
@@ -842,7 +879,7 @@ int launch(rpt_ctx *ctx) {
     }
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = v;
-    ctx->last_exact_rcp = (v == 41 || v == 43) && ctx->geo->exact_rcp_ok;
+    ctx->last_exact_rcp = (v == 41 || v == 43 || v == 241 || v == 243) && ctx->geo->exact_rcp_ok;
     return RPT_OK;
 }
 
@@ -910,7 +947,7 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
@@ -1120,6 +1157,32 @@ int rpt_set_debug_rgb(rpt_ctx *ctx, void *p) {
     return RPT_OK;
 }
 
+int rpt_set_doppler(rpt_ctx *ctx, int flags) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (flags & ~(RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING)) return fail(ctx, RPT_ERR_ARG, "rpt_set_doppler: flags are 0 or RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING");
+    ctx->doppler = flags;
+    return RPT_OK;
+}
+
+int rpt_set_debug_doppler(rpt_ctx *ctx, void *p) {
+    if (!ctx) return RPT_ERR_ARG;
+    ctx->want_owned_doppler = (p == (void *)1);
+    ctx->external_doppler = ctx->want_owned_doppler ? nullptr : p;
+    return RPT_OK;
+}
+
+int rpt_read_debug_doppler(rpt_ctx *ctx, void *host_dst, size_t bytes) {
+    if (!ctx || !host_dst) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    const void *src = ctx->external_doppler ? ctx->external_doppler : (ctx->want_owned_doppler ? ctx->owned_doppler.ptr : nullptr);
+    if (!src || !ctx->frame_rendered || !ctx->doppler_recorded)
+        return fail(ctx, RPT_ERR_STATE, "rpt_read_debug_doppler: the last frame was not rendered with Doppler on and the record hook set");
+    if (bytes > (size_t)ctx->width * ctx->height * RPT_DOPPLER_RECORD * sizeof(float)) return fail(ctx, RPT_ERR_ARG, "rpt_read_debug_doppler: too many bytes");
+    RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RPT_HIP(ctx, hipMemcpy(host_dst, src, bytes, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 int rpt_object_screen_rect(const void *object, int interval, const float *root_bounds_or_null, float rect_out[4]) {
     if (!object || !rect_out) return RPT_ERR_ARG;
     const rptb::Rect r = rptb::certified_object_rect(*(const rpt_object *)object, interval, root_bounds_or_null);
@@ -1230,10 +1293,12 @@ int rpt_verify_frame(rpt_ctx *ctx, unsigned long long *differing_pixels) {
     RPT_HIP(ctx, hipMemsetAsync(plane_a, 0, 2 * words * 4 + 8, ctx->stream));     // (rows of the last tile beyond the frame's height are never written)
     // render twice into the scratch planes: the kernel a frame would get, then the un-culled one; the context's own outputs,
     // its variant and its debug hook are put back whatever happens
-    struct Saved { void *plane, *rgb; bool colour_plane, want_rgb; int variant; } saved = {ctx->external_plane, ctx->external_rgb, ctx->colour_plane, ctx->want_owned_rgb, ctx->variant};
+    struct Saved { void *plane, *rgb, *dop; bool colour_plane, want_rgb, want_dop, dop_recorded; int variant; } saved = {ctx->external_plane, ctx->external_rgb, ctx->external_doppler, ctx->colour_plane, ctx->want_owned_rgb, ctx->want_owned_doppler, ctx->doppler_recorded, ctx->variant};
     ctx->colour_plane = true;
     ctx->external_rgb = nullptr;
     ctx->want_owned_rgb = false;
+    ctx->external_doppler = nullptr;         // (with Doppler on: the twin a frame would get against the un-culled twin, 203)
+    ctx->want_owned_doppler = false;
     int rc = RPT_OK;
     ctx->external_plane = plane_a;
     rc = launch(ctx);
@@ -1245,6 +1310,7 @@ int rpt_verify_frame(rpt_ctx *ctx, unsigned long long *differing_pixels) {
     }
     ctx->last_variant = verified_variant;
     ctx->external_plane = saved.plane; ctx->external_rgb = saved.rgb; ctx->colour_plane = saved.colour_plane; ctx->want_owned_rgb = saved.want_rgb; ctx->variant = saved.variant;
+    ctx->external_doppler = saved.dop; ctx->want_owned_doppler = saved.want_dop; ctx->doppler_recorded = saved.dop_recorded;
     if (rc != RPT_OK) return rc;
     if (words) {
         const unsigned int blocks = (unsigned int)std::min<size_t>((words + 255) / 256, 4096);
@@ -1504,8 +1570,8 @@ int rpt_read_wave_times(rpt_ctx *ctx, unsigned long long *out, size_t max_words,
 }
 
 int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int n) {
-    static const int in_w[6] = {15, 12, 4, 3, 3, 6}, out_w[6] = {4, 5, 3, 3, 2, 12};
-    if (!ctx || which < 0 || which > 5 || !host_in || !host_out || n <= 0) return RPT_ERR_ARG;
+    static const int in_w[7] = {15, 12, 4, 3, 3, 6, 5}, out_w[7] = {4, 5, 3, 3, 2, 12, 3};
+    if (!ctx || which < 0 || which > 6 || !host_in || !host_out || n <= 0) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     float *d_in = nullptr, *d_out = nullptr;
     RPT_HIP(ctx, hipMalloc((void **)&d_in, sizeof(float) * in_w[which] * n));
@@ -1516,7 +1582,8 @@ int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int 
     int rc = RPT_OK;
     if (hipMemcpy(d_in, host_in, sizeof(float) * in_w[which] * n, hipMemcpyHostToDevice) != hipSuccess) rc = RPT_ERR_DEVICE;
     if (!rc) {
-        hipLaunchKernelGGL(rptd::rpt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, which, d_in, d_out, n);
+        if (which == 6) hipLaunchKernelGGL(rptd::rpt_probe_doppler_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_in, d_out, n);
+        else hipLaunchKernelGGL(rptd::rpt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, which, d_in, d_out, n);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
             hipMemcpy(host_out, d_out, sizeof(float) * out_w[which] * n, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(ctx, RPT_ERR_DEVICE, "rpt_probe: device error");

@@ -137,6 +137,15 @@ struct KernelArgs {
                                     // iterations, [3..5] the same counted once per executing wave
 };
 
+// The Doppler kernels' arguments (rpt_set_doppler; not in the reference): KernelArgs with two fields appended at the end.  A struct
+// of its own rather than more KernelArgs fields, so that every other kernel keeps its argument block — and with it its code, the
+// probe kernels' trailing arguments included — byte for byte.  The Doppler bodies reach the fields through a static_cast of the
+// KernelArgs they are handed (it is always a DopplerArgs there).
+struct DopplerArgs : KernelArgs {
+    int doppler;                    // RPT_DOPPLER_SHIFT (1) | RPT_DOPPLER_BEAMING (2); the twins are launched only when != 0
+    float *debug_doppler;           // the Doppler debug kernel only: RPT_DOPPLER_RECORD floats per pixel (rpt_set_debug_doppler)
+};
+
 struct Hit {                 // opencl_kernel.cl:38-44
     float dist;
     f3 normal;
@@ -1023,11 +1032,62 @@ RPT_DEV bool sample_light_occluded(const KernelArgs &a, f4 origin4, f4 dir4, flo
     return false;
 }
 
+// ---- Doppler shift and searchlight beaming (not in the reference; DESIGN.md "Doppler and beaming") ------------------------
+// D = observed / emitted frequency.  Each RGB channel is a spectral sample at a fixed frequency relative to green (the CIE 1931
+// RGB primaries 700.0 / 546.1 / 435.8 nm); the knots are computed in double and rounded to float once (here, at compile time).
+// The emitted spectrum of a colour (r, g, b) is piecewise linear through (K0, 0), (NU_R, r), (1, g), (NU_B, b), (K4, 0) and 0
+// outside; channel k observes it at NU_k / D.  Only + - * / and compares: tests/test_doppler_model.py restates it in numpy
+// float32 and the probe (rpt_probe which = 6) must match that restatement bit for bit.
+#define RPT_DOPPLER_RECORD 11
+#define RPT_NU_R ((float)(546.1 / 700.0))
+#define RPT_NU_B ((float)(546.1 / 435.8))
+#define RPT_NU_K0 ((float)(2.0 * (546.1 / 700.0) - 1.0))
+#define RPT_NU_K4 ((float)(2.0 * (546.1 / 435.8) - 1.0))
+
+RPT_DEV float doppler_spectrum(float u, float r, float g, float b) {
+    if (!(u > RPT_NU_K0) || !(u < RPT_NU_K4)) return 0.0f;      // beyond the outer knots (and NaN): infrared / ultraviolet
+    float xa, xb, ya, yb;
+    if (u < RPT_NU_R) { xa = RPT_NU_K0; xb = RPT_NU_R; ya = 0.0f; yb = r; }
+    else if (u < 1.0f) { xa = RPT_NU_R; xb = 1.0f; ya = r; yb = g; }
+    else if (u < RPT_NU_B) { xa = 1.0f; xb = RPT_NU_B; ya = g; yb = b; }
+    else { xa = RPT_NU_B; xb = RPT_NU_K4; ya = b; yb = 0.0f; }
+    const float t = (u - xa) / (xb - xa);
+    return ya * (1.0f - t) + yb * t;                          // exact at both ends of the segment: continuous across every knot
+}
+
+// S_f(D, c): flags bit 0 = shift (the spectrum above), bit 1 = beaming (x D^3 with the shift: I_nu / nu^3 is invariant;
+// x D^4 without it: the bolometric form, hue unchanged).  D == 1 returns c bit for bit by an explicit test.
+RPT_DEV f3 doppler_colour(int flags, float D, f3 c) {
+    if (D == 1.0f) return c;
+    f3 o = c;
+    if (flags & 1) {
+        o.x = doppler_spectrum(RPT_NU_R / D, c.x, c.y, c.z);
+        o.y = doppler_spectrum(1.0f / D, c.x, c.y, c.z);
+        o.z = doppler_spectrum(RPT_NU_B / D, c.x, c.y, c.z);
+        if (flags & 2) {
+            const float d3 = (D * D) * D;
+            o = o * d3;
+        }
+    } else if (flags & 2) {
+        const float d2 = D * D;
+        o = c * (d2 * d2);
+    }
+    return o;
+}
+
+// What the Doppler debug kernel records per hit pixel (rpt_set_debug_doppler)
+struct DopplerRecord {
+    float dcam, dlight;      // camera factor; light factor of the first light that contributed (1 if none)
+    f3 ref, lit;             // the reference's colour (no Doppler); the colour after the light factors, before S(D_cam)
+};
+
 // opencl_kernel.cl:361-486 + 548-604: closest hit over the object list, surface colour, lights
 // Returns false (and leaves `color` untouched) when the ray hits nothing: the caller then uses the
 // per-frame background constants instead of tonemapping (0.15,0.15,0.25) again for every pixel.
-template <int V>
-RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mask, f3 &color_out) {
+// DOPPLER (the twins of rpt_set_doppler): each light's colour goes through S_f(D_i) and the summed colour through S_f(D_cam);
+// DREC (the Doppler debug kernel only) also fills *rec.  With light propagation off (interval 0) nothing changes.
+template <int V, bool DOPPLER = false, bool DREC = false>
+RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mask, f3 &color_out, DopplerRecord *rec = nullptr) {
     const float inf = 1e20f;
     Hit hit;
     hit.dist = inf;
@@ -1070,6 +1130,9 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
 
     f3 color = hcolor * (a.interval != 0 ? a.ambient : 1.0f);
     if (ho.light) color = color + hcolor;
+    [[maybe_unused]] f3 color_ref = color;       // (DREC only) the same sum with the reference's light colours
+    [[maybe_unused]] float dlight = 1.0f;
+    [[maybe_unused]] bool lit_any = false;
     if (a.interval != 0) {
         for (int i = 0; i < a.object_count; i++) {
             if (i != hit.object && a.objects[i].light) {
@@ -1095,10 +1158,36 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
                     if (!sample_light_occluded<V>(a, hitPos, shadowDir, length(yzw(lightDir)), i)) {
                         const float k = ndotl / (1.0f + 0.1f * length(lightDir3_ObjFrame) +
                                                  0.01f * dot(lightDir3_ObjFrame, lightDir3_ObjFrame));
-                        color = color + hcolor * k * ld3(lo.color);
+                        if constexpr (DOPPLER) {
+                            // light factor: time components of the light-to-surface vector in the surface's and the light's frame
+                            const float di = lightDir_ObjFrame.x / lightDir_LightFrame.x;
+                            if constexpr (DREC) {
+                                color_ref = color_ref + hcolor * k * ld3(lo.color);
+                                if (!lit_any) dlight = di;
+                                lit_any = true;
+                            }
+                            color = color + hcolor * k * doppler_colour(static_cast<const DopplerArgs &>(a).doppler, di, ld3(lo.color));
+                        } else {
+                            color = color + hcolor * k * ld3(lo.color);
+                        }
                     }
                 }
             }
+        }
+    }
+    if constexpr (DOPPLER) {
+        float dcam = 1.0f;
+        const f3 lit = color;
+        if (a.interval != 0) {
+            // camera factor: interval / (time component of the camera ray in the hit object's frame), the flash's float
+            dcam = (float)a.interval / dot(ld4(ho.Lorentz[0]), rayDir);
+            color = doppler_colour(static_cast<const DopplerArgs &>(a).doppler, dcam, color);
+        }
+        if constexpr (DREC) {
+            rec->dcam = dcam;
+            rec->dlight = dlight;
+            rec->ref = color_ref;
+            rec->lit = lit;
         }
     }
     color_out = color;
@@ -1178,7 +1267,8 @@ template <int V> RPT_DEV constexpr bool band_first_variant() { return V == 23 ||
 //   V = 23: 20 with the band of tile rows that holds the meshes dispatched first and the pipelined walk (the blocking rpt_render)
 //   V = 24: 20 without the octree walk compiled in (frames whose Object[] holds no mesh)
 //   other values: diagnostics build only (rpt_diag_kernels.hip.h)
-template <int V>
+//   DOPPLER: the Doppler twin of kernel V (rpt_set_doppler); DREC: also the per-pixel Doppler record (the debug kernel only)
+template <int V, bool DOPPLER = false, bool DREC = false>
 RPT_DEV void render_pixel_body(const KernelArgs &a) {
     const int lane = threadIdx.x & 63;
     // The product kernels are launched ONE WAVE per workgroup (blockDim 64, grid.x = tiles per row): a wave slot is handed back when
@@ -1222,17 +1312,27 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     f3 color;
     f3 mapped = mk3(0.0f, 0.0f, 0.0f);
     bool traced = false;
+    [[maybe_unused]] DopplerRecord drec;
     uint32_t packed = a.bg_packed;
     const bool masked = culled_variant<V>() || V == 10;
     if (!masked || object_mask != 0 || a.object_count > 64) {
         const f3 camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
-        if (trace<V>(a, camdir, object_mask, color)) {
+        if (trace<V, DOPPLER, DREC>(a, camdir, object_mask, color, DREC ? &drec : nullptr)) {
             packed = tonemap_pack(a, color, mapped);
             traced = true;
         }
     }
 
     const size_t id = (size_t)y_coord * a.width + x_coord;
+    if constexpr (DREC) {
+        // {D_cam, D_light, reference colour, after the light factors, final linear colour}; a miss pixel: all zero (D_cam = 0)
+        if (float *const rec_out = static_cast<const DopplerArgs &>(a).debug_doppler) {
+            float *r = rec_out + (size_t)RPT_DOPPLER_RECORD * id;
+            const float v[RPT_DOPPLER_RECORD] = {drec.dcam, drec.dlight, drec.ref.x, drec.ref.y, drec.ref.z, drec.lit.x, drec.lit.y, drec.lit.z,
+                                                 color.x, color.y, color.z};
+            for (int k = 0; k < RPT_DOPPLER_RECORD; k++) r[k] = traced ? v[k] : 0.0f;
+        }
+    }
 #ifdef RPT_DIAGNOSTICS
     if (V == 785 && object_mask == 0ull) return;      // EXPERIMENT (wrong image): what do the sky tiles' stores cost the walks?
 #endif
@@ -1316,6 +1416,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 // MSAASAMPLES > 1 (rpt_set_msaa): culled and un-culled; rpt_last_variant reports them as 46 / 47
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_w5(const KernelArgs a) { render_pixel_body_msaa<20>(a); }            // 46
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_unculled_w5(const KernelArgs a) { render_pixel_body_msaa<1>(a); }    // 47
+
+// Doppler twins (rpt_set_doppler != 0; not in the reference): the kernels above with the colour operator compiled in, launched with
+// the same shapes and occupancies.  The variant numbers rpt_last_variant reports are the twinned kernel's + 200; 241 / 243 fall back
+// to 248's / 249's code outside the exact reciprocal's domain as 41 / 43 do.  Variants 1, 50, 51 and MSAA > 1 have no twin.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_doppler_w5(const DopplerArgs a) { render_pixel_body<1, true>(a); }         // 203
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_doppler_w5(const DopplerArgs a) { render_pixel_body<21, true>(a); }          // 241
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_doppler_w5(const DopplerArgs a) { render_pixel_body<25, true>(a); }    // 243
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_doppler_w5(const DopplerArgs a) { render_pixel_body<20, true>(a); }     // 248
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_doppler_w5(const DopplerArgs a) { render_pixel_body<23, true>(a); }  // 249
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_doppler_w8(const DopplerArgs a) { render_pixel_body<24, true>(a); }     // 244
+// the Doppler debug kernel (rpt_set_debug_doppler): 203 that also writes the per-pixel record; launched instead of any twin while the hook is set
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_doppler_record_w5(const DopplerArgs a) { render_pixel_body<1, true, true>(a); }   // 240
 
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd
@@ -1453,6 +1565,17 @@ __global__ void rpt_probe_kernel(int which, const float *in, float *out, int n) 
         out[12 * i + 4] = (float)ca; out[12 * i + 5] = a.x; out[12 * i + 6] = a.y; out[12 * i + 7] = a.z;
         out[12 * i + 8] = (float)cb; out[12 * i + 9] = b.x; out[12 * i + 10] = b.y; out[12 * i + 11] = b.z;
     }
+}
+
+// rpt_probe which = 6: S_f of the Doppler kernels on n inputs {D, r, g, b, flags} -> 3 floats (a kernel of its own: rpt_probe_kernel stays as it was)
+__global__ __launch_bounds__(256) void rpt_probe_doppler_kernel(const float *in, float *out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 5 * i;
+    const f3 o = doppler_colour((int)p[4], p[0], mk3(p[1], p[2], p[3]));
+    out[3 * i + 0] = o.x;
+    out[3 * i + 1] = o.y;
+    out[3 * i + 2] = o.z;
 }
 
 // rpt_probe_division: are the shared-reciprocal quotients of rpt_device_math.hip.h equal to IEEE division bit for bit?  Every thread

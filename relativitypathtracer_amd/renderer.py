@@ -17,6 +17,8 @@ from .scene import Scene
 
 PIXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("rgba", "u1", (4,)), ("unspecified", "<u4")])
 TILE_ROWS = 8
+DOPPLER_SHIFT, DOPPLER_BEAMING = 1, 2     # rpt_set_doppler flags (include/rpt.h)
+DOPPLER_RECORD = 11                       # floats per pixel of the Doppler debug record
 
 
 class RenderError(RuntimeError):
@@ -108,6 +110,23 @@ class Renderer:
     def set_msaa(self, samples_per_axis: int):
         """MSAASAMPLES of opencl_kernel.cl:7 (1 = the reference as shipped)."""
         self._check(self._lib.rpt_set_msaa(self._h, int(samples_per_axis)), "rpt_set_msaa")
+
+    def set_doppler(self, shift: bool = True, beaming: bool = True):
+        """Relativistic Doppler shift and / or searchlight beaming (not in the reference; off by default).  set_doppler(False, False)
+        turns it off again.  Kernels without a Doppler twin (variants 1, 50, 51, MSAA > 1) then refuse at the launch."""
+        flags = (DOPPLER_SHIFT if shift else 0) | (DOPPLER_BEAMING if beaming else 0)
+        self._check(self._lib.rpt_set_doppler(self._h, flags), "rpt_set_doppler")
+
+    def set_debug_doppler(self, enable: bool = True):
+        """While enabled (and Doppler is on) frames come from the Doppler debug kernel, which writes the per-pixel record."""
+        self._check(self._lib.rpt_set_debug_doppler(self._h, C.c_void_p(1 if enable else 0)), "rpt_set_debug_doppler")
+
+    def read_debug_doppler(self) -> np.ndarray:
+        """(H, W, 11) float32: D_cam, D of the first contributing light, reference colour rgb, colour after the light factors rgb,
+        final linear colour rgb (include/rpt.h, rpt_set_debug_doppler); all zero on a miss pixel."""
+        out = np.empty((self.height, self.width, DOPPLER_RECORD), dtype=np.float32)
+        self._check(self._lib.rpt_read_debug_doppler(self._h, out.ctypes.data, out.nbytes), "rpt_read_debug_doppler")
+        return out
 
     def last_variant(self) -> int:
         """The kernel variant (include/rpt.h) the last launch of this context was made with: what variant 0 resolved to."""
@@ -222,6 +241,7 @@ class Renderer:
             self._lib.rpt_free_host(tris)
 
     def probe(self, which: int, inputs: np.ndarray, out_width: int) -> np.ndarray:
+        """rpt_probe (include/rpt.h); which = 6: the Doppler colour operator, (n, 5) {D, r, g, b, flags} -> (n, 3)."""
         inputs = np.ascontiguousarray(inputs, dtype=np.float32)
         n = inputs.shape[0]
         out = np.empty((n, out_width), dtype=np.float32)
