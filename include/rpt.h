@@ -23,7 +23,7 @@
  * rpt_last_frame_ms, rpt_timed_frames, rpt_timing_*, the *_async/stream calls, rpt_create_multi, rpt_set_rows /
  * rpt_set_tile_pattern (pixel-row tiles for multi-GPU sharding), rpt_pack_/rpt_scatter_* (the exchange's two kernels),
  * rpt_build_octree (GPU counterpart of Mesh::GenerateOctree) and the test hooks rpt_probe, rpt_probe_walk, rpt_probe_object,
- * rpt_probe_division, rpt_set_debug_rgb, rpt_verify_frame, rpt_object_screen_rect / _bounds / _bounds_proposed,
+ * rpt_set_debug_rgb, rpt_verify_frame, rpt_object_screen_rect / _bounds / _bounds_proposed,
  * rpt_certify_screen_bounds and rpt_mesh_segment_cull_record (the last five are host code: no device needed), and the opt-in
  * relativistic Doppler shift and searchlight beaming, which the reference does not render: rpt_set_doppler with its test hooks
  * rpt_set_debug_doppler / rpt_read_debug_doppler and rpt_probe which = 6 ("Doppler and beaming").
@@ -301,12 +301,6 @@ int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int 
  * transformPoint(InvM), transformPoint4D(Lorentz), transformDirection(InvM), applyTranspose(InvM)); 3 n primary rays given by
  * their camera direction through the form the default kernels use (3 in, 8 out as in 0). */
 int rpt_probe_object(rpt_ctx *ctx, int which, int object_index, const float *host_in, float *host_out, int n);
-/* Test hook / experiment (csrc/rpt_device_math.hip.h: three quotients by one scalar through ONE refined reciprocal): compares the
- * shared-reciprocal quotients with IEEE division on blocks * 256 * per_thread generated (x, y, z, s) sets on the device.  mode 0
- * random, 1 denominators with an all-ones significand, 2 normalize() (s = sqrt(dot(v, v))), 3 arbitrary bit patterns.  counts_out =
- * {sets inside the fast path's domain, mismatching quotients with one residual correction, with two, mismatches of the guarded
- * form over ALL sets, mismatching sets seen}; the first max_samples mismatching sets (4 floats each) go to samples_out. */
-int rpt_probe_division(rpt_ctx *ctx, int mode, unsigned int seed, int blocks, int per_thread, unsigned long long counts_out[5], float *samples_out, int max_samples);
 /* Test hook (csrc/rpt_device_math.hip.h rcp_newton / rcp_exact): every float s with lo <= |s| <= hi (0 < lo <= hi <= 2^127), both signs,
  * through the three reciprocal forms on the device, compared bit for bit with IEEE 1.0f / s.  counts_out = {values compared,
  * mismatches of form 1, 2, 3, mismatching values seen}; the first max_samples mismatches go to samples_out as {s, mask of the forms

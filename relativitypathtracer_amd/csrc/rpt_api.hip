@@ -35,7 +35,6 @@ extern "C" int rpt_launch_relaxed_kernel(int waves_per_simd, const void *args, s
 #else
 #define RPT_HOST_MARK(K) do { } while (0)
 #endif
-#define RPT_GRID_ROOTS_MAX 64     /* octree roots that get a descend_from_root table (16 KB each) */
 #define RPT_RECT_BATCH_MIN 3      /* screen bounds to recompute in one rpt_set_objects before the helper threads are asked (rpt_workers.hpp); 8 until the bounds were proven as well (round 4: twice the work per object) */
 
 namespace {
@@ -55,9 +54,6 @@ struct Geometry {
     DeviceBuffer vertices, normals, uvs, triangles, octrees, octreeTris, textures;
     DeviceBuffer dnodes, dtris, dlinks;       // derived layouts (rpt_kernels.hip.h)
     DeviceBuffer dfirst;                      // first triangle record of every node's list, by node index (the latency walk)
-    DeviceBuffer dseen;                       // (diagnostics library) per (node, face): {leaf across the face, mask of this leaf's list entries also in that leaf's list}
-    DeviceBuffer dgrids;                      // 16^3 cells per octree root: where four child steps from the root end (descend_from_root)
-    int grid_roots = 0;
     bool compact_ok = false;                  // derived octree layout usable (children consecutive)
     bool exact_rcp_ok = false;                // every triangle a walk tests lies in the exact reciprocal's domain (rpt_scene_exact_rcp)
     unsigned long long generation = 0;        // unique per upload (the rectangle cache of a context names its geometry by this, not by address)
@@ -70,7 +66,7 @@ struct Geometry {
     size_t vertex_count = 0, normal_count = 0, uv_count = 0, triangle_words = 0, octree_count = 0, octree_tri_count = 0;
     ~Geometry() {
         (void)hipSetDevice(device);
-        for (DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst, &dgrids, &dseen}) release(*b);
+        for (DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst}) release(*b);
     }
 };
 
@@ -255,7 +251,6 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
     Geometry &g = *ctx->geo;
     g.compact_ok = false;
     g.top_count = 0;
-    g.grid_roots = 0;
     g.node_new_index.clear();
     if (s.octree_count == 0) {
         g.compact_ok = true;
@@ -337,50 +332,6 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
         for (size_t k = 0; k < n; k++) if (nodes[k].leafCount > 0) first[k] = tris[(size_t)nodes[k].leafBegin];
         if (int rc = upload(ctx, g.dfirst, first.data(), first.size() * sizeof(rptd::DTri))) return rc;
     }
-#ifdef RPT_DIAGNOSTICS
-    {   // descend_from_root's tables (measurement arms 593 / 605): for every root (the first records of the breadth-first numbering; at most RPT_GRID_ROOTS_MAX of
-        // them) and every cell of the 16^3 grid over its box, the node that four child steps reach — or the leaf met before
-        size_t roots = 0;
-        for (size_t i = 0; i < n; i++) roots += is_child[i] ? 0 : 1;
-        if (roots > (size_t)RPT_GRID_ROOTS_MAX) roots = RPT_GRID_ROOTS_MAX;
-        std::vector<int32_t> grids(roots * RPT_GRID_CELLS);
-        for (size_t r = 0; r < roots; r++)
-            for (int cx = 0; cx < 16; cx++) for (int cy = 0; cy < 16; cy++) for (int cz = 0; cz < 16; cz++) {
-                int node = (int)r, lvl = 0;
-                while (nodes[(size_t)node].link != -1 && lvl < RPT_GRID_LEVELS) {
-                    const int sh = RPT_GRID_LEVELS - 1 - lvl;
-                    const int child = (((cx >> sh) & 1) << 2) | (((cy >> sh) & 1) << 1) | ((cz >> sh) & 1);      // opencl_kernel.cl:257: z + 2 y + 4 x
-                    node = (nodes[(size_t)node].link & RPT_LINK_CHILD_MASK) + child;
-                    lvl++;
-                }
-                grids[r * RPT_GRID_CELLS + (size_t)((cx * 16 + cy) * 16 + cz)] = node | (lvl << 24) | ((nodes[(size_t)node].link == -1 ? 1 : 0) << 28);
-            }
-        if (int rc = upload(ctx, g.dgrids, grids.data(), grids.size() * sizeof(int32_t))) return rc;
-        g.grid_roots = (int)roots;
-    }
-    {   // octree_walk<..., DEDUP>'s table (measurement arms 705 / 717): per leaf and face, the leaf across that face (if the link points
-        // at a leaf) and which of this leaf's first 32 list entries name a triangle that is also in THAT leaf's list
-        std::vector<uint32_t> seen(n * 12, 0u);
-        std::vector<int> sorted_ids;
-        for (size_t k = 0; k < n; k++) {
-            for (int f = 0; f < 6; f++) { seen[(k * 6 + f) * 2] = 0xffffffffu; seen[(k * 6 + f) * 2 + 1] = 0u; }
-            if (nodes[k].link != -1 || nodes[k].leafCount <= 0) continue;
-            for (int f = 0; f < 6; f++) {
-                const int q = nodes[k].nb[f];
-                if (q < 0 || nodes[(size_t)q].link != -1 || nodes[(size_t)q].leafCount <= 0) continue;
-                sorted_ids.clear();
-                for (int t = 0; t < nodes[(size_t)q].leafCount; t++) sorted_ids.push_back(tris[(size_t)nodes[(size_t)q].leafBegin + (size_t)t].tri);
-                std::sort(sorted_ids.begin(), sorted_ids.end());
-                uint32_t mask = 0u;
-                for (int t = 0; t < nodes[k].leafCount && t < 32; t++)
-                    if (std::binary_search(sorted_ids.begin(), sorted_ids.end(), tris[(size_t)nodes[k].leafBegin + (size_t)t].tri)) mask |= 1u << t;
-                seen[(k * 6 + f) * 2] = (uint32_t)q;
-                seen[(k * 6 + f) * 2 + 1] = mask;
-            }
-        }
-        if (int rc = upload(ctx, g.dseen, seen.data(), seen.size() * sizeof(uint32_t))) return rc;
-    }
-#endif
     for (size_t k = 0; k < n; k++)          // leafBegin | min(leafCount, 255) << 24: see load_node_rec
         nodes[k].leafBegin = (int)((unsigned int)nodes[k].leafBegin | ((unsigned int)(nodes[k].leafCount < 255 ? nodes[k].leafCount : 255) << 24));
     // (16 B of slack behind the triangle records: the cooperative 16-B staging loads of the persistent kernels never start past the
@@ -630,6 +581,12 @@ bool mesh_band(const rpt_ctx *ctx, float aspect, int tile_rows, int &ty0, int &t
     return ty1 >= ty0;
 }
 
+// The band-first kernels' dispatch order: whole-frame contexts only, a band that does not already start the frame, at most half of it.
+void set_band_first(const rpt_ctx *ctx, rptd::KernelArgs &a, int tiles) {
+    int ty0 = 0, ty1 = -1;
+    if (mesh_band(ctx, a.aspect, tiles, ty0, ty1) && ty0 > 0 && (ty1 - ty0 + 1) * 2 < tiles) { a.first_ty = ty0; a.first_h = ty1 - ty0 + 1; }
+}
+
 #ifdef RPT_DIAGNOSTICS
 // Persistent kernels (rpt_persistent.hip.h): claim geometry, counters, grid = what the chip holds at once.
 int launch_persistent(rpt_ctx *ctx, rptd::KernelArgs &a, int tiles, int v) {
@@ -672,6 +629,7 @@ int launch_persistent(rpt_ctx *ctx, rptd::KernelArgs &a, int tiles, int v) {
 // librpt_hip_diag.so only: the measurement arms (rpt_diag_kernels.hip.h)
 #define RPT_LAUNCH_X(N) case N: hipLaunchKernelGGL(rptd::rpt_render_kernel_x##N, grid, dim3(256), 0, ctx->stream, a); break;
 int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, int v) {
+    if (v == 143 || v == 2573 || (v >= 256 && v < 1000 && (v & 8))) set_band_first(ctx, a, tiles);     // (DiagPolicy::band_first)
     switch (v) {
     case 26: {   // round 1's default: per-tile object masks from a prepass kernel
         const int tiles_x = ((ctx->width + 31) / 32) * 4;          // tiles per row as the 32-pixel-wide blocks see them
@@ -696,16 +654,11 @@ int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, i
     }
     case 61: hipLaunchKernelGGL(rptd::rpt_render_kernel_queue_w5, grid, dim3(256), 0, ctx->stream, a); break;
     RPT_LAUNCH_X(256) RPT_LAUNCH_X(257) RPT_LAUNCH_X(259) RPT_LAUNCH_X(261) RPT_LAUNCH_X(263) RPT_LAUNCH_X(265) RPT_LAUNCH_X(269)
-    RPT_LAUNCH_X(273) RPT_LAUNCH_X(277) RPT_LAUNCH_X(285) RPT_LAUNCH_X(305) RPT_LAUNCH_X(317) RPT_LAUNCH_X(337) RPT_LAUNCH_X(349) RPT_LAUNCH_X(401) RPT_LAUNCH_X(785) RPT_LAUNCH_X(529) RPT_LAUNCH_X(541) RPT_LAUNCH_X(561) RPT_LAUNCH_X(573) RPT_LAUNCH_X(589) RPT_LAUNCH_X(605) RPT_LAUNCH_X(621) RPT_LAUNCH_X(625) RPT_LAUNCH_X(637) RPT_LAUNCH_X(641) RPT_LAUNCH_X(653) RPT_LAUNCH_X(593)
+    RPT_LAUNCH_X(273) RPT_LAUNCH_X(277) RPT_LAUNCH_X(285) RPT_LAUNCH_X(305) RPT_LAUNCH_X(317) RPT_LAUNCH_X(337) RPT_LAUNCH_X(349) RPT_LAUNCH_X(401) RPT_LAUNCH_X(785) RPT_LAUNCH_X(529) RPT_LAUNCH_X(541) RPT_LAUNCH_X(561) RPT_LAUNCH_X(573) RPT_LAUNCH_X(621) RPT_LAUNCH_X(641) RPT_LAUNCH_X(653)
     case 1257: hipLaunchKernelGGL(rptd::rpt_render_kernel_x257_w6, grid, dim3(256), 0, ctx->stream, a); break;
     case 2257: hipLaunchKernelGGL(rptd::rpt_render_kernel_x257_w4, grid, dim3(256), 0, ctx->stream, a); break;
     case 2259: hipLaunchKernelGGL(rptd::rpt_render_kernel_x259_w4, grid, dim3(256), 0, ctx->stream, a); break;
     case 2263: hipLaunchKernelGGL(rptd::rpt_render_kernel_x263_w4, grid, dim3(256), 0, ctx->stream, a); break;
-    case 657: hipLaunchKernelGGL(rptd::rpt_render_kernel_x657, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;
-    case 669: hipLaunchKernelGGL(rptd::rpt_render_kernel_x669, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;
-    case 673: hipLaunchKernelGGL(rptd::rpt_render_kernel_x673, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;
-    case 705: hipLaunchKernelGGL(rptd::rpt_render_kernel_x705, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;      // kernel 41's walk without the repeated triangle tests
-    case 717: hipLaunchKernelGGL(rptd::rpt_render_kernel_x717, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;      // kernel 43's walk likewise
     RPT_LAUNCH_X(689) RPT_LAUNCH_X(701)          // kernel 41's / 43's walk launched four waves per workgroup (what the product did before)
     case 2573: hipLaunchKernelGGL(rptd::rpt_render_kernel_x573_w4, grid, dim3(256), 0, ctx->stream, a); break;      // the latency kernel at 4 waves per SIMD (128 VGPRs, no scratch)
     case 7:
@@ -727,6 +680,61 @@ int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, i
 }
 #endif
 
+// ---- the product kernels: every fact launch() and rpt_set_variant() know about a variant, one row each ------------------------------
+// variant      what rpt_set_variant takes (settable rows) and rpt_last_variant reports; the other rows are reached through the
+//              msaa and doppler columns only
+// kernel       launched with grid (4 ceil(W / 32), row tiles) x 64 threads; null: the relaxed-arithmetic build (rpt_relaxed.hip),
+//              launched through rpt_launch_relaxed_kernel at relaxed_waves waves per SIMD
+// ieee         the kernel's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp); where a
+//              row has one, rpt_last_exact_rcp says whether the row's own kernel ran
+// doppler      the variant of the Doppler twin (0: none; while the record hook is set the debug kernel 240 stands in for every twin)
+// window       outside the window the screen regions are proven for, the un-culled kernel (3) renders the frame instead
+// band_first   the policy's own (rpt_kernels.hip.h): the band of tile rows that holds the meshes is dispatched first
+// msaa         the variant for MSAA > 1 (0: refused)
+enum : int { VARIANT_DEFAULT = 0, VARIANT_REF_LAYOUT = 1, VARIANT_UNCULLED = 3, VARIANT_BALLOT = 41, VARIANT_BALLOT_FIRST = 43,
+             VARIANT_ANALYTIC = 44, VARIANT_DOPPLER_RECORD = 240 };
+struct VariantRow {
+    int variant;
+    bool settable;
+    const void *kernel;
+    int relaxed_waves;
+    const void *ieee;
+    int doppler;
+    bool window;
+    bool band_first;
+    int msaa;
+};
+#define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
+const VariantRow variant_table[] = {
+    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa
+    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0},
+    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47},
+    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46},
+    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46},
+    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46},
+    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0},
+    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0},
+    // 50 / 51 cull with the same regions but keep culling outside their window: a known gap (third item), kept as it is here
+    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0},
+    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0},
+    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0},
+    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0},
+    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0},
+    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0},
+    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0},
+    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0},
+    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0},
+    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0},
+    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0},
+};
+#undef RPT_KERNEL
+
+const VariantRow *variant_row(int v) {
+    for (const VariantRow &r : variant_table)
+        if (r.variant == v) return &r;
+    return nullptr;
+}
+
 int launch(rpt_ctx *ctx) {
     if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
     if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_set_params");
@@ -738,9 +746,6 @@ int launch(rpt_ctx *ctx) {
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
     a.links = (const int *)ctx->geo->dlinks.ptr;
     a.first_tris = (const rptd::DTri *)ctx->geo->dfirst.ptr;
-    a.root_grids = (const int *)ctx->geo->dgrids.ptr;       // (null and 0 in the product library)
-    a.seen_before = (const uint2 *)ctx->geo->dseen.ptr;     // (likewise)
-    a.grid_roots = ctx->geo->grid_roots;
     a.top_count = ctx->geo->top_count;
     a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
     a.objects = (const rpt_object *)ctx->objects.ptr;
@@ -798,88 +803,54 @@ int launch(rpt_ctx *ctx) {
     // Kernels 41 and 43 take the triangle test's 1 / det through rcp_exact when the scene's triangles allow it (exact_rcp_ok,
     // rpt_scene_exact_rcp: the same floats as the IEEE division there) and the IEEE division otherwise; 48 / 49 are 41 / 43 with the
     // IEEE division whatever the scene (the A/B arm).  rpt_last_variant reports 41 / 43 either way, rpt_last_exact_rcp which ran.
-    int v = ctx->variant == 0 ? (!ctx->has_mesh ? 44 : (ctx->latency_call || small_frame ? 43 : 41)) : ctx->variant;
-    if (v == 44 && ctx->has_mesh) v = 41;          // (asked for explicitly on a scene with meshes: the full kernel)
-    if (!ctx->geo->compact_ok && v != 44) v = 1;
+    int v = ctx->variant == VARIANT_DEFAULT ? (!ctx->has_mesh ? VARIANT_ANALYTIC : (ctx->latency_call || small_frame ? VARIANT_BALLOT_FIRST : VARIANT_BALLOT))
+                                            : ctx->variant;
+    if (v == VARIANT_ANALYTIC && ctx->has_mesh) v = VARIANT_BALLOT;          // (asked for explicitly on a scene with meshes: the full kernel)
+    if (!ctx->geo->compact_ok && v != VARIANT_ANALYTIC) v = VARIANT_REF_LAYOUT;
+    const VariantRow *row = variant_row(v);
+    if (row && !row->settable) row = nullptr;          // (the diagnostics library takes any number: the MSAA and Doppler forms are reached below only)
     // The per-object regions are PROVEN for the window |u| <= 2, |v| <= 1/2 (rpt_bounds_certify.hpp): a frame wider than 4 : 1 has
     // pixels outside it, and beyond 2^20 pixels a side a tile's 1.5-pixel skirt is no longer large against float rounding — such
     // frames are rendered by the un-culled kernel (same pixels, every object tested everywhere).
     const bool window_holds_frame = 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U && ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
-    if (!window_holds_frame && (v == 41 || v == 43 || v == 44 || v == 48 || v == 49)) v = 3;
-    const bool band_first = v == 43 || v == 49
-#ifdef RPT_DIAGNOSTICS
-                            || v == 143 || v == 2573 || (v >= 256 && v < 1000 && (v & 8))
-#endif
-        ;
+    if (!window_holds_frame && row && row->window) row = variant_row(v = VARIANT_UNCULLED);
     a.first_h = 0;
-    if (band_first) {      // whole-frame contexts only: a band that does not already start the frame, at most half of it
-        int ty0 = 0, ty1 = -1;
-        if (mesh_band(ctx, a.aspect, tiles, ty0, ty1) && ty0 > 0 && (ty1 - ty0 + 1) * 2 < tiles) { a.first_ty = ty0; a.first_h = ty1 - ty0 + 1; }
-    }
+    if (row && row->band_first) set_band_first(ctx, a, tiles);
     a.msaa = ctx->msaa;
     if (ctx->msaa > 1) {       // MSAASAMPLES > 1: the multi-sample form of the default kernel (46), or of the un-culled one (47)
-        if (v != 3 && v != 41 && v != 43 && v != 44) return fail(ctx, RPT_ERR_ARG, "rpt_set_msaa > 1 is implemented for the default kernels and variant 3 (derived octree layouts)");
-        v = v == 3 ? 47 : 46;
+        if (!row || !row->msaa) return fail(ctx, RPT_ERR_ARG, "rpt_set_msaa > 1 is implemented for the default kernels and variant 3 (derived octree layouts)");
+        row = variant_row(v = row->msaa);
     }
-    // Doppler on (rpt_set_doppler): every kernel chosen above goes to its twin (its number + 200), or to the debug kernel (240, un-culled)
-    // while the record hook is set.  The kernels without a twin refuse here, at the launch: the setting may precede rpt_set_variant.
+    // Doppler on (rpt_set_doppler): every kernel chosen above goes to its twin, or to the debug kernel (240, un-culled) while the record
+    // hook is set.  The kernels without a twin refuse here, at the launch: the setting may precede rpt_set_variant.
     float *const record = ctx->doppler ? (float *)(ctx->external_doppler ? ctx->external_doppler : (ctx->want_owned_doppler ? ctx->owned_doppler.ptr : nullptr)) : nullptr;
     if (ctx->doppler) {
         if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_doppler: MSAA > 1 has no Doppler kernel");
-        if (v != 3 && v != 41 && v != 43 && v != 44 && v != 48 && v != 49)
-            return fail(ctx, RPT_ERR_ARG, v == 1 ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
-                                                  : "rpt_set_doppler: this kernel variant has no Doppler twin");
-        v = record ? 240 : v + 200;
+        if (!row || !row->doppler)
+            return fail(ctx, RPT_ERR_ARG, v == VARIANT_REF_LAYOUT ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
+                                                                  : "rpt_set_doppler: this kernel variant has no Doppler twin");
+        row = variant_row(v = record ? VARIANT_DOPPLER_RECORD : row->doppler);
     }
     rptd::DopplerArgs da;         // (the twins' arguments: this frame's KernelArgs + the two Doppler fields)
     static_cast<rptd::KernelArgs &>(da) = a;
     da.doppler = ctx->doppler;
     da.debug_doppler = record;
-    ctx->doppler_recorded = false;
-    switch (v) {
-    case 203: hipLaunchKernelGGL(rptd::rpt_render_kernel_unculled_doppler_w5, grid1, dim3(64), 0, ctx->stream, da); break;
-    case 240: hipLaunchKernelGGL(rptd::rpt_render_kernel_doppler_record_w5, grid1, dim3(64), 0, ctx->stream, da); ctx->doppler_recorded = true; break;
-    case 241:
-        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
-        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
-        break;
-    case 243:
-        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
-        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da);
-        break;
-    case 244: hipLaunchKernelGGL(rptd::rpt_render_kernel_analytic_doppler_w8, grid1, dim3(64), 0, ctx->stream, da); break;
-    case 248: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da); break;
-    case 249: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_doppler_w5, grid1, dim3(64), 0, ctx->stream, da); break;
-    case 46: hipLaunchKernelGGL(rptd::rpt_render_kernel_msaa_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 47: hipLaunchKernelGGL(rptd::rpt_render_kernel_msaa_unculled_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 1: hipLaunchKernelGGL(rptd::rpt_render_kernel_v0, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 3: hipLaunchKernelGGL(rptd::rpt_render_kernel_unculled_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 41:
-        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_w5, grid1, dim3(64), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_w5, grid1, dim3(64), 0, ctx->stream, a);
-        break;
-    case 43:
-        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_w5, grid1, dim3(64), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_w5, grid1, dim3(64), 0, ctx->stream, a);
-        break;
-    case 48: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 49: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_first_ieee_w5, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 44: hipLaunchKernelGGL(rptd::rpt_render_kernel_analytic_w8, grid1, dim3(64), 0, ctx->stream, a); break;
-    case 50:
-    case 51:
-        if (rpt_launch_relaxed_kernel(v == 51 ? 6 : 5, &a, sizeof a, grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
-        break;
-    default:
+    ctx->doppler_recorded = record != nullptr;
+    if (!row) {
 #ifdef RPT_DIAGNOSTICS
         if (int rc = launch_diagnostic(ctx, a, grid, tiles, v)) return rc;
-        break;
 #else
         return fail(ctx, RPT_ERR_ARG, "unknown kernel variant");
 #endif
+    } else if (row->relaxed_waves) {
+        if (rpt_launch_relaxed_kernel(row->relaxed_waves, &a, sizeof a, grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
+    } else {
+        void *args[] = {ctx->doppler ? (void *)&da : (void *)&a};
+        (void)hipLaunchKernel(row->ieee && !ctx->geo->exact_rcp_ok ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     }
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = v;
-    ctx->last_exact_rcp = (v == 41 || v == 43 || v == 241 || v == 243) && ctx->geo->exact_rcp_ok;
+    ctx->last_exact_rcp = row && row->ieee && ctx->geo->exact_rcp_ok;
     return RPT_OK;
 }
 
@@ -1233,15 +1204,11 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
 
 int rpt_set_variant(rpt_ctx *ctx, int variant) {
     if (!ctx) return RPT_ERR_ARG;
-    switch (variant) {
-    case 0: case 1: case 3: case 41: case 43: case 44: case 48: case 49: case 50: case 51: break;
-    default:
-#ifdef RPT_DIAGNOSTICS
-        break;       // the diagnostics library knows many more (rpt_diag_kernels.hip.h); an unknown number fails at the launch
-#else
+#ifndef RPT_DIAGNOSTICS     /* the diagnostics library knows many more (rpt_diag_kernels.hip.h); an unknown number fails at the launch */
+    const VariantRow *row = variant_row(variant);
+    if (variant != VARIANT_DEFAULT && !(row && row->settable))
         return fail(ctx, RPT_ERR_ARG, "rpt_set_variant: unknown variant (measurement arms and instrumented kernels exist in librpt_hip_diag.so only)");
 #endif
-    }
     ctx->variant = variant;
     return RPT_OK;
 }
@@ -1305,7 +1272,7 @@ int rpt_verify_frame(rpt_ctx *ctx, unsigned long long *differing_pixels) {
     const int verified_variant = ctx->last_variant;      // what rpt_last_variant reports afterwards: the kernel that was CHECKED, not the un-culled one
     if (rc == RPT_OK) {
         ctx->external_plane = plane_b;
-        ctx->variant = 3;
+        ctx->variant = VARIANT_UNCULLED;
         rc = launch(ctx);
     }
     ctx->last_variant = verified_variant;
@@ -1600,9 +1567,6 @@ static void probe_kernel_args(rpt_ctx *ctx, rptd::KernelArgs &a) {
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
     a.links = (const int *)ctx->geo->dlinks.ptr;
     a.first_tris = (const rptd::DTri *)ctx->geo->dfirst.ptr;
-    a.root_grids = (const int *)ctx->geo->dgrids.ptr;       // (null and 0 in the product library)
-    a.seen_before = (const uint2 *)ctx->geo->dseen.ptr;
-    a.grid_roots = ctx->geo->grid_roots;
     a.top_count = ctx->geo->top_count;
     a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
     a.objects = (const rpt_object *)ctx->objects.ptr;
@@ -1645,31 +1609,6 @@ int rpt_probe_walk(rpt_ctx *ctx, int object_index, const float *host_rays, float
     }
     (void)hipFree(d_in);
     (void)hipFree(d_out);
-    return rc;
-}
-
-int rpt_probe_division(rpt_ctx *ctx, int mode, unsigned int seed, int blocks, int per_thread, unsigned long long counts_out[5], float *samples_out, int max_samples) {
-    if (!ctx || !counts_out || mode < 0 || mode > 3 || blocks <= 0 || blocks > 65536 || per_thread <= 0 || max_samples < 0) return RPT_ERR_ARG;
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned long long *d_counts = nullptr;
-    float *d_samples = nullptr;
-    RPT_HIP(ctx, hipMalloc((void **)&d_counts, 5 * sizeof(unsigned long long)));
-    if (max_samples > 0 && samples_out && hipMalloc((void **)&d_samples, sizeof(float) * 4 * (size_t)max_samples) != hipSuccess) {
-        (void)hipFree(d_counts);
-        return fail(ctx, RPT_ERR_NOMEM, "rpt_probe_division: hipMalloc");
-    }
-    int rc = RPT_OK;
-    if (hipMemsetAsync(d_counts, 0, 5 * sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = RPT_ERR_DEVICE;
-    if (!rc && d_samples && hipMemsetAsync(d_samples, 0, sizeof(float) * 4 * (size_t)max_samples, ctx->stream) != hipSuccess) rc = RPT_ERR_DEVICE;
-    if (!rc) {
-        hipLaunchKernelGGL(rptd::rpt_probe_division_kernel, dim3((unsigned int)blocks), dim3(256), 0, ctx->stream, mode, (uint32_t)seed, per_thread, d_counts, d_samples, max_samples);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-            hipMemcpy(counts_out, d_counts, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess ||
-            (d_samples && hipMemcpy(samples_out, d_samples, sizeof(float) * 4 * (size_t)max_samples, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = fail(ctx, RPT_ERR_DEVICE, "rpt_probe_division: device error");
-    }
-    (void)hipFree(d_counts);
-    if (d_samples) (void)hipFree(d_samples);
     return rc;
 }
 

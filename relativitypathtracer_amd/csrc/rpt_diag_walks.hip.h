@@ -442,7 +442,7 @@ RPT_DEV bool octree_walk_nbrec(const KernelArgs &a, const rpt_object &obj, int r
     return true;
 }
 
-// Variants 561 / 573: the A/B arms of the product's latency walk (octree_walk<true, true>: a leaf's first triangle record is
+// Variants 561 / 573: the A/B arms of the product's latency walk (octree_walk<true, ...>: a leaf's first triangle record is
 // addressable by the node's index and asked for with the node record) in natural order / mesh band first, against 273 / 285.
 // per-wave timeline (V == 4): start / end of the wave on the 100 MHz wall clock + the loop accounting of rpt_diag_lds
 struct DiagWaveClock { unsigned long long t_start; };
@@ -473,24 +473,13 @@ RPT_DEV void diag_wave_end(const KernelArgs &a, DiagWaveClock c) {
     }
 }
 
-template <int V> RPT_DEV constexpr bool diag_walk_selected() { return V == 2 || V == 4 || V == 5 || V == 10 || V == 120 || V == 121 || V == 122 || V == 123 || V >= 256; }
 template <int V>
 RPT_DEV bool diag_walk(const KernelArgs &a, const rpt_object &obj, int root, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
-    if (V == 561 || V == 573) return octree_walk<true, true, false, false, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);    // = kernel 43's walk
-    if (V == 605) return octree_walk<true, true, false, true, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);           // 573 WITH the root table (descend_from_root; lost)
-    if (V == 593) return octree_walk<false, false, true, true, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);          // kernel 41's walk WITH the root table (level)
-    if (V == 589) return octree_walk<true, true, true, false, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);                // 573 WITH the packed leaf count (lost: r03_packed_count_ab.txt)
-    if (V == 625) return octree_walk<false, false, true, false, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);    // kernel 41's walk with the triangle id read with EVERY record (before LATE_ID), natural order
-    if (V == 637) return octree_walk<true, true, false, false, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);     // kernel 43's walk likewise, mesh band first
-    if (V == 641) return octree_walk<false, false, true, false, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);     // kernel 41's walk; the LANES of the wave follow the Z curve (render_pixel_body)
-    if (V == 653) return octree_walk<true, true, false, false, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // kernel 43's walk, likewise, mesh band first
-    if (V == 673) return octree_walk<false, false, true, false, true, 2>(a, obj, root, newRay, world_origin, world_dirlen, hit);        // likewise with ONE lane's vector loads + readfirstlane (UNIFORM = 2)
-    if (V == 657) return octree_walk<false, false, true, false, true, 1>(a, obj, root, newRay, world_origin, world_dirlen, hit);     // kernel 41's walk + UNIFORM (scalar loads where the wave stands in one node)
-    if (V == 669) return octree_walk<true, true, false, false, true, 1>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // kernel 43's walk + UNIFORM, mesh band first
-    if (V == 705) return octree_walk<false, false, true, false, true, 0, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // kernel 41's walk + DEDUP: list entries tested in the previous leaf are neither loaded nor tested
-    if (V == 717) return octree_walk<true, true, false, false, true, 0, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);       // kernel 43's walk + DEDUP (records are prefetched: the arithmetic only), mesh band first
-    if (V == 689) return octree_walk<false, false, true, false, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);     // kernel 41's walk launched FOUR waves per workgroup (a 32 x 8 strip), as every measurement arm is and the product was
-    if (V == 701) return octree_walk<true, true, false, false, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // kernel 43's walk, likewise, mesh band first
+    if (V == 561 || V == 573) return octree_walk<true, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);       // = kernel 49's walk
+    if (V == 641) return octree_walk<false, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);     // kernel 48's walk; the LANES of the wave follow the Z curve (render_pixel_body)
+    if (V == 653) return octree_walk<true, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // kernel 49's walk, likewise, mesh band first
+    if (V == 689) return octree_walk<false, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);     // kernel 48's walk launched FOUR waves per workgroup (a 32 x 8 strip), as every measurement arm is and the product was
+    if (V == 701) return octree_walk<true, false>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // kernel 49's walk, likewise, mesh band first
     if (V == 621) return octree_walk_nbrec<true, true>(a, obj, root, newRay, world_origin, world_dirlen, hit);      // 541 + a leaf's first triangle with its node: a whole step's data in one round trip
     if (V == 529 || V == 541) return octree_walk_nbrec<V == 541>(a, obj, root, newRay, world_origin, world_dirlen, hit);
     if (V >= 256) return octree_walk_x<((V == 785 ? 273 : V) & 247)>(a, obj, root, newRay, world_origin, world_dirlen, hit);

@@ -79,7 +79,7 @@ static_assert(sizeof(DObj) == 128, "DObj");
 struct KernelArgs {
     // ---- the first 64 bytes are everything a wave that hits nothing needs (its cull and its store): one scalar load at the top
     // of the kernel instead of one per place of first use (each is a dependent round trip in a wave that lives a microsecond)
-    // per-object image-plane rectangles (rpt_screen_bounds.hpp), tested lane-parallel by each wavefront (V >= 20)
+    // per-object image-plane rectangles (rpt_screen_bounds.hpp), tested lane-parallel by each wavefront (culled kernels)
     const float4 *rects;                     // [2 * object_count] per object: u0, v0, u1, v1 on the plane z = 0.5, then the
                                              // diagonal slabs p_lo, p_hi (u + v) and m_lo, m_hi (u - v)
     rpt_pixel *out16;        // 16 B/pixel framebuffer (full frame addressing) or null
@@ -95,7 +95,7 @@ struct KernelArgs {
     int first_tile, tile_step;      // local tile t holds global tile (t >> run_log2) * tile_step + first_tile + (t & (run - 1))
     int run_log2;                   // run = 1 << run_log2 consecutive tiles per period of tile_step tiles (rpt_set_tile_pattern)
     int interval;
-    // dispatch order (V == 23): the strips [first_sx, first_sx + first_w) x [first_ty, first_ty + first_h) — where the meshes
+    // dispatch order (band_first kernels): the strips [first_sx, first_sx + first_w) x [first_ty, first_ty + first_h) — where the meshes
     // are, i.e. where the frame's longest waves live — are handed out FIRST, the rest in natural order; first_w = 0: off
     int first_sx, first_ty, first_w, first_h;
     int msaa;                       // MSAASAMPLES of opencl_kernel.cl:7 when it is not 1 (rpt_set_msaa; the kernels of render_pixel_body_msaa only)
@@ -111,9 +111,7 @@ struct KernelArgs {
     const DObj *dobjs;
     const int *links;               // DNode::link of every node again, 4 B apart: what a descent reads per level
     const DTri *first_tris;         // per node: the first triangle record of its leaf list again, addressable by the NODE's index
-    const uint2 *seen_before;       // (diagnostics library: arms 705 / 717) per (node, entry face): {the leaf across that face, bit mask of this leaf's first 32 list entries that are also in THAT leaf's list}; product: null
-    const int *root_grids;          // (diagnostics library: arms 593 / 605) per octree root, 16^3 cells -> node | level << 24 | leaf << 28; product: null
-    int grid_roots;
+    alignas(8) char reserved[20];   // unused (held two tables of removed measurement arms): keeps the fields below, and the kernels' code, in place
     int top_count;                  // nodes [0, top_count) are the forest's top levels (whole levels, <= RPT_TOP_MAX)
     // persistent kernels (rpt_persistent.hip.h): the band of tile rows that holds the meshes (first_ty, first_h above) is
     // claimed tile by tile from per-queue counters, the other rows are dealt statically in runs of RPT_SKY_RUN tiles
@@ -233,46 +231,6 @@ RPT_DEV int getOppositeBoxSide(const ExitPlan &p, f3 &uv) {
     uv = uv + p.scaledDir * t;
     return side;
 }
-
-// EXPERIMENT, not in the product build (RPT_PACKED_EXIT_FACES=1 turns it on in the throughput walk): the same plan with the three
-// candidate exit faces in ONE register, picked by a shift that depends on the step.  Written as above, the compiler hoists 3 - sx,
-// 5 - sy, 1 - sz out of the leaf loop as three registers; in kernel 41 (96 registers for five waves) two of them are spilled and
-// reloaded inside the loop.  The packed form removes those reloads (scratch 12 -> 8 B, the rest outside the loops) for one
-// instruction more per step.  Measured twice, A/B/A/B/A/B against the library of record: -1.5 / -1.7 / -0.7 % in flight in one
-// build, +0.2 / -0.7 / -1.6 % in the next: inside the run-to-run spread of the bench line, so the record stays as it is
-// (profiles/r04_exitplan_ab.txt).
-#ifndef RPT_PACKED_EXIT_FACES
-#define RPT_PACKED_EXIT_FACES 0
-#endif
-struct PackedExitPlan { f3 scaledDir, inv_dir, far; int sides; };
-
-RPT_DEV PackedExitPlan makePackedExitPlan(f3 scaledDir) {
-    PackedExitPlan p;
-    p.scaledDir = scaledDir;
-    p.inv_dir = mk3(1.0f / scaledDir.x, 1.0f / scaledDir.y, 1.0f / scaledDir.z);
-    const int sx = p.inv_dir.x < 0, sy = p.inv_dir.y < 0, sz = p.inv_dir.z < 0;
-    p.far = mk3((float)(1 - sx), (float)(1 - sy), (float)(1 - sz));
-    p.sides = (3 - sx) | ((5 - sy) << 8) | ((1 - sz) << 16);
-    return p;
-}
-
-RPT_DEV int getOppositeBoxSide(const PackedExitPlan &p, f3 &uv) {
-    const float dx = (p.far.x - uv.x) * p.inv_dir.x;
-    const float dy = (p.far.y - uv.y) * p.inv_dir.y;
-    const float dz = (p.far.z - uv.z) * p.inv_dir.z;
-    float t;
-    int shift;
-    if (dx < dy) {
-        if (dx < dz) { t = dx; shift = 0; } else { t = dz; shift = 16; }
-    } else {
-        if (dy < dz) { t = dy; shift = 8; } else { t = dz; shift = 16; }
-    }
-    uv = uv + p.scaledDir * t;
-    return (p.sides >> shift) & 0xff;
-}
-
-template <bool PACKED> struct ExitPlanOf { typedef ExitPlan type; static RPT_DEV ExitPlan make(f3 d) { return makeExitPlan(d); } };
-template <> struct ExitPlanOf<true> { typedef PackedExitPlan type; static RPT_DEV PackedExitPlan make(f3 d) { return makePackedExitPlan(d); } };
 
 // The same step for the common case 0 <= uv < 1.5 on every axis (+0 included, -0/NaN/negative excluded by
 // the unsigned compare on the bit patterns): there round(c) is (c >= 0.5), min(c, 1-eps) keeps that bit, and
@@ -457,7 +415,7 @@ RPT_DEV bool octree_core_ref(const KernelArgs &a, const rpt_object &obj, const R
 //     level is spent on finding that out;
 //   * the exit face of a leaf does not depend on its triangles (getOppositeBoxSide works on the ray and the entry point alone):
 //     it is found BEFORE the triangle loop, and the neighbour's index travels while the triangles are tested;
-//   * PIPELINE + FIRST (kernel 43: the blocking call, whose frame is as long as its longest wave, and small frames in flight):
+//   * the latency form (LATENCY; kernel 43: the blocking call, whose frame is as long as its longest wave, and small frames in flight):
 //     triangle records are asked for one iteration ahead, and a leaf's first record together with its node record
 //     (load_first_tri).  Ten more live registers: 44 B of scratch at five waves per SIMD, worth it where frames wait for
 //     latency (bunny 4K one frame at a time 0.196 -> 0.186 ms, 1080p 0.166 -> 0.151), not where the chip is full of walks
@@ -466,7 +424,7 @@ RPT_DEV bool octree_core_ref(const KernelArgs &a, const rpt_object &obj, const R
 // one at a time; zero scratch instead of 12 B.  What was tried on top and lost is in the diagnostics build (rpt_diag_walks.hip.h).
 // hi.w of a node record = leafBegin | min(leafCount, 255) << 24 (build_derived_geometry): the count of a leaf's list travels with the
 // box, so a node visit of the throughput walk is two 16-B loads, not three instructions; a list of 255 or more reads the full count
-// from its own field, and so does the latency walk always (PACKED_COUNT = false: see mesh_walk).
+// from its own field, and so does the latency walk always (PACKED_COUNT = false: see octree_walk).
 #define RPT_NODE_BEGIN_MASK 0x00ffffff
 struct NodeRec { v4f lo, hi; int count; };
 template <bool PACKED_COUNT = true>
@@ -547,114 +505,18 @@ RPT_DEV int descend_to_leaf(const KernelArgs &a, int link, f3 &uv) {
     return idx;
 }
 
-// PIPELINE: triangle records one iteration ahead.  FIRST (with PIPELINE): the first record of a leaf comes with its node record.
-// MEASUREMENT ARM (ROOT_GRID; diagnostics library, arms 593 / 605; exact, and not adopted: profiles/r03_root_grid_ab.txt — the link words of
-// an octree's top levels are a handful of hot addresses, a 16-KB table read per lane is not).
-// The descent from a ROOT (opencl_kernel.cl:256-261 at the start of a walk) in one lookup.  For 0 <= c < 1.5 the child step of a
-// component is a bit extraction (octree_child_step_fast): with m = min(c, 1 - eps), the child bit at level k is bit k of m's binary
-// fraction and the re-normalised coordinate after L levels is frac(2^L m) — every product and difference exact.  A component in
-// (-2^-10, 0) — an entry point a rounding below its face — selects child 0 at every level (round(c) = -0) and is doubled per level
-// (2 fmod(c, 0.5) = 2 c, exact): truncation gives both.  So the cell (trunc(16 m.x), trunc(16 m.y), trunc(16 m.z)) of a 16^3 table
-// names the node four levels down, or the leaf above that level with the level it lives on, and uv leaves as L single child steps
-// would leave it; deeper trees continue from there.  Any other component (NaN, >= 1.5, more negative) takes the serial descent.
-#define RPT_GRID_LEVELS 4
-#define RPT_GRID_CELLS 4096
-#ifndef RPT_DIAGNOSTICS
-RPT_DEV int descend_from_root(const KernelArgs &a, int, int link, f3 &uv) { return descend_to_leaf(a, link, uv); }     // (the product library has no tables)
-#else
-RPT_DEV int descend_from_root(const KernelArgs &a, int root, int link, f3 &uv) {
-    const float lo = -0x1p-10f;
-    const bool ok = (uv.x > lo) & (uv.x < 1.5f) & (uv.y > lo) & (uv.y < 1.5f) & (uv.z > lo) & (uv.z < 1.5f) & (root < a.grid_roots);
-    if (!ok) return descend_to_leaf(a, link, uv);
-    const float top = 1.0f - RPT_EPSILON;
-    const float mx = top < uv.x ? top : uv.x, my = top < uv.y ? top : uv.y, mz = top < uv.z ? top : uv.z;
-    const int cx = (int)(mx * 16.0f), cy = (int)(my * 16.0f), cz = (int)(mz * 16.0f);
-    const int e = a.root_grids[root * RPT_GRID_CELLS + ((cx * 16 + cy) * 16 + cz)];
-    const float s = (float)(1 << ((e >> 24) & 7));
-    const float x = mx * s, y = my * s, z = mz * s;
-    uv.x = x - (float)(int)x;
-    uv.y = y - (float)(int)y;
-    uv.z = z - (float)(int)z;
-    int node = e & RPT_LINK_CHILD_MASK;
-    if (!((e >> 28) & 1)) node = descend_to_leaf(a, a.links[node], uv);       // an inner node four levels down: the tree goes deeper here
-    return node;
-}
-
-#endif
-
-// MEASUREMENT ARMS (UNIFORM = 1 / 2; diagnostics library, arms 657 / 669 / 673; bit-identical, 3-16 % slower: profiles/r03_td_bound.txt).
-#ifndef RPT_DIAGNOSTICS
-template <bool PACKED_COUNT, int UNIFORM>
-RPT_DEV NodeRec load_node_rec_u(const KernelArgs &a, int curr, bool &uni) { uni = false; return load_node_rec<PACKED_COUNT>(a, curr); }
-template <bool LATE_ID>
-RPT_DEV TriRec load_tri_rec_leader(const KernelArgs &a, int k) { return load_tri_rec<LATE_ID>(a, k); }
-#else
-// UNIFORM = 1: where every active lane of the wave stands in the SAME node (bunny 4K: 42 % of the wave's leaf steps, shadows
-// 74 %: profiles/r02_divergence.txt) the node record and the leaf's triangle records are read ONCE for the wave — the address is made
-// wave-uniform with readfirstlane, so the loads go through the scalar cache into SGPRs instead of 64 times through the vector L1's
-// return path — and the arithmetic takes them as scalar operands.  Same operations on the same values.
-// UNIFORM = 1: through the scalar cache (above).  UNIFORM = 2: ONE lane of the wave makes the vector loads (an L1 hit as before, one
-// lane's worth of work for the return path instead of the wave's) and readfirstlane hands the dwords to everybody as scalars.
-RPT_DEV float bcast_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-RPT_DEV v4f bcast_v4(v4f v) { v4f r; r.x = bcast_f(v.x); r.y = bcast_f(v.y); r.z = bcast_f(v.z); r.w = bcast_f(v.w); return r; }
-template <bool PACKED_COUNT, int UNIFORM>
-RPT_DEV NodeRec load_node_rec_u(const KernelArgs &a, int curr, bool &uni) {
-    uni = false;
-    if (UNIFORM) {
-        const int u = __builtin_amdgcn_readfirstlane(curr);
-        uni = __ballot(curr != u) == 0ull;
-        if (uni && UNIFORM == 1) return load_node_rec<PACKED_COUNT>(a, u);
-        if (uni) {
-            const bool leader = (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(true)) - 1;
-            NodeRec r;
-            r.lo = r.hi = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-            r.count = 0;
-            if (leader) r = load_node_rec<PACKED_COUNT>(a, curr);
-            r.lo = bcast_v4(r.lo);
-            r.hi = bcast_v4(r.hi);
-            r.count = __builtin_amdgcn_readfirstlane(r.count);
-            return r;
-        }
-    }
-    return load_node_rec<PACKED_COUNT>(a, curr);
-}
-template <bool LATE_ID>
-RPT_DEV TriRec load_tri_rec_leader(const KernelArgs &a, int k) {
-    const bool leader = (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(true)) - 1;
-    TriRec r;
-    r.t0 = r.t1 = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    r.e2z = 0.0f;
-    r.tri = 0;
-    if (leader) r = load_tri_rec<LATE_ID>(a, k);
-    r.t0 = bcast_v4(r.t0);
-    r.t1 = bcast_v4(r.t1);
-    r.e2z = bcast_f(r.e2z);
-    r.tri = __builtin_amdgcn_readfirstlane(r.tri);
-    return r;
-}
-
-#endif
-
-// DEDUP (measurement arms 705 / 717): a triangle that overlaps k leaves is in all k lists, and one walk tests it up
-// to k times (23.8 % of the bunny's triangle tests, 28.4 % of the pear's: profiles/r04_repeated_triangle_tests.txt).  A repeat can
-// never change the walk's state — the test's outcome depends on the ray and the triangle only, and the update rule
-// 0 <= dist < hit.dist (opencl_kernel.cl:270) with a non-increasing hit.dist makes a second application a no-op (accepted before:
-// now dist == hit.dist or larger, not "<"; rejected before: rejected again; NaN: false both times).  Skipped are list entries whose
-// triangle is ALSO IN THE LIST OF THE LEAF THIS WALK VISITED IMMEDIATELY BEFORE: the host marks, per leaf and face, which of the
-// leaf's first 32 entries are in the list of the leaf across that face (seen_before[node * 6 + face] = {that leaf, mask}); the lane
-// uses the mask of the face it entered through (the previous step's exit face, flipped) only if the leaf recorded there IS the
-// leaf it came from — an integer compare, nothing geometric is assumed — and every entry of that leaf's list was either tested
-// in the previous step or skipped there for the same reason (induction over the steps).  The record's address is known with
-// the node's: its load travels with the node record and does not lengthen the chain.
+// The two forms the kernels use; both read the triangle's id late (load_tri_rec<true>: the walk remembers the RECORD it hit).
+//   throughput (LATENCY = false; kernels 41 / 48): one record at a time, the leaf count packed with the box;
+//   latency (LATENCY = true; kernels 43 / 49): records an iteration ahead, a leaf's first record with its node record, the count from
+//   its own field (the packed count pays in the throughput walk — one instruction less per node visit, -0.5...-1 % — and costs the
+//   latency walk 2-4.5 %, whose count then sits behind a shift and a compare instead of arriving beside the box:
+//   profiles/r03_packed_count_ab.txt).
 // EXACT_RCP: the triangle test's 1 / det without the IEEE scaling (intersect_triangle_edges); the host selects it per scene.
-template <bool PIPELINE, bool FIRST, bool PACKED_COUNT = true, bool ROOT_GRID = false, bool LATE_ID = false, int UNIFORM = 0, bool DEDUP = false,
-          bool EXACT_RCP = false>
+template <bool LATENCY, bool EXACT_RCP>
 RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, const Ray &newRay, f3 world_origin,
                          float world_dirlen, Hit &hit) {
     int curr = root;
-    int prev_leaf = -1, entry_face = 0;
-    bool uni = false;
-    NodeRec rec = load_node_rec<PACKED_COUNT>(a, curr);
+    NodeRec rec = load_node_rec<!LATENCY>(a, curr);
     f2 d;
     int closeSide, farSide;
     f3 nmin = mk3(rec.lo.x, rec.lo.y, rec.lo.z), nmax = mk3(rec.hi.x, rec.hi.y, rec.hi.z);
@@ -663,73 +525,57 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
     if (d.x < 0) {   // ray starts inside the root: descend to the leaf holding the origin
         uv = (newRay.origin - nmin) / (nmax - nmin);
         if (__float_as_int(rec.lo.w) != -1) {
-            curr = ROOT_GRID ? descend_from_root(a, root, __float_as_int(rec.lo.w), uv) : descend_to_leaf(a, __float_as_int(rec.lo.w), uv);
-            rec = load_node_rec_u<PACKED_COUNT, UNIFORM>(a, curr, uni);
+            curr = descend_to_leaf(a, __float_as_int(rec.lo.w), uv);
+            rec = load_node_rec<!LATENCY>(a, curr);
         }
         nmin = mk3(rec.lo.x, rec.lo.y, rec.lo.z);
         nmax = mk3(rec.hi.x, rec.hi.y, rec.hi.z);
         if (!intersect_AABB(nmin, nmax, newRay, d, closeSide, farSide)) return false;
         uv = newRay.origin + newRay.dir * d.x;
     }
-    const typename ExitPlanOf<PACKED_COUNT && RPT_PACKED_EXIT_FACES>::type plan = ExitPlanOf<PACKED_COUNT && RPT_PACKED_EXIT_FACES>::make(normalize(newRay.dir / (nmax - nmin)));
+    const ExitPlan plan = makeExitPlan(normalize(newRay.dir / (nmax - nmin)));
     bool didHit = false;
     int hitTri = 0;
     TriRec first;
-    if (FIRST) first = load_first_tri<LATE_ID>(a, curr);
+    if (LATENCY) first = load_first_tri<true>(a, curr);
     for (int steps = 1; steps <= RPT_MAX_LEAF_STEPS; steps++) {
         nmin = mk3(rec.lo.x, rec.lo.y, rec.lo.z);
         nmax = mk3(rec.hi.x, rec.hi.y, rec.hi.z);
         uv = (uv - nmin) / (nmax - nmin);
         if (__float_as_int(rec.lo.w) != -1) {
             // (only a walk's first step can stand on a root: nobody's neighbour link points at one)
-            curr = (ROOT_GRID && steps == 1) ? descend_from_root(a, root, __float_as_int(rec.lo.w), uv) : descend_to_leaf(a, __float_as_int(rec.lo.w), uv);
-            rec = load_node_rec_u<PACKED_COUNT, UNIFORM>(a, curr, uni);
-            if (FIRST) first = load_first_tri<LATE_ID>(a, curr);
+            curr = descend_to_leaf(a, __float_as_int(rec.lo.w), uv);
+            rec = load_node_rec<!LATENCY>(a, curr);
+            if (LATENCY) first = load_first_tri<true>(a, curr);
             nmin = mk3(rec.lo.x, rec.lo.y, rec.lo.z);
             nmax = mk3(rec.hi.x, rec.hi.y, rec.hi.z);
         }
         int i = __float_as_int(rec.hi.w) & RPT_NODE_BEGIN_MASK;
         const int trisEnd = i + rec.count;
-        unsigned int seen = 0u;
-        if (DEDUP && prev_leaf >= 0) {
-            const uint2 e = a.seen_before[(size_t)curr * 6 + entry_face];
-            seen = (int)e.x == prev_leaf ? e.y : 0u;
-        }
-        const int listBegin = i;
         farSide = getOppositeBoxSide(plan, uv);             // the way out, before the triangles
         const int next = a.dnodes[curr].nb[farSide];
-        if (UNIFORM && uni) {          // one list for the whole wave: records through the scalar cache
-            const int ue = __builtin_amdgcn_readfirstlane(trisEnd);
-            for (int k = __builtin_amdgcn_readfirstlane(i); k < ue; k++)
-                test_tri_rec<EXACT_RCP>(UNIFORM == 2 ? load_tri_rec_leader<LATE_ID>(a, k) : load_tri_rec<LATE_ID>(a, k), newRay, hit, hitTri, didHit);
-        } else if (PIPELINE) {
+        if (LATENCY) {
             if (i < trisEnd) {
-                TriRec cur = FIRST ? first : load_tri_rec<LATE_ID>(a, i);
+                TriRec cur = first;
                 for (; i < trisEnd; i++) {
                     TriRec nxt = cur;
-                    if (i + 1 < trisEnd) nxt = load_tri_rec<LATE_ID>(a, i + 1);
-                    if (LATE_ID) cur.tri = i;
-                    if (!(DEDUP && i - listBegin < 32 && ((seen >> (i - listBegin)) & 1u))) test_tri_rec<EXACT_RCP>(cur, newRay, hit, hitTri, didHit);     // (the record was asked for an iteration ago: only the arithmetic is saved here)
+                    if (i + 1 < trisEnd) nxt = load_tri_rec<true>(a, i + 1);
+                    cur.tri = i;
+                    test_tri_rec<EXACT_RCP>(cur, newRay, hit, hitTri, didHit);     // (the record was asked for an iteration ago: only the arithmetic is saved here)
                     cur = nxt;
                 }
             }
-        } else if (DEDUP) {
-            for (; i < trisEnd; i++) {
-                if (i - listBegin < 32 && ((seen >> (i - listBegin)) & 1u)) continue;                    // tested in the previous leaf: neither loaded nor tested
-                test_tri_rec<EXACT_RCP>(load_tri_rec<LATE_ID>(a, i), newRay, hit, hitTri, didHit);
-            }
         } else {
-            for (; i < trisEnd; i++) test_tri_rec<EXACT_RCP>(load_tri_rec<LATE_ID>(a, i), newRay, hit, hitTri, didHit);
+            for (; i < trisEnd; i++) test_tri_rec<EXACT_RCP>(load_tri_rec<true>(a, i), newRay, hit, hitTri, didHit);
         }
         uv = nmin + uv * (nmax - nmin);
         if (exit_is_past_hit(uv - newRay.origin, hit.dist, didHit) || next == -1) break;
-        if (DEDUP) { prev_leaf = curr; entry_face = farSide ^ 1; }      // sides 0/1 = -z/+z, 2/3 = -x/+x, 4/5 = -y/+y: the face entered is the face left, flipped
         curr = next;
-        rec = load_node_rec_u<PACKED_COUNT, UNIFORM>(a, curr, uni);
-        if (FIRST) first = load_first_tri<LATE_ID>(a, curr);
+        rec = load_node_rec<!LATENCY>(a, curr);
+        if (LATENCY) first = load_first_tri<true>(a, curr);
     }
     if (!didHit) return false;
-    if (LATE_ID) hitTri = a.dtris[hitTri].tri;
+    hitTri = a.dtris[hitTri].tri;
     mesh_hit_finish(a, obj, newRay.origin, newRay.dir, hitTri, world_origin, world_dirlen, hit);
     return true;
 }
@@ -740,21 +586,42 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
 namespace rptd {
 #endif
 
-// Which walk a kernel variant uses.  V = 0: the reference's layouts; V = 23 (kernel 43: the blocking call, and frames in flight
-// too small to fill the chip with walks): the latency form — records an iteration ahead, a leaf's first record with its node.
-// V = 21 / 25: the walks of 20 / 23 with the triangle test's exact reciprocal (EXACT_RCP), for scenes inside its domain.
-template <int V> RPT_DEV constexpr bool latency_walk() { return V == 23 || V == 25; }
-template <int V> RPT_DEV constexpr bool exact_rcp_walk() { return V == 21 || V == 25; }
-template <int V>
+// ---- what a render kernel is: its policy, a type of static constexpr members that render_pixel_body and everything it calls read.
+// KernelPolicy holds the defaults (kernel 48); each product kernel below derives its own; the diagnostics build adds DiagPolicy<N>
+// (rpt_diag_kernels.hip.h).  rpt_api.hip's table of variants reads band_first from the same types.
+enum class Walk {
+    reference,       // octree_core_ref on the reference's layouts (any valid octree)
+    none,            // no octree walk compiled in: for Object[]s without a mesh
+    throughput,      // octree_walk<false, ...>: one record at a time, the packed leaf count
+    latency,         // octree_walk<true, ...>: records an iteration ahead, a leaf's first record with its node record
+};
+struct KernelPolicy {
+    static constexpr Walk walk = Walk::throughput;
+    static constexpr bool exact_rcp = false;     // the triangle test's 1 / det through rcp_exact (the host picks it per scene)
+    static constexpr bool culled = true;         // the wave's object mask (wave_object_mask) and the shadow-segment culls
+    static constexpr bool band_first = false;    // the band of tile rows that holds the meshes is dispatched first (KernelArgs::first_h)
+    static constexpr bool one_wave = true;       // one wave (an 8x8 tile) per workgroup, not four (a 32x8 strip)
+    static constexpr bool doppler = false;       // the Doppler twin (rpt_set_doppler; the arguments are a DopplerArgs)
+    static constexpr bool drec = false;          // ... that also writes the per-pixel Doppler record (the debug kernel only)
+    static constexpr int diag = 0;               // the measurement arm's number (diagnostics build only); 0 in every product policy
+};
+struct RefLayout : KernelPolicy { static constexpr Walk walk = Walk::reference; static constexpr bool culled = false; };        // 1
+struct Unculled : KernelPolicy { static constexpr bool culled = false; };                                                       // 3, 47
+struct Ballot : KernelPolicy {};                                                                                                // 48, 46, 50, 51
+struct BallotExact : Ballot { static constexpr bool exact_rcp = true; };                                                        // 41
+struct BallotFirst : KernelPolicy { static constexpr Walk walk = Walk::latency; static constexpr bool band_first = true; };     // 49
+struct BallotFirstExact : BallotFirst { static constexpr bool exact_rcp = true; };                                              // 43
+struct Analytic : KernelPolicy { static constexpr Walk walk = Walk::none; };                                                    // 44
+template <class P> struct DopplerTwin : P { static constexpr bool doppler = true; };                                            // 2xx
+struct DopplerRecorded : DopplerTwin<Unculled> { static constexpr bool drec = true; };                                          // 240
+
+template <class P>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
 #ifdef RPT_DIAGNOSTICS
-    if (diag_walk_selected<V>()) return diag_walk<V>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
+    if constexpr (P::diag != 0) return diag_walk<P::diag>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
 #endif
-    if (V == 0) return octree_core_ref(a, obj, newRay, world_origin, world_dirlen, hit);
-    // (the packed leaf count pays in the throughput walk — one instruction less per node visit, -0.5...-1 % — and costs the latency
-    // walk 2-4.5 %, whose count then sits behind a shift and a compare instead of arriving beside the box: profiles/r03_packed_count_ab.txt)
-    return octree_walk<latency_walk<V>(), latency_walk<V>(), !latency_walk<V>(), false, true, 0, false, exact_rcp_walk<V>()>(a, obj, a.dobjs[i].root, newRay, world_origin,
-                                                                                                                      world_dirlen, hit);
+    if (P::walk == Walk::reference) return octree_core_ref(a, obj, newRay, world_origin, world_dirlen, hit);
+    return octree_walk<P::walk == Walk::latency, P::exact_rcp>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
 }
 
 RPT_DEV float max3(f3 v) { return cl_max(cl_max(v.x, v.y), v.z); }   // opencl_kernel.cl:310
@@ -907,21 +774,21 @@ RPT_DEV bool mesh_ray_misses_root(const DObj &pre, f3 origin, f3 dir) {
 }
 
 // One object against one ray given as a 4-D event + 4-D direction in the object's rest frame
-// (the general form: shadow rays, and primary rays of the V = 0 kernel).
+// (the general form: shadow rays, and primary rays of the RefLayout kernel).
 // seg_max > 0 (shadow rays): the caller only asks whether the object is hit at a distance below seg_max (sample_light:
 // dist < lightDist); if no lane of the wave can get "yes" (unit_segment_apart / mesh_segment_apart above, __ballot), the
 // normalisation, its three IEEE divisions and the intersector are skipped for the whole wave.
 // (Measured also: the slab test with v_rcp_f32 as a second stage, and the same for mesh roots as a ray test: no
 // further gain on any scene — three quarter-rate reciprocals cost what they save)
-template <int V>
+template <class P>
 RPT_DEV bool intersect_object(const KernelArgs &a, int i, f4 origin4, f4 dir4, Hit &hit, float seg_max = -1.0f) {
     const rpt_object &obj = a.objects[i];
     const f3 origin = transformPoint(obj.InvM, yzw(origin4));
     f3 dir = transformDirection(obj.InvM, yzw(dir4));
-    if (V >= 20 && seg_max > 0.0f && obj.type != RPT_MESH) {
+    if (P::culled && seg_max > 0.0f && obj.type != RPT_MESH) {
         if (__ballot(!unit_segment_apart(origin, dir, seg_max)) == 0ull) return false;
     }
-    if (V >= 20 && seg_max > 0.0f && obj.type == RPT_MESH && a.dobjs[i].mh[0] >= 0.0f) {
+    if (P::culled && seg_max > 0.0f && obj.type == RPT_MESH && a.dobjs[i].mh[0] >= 0.0f) {
         const DObj &pre = a.dobjs[i];
         bool idle = mesh_ray_misses_root(pre, origin, dir);
         if (pre.mslope >= 0.0f) idle = idle | mesh_segment_apart(pre, yzw(origin4), origin, dir, seg_max);      // (wave-uniform branch)
@@ -937,21 +804,21 @@ RPT_DEV bool intersect_object(const KernelArgs &a, int i, f4 origin4, f4 dir4, H
     case RPT_CUBE:
         return cube_core(obj, origin, cube_winding(origin), dir, scale, hit);
     case RPT_MESH: {
-        if (V == 24) return false;      // the analytic-only kernel is launched for scenes without mesh objects only
+        if (P::walk == Walk::none) return false;      // the analytic-only kernel is launched for scenes without mesh objects only
         Ray newRay;
         newRay.origin = origin;
         newRay.dir = dir;
-        return mesh_walk<V>(a, obj, i, newRay, yzw(origin4), length(yzw(dir4)), hit);
+        return mesh_walk<P>(a, obj, i, newRay, yzw(origin4), length(yzw(dir4)), hit);
     }
     default:
         return false;
     }
 }
 
-// Primary rays of the V >= 1 kernels: the object-space origin and what depends on it alone come
+// Primary rays of the kernels on the derived layouts: the object-space origin and what depends on it alone come
 // from the per-frame DObj record; only rows 1..3 of Lorentz * (interval, d) are formed (row 0, the
 // time component, is needed for the flash test of the final hit only).
-template <int V>
+template <class P>
 RPT_DEV bool intersect_object_primary(const KernelArgs &a, int i, f4 rayDir, Hit &hit) {
     const rpt_object &obj = a.objects[i];
     const DObj &pre = a.dobjs[i];
@@ -966,12 +833,12 @@ RPT_DEV bool intersect_object_primary(const KernelArgs &a, int i, f4 rayDir, Hit
     case RPT_CUBE:
         return cube_core(obj, origin, pre.winding, dir, scale, hit);
     case RPT_MESH: {
-        if (V == 24) return false;
+        if (P::walk == Walk::none) return false;
         Ray newRay;
         newRay.origin = origin;
         newRay.dir = dir;
         const f3 cam3 = mk3(obj.stationaryCam.y, obj.stationaryCam.z, obj.stationaryCam.w);
-        return mesh_walk<V>(a, obj, i, newRay, cam3, length(d3), hit);
+        return mesh_walk<P>(a, obj, i, newRay, cam3, length(d3), hit);
     }
     default:
         return false;
@@ -1014,7 +881,7 @@ RPT_DEV f3 sample_texture(const KernelArgs &a, const rpt_object &ho, f2 huv) {
 }
 
 // opencl_kernel.cl:488-545: true when something other than the light blocks the segment
-template <int V>
+template <class P>
 RPT_DEV bool sample_light_occluded(const KernelArgs &a, f4 origin4, f4 dir4, float lightDist, int lightIndex) {
     const f3 nd = normalize(yzw(dir4));
     const f4 lightDir0 = mk4((float)a.interval, nd.x, nd.y, nd.z);
@@ -1024,7 +891,7 @@ RPT_DEV bool sample_light_occluded(const KernelArgs &a, f4 origin4, f4 dir4, flo
             newHit.dist = 1e20f;
             const f4 newEvent0 = transformPoint4D(a.objects[i].Lorentz, origin4);
             const f4 lightDir = transformPoint4D(a.objects[i].Lorentz, lightDir0);
-            if (intersect_object<V>(a, i, newEvent0, lightDir, newHit, lightDist)) {
+            if (intersect_object<P>(a, i, newEvent0, lightDir, newHit, lightDist)) {
                 if (newHit.dist < lightDist) return true;
             }
         }
@@ -1084,9 +951,9 @@ struct DopplerRecord {
 // opencl_kernel.cl:361-486 + 548-604: closest hit over the object list, surface colour, lights
 // Returns false (and leaves `color` untouched) when the ray hits nothing: the caller then uses the
 // per-frame background constants instead of tonemapping (0.15,0.15,0.25) again for every pixel.
-// DOPPLER (the twins of rpt_set_doppler): each light's colour goes through S_f(D_i) and the summed colour through S_f(D_cam);
-// DREC (the Doppler debug kernel only) also fills *rec.  With light propagation off (interval 0) nothing changes.
-template <int V, bool DOPPLER = false, bool DREC = false>
+// P::doppler (the twins of rpt_set_doppler): each light's colour goes through S_f(D_i) and the summed colour through S_f(D_cam);
+// P::drec (the Doppler debug kernel only) also fills *rec.  With light propagation off (interval 0) nothing changes.
+template <class P>
 RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mask, f3 &color_out, DopplerRecord *rec = nullptr) {
     const float inf = 1e20f;
     Hit hit;
@@ -1102,8 +969,8 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
         Hit newHit;
         newHit.dist = inf;
         bool got;
-        if (V == 0) got = intersect_object<0>(a, i, ld4(a.objects[i].stationaryCam), transformPoint4D(a.objects[i].Lorentz, rayDir), newHit);
-        else got = intersect_object_primary<V>(a, i, rayDir, newHit);
+        if (P::walk == Walk::reference) got = intersect_object<P>(a, i, ld4(a.objects[i].stationaryCam), transformPoint4D(a.objects[i].Lorentz, rayDir), newHit);
+        else got = intersect_object_primary<P>(a, i, rayDir, newHit);
         if (got) {
             if (newHit.dist < hit.dist) {
                 hit = newHit;
@@ -1113,7 +980,7 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
     }
     if (hit.object < 0) return false;
 #ifdef RPT_DIAGNOSTICS
-    if (V == 5) {   // stop after the closest hit (timing of the primary walk alone)
+    if (P::diag == 5) {   // stop after the closest hit (timing of the primary walk alone)
         color_out = mk3(hit.dist, hit.normal.x + hit.uv.x, hit.normal.y + hit.normal.z + hit.uv.y);
         return true;
     }
@@ -1130,7 +997,7 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
 
     f3 color = hcolor * (a.interval != 0 ? a.ambient : 1.0f);
     if (ho.light) color = color + hcolor;
-    [[maybe_unused]] f3 color_ref = color;       // (DREC only) the same sum with the reference's light colours
+    [[maybe_unused]] f3 color_ref = color;       // (P::drec only) the same sum with the reference's light colours
     [[maybe_unused]] float dlight = 1.0f;
     [[maybe_unused]] bool lit_any = false;
     if (a.interval != 0) {
@@ -1155,13 +1022,13 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
                 if (ndotl > 0) {
                     const f3 ld = normalize(yzw(lightDir));
                     const f4 shadowDir = mk4((float)a.interval, ld.x, ld.y, ld.z);
-                    if (!sample_light_occluded<V>(a, hitPos, shadowDir, length(yzw(lightDir)), i)) {
+                    if (!sample_light_occluded<P>(a, hitPos, shadowDir, length(yzw(lightDir)), i)) {
                         const float k = ndotl / (1.0f + 0.1f * length(lightDir3_ObjFrame) +
                                                  0.01f * dot(lightDir3_ObjFrame, lightDir3_ObjFrame));
-                        if constexpr (DOPPLER) {
+                        if constexpr (P::doppler) {
                             // light factor: time components of the light-to-surface vector in the surface's and the light's frame
                             const float di = lightDir_ObjFrame.x / lightDir_LightFrame.x;
-                            if constexpr (DREC) {
+                            if constexpr (P::drec) {
                                 color_ref = color_ref + hcolor * k * ld3(lo.color);
                                 if (!lit_any) dlight = di;
                                 lit_any = true;
@@ -1175,7 +1042,7 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
             }
         }
     }
-    if constexpr (DOPPLER) {
+    if constexpr (P::doppler) {
         float dcam = 1.0f;
         const f3 lit = color;
         if (a.interval != 0) {
@@ -1183,7 +1050,7 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
             dcam = (float)a.interval / dot(ld4(ho.Lorentz[0]), rayDir);
             color = doppler_colour(static_cast<const DopplerArgs &>(a).doppler, dcam, color);
         }
-        if constexpr (DREC) {
+        if constexpr (P::drec) {
             rec->dcam = dcam;
             rec->dlight = dlight;
             rec->ref = color_ref;
@@ -1254,33 +1121,22 @@ RPT_DEV unsigned long long wave_object_mask(const KernelArgs &a, int tile_x0, in
     return __ballot(keep);
 }
 
-template <int V> RPT_DEV constexpr bool culled_variant() { return V >= 20; }
-template <int V> RPT_DEV constexpr bool zorder_lanes() { return V == 641 || V == 653; }
-template <int V> RPT_DEV constexpr bool one_wave_workgroups() { return V == 0 || V == 1 || V == 20 || V == 21 || V == 23 || V == 24 || V == 25 || V == 657 || V == 669 || V == 673 || V == 705 || V == 717; }     // the product kernels (+ three arms re-measured that way)
-template <int V> RPT_DEV constexpr bool band_first_variant() { return V == 23 || V == 25 || V == 123 || (V >= 256 && V < 1000 && (V & 8)); }
-
 // ---------------------------------------------------------------------------------------------
-// One thread per pixel, wave = 8x8 tile, workgroup = 32x8 strip.
-//   V = 0: reads the reference layouts only (general fallback, any valid octree; no culling)
-//   V = 1: derived layouts, every object tested for every pixel (the un-culled form rpt_verify_frame compares with)
-//   V = 20: derived layouts + the wave's object mask from per-object image-plane rectangles + __ballot (rpt_render_async)
-//   V = 23: 20 with the band of tile rows that holds the meshes dispatched first and the pipelined walk (the blocking rpt_render)
-//   V = 24: 20 without the octree walk compiled in (frames whose Object[] holds no mesh)
-//   other values: diagnostics build only (rpt_diag_kernels.hip.h)
-//   DOPPLER: the Doppler twin of kernel V (rpt_set_doppler); DREC: also the per-pixel Doppler record (the debug kernel only)
-template <int V, bool DOPPLER = false, bool DREC = false>
+// One thread per pixel, wave = 8x8 tile, workgroup = one wave or a 32x8 strip; what else the kernel does is its policy P
+// (KernelPolicy above; the product kernels' policies are listed there, the measurement arms' in rpt_diag_kernels.hip.h).
+template <class P>
 RPT_DEV void render_pixel_body(const KernelArgs &a) {
     const int lane = threadIdx.x & 63;
     // The product kernels are launched ONE WAVE per workgroup (blockDim 64, grid.x = tiles per row): a wave slot is handed back when
     // its wave ends, not when the longest of four neighbours does — next to a tile that walks for 70 us sit tiles that only store
     // (profiles/r03_one_wave_workgroups_ab.txt: bunny 4K in flight -8 %, one at a time -3 %).  The measurement arms keep 4 x 64.
-    const int wave = one_wave_workgroups<V>() ? ((int)blockIdx.x & 3) : (int)(threadIdx.x >> 6);
-    const int strip = one_wave_workgroups<V>() ? ((int)blockIdx.x >> 2) : (int)blockIdx.x;      // 32-pixel-wide strip of that row
+    const int wave = P::one_wave ? ((int)blockIdx.x & 3) : (int)(threadIdx.x >> 6);
+    const int strip = P::one_wave ? ((int)blockIdx.x >> 2) : (int)blockIdx.x;      // 32-pixel-wide strip of that row
 #ifdef RPT_DIAGNOSTICS
-    const DiagWaveClock diag_clock0 = diag_wave_begin<V>();
+    const DiagWaveClock diag_clock0 = diag_wave_begin<P::diag>();
 #endif
     int tile_row = (int)blockIdx.y;              // 8-row tiles of this context, natural order
-    if (band_first_variant<V>() && a.first_h > 0) {
+    if (P::band_first && a.first_h > 0) {
         // Workgroups are handed out in the order of their linear index, i.e. row of strips by row of strips.  One frame at a
         // time, what ends the frame is the last of its long waves, so the band of tile rows that holds the meshes goes first
         // (whole rows, in their natural order: neighbours stay neighbours) and the other rows follow in order.
@@ -1290,8 +1146,9 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // lane -> pixel of the wave's 8x8 tile: row by row.  Diagnostics library, arms 641 / 653: along the Z curve, so that the four lanes the
     // memory pipeline handles together are a 2x2 block of pixels, not a 4x1 run (level, +1 % in flight at 4K and 8K: r03_td_bound.txt)
 #ifdef RPT_DIAGNOSTICS
-    const int col_in_tile = zorder_lanes<V>() ? ((lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4)) : (lane & 7);
-    const int row_in_tile = zorder_lanes<V>() ? (((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4)) : (lane >> 3);
+    const bool zorder_lanes = P::diag == 641 || P::diag == 653;
+    const int col_in_tile = zorder_lanes ? ((lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4)) : (lane & 7);
+    const int row_in_tile = zorder_lanes ? (((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4)) : (lane >> 3);
     const int x_coord = strip * 32 + wave * 8 + col_in_tile;
 #else
     const int row_in_tile = lane >> 3;
@@ -1303,9 +1160,9 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // the wave's object mask comes from a __ballot over ALL 64 lanes (lane i answers for object i), so it is formed
     // before the lanes of a partial tile leave
     unsigned long long object_mask = ~0ull;
-    if (culled_variant<V>()) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    if (P::culled) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
 #ifdef RPT_DIAGNOSTICS
-    if (V == 10) object_mask = a.tile_masks[__builtin_amdgcn_readfirstlane(tile_row * a.mask_tiles_x + (int)blockIdx.x * 4 + wave)];   // the prepass's per-tile mask
+    if (P::diag == 10) object_mask = a.tile_masks[__builtin_amdgcn_readfirstlane(tile_row * a.mask_tiles_x + (int)blockIdx.x * 4 + wave)];   // the prepass's per-tile mask
 #endif
     if (x_coord >= a.width || y_coord >= a.height) return;   // the reference has no guard (UB)
 
@@ -1314,17 +1171,17 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     bool traced = false;
     [[maybe_unused]] DopplerRecord drec;
     uint32_t packed = a.bg_packed;
-    const bool masked = culled_variant<V>() || V == 10;
+    const bool masked = P::culled || P::diag == 10;
     if (!masked || object_mask != 0 || a.object_count > 64) {
         const f3 camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
-        if (trace<V, DOPPLER, DREC>(a, camdir, object_mask, color, DREC ? &drec : nullptr)) {
+        if (trace<P>(a, camdir, object_mask, color, P::drec ? &drec : nullptr)) {
             packed = tonemap_pack(a, color, mapped);
             traced = true;
         }
     }
 
     const size_t id = (size_t)y_coord * a.width + x_coord;
-    if constexpr (DREC) {
+    if constexpr (P::drec) {
         // {D_cam, D_light, reference colour, after the light factors, final linear colour}; a miss pixel: all zero (D_cam = 0)
         if (float *const rec_out = static_cast<const DopplerArgs &>(a).debug_doppler) {
             float *r = rec_out + (size_t)RPT_DOPPLER_RECORD * id;
@@ -1334,7 +1191,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
         }
     }
 #ifdef RPT_DIAGNOSTICS
-    if (V == 785 && object_mask == 0ull) return;      // EXPERIMENT (wrong image): what do the sky tiles' stores cost the walks?
+    if (P::diag == 785 && object_mask == 0ull) return;      // EXPERIMENT (wrong image): what do the sky tiles' stores cost the walks?
 #endif
     if (a.out16) store_pixel(a.out16, id, __float_as_uint((float)x_coord), __float_as_uint((float)y_coord), packed, 0u);
     // (the 4-byte plane likewise: measured against the default policy on a rank's share of the frame, bunny 4K 0.0581 -> 0.0566 ms, shadows the same)
@@ -1346,16 +1203,16 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
         a.debug_rgb[3 * id + 2] = mapped.z;
     }
 #ifdef RPT_DIAGNOSTICS
-    diag_wave_end<V>(a, diag_clock0);
+    diag_wave_end<P::diag>(a, diag_clock0);
 #endif
 }
 
 // opencl_kernel.cl:641-648 with MSAASAMPLES = a.msaa > 1 (a compile-time constant of the reference, 1 as shipped; rpt_set_msaa): a.msaa^2
 // camera rays per pixel at (x + sx/n, y + sy/n), colours summed in the reference's order (a miss contributes the background of :565)
-// and divided by n^2 before the tonemap.  A function of its own so that the one-sample kernels stay what they are.  V = 20: the
+// and divided by n^2 before the tonemap.  A function of its own so that the one-sample kernels stay what they are.  Ballot: the
 // wave's object mask as in render_pixel_body — the tile it is tested against is grown by a pixel and a half, the samples stay
-// within one pixel; V = 1: no cull (what rpt_verify_frame compares with).
-template <int V>
+// within one pixel; Unculled: no cull (what rpt_verify_frame compares with).
+template <class P>
 RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
     const int lane = threadIdx.x & 63;
     const int wave = (int)blockIdx.x & 3;              // one wave per workgroup, as the one-sample product kernels
@@ -1367,9 +1224,9 @@ RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
     const int global_tile = (tile_row >> a.run_log2) * a.tile_step + a.first_tile + (tile_row & ((1 << a.run_log2) - 1));
     const int y_coord = global_tile * RPT_TILE_ROWS + row_in_tile;
     unsigned long long object_mask = ~0ull;
-    if (culled_variant<V>()) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    if (P::culled) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
     if (x_coord >= a.width || y_coord >= a.height) return;
-    const bool any = !culled_variant<V>() || object_mask != 0 || a.object_count > 64;
+    const bool any = !P::culled || object_mask != 0 || a.object_count > 64;
     const int n = a.msaa;
     f3 sum = mk3(0.0f, 0.0f, 0.0f);
     for (int sy = 0; sy < n; sy++) {
@@ -1378,7 +1235,7 @@ RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
             if (any) {
                 const f3 camdir = createCamRayDir((float)x_coord + (float)sx / (float)n, (float)y_coord + (float)sy / (float)n, a.width, a.height, a.aspect);
                 f3 traced;
-                if (trace<V>(a, camdir, object_mask, traced)) c = traced;
+                if (trace<P>(a, camdir, object_mask, traced)) c = traced;
             }
             sum = sum + c;
         }
@@ -1399,35 +1256,35 @@ RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
 
 #ifndef RPT_RELAXED_FP    /* rpt_relaxed.hip instantiates its own two kernels and nothing else from here on */
 // Product kernels (rpt_set_variant; the number in the comment is the variant).
-__global__ __launch_bounds__(64) void rpt_render_kernel_v0(const KernelArgs a) { render_pixel_body<0>(a); }                                                              // 1: any valid octree
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_w5(const KernelArgs a) { render_pixel_body<1>(a); }         // 3: no cull (rpt_verify_frame; the escape hatch)
+__global__ __launch_bounds__(64) void rpt_render_kernel_v0(const KernelArgs a) { render_pixel_body<RefLayout>(a); }                                                              // 1: any valid octree
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_w5(const KernelArgs a) { render_pixel_body<Unculled>(a); }         // 3: no cull (rpt_verify_frame; the escape hatch)
 // the wave's object mask from the per-object screen rectangles by lane-parallel test + __ballot, 5 waves per SIMD (96 VGPRs, 8 B of scratch outside the loops)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_w5(const KernelArgs a) { render_pixel_body<21>(a); }          // 41 = rpt_render_async
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_w5(const KernelArgs a) { render_pixel_body<BallotExact>(a); }          // 41 = rpt_render_async
 // the same with the tile rows that hold the meshes dispatched first and the latency walk (44 B of scratch): latency, not throughput
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_w5(const KernelArgs a) { render_pixel_body<25>(a); }    // 43 = the blocking rpt_render; rpt_render_async below RPT_LATENCY_KERNEL_MAX_PIXELS
-// 41 and 43 above take the triangle test's 1 / det through rcp_exact (V = 21 / 25); these two keep the IEEE division, for scenes
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_w5(const KernelArgs a) { render_pixel_body<BallotFirstExact>(a); }    // 43 = the blocking rpt_render; rpt_render_async below RPT_LATENCY_KERNEL_MAX_PIXELS
+// 41 and 43 above take the triangle test's 1 / det through rcp_exact (BallotExact / BallotFirstExact); these two keep the IEEE division, for scenes
 // outside rcp_exact's domain (rpt_scene_exact_rcp) and as variants 48 / 49
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_w5(const KernelArgs a) { render_pixel_body<20>(a); }        // 48 (and 41 outside the domain)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_w5(const KernelArgs a) { render_pixel_body<23>(a); }  // 49 (and 43 outside the domain)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_w5(const KernelArgs a) { render_pixel_body<Ballot>(a); }        // 48 (and 41 outside the domain)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_w5(const KernelArgs a) { render_pixel_body<BallotFirst>(a); }  // 49 (and 43 outside the domain)
 // without the octree walk compiled in, for frames whose Object[] holds no mesh: 61 VGPRs, no scratch, EIGHT waves per SIMD
 // (arch 1080p 0.0370 -> 0.0301 ms per frame in flight, cubes.txt 4K 0.0898 -> 0.0725)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_w8(const KernelArgs a) { render_pixel_body<24>(a); }        // 44
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_w8(const KernelArgs a) { render_pixel_body<Analytic>(a); }        // 44
 
 // MSAASAMPLES > 1 (rpt_set_msaa): culled and un-culled; rpt_last_variant reports them as 46 / 47
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_w5(const KernelArgs a) { render_pixel_body_msaa<20>(a); }            // 46
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_unculled_w5(const KernelArgs a) { render_pixel_body_msaa<1>(a); }    // 47
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_w5(const KernelArgs a) { render_pixel_body_msaa<Ballot>(a); }            // 46
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_unculled_w5(const KernelArgs a) { render_pixel_body_msaa<Unculled>(a); }    // 47
 
 // Doppler twins (rpt_set_doppler != 0; not in the reference): the kernels above with the colour operator compiled in, launched with
 // the same shapes and occupancies.  The variant numbers rpt_last_variant reports are the twinned kernel's + 200; 241 / 243 fall back
 // to 248's / 249's code outside the exact reciprocal's domain as 41 / 43 do.  Variants 1, 50, 51 and MSAA > 1 have no twin.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_doppler_w5(const DopplerArgs a) { render_pixel_body<1, true>(a); }         // 203
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_doppler_w5(const DopplerArgs a) { render_pixel_body<21, true>(a); }          // 241
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_doppler_w5(const DopplerArgs a) { render_pixel_body<25, true>(a); }    // 243
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_doppler_w5(const DopplerArgs a) { render_pixel_body<20, true>(a); }     // 248
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_doppler_w5(const DopplerArgs a) { render_pixel_body<23, true>(a); }  // 249
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_doppler_w8(const DopplerArgs a) { render_pixel_body<24, true>(a); }     // 244
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_doppler_w5(const DopplerArgs a) { render_pixel_body<DopplerTwin<Unculled>>(a); }         // 203
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_doppler_w5(const DopplerArgs a) { render_pixel_body<DopplerTwin<BallotExact>>(a); }          // 241
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_doppler_w5(const DopplerArgs a) { render_pixel_body<DopplerTwin<BallotFirstExact>>(a); }    // 243
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_doppler_w5(const DopplerArgs a) { render_pixel_body<DopplerTwin<Ballot>>(a); }     // 248
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_doppler_w5(const DopplerArgs a) { render_pixel_body<DopplerTwin<BallotFirst>>(a); }  // 249
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_doppler_w8(const DopplerArgs a) { render_pixel_body<DopplerTwin<Analytic>>(a); }     // 244
 // the Doppler debug kernel (rpt_set_debug_doppler): 203 that also writes the per-pixel record; launched instead of any twin while the hook is set
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_doppler_record_w5(const DopplerArgs a) { render_pixel_body<1, true, true>(a); }   // 240
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_doppler_record_w5(const DopplerArgs a) { render_pixel_body<DopplerRecorded>(a); }   // 240
 
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd
@@ -1578,63 +1435,6 @@ __global__ __launch_bounds__(256) void rpt_probe_doppler_kernel(const float *in,
     out[3 * i + 2] = o.z;
 }
 
-// rpt_probe_division: are the shared-reciprocal quotients of rpt_device_math.hip.h equal to IEEE division bit for bit?  Every thread
-// draws `per_thread` (numerators, denominator) sets from a counter-based generator and compares div3_shared_unguarded<1> and <2>
-// with x / s on those INSIDE the fast path's domain, and the guarded div3_shared<2> on ALL of them.  mode 0: random significands,
-// exponents over the whole domain (and beyond it for the guarded form); 1: the same with the denominator's significand all ones;
-// 2: normalize() itself — a random vector, s = sqrt(dot(v, v)) as length() forms it; 3: arbitrary bit patterns (NaN, infinities,
-// zeros, denormals: only the guarded form is compared).  counts[0..3] = sets compared unguarded, mismatching quotients with one
-// round, with two rounds, mismatches of the guarded form; the first few mismatching sets go to `samples` (4 floats each).
-RPT_DEV uint32_t probe_hash(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__global__ __launch_bounds__(256) void rpt_probe_division_kernel(int mode, uint32_t seed, int per_thread, unsigned long long *counts, float *samples, int max_samples) {
-    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long n_cmp = 0, bad1 = 0, bad2 = 0, badg = 0;
-    for (int it = 0; it < per_thread; it++) {
-        const uint32_t base = probe_hash(seed ^ probe_hash(tid * 0x9e3779b9u + (uint32_t)it));
-        uint32_t w[4];
-        for (int k = 0; k < 4; k++) w[k] = probe_hash(base + 0x632be5abu * (uint32_t)(k + 1));
-        float v[4];
-        if (mode == 3) {
-            for (int k = 0; k < 4; k++) v[k] = __uint_as_float(w[k]);
-        } else {
-            for (int k = 0; k < 4; k++) {
-                const uint32_t sign = w[k] & 0x80000000u, mant = (mode == 1 && k == 3) ? 0x7fffffu : (w[k] & 0x7fffffu);
-                const int span = k == 3 ? 100 : 140;                      // exponents: the domain and a little beyond
-                const int e = 127 - span / 2 + (int)((w[k] >> 23) % (uint32_t)span);
-                v[k] = __uint_as_float(sign | ((uint32_t)e << 23) | mant);
-            }
-            if (mode == 2) {
-                const f3 t = mk3(v[0], v[1], v[2]);
-                v[3] = length(t);
-            }
-        }
-        const f3 a = mk3(v[0], v[1], v[2]);
-        const float s = v[3];
-        const f3 ref = mk3(a.x / s, a.y / s, a.z / s);
-        auto same = [](float p, float q) { return __float_as_uint(p) == __float_as_uint(q) || (p != p && q != q); };
-        bool report = false;
-        if (div3_shared_domain(a, s)) {
-            n_cmp++;
-            const f3 q1 = div3_shared_unguarded<1>(a, s), q2 = div3_shared_unguarded<2>(a, s);
-            const int b1 = !same(q1.x, ref.x) + !same(q1.y, ref.y) + !same(q1.z, ref.z);
-            const int b2 = !same(q2.x, ref.x) + !same(q2.y, ref.y) + !same(q2.z, ref.z);
-            bad1 += b1; bad2 += b2;
-            report = b2 != 0 || (b1 != 0 && mode != 1);
-        }
-        const f3 g = div3_shared<2>(a, s);
-        const int bg = !same(g.x, ref.x) + !same(g.y, ref.y) + !same(g.z, ref.z);
-        badg += bg;
-        if ((report || bg) && samples) {
-            const unsigned long long slot = atomicAdd(&counts[4], 1ull);
-            if (slot < (unsigned long long)max_samples) { float *o = samples + 4 * slot; o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = s; }
-        }
-    }
-    atomicAdd(&counts[0], n_cmp); atomicAdd(&counts[1], bad1); atomicAdd(&counts[2], bad2); atomicAdd(&counts[3], badg);
-}
-
 // The exact reciprocal against IEEE 1 / s (rpt_probe_reciprocal): every float s whose bit pattern lies in [lo_bits, lo_bits + per_sign),
 // with both signs.  counts = {values compared, mismatches of rcp_newton<1>, <2>, <3> (rpt_device_math.hip.h), samples written}; the
 // first max_samples mismatching s go to samples as {s, bit mask of the forms that missed (1, 2, 4)}.
@@ -1661,7 +1461,7 @@ __global__ __launch_bounds__(256) void rpt_probe_reciprocal_kernel(uint32_t lo_b
 
 // Known-answer probes at OBJECT level (rpt_probe_object; the oracle's counterpart is rpt_oracle_object_rays): which =
 //   0: one 4-D ray {origin4, dir4} in the rest frame of object `object` through intersect_object, the general form every shadow ray
-//      and the V = 0 kernel's primary rays take: out 8 = {hit, dist, normal.xyz, uv.xy, 0}   (opencl_kernel.cl:312-359, 200-308)
+//      and the RefLayout kernel's primary rays take: out 8 = {hit, dist, normal.xyz, uv.xy, 0}   (opencl_kernel.cl:312-359, 200-308)
 //   1: sample_light on a shadow ray {origin4, dir4, lightDist} of the camera frame with light `object`: out 2 = {occluded as the
 //      un-culled kernel decides it, occluded as the culled kernels decide it (segment culls, __ballot over the wave)}   (:488-545)
 //   2: the transforms on {x, y, z, w}: out 16 = transformPoint(InvM), transformPoint4D(Lorentz), transformDirection(InvM),
@@ -1680,11 +1480,11 @@ __global__ __launch_bounds__(64) void rpt_probe_object_kernel(const KernelArgs a
         bool h;
         if (which == 0) {
             const float *p = in + 8 * (size_t)j;
-            h = intersect_object<1>(a, object, mk4(p[0], p[1], p[2], p[3]), mk4(p[4], p[5], p[6], p[7]), hit);
+            h = intersect_object<Unculled>(a, object, mk4(p[0], p[1], p[2], p[3]), mk4(p[4], p[5], p[6], p[7]), hit);
         } else {
             const float *p = in + 3 * (size_t)j;
             const f3 nd = normalize(mk3(p[0], p[1], p[2]));
-            h = intersect_object_primary<20>(a, object, mk4((float)a.interval, nd.x, nd.y, nd.z), hit);
+            h = intersect_object_primary<Ballot>(a, object, mk4((float)a.interval, nd.x, nd.y, nd.z), hit);
         }
         if (i < n) {
             float *o = out + 8 * (size_t)i;
@@ -1697,8 +1497,8 @@ __global__ __launch_bounds__(64) void rpt_probe_object_kernel(const KernelArgs a
     } else if (which == 1) {
         const float *p = in + 9 * (size_t)j;
         const f4 o4 = mk4(p[0], p[1], p[2], p[3]), d4 = mk4(p[4], p[5], p[6], p[7]);
-        const bool plain = sample_light_occluded<1>(a, o4, d4, p[8], object);
-        const bool culled = sample_light_occluded<20>(a, o4, d4, p[8], object);
+        const bool plain = sample_light_occluded<Unculled>(a, o4, d4, p[8], object);
+        const bool culled = sample_light_occluded<Ballot>(a, o4, d4, p[8], object);
         if (i < n) { out[2 * (size_t)i] = plain ? 1.0f : 0.0f; out[2 * (size_t)i + 1] = culled ? 1.0f : 0.0f; }
     } else if (i < n) {
         const float *p = in + 4 * (size_t)i;
@@ -1717,8 +1517,8 @@ __global__ __launch_bounds__(64) void rpt_probe_object_kernel(const KernelArgs a
 }
 
 // Known-answer probe of the octree walk at RAY level: every ray (object-space origin and direction) through the three walks the
-// product library holds — the reference's layouts (octree_core_ref), the throughput walk (octree_walk<false, false>) and the latency
-// walk (octree_walk<true, true>) — with the hit re-measured from the origin (0, 0, 0) at unit direction length.  8 floats per walk
+// product library holds — the reference's layouts (octree_core_ref), the throughput walk (octree_walk<false, ...>) and the latency
+// walk (octree_walk<true, ...>) — with the hit re-measured from the origin (0, 0, 0) at unit direction length.  8 floats per walk
 // and ray: hit flag, dist, normal.xyz, uv.xy, 0.
 // exact = 1: the two derived-layout walks in the EXACT_RCP form kernels 41 / 43 launch on this scene (its triangles are in the domain)
 __global__ __launch_bounds__(256) void rpt_probe_walk_kernel(const KernelArgs a, int object, const float *rays, float *out, int n, int exact) {
@@ -1737,10 +1537,10 @@ __global__ __launch_bounds__(256) void rpt_probe_walk_kernel(const KernelArgs a,
         hit.object = -1;
         const f3 o0 = mk3(0.0f, 0.0f, 0.0f);
         const bool h = w == 0 ? octree_core_ref(a, obj, r, o0, 1.0f, hit)
-                     : w == 1 ? (exact ? octree_walk<false, false, true, false, true, 0, false, true>(a, obj, root, r, o0, 1.0f, hit)
-                                       : octree_walk<false, false, true, false, true>(a, obj, root, r, o0, 1.0f, hit))
-                              : (exact ? octree_walk<true, true, false, false, true, 0, false, true>(a, obj, root, r, o0, 1.0f, hit)
-                                       : octree_walk<true, true, false, false, true>(a, obj, root, r, o0, 1.0f, hit));
+                     : w == 1 ? (exact ? octree_walk<false, true>(a, obj, root, r, o0, 1.0f, hit)
+                                       : octree_walk<false, false>(a, obj, root, r, o0, 1.0f, hit))
+                              : (exact ? octree_walk<true, true>(a, obj, root, r, o0, 1.0f, hit)
+                                       : octree_walk<true, false>(a, obj, root, r, o0, 1.0f, hit));
         float *o = out + ((size_t)i * 3 + w) * 8;
         o[0] = h ? 1.0f : 0.0f;
         o[1] = h ? hit.dist : 0.0f;

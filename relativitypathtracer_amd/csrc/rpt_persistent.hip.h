@@ -400,7 +400,7 @@ RPT_DEV void render_tile_classic(const KernelArgs &a, const Outputs &o, int tile
         bool traced = false;
         if (object_mask != 0ull || a.object_count > 64) {
             const f3 camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
-            if (trace<20>(a, camdir, object_mask, color)) {
+            if (trace<Ballot>(a, camdir, object_mask, color)) {
                 packed = tonemap_pack(a, color, mapped);
                 traced = true;
             }

@@ -16,8 +16,8 @@
 #include "rpt_kernels.hip.h"
 
 namespace rptd_relaxed {
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_relaxed_w5(const KernelArgs a) { render_pixel_body<20>(a); }
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_relaxed_w6(const KernelArgs a) { render_pixel_body<20>(a); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_relaxed_w5(const KernelArgs a) { render_pixel_body<Ballot>(a); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_relaxed_w6(const KernelArgs a) { render_pixel_body<Ballot>(a); }
 }  // namespace rptd_relaxed
 
 // args: the exact build's rptd::KernelArgs, byte for byte (same struct definition, other namespace)

@@ -12,12 +12,7 @@ renders something else would be worthless.  So they are held to the product's ba
   256+f     the product walk with its round trips re-ordered further (flags: rpt_diag_walks.hip.h)
   529, 541, 621   the six neighbour indices read with the node record (/ + records ahead / + the first triangle too: a step in one round trip)
   561, 573  = kernel 43's latency walk, natural order / mesh band first;  2573 the same at four waves per SIMD
-  589       the latency walk with the packed leaf count;  625, 637 kernel 41's / 43's walk with the triangle id read with every record
-  593, 605  the 16^3 root table (descend_from_root) in kernel 41's / 43's walk
   641, 653  the lanes of a wave along the Z curve through its tile
-  657, 669, 673   records read once per wave where the wave stands in one node: through the scalar cache / by one lane + readfirstlane
-  705, 717  round 4: kernel 41's / 43's walk WITHOUT the repeated triangle tests (list entries whose triangle was in the previous
-            leaf's list are skipped: exact, see octree_walk's DEDUP in csrc/rpt_kernels.hip.h)
 """
 import numpy as np
 import pytest
@@ -27,7 +22,7 @@ from conftest import load_config
 
 pytestmark = pytest.mark.gpu
 
-ARMS = [26, 40, 42, 141, 143, 60, 61, 62, 63, 256, 257, 259, 261, 263, 265, 269, 273, 277, 285, 305, 317, 337, 349, 401, 1257, 2257, 2259, 2263, 529, 541, 561, 573, 589, 593, 605, 621, 625, 637, 641, 653, 657, 669, 673, 689, 701, 2573, 705, 717]
+ARMS = [26, 40, 42, 141, 143, 60, 61, 62, 63, 256, 257, 259, 261, 263, 265, 269, 273, 277, 285, 305, 317, 337, 349, 401, 1257, 2257, 2259, 2263, 529, 541, 561, 573, 621, 641, 653, 689, 701, 2573]
 SCENES = {"bunny": (480, 270), "shadows": (480, 270), "arch": (480, 270), "cubes": (320, 184), "soccer": (320, 184), "cube": (333, 77)}
 
 

@@ -5,7 +5,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SHIPPED_FORM = 1          # RPT_RCP_FORM of the product build (rpt_device_math.hip.h)
+SHIPPED_FORM = 1          # the rcp_newton form rcp_exact takes (rpt_device_math.hip.h)
 
 
 def _bits(x):

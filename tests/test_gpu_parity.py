@@ -80,16 +80,17 @@ def test_msaa_matches_oracle(name, msaa):
     r = Renderer(0)
     try:
         r.set_msaa(msaa)
-        for variant, kernel in ((0, 46), (3, 47)):
+        for variant, kernel in ((0, 46), (3, 47), (41, 46), (43, 46), (44, 46)):
             px, rgb = _render_gpu(r, scene, W, H, variant)
             assert r.last_variant() == kernel
             assert np.array_equal(rgb.view(np.uint32), orgb.view(np.uint32)), f"{name} msaa {msaa} variant {variant}: float RGB not bit-identical"
             assert np.array_equal(px["rgba"], opx["rgba"]) and np.array_equal(px["x"], opx["x"]) and np.array_equal(px["y"], opx["y"])
         r.set_variant(0)
         assert r.verify_frame() == 0
-        r.set_variant(1)
-        with pytest.raises(RenderError):
-            r.render()                       # the reference-layout kernel has no multi-sample form
+        for variant in (1, 48, 49, 50, 51):
+            r.set_variant(variant)
+            with pytest.raises(RenderError):
+                r.render()                   # the reference-layout kernel and the A/B and relaxed variants have no multi-sample form
         r.set_variant(0)
         with pytest.raises(RenderError):
             r.set_msaa(0)
@@ -143,9 +144,12 @@ def test_frames_wider_than_the_proven_window_render_unculled(renderer):
         assert renderer.last_variant() in kernels, (W, H, renderer.last_variant())
         opx, orgb, _ = oracle_ffi.render(scene, W, H)
         assert np.array_equal(px["rgba"], opx["rgba"]) and np.array_equal(rgb.view(np.uint32), orgb.view(np.uint32)), (W, H)
-        for variant in (41, 43):          # asked for explicitly on a frame they are not proven for: the un-culled kernel all the same
+        # asked for explicitly on a frame they are not proven for: the un-culled kernel all the same (44 on a scene with meshes is 41).
+        # 50 / 51 keep their kernel: a known gap (third item), pinned here until it is closed.
+        for variant, inside in ((41, 41), (43, 43), (44, 41), (48, 48), (49, 49), (50, 50), (51, 51)):
             _render_gpu(renderer, scene, W, H, variant)
-            assert renderer.last_variant() == (variant if kernels != (3,) else 3), (W, H, variant, renderer.last_variant())
+            want = inside if kernels != (3,) or variant in (50, 51) else 3
+            assert renderer.last_variant() == want, (W, H, variant, renderer.last_variant())
     renderer.set_variant(0)
 
 
