@@ -26,7 +26,9 @@
  * rpt_set_debug_rgb, rpt_verify_frame, rpt_object_screen_rect / _bounds / _bounds_proposed,
  * rpt_certify_screen_bounds and rpt_mesh_segment_cull_record (the last five are host code: no device needed), and the opt-in
  * relativistic Doppler shift and searchlight beaming, which the reference does not render: rpt_set_doppler with its test hooks
- * rpt_set_debug_doppler / rpt_read_debug_doppler and rpt_probe which = 6 ("Doppler and beaming").
+ * rpt_set_debug_doppler / rpt_read_debug_doppler and rpt_probe which = 6 ("Doppler and beaming"), and the opt-in
+ * equirectangular panorama camera, which the reference (a fixed pinhole looking down +z) does not have: rpt_set_projection and
+ * rpt_projection_tables (host code, no device needed; DESIGN.md, "Panorama camera").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -131,6 +133,28 @@ int rpt_set_doppler(rpt_ctx *ctx, int flags);
  * the last frame (RPT_ERR_STATE if the last frame was not rendered by the debug kernel). */
 int rpt_set_debug_doppler(rpt_ctx *ctx, void *device_ptr_or_null_or_1);
 int rpt_read_debug_doppler(rpt_ctx *ctx, void *host_dst, size_t bytes);
+
+/* The camera's projection (not in the reference; DESIGN.md "Panorama camera"), per context, RPT_PROJECTION_PINHOLE by default, not
+ * shared by rpt_share_scene.  PINHOLE is the reference's camera (opencl_kernel.cl:55-73), params must be NULL.  EQUIRECT is a
+ * panorama: params = {h_fov, v_fov, yaw} in radians with h_fov in (0, 2 pi], v_fov in (0, pi] (the floats nearest 2 pi and pi
+ * included), yaw finite; NULL = {2 pi, pi, 0}, the full sphere.  Anything else is RPT_ERR_ARG at the call.
+ * Pixel (x, y) of a W x H frame (row 0 the bottom, as everywhere) looks along normalize(p), p = (cos phi sin lambda, sin phi,
+ * cos phi cos lambda) as three float products, with lambda = yaw + h_fov ((x + 0.5)/W - 0.5) and phi = v_fov ((y + 0.5)/H - 0.5)
+ * evaluated in double and their sine and cosine rounded to float (rpt_projection_tables): yaw 0 puts the image centre on +z, the
+ * reference's view direction, column x grows towards +x, and W = 2 H gives square pixels on the full sphere.
+ * In panorama, variant 0 launches 344 (no mesh in Object[]) or 341 (the octree walk; with rpt_last_exact_rcp as for 41), variant 3
+ * launches 303 (un-culled, what rpt_verify_frame compares with), and with Doppler on their twins 544 / 541 / 503, or the debug kernel 540
+ * while rpt_set_debug_doppler is set.  They skip the per-object screen regions (proven on the pinhole's image plane only) and keep the
+ * shadow-ray culls.  Every other variant, MSAA > 1 and an octree whose children are not consecutive make rpt_render /
+ * rpt_render_async / rpt_verify_frame return RPT_ERR_ARG at the LAUNCH.  Back to PINHOLE, every kernel choice is the reference
+ * camera's again. */
+#define RPT_PROJECTION_PINHOLE 0
+#define RPT_PROJECTION_EQUIRECT 1
+int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params);
+/* Host code, no device: the two tables the panorama kernels read for a W x H frame.  cols_out gets 2 W floats {sin lambda_x,
+ * cos lambda_x}, rows_out 2 H floats {sin phi_y, cos phi_y}.  mode must be RPT_PROJECTION_EQUIRECT (the pinhole has no tables), params
+ * as for rpt_set_projection, 1 <= W, H and W H < 2^31; anything else is RPT_ERR_ARG. */
+int rpt_projection_tables(int mode, const float *params, int width, int height, float *cols_out, float *rows_out);
 
 /* Kernel variant: 0 = default (fastest validated); the others select alternative implementations of the same path for
  * A/B measurement.  All produce identical results.

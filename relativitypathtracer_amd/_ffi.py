@@ -174,6 +174,8 @@ HIP_SYMBOLS = {
     "rpt_set_doppler": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_set_debug_doppler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rpt_read_debug_doppler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_set_projection": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "rpt_projection_tables": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -134,6 +134,15 @@ struct rpt_ctx {
     bool want_owned_doppler = false;
     bool doppler_recorded = false;                    // the last launch was the Doppler debug kernel (the record is the last frame's)
     DeviceBuffer owned_doppler;
+    // rpt_set_projection (not in the reference): RPT_PROJECTION_*, per context, never shared
+    int projection = RPT_PROJECTION_PINHOLE;
+    float projection_params[3] = {0, 0, 0};           // {h_fov, v_fov, yaw} of the equirectangular camera
+    DeviceBuffer pano_tables;                         // [width + height] float2: the column table, then the row table
+    float *pano_host = nullptr;                       // pinned: what the last upload of the tables was copied from
+    size_t pano_host_capacity = 0;
+    hipEvent_t pano_copied = nullptr;                 // recorded after that copy: pano_host is rewritten only once it has passed
+    bool pano_valid = false;                          // the device tables are those of (pano_width, pano_height, projection_params)
+    int pano_width = 0, pano_height = 0;
 };
 
 namespace {
@@ -680,6 +689,57 @@ int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, i
 }
 #endif
 
+// ---- the equirectangular camera (rpt_set_projection, rpt_projection_tables) ---------------------------------------------------------
+// {h_fov, v_fov, yaw}: NULL = the full sphere; h_fov in (0, 2 pi], v_fov in (0, pi] (the float nearest 2 pi and pi included), yaw finite
+bool projection_params(const float *params, float out[3]) {
+    const float p[3] = {params ? params[0] : (float)(2.0 * RPT_PI_D), params ? params[1] : (float)RPT_PI_D, params ? params[2] : 0.0f};
+    if (!(p[0] > 0.0f && p[0] <= (float)(2.0 * RPT_PI_D)) || !(p[1] > 0.0f && p[1] <= (float)RPT_PI_D) || !std::isfinite(p[2])) return false;
+    for (int k = 0; k < 3; k++) out[k] = p[k];
+    return true;
+}
+
+// lambda_x = yaw + h_fov ((x + 0.5) / W - 0.5), phi_y = v_fov ((y + 0.5) / H - 0.5), in double from the float parameters; the tables hold
+// the float-rounded sine and cosine of each (cols: 2 W floats, rows: 2 H floats)
+void projection_fill(const float params[3], int width, int height, float *cols, float *rows) {
+    const double h_fov = params[0], v_fov = params[1], yaw = params[2];
+    for (int x = 0; x < width; x++) {
+        const double lambda = yaw + h_fov * (((double)x + 0.5) / (double)width - 0.5);
+        cols[2 * (size_t)x] = (float)std::sin(lambda);
+        cols[2 * (size_t)x + 1] = (float)std::cos(lambda);
+    }
+    for (int y = 0; y < height; y++) {
+        const double phi = v_fov * (((double)y + 0.5) / (double)height - 0.5);
+        rows[2 * (size_t)y] = (float)std::sin(phi);
+        rows[2 * (size_t)y + 1] = (float)std::cos(phi);
+    }
+}
+
+// The context's device tables for this frame's size and parameters.  Rebuilt only when one of them changed, and uploaded in stream order
+// from a pinned buffer that is not rewritten before its previous copy has run: a frame still in flight reads the tables it was launched
+// with, a later one the new ones.
+int ensure_panorama_tables(rpt_ctx *ctx) {
+    if (ctx->pano_valid && ctx->pano_width == ctx->width && ctx->pano_height == ctx->height) return RPT_OK;
+    const size_t floats = 2 * ((size_t)ctx->width + (size_t)ctx->height), bytes = floats * sizeof(float);
+    if (!ctx->pano_copied) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->pano_copied, hipEventDisableTiming));
+    else RPT_HIP(ctx, hipEventSynchronize(ctx->pano_copied));
+    if (bytes > ctx->pano_host_capacity) {
+        if (ctx->pano_host) RPT_HIP(ctx, hipHostFree(ctx->pano_host));
+        ctx->pano_host = nullptr;
+        ctx->pano_host_capacity = 0;
+        RPT_HIP(ctx, hipHostMalloc((void **)&ctx->pano_host, bytes, hipHostMallocDefault));
+        ctx->pano_host_capacity = bytes;
+    }
+    if (bytes > ctx->pano_tables.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
+    if (int rc = reserve(ctx, ctx->pano_tables, bytes)) return rc;
+    projection_fill(ctx->projection_params, ctx->width, ctx->height, ctx->pano_host, ctx->pano_host + 2 * (size_t)ctx->width);
+    RPT_HIP(ctx, hipMemcpyAsync(ctx->pano_tables.ptr, ctx->pano_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(ctx->pano_copied, ctx->stream));
+    ctx->pano_valid = true;
+    ctx->pano_width = ctx->width;
+    ctx->pano_height = ctx->height;
+    return RPT_OK;
+}
+
 // ---- the product kernels: every fact launch() and rpt_set_variant() know about a variant, one row each ------------------------------
 // variant      what rpt_set_variant takes (settable rows) and rpt_last_variant reports; the other rows are reached through the
 //              msaa and doppler columns only
@@ -691,8 +751,10 @@ int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, i
 // window       outside the window the screen regions are proven for, the un-culled kernel (3) renders the frame instead
 // band_first   the policy's own (rpt_kernels.hip.h): the band of tile rows that holds the meshes is dispatched first
 // msaa         the variant for MSAA > 1 (0: refused)
+// panorama     the variant with the equirectangular camera (rpt_set_projection; 0: none).  Only variant 0's choices and variant 3 have one:
+//              every other variant set explicitly is refused in panorama, whatever this column says
 enum : int { VARIANT_DEFAULT = 0, VARIANT_REF_LAYOUT = 1, VARIANT_UNCULLED = 3, VARIANT_BALLOT = 41, VARIANT_BALLOT_FIRST = 43,
-             VARIANT_ANALYTIC = 44, VARIANT_DOPPLER_RECORD = 240 };
+             VARIANT_ANALYTIC = 44, VARIANT_DOPPLER_RECORD = 240, VARIANT_PANORAMA_RECORD = 540 };
 struct VariantRow {
     int variant;
     bool settable;
@@ -703,29 +765,38 @@ struct VariantRow {
     bool window;
     bool band_first;
     int msaa;
+    int panorama;
 };
 #define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
 const VariantRow variant_table[] = {
-    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa
-    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0},
-    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47},
-    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46},
-    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46},
-    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46},
-    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0},
-    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0},
+    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa  pano
+    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0, 0},
+    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47, 303},
+    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46, 341},
+    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46, 341},
+    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46, 344},
+    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0, 0},
+    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0, 0},
     // 50 / 51 cull with the same regions but keep culling outside their window: a known gap (third item), kept as it is here
-    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0},
-    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0},
-    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0},
-    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0},
-    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0},
-    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0},
-    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0},
-    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0},
-    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0},
-    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0},
-    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0},
+    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0},
+    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0},
+    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0},
+    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0, 0},
+    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0, 0},
+    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0, 0},
+    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0, 0},
+    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0, 0},
+    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0, 0},
+    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0, 0},
+    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0, 0},
+    // the panorama kernels: reached through the panorama column only
+    {303, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),               0, nullptr,                                                  503, false, rptd::PanoramaUnculled::band_first,          0, 0},
+    {341, false, RPT_KERNEL(rpt_render_kernel_pano_w5),                        0, RPT_KERNEL(rpt_render_kernel_pano_ieee_w5),               541, false, rptd::PanoramaWalk::band_first,              0, 0},
+    {344, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),               0, nullptr,                                                  544, false, rptd::PanoramaAnalytic::band_first,          0, 0},
+    {503, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaUnculled>::band_first, 0, 0},
+    {540, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),         0, nullptr,                                                  0,   false, rptd::PanoramaRecorded::band_first,          0, 0},
+    {541, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),                0, RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5),       0,   false, rptd::DopplerTwin<rptd::PanoramaWalk>::band_first, 0, 0},
+    {544, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaAnalytic>::band_first, 0, 0},
 };
 #undef RPT_KERNEL
 
@@ -809,6 +880,18 @@ int launch(rpt_ctx *ctx) {
     if (!ctx->geo->compact_ok && v != VARIANT_ANALYTIC) v = VARIANT_REF_LAYOUT;
     const VariantRow *row = variant_row(v);
     if (row && !row->settable) row = nullptr;          // (the diagnostics library takes any number: the MSAA and Doppler forms are reached below only)
+    // The equirectangular camera (rpt_set_projection): variant 0's choice and variant 3 go to their panorama kernels (341 / 344, 303), whose
+    // rays leave the pinhole's proven window anyway; everything else refuses here, at the launch, like the kernels without a Doppler twin.
+    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
+    if (panorama) {
+        if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: variant " + std::to_string(ctx->variant) + " has no panorama kernel (variants 0 and 3 have)");
+        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: MSAA > 1 has no panorama kernel");
+        if (v == VARIANT_REF_LAYOUT || !row || !row->panorama)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: the panorama kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+        row = variant_row(v = row->panorama);
+        if (int rc = ensure_panorama_tables(ctx)) return rc;
+    }
     // The per-object regions are PROVEN for the window |u| <= 2, |v| <= 1/2 (rpt_bounds_certify.hpp): a frame wider than 4 : 1 has
     // pixels outside it, and beyond 2^20 pixels a side a tile's 1.5-pixel skirt is no longer large against float rounding — such
     // frames are rendered by the un-culled kernel (same pixels, every object tested everywhere).
@@ -829,13 +912,17 @@ int launch(rpt_ctx *ctx) {
         if (!row || !row->doppler)
             return fail(ctx, RPT_ERR_ARG, v == VARIANT_REF_LAYOUT ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
                                                                   : "rpt_set_doppler: this kernel variant has no Doppler twin");
-        row = variant_row(v = record ? VARIANT_DOPPLER_RECORD : row->doppler);
+        row = variant_row(v = record ? (panorama ? VARIANT_PANORAMA_RECORD : VARIANT_DOPPLER_RECORD) : row->doppler);
     }
     rptd::DopplerArgs da;         // (the twins' arguments: this frame's KernelArgs + the two Doppler fields)
     static_cast<rptd::KernelArgs &>(da) = a;
     da.doppler = ctx->doppler;
     da.debug_doppler = record;
     ctx->doppler_recorded = record != nullptr;
+    rptd::PanoramaArgs pa;        // (the panorama kernels' arguments: the above + the two tables)
+    static_cast<rptd::DopplerArgs &>(pa) = da;
+    pa.pano_cols = panorama ? (const float2 *)ctx->pano_tables.ptr : nullptr;
+    pa.pano_rows = panorama ? (const float2 *)ctx->pano_tables.ptr + ctx->width : nullptr;
     if (!row) {
 #ifdef RPT_DIAGNOSTICS
         if (int rc = launch_diagnostic(ctx, a, grid, tiles, v)) return rc;
@@ -845,7 +932,7 @@ int launch(rpt_ctx *ctx) {
     } else if (row->relaxed_waves) {
         if (rpt_launch_relaxed_kernel(row->relaxed_waves, &a, sizeof a, grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
     } else {
-        void *args[] = {ctx->doppler ? (void *)&da : (void *)&a};
+        void *args[] = {panorama ? (void *)&pa : (ctx->doppler ? (void *)&da : (void *)&a)};
         (void)hipLaunchKernel(row->ieee && !ctx->geo->exact_rcp_ok ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     }
     RPT_HIP(ctx, hipGetLastError());
@@ -918,9 +1005,11 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
+    if (ctx->pano_host) (void)hipHostFree(ctx->pano_host);
+    if (ctx->pano_copied) (void)hipEventDestroy(ctx->pano_copied);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -1139,6 +1228,31 @@ int rpt_set_debug_doppler(rpt_ctx *ctx, void *p) {
     if (!ctx) return RPT_ERR_ARG;
     ctx->want_owned_doppler = (p == (void *)1);
     ctx->external_doppler = ctx->want_owned_doppler ? nullptr : p;
+    return RPT_OK;
+}
+
+int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params) {
+    if (!ctx) return RPT_ERR_ARG;
+    float p[3] = {0, 0, 0};
+    if (mode == RPT_PROJECTION_PINHOLE) {
+        if (params) return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: RPT_PROJECTION_PINHOLE takes no parameters (NULL)");
+    } else if (mode == RPT_PROJECTION_EQUIRECT) {
+        if (!projection_params(params, p))
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: equirect parameters are {h_fov in (0, 2 pi], v_fov in (0, pi], finite yaw} in radians, or NULL");
+    } else {
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: mode is RPT_PROJECTION_PINHOLE or RPT_PROJECTION_EQUIRECT");
+    }
+    ctx->projection = mode;
+    if (std::memcmp(p, ctx->projection_params, sizeof p) != 0) ctx->pano_valid = false;
+    std::memcpy(ctx->projection_params, p, sizeof p);
+    return RPT_OK;
+}
+
+int rpt_projection_tables(int mode, const float *params, int width, int height, float *cols_out, float *rows_out) {
+    float p[3];
+    if (mode != RPT_PROJECTION_EQUIRECT || !projection_params(params, p)) return RPT_ERR_ARG;
+    if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 31) - 1 || !cols_out || !rows_out) return RPT_ERR_ARG;
+    projection_fill(p, width, height, cols_out, rows_out);
     return RPT_OK;
 }
 

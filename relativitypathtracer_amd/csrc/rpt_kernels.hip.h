@@ -144,6 +144,14 @@ struct DopplerArgs : KernelArgs {
     float *debug_doppler;           // the Doppler debug kernel only: RPT_DOPPLER_RECORD floats per pixel (rpt_set_debug_doppler)
 };
 
+// The panorama kernels' arguments (rpt_set_projection; not in the reference): DopplerArgs with the two tables of the equirectangular
+// camera appended, for the same reason — no other kernel's argument block changes.  Every panorama kernel takes them, its Doppler
+// twins and the others alike (doppler = 0 there).
+struct PanoramaArgs : DopplerArgs {
+    const float2 *pano_cols;        // [width]  {sin, cos} of the longitude of column x (global x)
+    const float2 *pano_rows;        // [height] {sin, cos} of the latitude of row y (global y: row tiles and tile patterns need nothing else)
+};
+
 struct Hit {                 // opencl_kernel.cl:38-44
     float dist;
     f3 normal;
@@ -161,6 +169,15 @@ RPT_DEV f3 createCamRayDir(float x_coord, float y_coord, int width, int height, 
     const float fx2 = (fx - 0.5f) * aspect_ratio;
     const float fy2 = fy - 0.5f;
     return normalize(mk3(fx2, fy2, 0.5f));
+}
+
+// The equirectangular camera (rpt_set_projection; not in the reference): p = (cos phi sin lambda, sin phi, cos phi cos lambda) from the
+// host's tables (rpt_projection_tables: (float) sin / cos of angles evaluated in double), three float products, then the pinhole's
+// normalize.  Yaw 0 looks down +z at the centre column; x grows towards +x, row 0 is the bottom.
+RPT_DEV f3 equirectCamDir(const PanoramaArgs &a, int x, int y) {
+    const float2 c = a.pano_cols[x];
+    const float2 r = a.pano_rows[y];
+    return normalize(mk3(r.y * c.x, r.x, r.y * c.y));
 }
 
 // opencl_kernel.cl:106-126
@@ -595,10 +612,16 @@ enum class Walk {
     throughput,      // octree_walk<false, ...>: one record at a time, the packed leaf count
     latency,         // octree_walk<true, ...>: records an iteration ahead, a leaf's first record with its node record
 };
+enum class Camera {
+    pinhole,         // createCamRayDir: the reference's image plane z = 0.5
+    equirect,        // equirectCamDir: the panorama tables (rpt_set_projection); the arguments are a PanoramaArgs
+};
 struct KernelPolicy {
     static constexpr Walk walk = Walk::throughput;
+    static constexpr Camera camera = Camera::pinhole;
     static constexpr bool exact_rcp = false;     // the triangle test's 1 / det through rcp_exact (the host picks it per scene)
     static constexpr bool culled = true;         // the wave's object mask (wave_object_mask) and the shadow-segment culls
+    static constexpr bool object_mask = true;    // ... of which the object mask, proven on the pinhole's image plane only (culled && object_mask)
     static constexpr bool band_first = false;    // the band of tile rows that holds the meshes is dispatched first (KernelArgs::first_h)
     static constexpr bool one_wave = true;       // one wave (an 8x8 tile) per workgroup, not four (a 32x8 strip)
     static constexpr bool doppler = false;       // the Doppler twin (rpt_set_doppler; the arguments are a DopplerArgs)
@@ -612,8 +635,16 @@ struct BallotExact : Ballot { static constexpr bool exact_rcp = true; };        
 struct BallotFirst : KernelPolicy { static constexpr Walk walk = Walk::latency; static constexpr bool band_first = true; };     // 49
 struct BallotFirstExact : BallotFirst { static constexpr bool exact_rcp = true; };                                              // 43
 struct Analytic : KernelPolicy { static constexpr Walk walk = Walk::none; };                                                    // 44
-template <class P> struct DopplerTwin : P { static constexpr bool doppler = true; };                                            // 2xx
+template <class P> struct DopplerTwin : P { static constexpr bool doppler = true; };                                            // 2xx, 5xx
 struct DopplerRecorded : DopplerTwin<Unculled> { static constexpr bool drec = true; };                                          // 240
+// the panorama kernels (rpt_set_projection): the equirectangular camera, no object mask (its regions live on the pinhole's plane), the
+// shadow-segment culls kept (they do not depend on the camera)
+template <class P> struct Panorama : P { static constexpr Camera camera = Camera::equirect; static constexpr bool object_mask = false; };
+struct PanoramaWalk : Panorama<BallotExact> {};                                                                                 // 341
+struct PanoramaWalkIeee : Panorama<Ballot> {};                                                                                  // (341 outside the domain)
+struct PanoramaAnalytic : Panorama<Analytic> {};                                                                                // 344
+struct PanoramaUnculled : Panorama<Unculled> {};                                                                                // 303
+struct PanoramaRecorded : Panorama<DopplerRecorded> {};                                                                         // 540
 
 template <class P>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
@@ -1160,7 +1191,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // the wave's object mask comes from a __ballot over ALL 64 lanes (lane i answers for object i), so it is formed
     // before the lanes of a partial tile leave
     unsigned long long object_mask = ~0ull;
-    if (P::culled) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    if (P::culled && P::object_mask) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
 #ifdef RPT_DIAGNOSTICS
     if (P::diag == 10) object_mask = a.tile_masks[__builtin_amdgcn_readfirstlane(tile_row * a.mask_tiles_x + (int)blockIdx.x * 4 + wave)];   // the prepass's per-tile mask
 #endif
@@ -1171,9 +1202,11 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     bool traced = false;
     [[maybe_unused]] DopplerRecord drec;
     uint32_t packed = a.bg_packed;
-    const bool masked = P::culled || P::diag == 10;
+    const bool masked = (P::culled && P::object_mask) || P::diag == 10;
     if (!masked || object_mask != 0 || a.object_count > 64) {
-        const f3 camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
+        f3 camdir;
+        if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(static_cast<const PanoramaArgs &>(a), x_coord, y_coord);
+        else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
         if (trace<P>(a, camdir, object_mask, color, P::drec ? &drec : nullptr)) {
             packed = tonemap_pack(a, color, mapped);
             traced = true;
@@ -1285,6 +1318,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_doppler_w8(const DopplerArgs a) { render_pixel_body<DopplerTwin<Analytic>>(a); }     // 244
 // the Doppler debug kernel (rpt_set_debug_doppler): 203 that also writes the per-pixel record; launched instead of any twin while the hook is set
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_doppler_record_w5(const DopplerArgs a) { render_pixel_body<DopplerRecorded>(a); }   // 240
+
+// Panorama kernels (rpt_set_projection with RPT_PROJECTION_EQUIRECT; not in the reference): the product kernels' shapes and occupancies
+// with the equirectangular camera and without the object mask.  341 takes 1 / det through rcp_exact like 41, with its IEEE form for
+// scenes outside the domain; 5xx are the Doppler twins, 540 the un-culled Doppler debug kernel.  DESIGN.md "Panorama camera".
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_w5(const PanoramaArgs a) { render_pixel_body<PanoramaWalk>(a); }                       // 341
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_ieee_w5(const PanoramaArgs a) { render_pixel_body<PanoramaWalkIeee>(a); }              // (341)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_pano_analytic_w8(const PanoramaArgs a) { render_pixel_body<PanoramaAnalytic>(a); }          // 344
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_unculled_w5(const PanoramaArgs a) { render_pixel_body<PanoramaUnculled>(a); }          // 303
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_doppler_w5(const PanoramaArgs a) { render_pixel_body<DopplerTwin<PanoramaWalk>>(a); }        // 541
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_ieee_doppler_w5(const PanoramaArgs a) { render_pixel_body<DopplerTwin<PanoramaWalkIeee>>(a); } // (541)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_pano_analytic_doppler_w8(const PanoramaArgs a) { render_pixel_body<DopplerTwin<PanoramaAnalytic>>(a); } // 544
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_unculled_doppler_w5(const PanoramaArgs a) { render_pixel_body<DopplerTwin<PanoramaUnculled>>(a); } // 503
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_doppler_record_w5(const PanoramaArgs a) { render_pixel_body<PanoramaRecorded>(a); }      // 540
 
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd

@@ -8,7 +8,8 @@ the eight buffer uploads of main.cpp:33-55 -> ``upload_scene``, ``initCLKernel``
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+import math
+from typing import Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -19,10 +20,31 @@ PIXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("rgba", "u1", (4,)), ("unsp
 TILE_ROWS = 8
 DOPPLER_SHIFT, DOPPLER_BEAMING = 1, 2     # rpt_set_doppler flags (include/rpt.h)
 DOPPLER_RECORD = 11                       # floats per pixel of the Doppler debug record
+PROJECTIONS = {"pinhole": 0, "equirect": 1}   # RPT_PROJECTION_* (include/rpt.h)
 
 
 class RenderError(RuntimeError):
     pass
+
+
+def _projection_args(mode: str, h_fov: float, v_fov: float, yaw: float):
+    if mode not in PROJECTIONS:
+        raise ValueError(f"projection is one of {sorted(PROJECTIONS)}, not {mode!r}")
+    params = None if mode == "pinhole" else (C.c_float * 3)(h_fov, v_fov, yaw)
+    return PROJECTIONS[mode], params
+
+
+def projection_tables(width: int, height: int, h_fov: float = 2 * math.pi, v_fov: float = math.pi, yaw: float = 0.0,
+                      mode: str = "equirect") -> Tuple[np.ndarray, np.ndarray]:
+    """The two tables the panorama kernels read for a width x height frame (rpt_projection_tables; host code, no device needed):
+    cols (width, 2) = {sin, cos} of each column's longitude, rows (height, 2) = {sin, cos} of each row's latitude, float32."""
+    m, params = _projection_args(mode, h_fov, v_fov, yaw)
+    cols = np.empty((max(int(width), 0), 2), dtype=np.float32)
+    rows = np.empty((max(int(height), 0), 2), dtype=np.float32)
+    rc = _ffi.hip().rpt_projection_tables(m, params, int(width), int(height), cols.ctypes.data, rows.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"rpt_projection_tables({mode!r}, {h_fov}, {v_fov}, {yaw}, {width}x{height}) failed ({rc})")
+    return cols, rows
 
 
 class Renderer:
@@ -116,6 +138,14 @@ class Renderer:
         turns it off again.  Kernels without a Doppler twin (variants 1, 50, 51, MSAA > 1) then refuse at the launch."""
         flags = (DOPPLER_SHIFT if shift else 0) | (DOPPLER_BEAMING if beaming else 0)
         self._check(self._lib.rpt_set_doppler(self._h, flags), "rpt_set_doppler")
+
+    def set_projection(self, mode: str = "pinhole", h_fov: float = 2 * math.pi, v_fov: float = math.pi, yaw: float = 0.0):
+        """The camera: "pinhole" (the reference's, the default) or "equirect", a panorama of h_fov x v_fov radians centred on longitude
+        yaw (0 = +z; include/rpt.h, rpt_set_projection).  Per context.  In panorama only variants 0 and 3 render, at MSAA 1."""
+        m, params = _projection_args(mode, h_fov, v_fov, yaw)
+        self._check(self._lib.rpt_set_projection(self._h, m, params), "rpt_set_projection")
+
+    projection_tables = staticmethod(projection_tables)
 
     def set_debug_doppler(self, enable: bool = True):
         """While enabled (and Doppler is on) frames come from the Doppler debug kernel, which writes the per-pixel record."""
@@ -279,10 +309,14 @@ class Renderer:
         return out
 
 
-def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False):
-    """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None)."""
+def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
+                 projection: Union[None, str, Mapping] = None):
+    """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None).  projection: None (the pinhole), a mode name
+    for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}."""
     r = Renderer(device)
     try:
+        if projection is not None:
+            r.set_projection(**({"mode": projection} if isinstance(projection, str) else dict(projection)))
         r.upload_scene(scene)
         r.set_scene_params(scene, width, height)
         r.set_output(None)
