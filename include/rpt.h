@@ -28,7 +28,9 @@
  * relativistic Doppler shift and searchlight beaming, which the reference does not render: rpt_set_doppler with its test hooks
  * rpt_set_debug_doppler / rpt_read_debug_doppler and rpt_probe which = 6 ("Doppler and beaming"), and the opt-in
  * equirectangular panorama camera, which the reference (a fixed pinhole looking down +z) does not have: rpt_set_projection and
- * rpt_projection_tables (host code, no device needed; DESIGN.md, "Panorama camera").
+ * rpt_projection_tables (host code, no device needed; DESIGN.md, "Panorama camera"), and the opt-in sky environment map, seen through a
+ * Lorentz matrix of its own (the reference paints every miss one constant colour): rpt_set_environment, rpt_set_environment_frame and
+ * rpt_probe which = 7 ("Environment map").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -155,6 +157,30 @@ int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params);
  * cos lambda_x}, rows_out 2 H floats {sin phi_y, cos phi_y}.  mode must be RPT_PROJECTION_EQUIRECT (the pinhole has no tables), params
  * as for rpt_set_projection, 1 <= W, H and W H < 2^31; anything else is RPT_ERR_ARG. */
 int rpt_projection_tables(int mode, const float *params, int width, int height, float *cols_out, float *rows_out);
+
+/* The sky (not in the reference; DESIGN.md "Environment map"), per context, off by default, not shared by rpt_share_scene.
+ * rgb8 is an equirectangular image of width x height interleaved R, G, B bytes, row 0 the top (+y), as object textures are; it is
+ * COPIED (the caller keeps its buffer).  NULL switches the sky off: the constant background and every kernel choice are those of a
+ * context that never had one.  width < 1, height < 1 or 3 width height >= 2^31 is RPT_ERR_ARG.  The image may be replaced or switched
+ * off while frames are in flight: the upload runs in stream order, so a frame already launched reads the image it was launched with.
+ * With a sky, a primary ray that hits nothing is no longer painted (0.15, 0.15, 0.25).  Its look-back path (interval, n), n the
+ * pixel's unit camera direction (pinhole or equirect), goes through the matrix E of rpt_set_environment_frame: k = E (interval, n),
+ * d = normalize(k.yzw), u = 0.5 + atan2(d.z, d.x) / 2 pi, v = asin(clamp(d.y, -1, 1)) / pi + 0.5 (the textured sphere's own (u, v): the
+ * image centre u = 1/2 looks down +x, +z is at u = 3/4, the seam u = 0 = 1 at -x), the colour is the bilinear fetch of the
+ * object textures except that the column neighbour wraps around, and with rpt_set_doppler on and interval != 0 it goes through the
+ * same colour operator with D = interval / k.x.  Then the tonemap, as for a hit pixel.  No ambient factor, no lights, no flash;
+ * the sky lights nothing and shadow rays ignore it.
+ * Kernels (rpt_last_variant): 641 / 643 / 644 / 603 stand in for 41 / 43 / 44 / 3, and 741 / 744 / 703 for the panorama's 341 / 344 /
+ * 303; each serves Doppler off and on (no separate twin; rpt_last_exact_rcp as for 41).  rpt_verify_frame compares with 603 / 703.
+ * Variants 1 and 48-51 set explicitly, MSAA > 1, the Doppler debug kernels (rpt_set_debug_doppler with Doppler on) and an octree whose
+ * children are not consecutive make rpt_render / rpt_render_async / rpt_verify_frame return RPT_ERR_ARG at the LAUNCH. */
+int rpt_set_environment(rpt_ctx *ctx, const unsigned char *rgb8, int width, int height);
+/* E: the Lorentz matrix from the camera frame to the rest frame of the sky, row-major, four rows, t first: the layout and meaning of
+ * Object.Lorentz.  For a sky at rest in the scene's frame it is the camera's inverse boost, inv_lorentz of
+ * rpt_scene_get_camera_lorentz, to be set every frame next to rpt_set_objects.  NULL = the identity (the default: the sky moves with
+ * the camera, a plain lookup of n).  A non-finite entry is RPT_ERR_ARG.  A kernel argument: a frame in flight keeps the matrix it
+ * was launched with. */
+int rpt_set_environment_frame(rpt_ctx *ctx, const float lorentz[16]);
 
 /* Kernel variant: 0 = default (fastest validated); the others select alternative implementations of the same path for
  * A/B measurement.  All produce identical results.
@@ -315,7 +341,9 @@ void rpt_free_host(void *p);
 /* Known-answer probes of individual device functions (tests): which = 0 intersect_triangle
  * (in 15 floats -> out 4), 1 intersect_AABB (12 -> 5), 2 createCamRay (4 -> 3), 3 hable (3 -> 3), 4 asin / atan2 of the
  * textured-sphere (u,v) (3 -> 2), 5 the walk's pure steps: exit face of a leaf and child selection, general and fast (6 -> 12),
- * 6 the Doppler kernels' colour operator S_f (5 -> 3: {D, r, g, b, flags as a float} -> the operated r, g, b). */
+ * 6 the Doppler kernels' colour operator S_f (5 -> 3: {D, r, g, b, flags as a float} -> the operated r, g, b),
+ * 7 the sky lookup alone on the context's current environment (3 -> 5: a direction {d.x, d.y, d.z} of the sky's rest frame, normalised
+ * by the probe, -> {u, v, r, g, b}; RPT_ERR_STATE without an environment). */
 int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int n);
 /* Test hook, one object's functions at ray level (the oracle's counterpart: rpt_oracle_object_rays): which = 0 n 4-D rays
  * {origin4, dir4} of object `object_index`'s rest frame through its intersector in the general form of opencl_kernel.cl:312-359 /

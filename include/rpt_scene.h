@@ -69,6 +69,11 @@ int rpt_scene_toggle_interval(rpt_scene *s);
 
 /* per-frame refresh of Object.Lorentz / InvLorentz / stationaryCam from the camera and object velocities */
 int rpt_scene_update_objects(rpt_scene *s);
+/* the two camera matrices of the last rpt_scene_update_objects, row-major, t first: lorentz = boost(v_cam) (scene frame -> camera
+ * frame) and inv_lorentz = boost(-v_cam) (camera frame -> scene frame), as an object of zero velocity receives them in
+ * Object.InvLorentz and Object.Lorentz.  inv_lorentz is what rpt_set_environment_frame (rpt.h) takes for a sky at rest in the
+ * scene's frame.  Either pointer may be null.  Fails (nonzero) before the first rpt_scene_update_objects. */
+int rpt_scene_get_camera_lorentz(const rpt_scene *s, float lorentz[16], float inv_lorentz[16]);
 
 /* views of the current buffers and scalars; pointers stay valid until the scene is next modified */
 int rpt_scene_get_desc(const rpt_scene *s, rpt_scene_desc *out);

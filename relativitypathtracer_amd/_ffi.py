@@ -102,6 +102,7 @@ def scene_lib() -> C.CDLL:
             "rpt_scene_set_interval": (I, [P, I]),
             "rpt_scene_toggle_interval": (I, [P]),
             "rpt_scene_update_objects": (I, [P]),
+            "rpt_scene_get_camera_lorentz": (I, [P, FP, FP]),
             "rpt_scene_get_desc": (I, [P, C.POINTER(SceneDesc)]),
             "rpt_scene_get_params": (I, [P, FP, FP, C.POINTER(C.c_int)]),
             "rpt_scene_get_velocities": (I, [P, C.POINTER(P), C.POINTER(C.c_size_t)]),
@@ -176,6 +177,8 @@ HIP_SYMBOLS = {
     "rpt_read_debug_doppler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_set_projection": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "rpt_projection_tables": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rpt_set_environment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "rpt_set_environment_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

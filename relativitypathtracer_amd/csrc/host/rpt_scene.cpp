@@ -354,6 +354,16 @@ void Scene::updateObjects() {
         o.stationaryCam = make_float4(dot(o.Lorentz[0], cameraPos), dot(o.Lorentz[1], cameraPos),
                                       dot(o.Lorentz[2], cameraPos), dot(o.Lorentz[3], cameraPos));
     }
+    // the same two products for an object of zero velocity: what a sky at rest in the scene's frame is seen through
+    rpt_object atRest = defaultObject();
+    setLorentzBoost(atRest, make_float3(0, 0, 0));
+    MatrixMultiplyLeft(atRest.Lorentz, cameraInvLorentz);
+    MatrixMultiplyRight(cameraLorentz, atRest.InvLorentz);
+    for (int r = 0; r < 4; r++) {
+        this->cameraInvLorentz[r] = atRest.Lorentz[r];
+        this->cameraLorentz[r] = atRest.InvLorentz[r];
+    }
+    cameraLorentzValid = true;
 }
 
 // Render.cpp:159-176 — one frame of held WASDQE keys: rapidity step tanh(ms/5000) along `direction`

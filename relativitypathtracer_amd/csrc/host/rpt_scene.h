@@ -73,6 +73,9 @@ struct Scene {
     std::string resolve(const std::string &path) const;
     rpt_scene_desc desc() const;
     bool finalized = false;
+    // the camera's matrices of the last updateObjects(), as an object of zero velocity receives them (rpt_scene_get_camera_lorentz)
+    rpt_float4 cameraLorentz[4] = {}, cameraInvLorentz[4] = {};
+    bool cameraLorentzValid = false;
 };
 
 bool ReadPPM(const std::string &path, TextureImage &out, std::string &err);

@@ -170,6 +170,14 @@ int rpt_scene_update_objects(rpt_scene *s) {
     RPT_END(s)
 }
 
+int rpt_scene_get_camera_lorentz(const rpt_scene *s, float lorentz[16], float inv_lorentz[16]) {
+    if (!s) return -1;
+    if (!s->scene.cameraLorentzValid) return 2;      // (no rpt_scene_update_objects yet; const scene: no error text to leave)
+    if (lorentz) std::memcpy(lorentz, s->scene.cameraLorentz, 16 * sizeof(float));
+    if (inv_lorentz) std::memcpy(inv_lorentz, s->scene.cameraInvLorentz, 16 * sizeof(float));
+    return 0;
+}
+
 int rpt_scene_get_desc(const rpt_scene *s, rpt_scene_desc *out) {
     if (!s || !out) return -1;
     *out = s->scene.desc();

@@ -143,6 +143,14 @@ struct rpt_ctx {
     hipEvent_t pano_copied = nullptr;                 // recorded after that copy: pano_host is rewritten only once it has passed
     bool pano_valid = false;                          // the device tables are those of (pano_width, pano_height, projection_params)
     int pano_width = 0, pano_height = 0;
+    // rpt_set_environment / rpt_set_environment_frame (not in the reference): the sky image, per context, never shared
+    bool env_on = false;
+    int env_width = 0, env_height = 0;
+    float env_frame[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // E, row-major, t first; a kernel ARGUMENT (a frame in flight keeps its own)
+    DeviceBuffer env_texels;                          // [env_width * env_height] dwords R | G << 8 | B << 16
+    uint32_t *env_host = nullptr;                     // pinned: what the last upload of the image was copied from
+    size_t env_host_capacity = 0;
+    hipEvent_t env_copied = nullptr;                  // recorded after that copy: env_host is rewritten only once it has passed
 };
 
 namespace {
@@ -753,6 +761,9 @@ int ensure_panorama_tables(rpt_ctx *ctx) {
 // msaa         the variant for MSAA > 1 (0: refused)
 // panorama     the variant with the equirectangular camera (rpt_set_projection; 0: none).  Only variant 0's choices and variant 3 have one:
 //              every other variant set explicitly is refused in panorama, whatever this column says
+// environment  the variant with the sky image (rpt_set_environment; 0: none): the kernels variant 0 can select and the un-culled one, in
+//              pinhole and panorama.  Looked up in the row chosen BEFORE the Doppler column: an environment kernel carries Doppler as a
+//              run-time flag and serves both
 enum : int { VARIANT_DEFAULT = 0, VARIANT_REF_LAYOUT = 1, VARIANT_UNCULLED = 3, VARIANT_BALLOT = 41, VARIANT_BALLOT_FIRST = 43,
              VARIANT_ANALYTIC = 44, VARIANT_DOPPLER_RECORD = 240, VARIANT_PANORAMA_RECORD = 540 };
 struct VariantRow {
@@ -766,37 +777,46 @@ struct VariantRow {
     bool band_first;
     int msaa;
     int panorama;
+    int environment;
 };
 #define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
 const VariantRow variant_table[] = {
-    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa  pano
-    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0, 0},
-    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47, 303},
-    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46, 341},
-    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46, 341},
-    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46, 344},
-    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0, 0},
-    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0, 0},
+    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa  pano env
+    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0, 0, 0},
+    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47, 303, 603},
+    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46, 341, 641},
+    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46, 341, 643},
+    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46, 344, 644},
+    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0, 0, 0},
+    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0, 0, 0},
     // 50 / 51 cull with the same regions but keep culling outside their window: a known gap (third item), kept as it is here
-    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0},
-    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0},
-    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0},
-    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0, 0},
-    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0, 0},
-    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0, 0},
-    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0, 0},
-    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0, 0},
-    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0, 0},
-    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0, 0},
-    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0, 0},
+    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0},
+    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0},
+    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0},
+    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0, 0, 0},
+    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0, 0, 0},
+    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0, 0, 0},
+    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0, 0, 0},
+    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0, 0, 0},
+    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0, 0, 0},
+    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0, 0, 0},
+    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0, 0, 0},
     // the panorama kernels: reached through the panorama column only
-    {303, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),               0, nullptr,                                                  503, false, rptd::PanoramaUnculled::band_first,          0, 0},
-    {341, false, RPT_KERNEL(rpt_render_kernel_pano_w5),                        0, RPT_KERNEL(rpt_render_kernel_pano_ieee_w5),               541, false, rptd::PanoramaWalk::band_first,              0, 0},
-    {344, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),               0, nullptr,                                                  544, false, rptd::PanoramaAnalytic::band_first,          0, 0},
-    {503, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaUnculled>::band_first, 0, 0},
-    {540, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),         0, nullptr,                                                  0,   false, rptd::PanoramaRecorded::band_first,          0, 0},
-    {541, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),                0, RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5),       0,   false, rptd::DopplerTwin<rptd::PanoramaWalk>::band_first, 0, 0},
-    {544, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaAnalytic>::band_first, 0, 0},
+    {303, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),               0, nullptr,                                                  503, false, rptd::PanoramaUnculled::band_first,          0, 0, 703},
+    {341, false, RPT_KERNEL(rpt_render_kernel_pano_w5),                        0, RPT_KERNEL(rpt_render_kernel_pano_ieee_w5),               541, false, rptd::PanoramaWalk::band_first,              0, 0, 741},
+    {344, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),               0, nullptr,                                                  544, false, rptd::PanoramaAnalytic::band_first,          0, 0, 744},
+    {503, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaUnculled>::band_first, 0, 0, 0},
+    {540, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),         0, nullptr,                                                  0,   false, rptd::PanoramaRecorded::band_first,          0, 0, 0},
+    {541, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),                0, RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5),       0,   false, rptd::DopplerTwin<rptd::PanoramaWalk>::band_first, 0, 0, 0},
+    {544, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaAnalytic>::band_first, 0, 0, 0},
+    // the environment kernels (rpt_set_environment): reached through the environment column only; each serves Doppler off and on
+    {603, false, RPT_KERNEL(rpt_render_kernel_env_unculled_w5),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Unculled>::band_first, 0, 0, 0},
+    {641, false, RPT_KERNEL(rpt_render_kernel_env_ballot_w5),                   0, RPT_KERNEL(rpt_render_kernel_env_ballot_ieee_w5),          0,   false, rptd::Environment<rptd::BallotExact>::band_first, 0, 0, 0},
+    {643, false, RPT_KERNEL(rpt_render_kernel_env_ballot_first_w5),             0, RPT_KERNEL(rpt_render_kernel_env_ballot_first_ieee_w5),    0,   false, rptd::Environment<rptd::BallotFirstExact>::band_first, 0, 0, 0},
+    {644, false, RPT_KERNEL(rpt_render_kernel_env_analytic_w8),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Analytic>::band_first, 0, 0, 0},
+    {703, false, RPT_KERNEL(rpt_render_kernel_env_pano_unculled_w5),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaUnculled>::band_first, 0, 0, 0},
+    {741, false, RPT_KERNEL(rpt_render_kernel_env_pano_w5),                     0, RPT_KERNEL(rpt_render_kernel_env_pano_ieee_w5),            0,   false, rptd::Environment<rptd::PanoramaWalk>::band_first, 0, 0, 0},
+    {744, false, RPT_KERNEL(rpt_render_kernel_env_pano_analytic_w8),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaAnalytic>::band_first, 0, 0, 0},
 };
 #undef RPT_KERNEL
 
@@ -907,7 +927,18 @@ int launch(rpt_ctx *ctx) {
     // Doppler on (rpt_set_doppler): every kernel chosen above goes to its twin, or to the debug kernel (240, un-culled) while the record
     // hook is set.  The kernels without a twin refuse here, at the launch: the setting may precede rpt_set_variant.
     float *const record = ctx->doppler ? (float *)(ctx->external_doppler ? ctx->external_doppler : (ctx->want_owned_doppler ? ctx->owned_doppler.ptr : nullptr)) : nullptr;
-    if (ctx->doppler) {
+    // The sky image (rpt_set_environment): the kernel chosen above goes to its environment form, which serves Doppler off and on.  What has
+    // none refuses here, at the launch, like the precedents: the setting may precede rpt_set_variant.
+    const bool environment = ctx->env_on;
+    if (environment) {
+        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_environment: MSAA > 1 has no environment kernel");
+        if (record) return fail(ctx, RPT_ERR_ARG, "rpt_set_environment: the Doppler debug kernels (rpt_set_debug_doppler) have no environment form");
+        if (!row || !row->environment)
+            return fail(ctx, RPT_ERR_ARG, v == VARIANT_REF_LAYOUT && ctx->variant != VARIANT_REF_LAYOUT
+                                              ? "rpt_set_environment: the environment kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)"
+                                              : "rpt_set_environment: variant " + std::to_string(ctx->variant) + " has no environment kernel (variants 0, 3, 41, 43 and 44 have)");
+        row = variant_row(v = row->environment);
+    } else if (ctx->doppler) {
         if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_doppler: MSAA > 1 has no Doppler kernel");
         if (!row || !row->doppler)
             return fail(ctx, RPT_ERR_ARG, v == VARIANT_REF_LAYOUT ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
@@ -923,6 +954,12 @@ int launch(rpt_ctx *ctx) {
     static_cast<rptd::DopplerArgs &>(pa) = da;
     pa.pano_cols = panorama ? (const float2 *)ctx->pano_tables.ptr : nullptr;
     pa.pano_rows = panorama ? (const float2 *)ctx->pano_tables.ptr + ctx->width : nullptr;
+    rptd::EnvironmentArgs ea;     // (the environment kernels' arguments: the above + the image and its frame)
+    static_cast<rptd::PanoramaArgs &>(ea) = pa;
+    ea.env_texels = environment ? (const uint32_t *)ctx->env_texels.ptr : nullptr;
+    ea.env_width = ctx->env_width;
+    ea.env_height = ctx->env_height;
+    std::memcpy(ea.env_frame, ctx->env_frame, sizeof ea.env_frame);
     if (!row) {
 #ifdef RPT_DIAGNOSTICS
         if (int rc = launch_diagnostic(ctx, a, grid, tiles, v)) return rc;
@@ -932,7 +969,7 @@ int launch(rpt_ctx *ctx) {
     } else if (row->relaxed_waves) {
         if (rpt_launch_relaxed_kernel(row->relaxed_waves, &a, sizeof a, grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
     } else {
-        void *args[] = {panorama ? (void *)&pa : (ctx->doppler ? (void *)&da : (void *)&a)};
+        void *args[] = {environment ? (void *)&ea : (panorama ? (void *)&pa : (ctx->doppler ? (void *)&da : (void *)&a))};
         (void)hipLaunchKernel(row->ieee && !ctx->geo->exact_rcp_ok ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     }
     RPT_HIP(ctx, hipGetLastError());
@@ -1005,11 +1042,13 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables, &ctx->env_texels})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     if (ctx->pano_host) (void)hipHostFree(ctx->pano_host);
     if (ctx->pano_copied) (void)hipEventDestroy(ctx->pano_copied);
+    if (ctx->env_host) (void)hipHostFree(ctx->env_host);
+    if (ctx->env_copied) (void)hipEventDestroy(ctx->env_copied);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -1253,6 +1292,51 @@ int rpt_projection_tables(int mode, const float *params, int width, int height, 
     if (mode != RPT_PROJECTION_EQUIRECT || !projection_params(params, p)) return RPT_ERR_ARG;
     if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 31) - 1 || !cols_out || !rows_out) return RPT_ERR_ARG;
     projection_fill(p, width, height, cols_out, rows_out);
+    return RPT_OK;
+}
+
+// The image goes to the device as one dword per texel, in stream order from a pinned buffer that is not rewritten before its previous
+// copy has run (the panorama tables' discipline): a frame still in flight reads the image it was launched with, a later one the new
+// one.  Switching off frees nothing (rpt_destroy does), so it cannot pull the image from under a frame either.
+int rpt_set_environment(rpt_ctx *ctx, const unsigned char *rgb8, int width, int height) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (!rgb8) {
+        ctx->env_on = false;
+        return RPT_OK;
+    }
+    if (width < 1 || height < 1 || 3ll * width * height >= (1ll << 31))
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_environment: width and height are >= 1 and 3 width height < 2^31");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t texels = (size_t)width * (size_t)height, bytes = texels * sizeof(uint32_t);
+    ctx->env_on = false;         // (until the new image is in place)
+    if (!ctx->env_copied) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->env_copied, hipEventDisableTiming));
+    else RPT_HIP(ctx, hipEventSynchronize(ctx->env_copied));
+    if (bytes > ctx->env_host_capacity) {
+        if (ctx->env_host) RPT_HIP(ctx, hipHostFree(ctx->env_host));
+        ctx->env_host = nullptr;
+        ctx->env_host_capacity = 0;
+        RPT_HIP(ctx, hipHostMalloc((void **)&ctx->env_host, bytes, hipHostMallocDefault));
+        ctx->env_host_capacity = bytes;
+    }
+    if (bytes > ctx->env_texels.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
+    if (int rc = reserve(ctx, ctx->env_texels, bytes)) return rc;
+    for (size_t i = 0; i < texels; i++)
+        ctx->env_host[i] = (uint32_t)rgb8[3 * i] | ((uint32_t)rgb8[3 * i + 1] << 8) | ((uint32_t)rgb8[3 * i + 2] << 16);
+    RPT_HIP(ctx, hipMemcpyAsync(ctx->env_texels.ptr, ctx->env_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(ctx->env_copied, ctx->stream));
+    ctx->env_width = width;
+    ctx->env_height = height;
+    ctx->env_on = true;
+    return RPT_OK;
+}
+
+int rpt_set_environment_frame(rpt_ctx *ctx, const float lorentz[16]) {
+    if (!ctx) return RPT_ERR_ARG;
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const float *m = lorentz ? lorentz : identity;
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(m[k])) return fail(ctx, RPT_ERR_ARG, "rpt_set_environment_frame: every entry must be finite");
+    std::memcpy(ctx->env_frame, m, sizeof ctx->env_frame);
     return RPT_OK;
 }
 
@@ -1651,8 +1735,9 @@ int rpt_read_wave_times(rpt_ctx *ctx, unsigned long long *out, size_t max_words,
 }
 
 int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int n) {
-    static const int in_w[7] = {15, 12, 4, 3, 3, 6, 5}, out_w[7] = {4, 5, 3, 3, 2, 12, 3};
-    if (!ctx || which < 0 || which > 6 || !host_in || !host_out || n <= 0) return RPT_ERR_ARG;
+    static const int in_w[8] = {15, 12, 4, 3, 3, 6, 5, 3}, out_w[8] = {4, 5, 3, 3, 2, 12, 3, 5};
+    if (!ctx || which < 0 || which > 7 || !host_in || !host_out || n <= 0) return RPT_ERR_ARG;
+    if (which == 7 && !ctx->env_on) return fail(ctx, RPT_ERR_STATE, "rpt_probe 7: the context has no environment (rpt_set_environment)");
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     float *d_in = nullptr, *d_out = nullptr;
     RPT_HIP(ctx, hipMalloc((void **)&d_in, sizeof(float) * in_w[which] * n));
@@ -1664,6 +1749,7 @@ int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int 
     if (hipMemcpy(d_in, host_in, sizeof(float) * in_w[which] * n, hipMemcpyHostToDevice) != hipSuccess) rc = RPT_ERR_DEVICE;
     if (!rc) {
         if (which == 6) hipLaunchKernelGGL(rptd::rpt_probe_doppler_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_in, d_out, n);
+        else if (which == 7) hipLaunchKernelGGL(rptd::rpt_probe_environment_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->env_texels.ptr, ctx->env_width, ctx->env_height, d_in, d_out, n);
         else hipLaunchKernelGGL(rptd::rpt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, which, d_in, d_out, n);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
             hipMemcpy(host_out, d_out, sizeof(float) * out_w[which] * n, hipMemcpyDeviceToHost) != hipSuccess)

@@ -152,6 +152,15 @@ struct PanoramaArgs : DopplerArgs {
     const float2 *pano_rows;        // [height] {sin, cos} of the latitude of row y (global y: row tiles and tile patterns need nothing else)
 };
 
+// The environment kernels' arguments (rpt_set_environment; not in the reference): PanoramaArgs with the sky image and its frame appended,
+// for the same reason again.  Every environment kernel takes them, pinhole and panorama, with Doppler on or off (they carry
+// `doppler` as a run-time flag: 0 there means no Doppler).
+struct EnvironmentArgs : PanoramaArgs {
+    const uint32_t *env_texels;     // [env_width * env_height] one dword per texel, R | G << 8 | B << 16, row 0 the top (+y)
+    int env_width, env_height;
+    rpt_float4 env_frame[4];        // E: camera frame -> the sky's rest frame, rows t, x, y, z (rpt_set_environment_frame)
+};
+
 struct Hit {                 // opencl_kernel.cl:38-44
     float dist;
     f3 normal;
@@ -626,6 +635,7 @@ struct KernelPolicy {
     static constexpr bool one_wave = true;       // one wave (an 8x8 tile) per workgroup, not four (a 32x8 strip)
     static constexpr bool doppler = false;       // the Doppler twin (rpt_set_doppler; the arguments are a DopplerArgs)
     static constexpr bool drec = false;          // ... that also writes the per-pixel Doppler record (the debug kernel only)
+    static constexpr bool environment = false;   // a pixel that hits nothing looks the sky image up (rpt_set_environment; the arguments are an EnvironmentArgs)
     static constexpr int diag = 0;               // the measurement arm's number (diagnostics build only); 0 in every product policy
 };
 struct RefLayout : KernelPolicy { static constexpr Walk walk = Walk::reference; static constexpr bool culled = false; };        // 1
@@ -645,6 +655,9 @@ struct PanoramaWalkIeee : Panorama<Ballot> {};                                  
 struct PanoramaAnalytic : Panorama<Analytic> {};                                                                                // 344
 struct PanoramaUnculled : Panorama<Unculled> {};                                                                                // 303
 struct PanoramaRecorded : Panorama<DopplerRecorded> {};                                                                         // 540
+// the environment kernels (rpt_set_environment): one family for Doppler off and on — the twin's code with EnvironmentArgs::doppler as a
+// run-time flag; with flags 0 S_f is the identity (doppler_colour returns its colour untouched), so the frame is the plain kernel's
+template <class P> struct Environment : DopplerTwin<P> { static constexpr bool environment = true; };                           // 6xx, 7xx
 
 template <class P>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
@@ -973,6 +986,56 @@ RPT_DEV f3 doppler_colour(int flags, float D, f3 c) {
     return o;
 }
 
+// ---- The sky (rpt_set_environment; not in the reference; DESIGN.md "Environment map") -------------------------------------------------
+// (u, v) of a unit direction d in the sky's rest frame: sphere_core's own two lines (the textured sphere's), with d.y clamped into
+// asin's domain first (a normalised d can exceed 1 by an ulp; a NaN passes through and ends on texel (0, 0) below).
+RPT_DEV f2 environment_uv(f3 d) {
+    const float dy = d.y < -1.0f ? -1.0f : (d.y > 1.0f ? 1.0f : d.y);
+    f2 uv;
+    uv.x = (float)(0.5f + rpt_atan2f(d.z, d.x) / (2 * RPT_PI_D));
+    uv.y = (float)(rpt_asinf(dy) / RPT_PI_D + 0.5f);
+    return uv;
+}
+RPT_DEV f3 environment_texel(const uint32_t *texels, int width, int x, int y) {
+    const uint32_t t = texels[(size_t)y * width + x];
+    return mk3((t & 255u) / 255.0f, ((t >> 8) & 255u) / 255.0f, ((t >> 16) & 255u) / 255.0f);
+}
+// sample_texture's four taps in its order, on the sky image: the column neighbour WRAPS (x + 1 == W -> 0, x - 1 == -1 -> W - 1; u = 0 and
+// u = 1 are the same meridian), rows clamp as there.  x and y are clamped into the image on BOTH sides before they address anything
+// (f2i_sat: NaN -> 0), so no direction, finite or not, reads outside the width * height dwords.
+RPT_DEV f3 environment_bilinear(const uint32_t *texels, int width, int height, f2 uv) {
+    const float u = width * uv.x;
+    const float v = height * (1.0f - uv.y);
+    int x = iclamp(f2i_sat(__builtin_floorf(u)), 0, width - 1);
+    int y = iclamp(f2i_sat(__builtin_floorf(v)), 0, height - 1);
+    const float u_ratio = u - x;
+    const float v_ratio = v - y;
+    const float u_opp = 1 - u_ratio;
+    const float v_opp = 1 - v_ratio;
+    f3 result = environment_texel(texels, width, x, y) * u_opp;
+    x = x + 1 >= width ? 0 : x + 1;
+    result = result + environment_texel(texels, width, x, y) * u_ratio;
+    result = result * v_opp;
+    y = iclamp(y + 1, 0, height - 1);
+    f3 result2 = environment_texel(texels, width, x, y) * u_ratio;
+    x = x - 1 < 0 ? width - 1 : x - 1;
+    result2 = result2 + environment_texel(texels, width, x, y) * u_opp;
+    result2 = result2 * v_ratio;
+    return result + result2;
+}
+// A primary ray that hit nothing: its look-back path (interval, n) goes through E into the sky's rest frame, the spatial part is the
+// direction the image is looked up at, and with Doppler on the time parts give D_env = interval / k.x exactly as D_cam comes from an
+// object's Lorentz[0] (interval 0: D_env := 1, nothing to shift).  No ambient factor, no lights, no flash.
+RPT_DEV f3 environment_colour(const EnvironmentArgs &a, f3 camdir) {
+    const f3 nd = normalize(camdir);             // (trace()'s own first line: the same float triple)
+    const f4 rayDir = mk4((float)a.interval, nd.x, nd.y, nd.z);
+    const f4 k = transformPoint4D(a.env_frame, rayDir);
+    const f3 d = normalize(yzw(k));
+    f3 c = environment_bilinear(a.env_texels, a.env_width, a.env_height, environment_uv(d));
+    if (a.doppler != 0 && a.interval != 0) c = doppler_colour(a.doppler, (float)a.interval / k.x, c);
+    return c;
+}
+
 // What the Doppler debug kernel records per hit pixel (rpt_set_debug_doppler)
 struct DopplerRecord {
     float dcam, dlight;      // camera factor; light factor of the first light that contributed (1 if none)
@@ -1203,7 +1266,16 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     [[maybe_unused]] DopplerRecord drec;
     uint32_t packed = a.bg_packed;
     const bool masked = (P::culled && P::object_mask) || P::diag == 10;
-    if (!masked || object_mask != 0 || a.object_count > 64) {
+    if constexpr (P::environment) {
+        // every pixel has a colour of its own: the camera direction is formed for all, and a wave whose object mask is empty goes
+        // straight to the sky (no object loop, no scene load)
+        f3 camdir;
+        if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(static_cast<const PanoramaArgs &>(a), x_coord, y_coord);
+        else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
+        if (!masked || object_mask != 0 || a.object_count > 64) traced = trace<P>(a, camdir, object_mask, color);
+        if (!traced) color = environment_colour(static_cast<const EnvironmentArgs &>(a), camdir);
+        packed = tonemap_pack(a, color, mapped);
+    } else if (!masked || object_mask != 0 || a.object_count > 64) {
         f3 camdir;
         if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(static_cast<const PanoramaArgs &>(a), x_coord, y_coord);
         else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
@@ -1230,7 +1302,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // (the 4-byte plane likewise: measured against the default policy on a rank's share of the frame, bunny 4K 0.0581 -> 0.0566 ms, shadows the same)
     if (a.plane) __builtin_nontemporal_store(packed, a.plane + (size_t)local_row * a.width + x_coord);
     if (a.debug_rgb) {
-        if (!traced) mapped = mk3(a.bg_mapped[0], a.bg_mapped[1], a.bg_mapped[2]);      // (read here only: a miss pixel's store needs nothing beyond the first line of the arguments)
+        if (!traced && !P::environment) mapped = mk3(a.bg_mapped[0], a.bg_mapped[1], a.bg_mapped[2]);      // (read here only: a miss pixel's store needs nothing beyond the first line of the arguments)
         a.debug_rgb[3 * id + 0] = mapped.x;
         a.debug_rgb[3 * id + 1] = mapped.y;
         a.debug_rgb[3 * id + 2] = mapped.z;
@@ -1331,6 +1403,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_pano_analytic_doppler_w8(const PanoramaArgs a) { render_pixel_body<DopplerTwin<PanoramaAnalytic>>(a); } // 544
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_unculled_doppler_w5(const PanoramaArgs a) { render_pixel_body<DopplerTwin<PanoramaUnculled>>(a); } // 503
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_pano_doppler_record_w5(const PanoramaArgs a) { render_pixel_body<PanoramaRecorded>(a); }      // 540
+
+// Environment kernels (rpt_set_environment; not in the reference): the kernels variant 0 can select and the un-culled one, pinhole (6xx)
+// and panorama (7xx), each serving Doppler off and on through the run-time flag.  DESIGN.md "Environment map".
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_unculled_w5(const EnvironmentArgs a) { render_pixel_body<Environment<Unculled>>(a); }                  // 603
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_ballot_w5(const EnvironmentArgs a) { render_pixel_body<Environment<BallotExact>>(a); }                 // 641
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_ballot_ieee_w5(const EnvironmentArgs a) { render_pixel_body<Environment<Ballot>>(a); }                 // (641)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_ballot_first_w5(const EnvironmentArgs a) { render_pixel_body<Environment<BallotFirstExact>>(a); }      // 643
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_ballot_first_ieee_w5(const EnvironmentArgs a) { render_pixel_body<Environment<BallotFirst>>(a); }      // (643)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_env_analytic_w8(const EnvironmentArgs a) { render_pixel_body<Environment<Analytic>>(a); }                  // 644
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_pano_unculled_w5(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaUnculled>>(a); }     // 703
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_pano_w5(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaWalk>>(a); }                  // 741
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_pano_ieee_w5(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaWalkIeee>>(a); }         // (741)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_env_pano_analytic_w8(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaAnalytic>>(a); }     // 744
 
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd
@@ -1479,6 +1564,17 @@ __global__ __launch_bounds__(256) void rpt_probe_doppler_kernel(const float *in,
     out[3 * i + 0] = o.x;
     out[3 * i + 1] = o.y;
     out[3 * i + 2] = o.z;
+}
+
+// rpt_probe which = 7: the sky lookup alone on n directions {d.x, d.y, d.z} of the sky's rest frame (normalised here, as the render path
+// normalises E's output) -> {u, v, r, g, b}
+__global__ __launch_bounds__(256) void rpt_probe_environment_kernel(const uint32_t *texels, int width, int height, const float *in, float *out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f2 uv = environment_uv(normalize(mk3(in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2])));
+    const f3 c = environment_bilinear(texels, width, height, uv);
+    float *o = out + 5 * (size_t)i;
+    o[0] = uv.x; o[1] = uv.y; o[2] = c.x; o[3] = c.y; o[4] = c.z;
 }
 
 // The exact reciprocal against IEEE 1 / s (rpt_probe_reciprocal): every float s whose bit pattern lies in [lo_bits, lo_bits + per_sign),

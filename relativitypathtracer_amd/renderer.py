@@ -147,6 +147,28 @@ class Renderer:
 
     projection_tables = staticmethod(projection_tables)
 
+    def set_environment(self, image: Optional[np.ndarray]):
+        """The sky: an equirectangular H x W x 3 uint8 image (row 0 the top), copied by the library; None switches it off (the constant
+        background again).  Per context.  Seen through the matrix of set_environment_frame (include/rpt.h, rpt_set_environment)."""
+        if image is None:
+            self._check(self._lib.rpt_set_environment(self._h, None, 0, 0), "rpt_set_environment")
+            return
+        img = np.ascontiguousarray(image)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"the environment is an H x W x 3 uint8 array, not {img.dtype} {img.shape}")
+        self._check(self._lib.rpt_set_environment(self._h, img.ctypes.data, int(img.shape[1]), int(img.shape[0])), "rpt_set_environment")
+
+    def set_environment_frame(self, matrix=None):
+        """E, the 4 x 4 Lorentz matrix from the camera frame to the sky's rest frame (rows t, x, y, z); None = the identity.  For a sky
+        at rest in the scene's frame: Scene.camera_lorentz()[1], every frame."""
+        if matrix is None:
+            self._check(self._lib.rpt_set_environment_frame(self._h, None), "rpt_set_environment_frame")
+            return
+        m = np.ascontiguousarray(matrix, dtype=np.float32)
+        if m.size != 16:
+            raise ValueError("the environment frame is a 4 x 4 matrix")
+        self._check(self._lib.rpt_set_environment_frame(self._h, m.ctypes.data_as(C.POINTER(C.c_float))), "rpt_set_environment_frame")
+
     def set_debug_doppler(self, enable: bool = True):
         """While enabled (and Doppler is on) frames come from the Doppler debug kernel, which writes the per-pixel record."""
         self._check(self._lib.rpt_set_debug_doppler(self._h, C.c_void_p(1 if enable else 0)), "rpt_set_debug_doppler")
@@ -310,13 +332,17 @@ class Renderer:
 
 
 def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
-                 projection: Union[None, str, Mapping] = None):
+                 projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None).  projection: None (the pinhole), a mode name
-    for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}."""
+    for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}.  environment: an
+    H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first)."""
     r = Renderer(device)
     try:
         if projection is not None:
             r.set_projection(**({"mode": projection} if isinstance(projection, str) else dict(projection)))
+        if environment is not None:
+            r.set_environment(environment)
+            r.set_environment_frame(scene.camera_lorentz()[1])
         r.upload_scene(scene)
         r.set_scene_params(scene, width, height)
         r.set_output(None)

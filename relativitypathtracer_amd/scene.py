@@ -151,6 +151,17 @@ class Scene:
         """Per-frame refresh of Object.Lorentz / InvLorentz / stationaryCam (Render.cpp:179-200)."""
         self._check(self._lib.rpt_scene_update_objects(self._h), "update_objects")
 
+    def camera_lorentz(self):
+        """(lorentz, inv_lorentz): the camera's two 4x4 float32 matrices of the last update_objects() (rows t, x, y, z).  inv_lorentz is
+        what Renderer.set_environment_frame takes for a sky at rest in the scene's frame.  Raises before the first update_objects()."""
+        lorentz = np.empty((4, 4), dtype=np.float32)
+        inv = np.empty((4, 4), dtype=np.float32)
+        FP = C.POINTER(C.c_float)
+        rc = self._lib.rpt_scene_get_camera_lorentz(self._h, lorentz.ctypes.data_as(FP), inv.ctypes.data_as(FP))
+        if rc != 0:
+            raise SceneError("camera_lorentz() before the first update_objects()")
+        return lorentz, inv
+
     # -- views ----------------------------------------------------------------------------
     def desc(self) -> _ffi.SceneDesc:
         d = _ffi.SceneDesc()
