@@ -3,7 +3,11 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//
+// --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
+// rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
+// context, made once, BEFORE the objects are handed over; the per-frame loop stays the reference's.
 //
 // With `frames` > 1 the clock runs (16 ms per frame, as the reference's timer does) and the frames are rendered with
 // `in_flight` of them overlapping on the GPU: rpt::FrameRing (include/rpt_frames.hpp) — one context per frame slot
@@ -12,7 +16,9 @@
 // Textures are read with the library's built-in binary PPM reader (convert the JPEGs first, e.g. with
 // Pillow) — decoding JPEG is the job of CImg/libjpeg in the reference and is outside the render path.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 #include <iostream>
 #include <iterator>
@@ -25,8 +31,27 @@
 #include "rpt_scene.h"
 
 int main(int argc, char **argv) {
+    // the free-look options (degrees), taken out of argv; what is left is positional
+    float ypr[3] = {0, 0, 0}, v_fov = 0;
+    bool turned = false;
+    {
+        const double deg = 3.14159265358979323846 / 180.0;
+        int kept = 1;
+        for (int i = 1; i < argc; i++) {
+            const bool has_value = i + 1 < argc;
+            if (has_value && !std::strcmp(argv[i], "--yaw")) { ypr[0] = (float)(std::atof(argv[++i]) * deg); turned = true; }
+            else if (has_value && !std::strcmp(argv[i], "--pitch")) { ypr[1] = (float)(std::atof(argv[++i]) * deg); turned = true; }
+            else if (has_value && !std::strcmp(argv[i], "--roll")) { ypr[2] = (float)(std::atof(argv[++i]) * deg); turned = true; }
+            else if (has_value && !std::strcmp(argv[i], "--fov")) v_fov = (float)(std::atof(argv[++i]) * deg);
+            else if (!std::strcmp(argv[i], "--yaw") || !std::strcmp(argv[i], "--pitch") || !std::strcmp(argv[i], "--roll") || !std::strcmp(argv[i], "--fov")) {
+                std::fprintf(stderr, "%s needs a value (degrees)\n", argv[i]);
+                return 2;
+            } else argv[kept++] = argv[i];
+        }
+        argc = kept;
+    }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -55,7 +80,10 @@ int main(int argc, char **argv) {
     float wp[3], ambient;
     int interval;
     rpt_scene_get_params(scene, wp, &ambient, &interval);
-    int rc = rpt_upload_scene(ctx, &desc);                       // 8x cl::Buffer + write    main.cpp:33-55
+    int rc = RPT_OK;
+    if (turned) rc = rpt_set_orientation(ctx, ypr);              // the context's view: before any Object[] is handed over
+    if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ctx, v_fov);
+    if (!rc) rc = rpt_upload_scene(ctx, &desc);                  // 8x cl::Buffer + write    main.cpp:33-55
     if (!rc) rc = rpt_set_params(ctx, wp, ambient, width, height, interval);   // initCLKernel()  main.cpp:62
     if (!rc) rc = rpt_set_output(ctx, nullptr);                  // BufferGL(vbo)           main.cpp:58
     if (!rc) rc = rpt_set_objects(ctx, desc.objects, (int)desc.object_count);   //          Render.cpp:202
@@ -73,6 +101,10 @@ int main(int argc, char **argv) {
         ring_owner.reset(new rpt::FrameRing(0, in_flight));
         rpt::FrameRing &ring = *ring_owner;
         rc = ring.status();
+        for (int k = 0; k < ring.frames_in_flight() && !rc; k++) {      // the view is per context: every frame slot gets it
+            if (turned) rc = rpt_set_orientation(ring.slot(k), ypr);
+            if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ring.slot(k), v_fov);
+        }
         if (!rc) rc = ring.upload(desc);
         if (!rc) rc = ring.set_params(wp, ambient, width, height, interval);
         rpt_scene_set_paused(scene, 0);

@@ -30,7 +30,8 @@
  * equirectangular panorama camera, which the reference (a fixed pinhole looking down +z) does not have: rpt_set_projection and
  * rpt_projection_tables (host code, no device needed; DESIGN.md, "Panorama camera"), and the opt-in sky environment map, seen through a
  * Lorentz matrix of its own (the reference paints every miss one constant colour): rpt_set_environment, rpt_set_environment_frame and
- * rpt_probe which = 7 ("Environment map").
+ * rpt_probe which = 7 ("Environment map"), and the opt-in free-look camera — an orientation and a pinhole zoom: rpt_set_orientation,
+ * rpt_set_field_of_view, and rpt_orient_objects / rpt_orient_matrix (host code, no device needed; DESIGN.md, "Free-look camera").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -181,6 +182,52 @@ int rpt_set_environment(rpt_ctx *ctx, const unsigned char *rgb8, int width, int 
  * the camera, a plain lookup of n).  A non-finite entry is RPT_ERR_ARG.  A kernel argument: a frame in flight keeps the matrix it
  * was launched with. */
 int rpt_set_environment_frame(rpt_ctx *ctx, const float lorentz[16]);
+
+/* The free-look camera (not in the reference, whose camera looks down +z through a fixed 90-degree lens; DESIGN.md "Free-look camera"):
+ * an orientation and a pinhole zoom, per context, both off by default, not shared by rpt_share_scene.
+ *
+ * rpt_set_orientation: ypr = {yaw, pitch, roll} in radians, each finite (else RPT_ERR_ARG); NULL = none (the same as three zeros).
+ * R = Ry(yaw) Rx(pitch) Rz(roll), evaluated in double from the float angles, with
+ *     Ry = | c 0 s |    Rx = | 1  0 0 |    Rz = |  c s 0 |
+ *          | 0 1 0 |         | 0  c s |         | -s c 0 |
+ *          |-s 0 c |         | 0 -s c |         |  0 0 1 |
+ * A direction n of the turned camera (pixel directions are formed exactly as before) is the direction R n of the camera the caller's
+ * Object[] was computed for; the view direction is R (0, 0, 1).  The convention continues the panorama's yaw:
+ *   yaw   = +pi/2 alone: R (0,0,1) = (1,0,0)  — the view has turned towards +x, what was on the right is in the image centre;
+ *   pitch = +pi/2 alone: R (0,0,1) = (0,1,0)  — the view has turned towards +y, the camera looks straight up;
+ *   roll  = +pi/2 alone: R (0,0,1) = (0,0,1), R (1,0,0) = (0,-1,0), R (0,1,0) = (1,0,0) — the view direction stays and the IMAGE turns
+ *                        counter-clockwise by a quarter turn: what was up (+y) is drawn on the left.
+ * The camera direction enters the path through Object.Lorentz (and leaves it through Object.InvLorentz) only, so the turn is a change
+ * of basis of the camera frame, applied by the library to its COPY of every Object[] it is given from then on (rpt_set_objects, the
+ * Object[] of rpt_upload_scene, the owner's objects in rpt_share_scene):
+ *     Lorentz' = Lorentz diag(1, R),    InvLorentz' = diag(1, R^T) InvLorentz,    stationaryCam and everything else unchanged,
+ * each entry the three-term sum, in double, of float entries times double entries of R, rounded to float once (rpt_orient_objects is
+ * that arithmetic as host code).  Screen regions, their proofs, the per-object records and the shadow culls are derived from the
+ * re-based objects like from any other Object[]; no kernel choice changes and nothing is refused.  The call itself re-derives them
+ * at once from a kept copy of the caller's last Object[]: it takes effect at the next launch whether it comes before or after
+ * rpt_set_objects.  With R = I the device holds the caller's bytes.  The sky's matrix is re-based at the launch (E' = E diag(1, R)): a
+ * sky at rest in the scene stays at rest when the head turns.  In panorama the turn composes with the projection's own yaw: pixel
+ * direction p of rpt_set_projection looks along R p.  The test hooks that read the context's objects (rpt_probe_object,
+ * rpt_mesh_segment_cull_record, rpt_verify_frame) see the re-based ones.
+ *
+ * rpt_set_field_of_view: the pinhole's vertical field of view in radians, 0.01 <= v_fov <= 3.0 (else RPT_ERR_ARG); 0 = the reference's
+ * lens (the default).  s = (float)tan((double)v_fov / 2); pixel (x, y) looks along normalize(s * fx2, s * fy2, 0.5f) with fx2, fy2 as
+ * the reference forms them (opencl_kernel.cl:57-63): two more float products.  v_fov = (float)(pi/2) gives s = 1.0f and the
+ * reference's frame bit for bit.  Frames with a lens set are rendered by the lens kernels (rpt_last_variant): 841 / 843 / 844 / 803
+ * stand in for 41 / 43 / 44 / 3 (841 and 843 with IEEE forms, rpt_last_exact_rcp as for 41), 851 / 853 / 854 / 813 for their Doppler
+ * twins and 861 / 863 / 864 / 823 for the environment kernels.  The culled ones run while the lens keeps every pixel inside the window
+ * the screen regions are proven for (s <= 1 and s * width / height / 2 <= 2); a wider lens is rendered by the un-culled lens kernel.
+ * With a lens set, the panorama (it has its own fields of view), MSAA > 1, variants other than 0, 3, 41, 43, 44, the Doppler debug
+ * kernel (rpt_set_debug_doppler with Doppler on) and an octree whose children are not consecutive make rpt_render / rpt_render_async
+ * / rpt_verify_frame return RPT_ERR_ARG at the LAUNCH; the call itself accepts any valid angle.  (rpt_verify_frame sets the record hook
+ * aside and compares the Doppler twins, as it does without a lens: it never launches the debug kernel, so the hook does not refuse it.) */
+int rpt_set_orientation(rpt_ctx *ctx, const float ypr[3]);
+int rpt_set_field_of_view(rpt_ctx *ctx, float v_fov);
+/* Host code, no device: the re-basing above on `count` 320-B objects (objects_out may be objects_in) and on one 4 x 4 matrix of the
+ * layout of Object.Lorentz (E of rpt_set_environment_frame).  ypr = NULL or three zeros (any R that is exactly I): the output bytes
+ * equal the input bytes.  A non-finite angle, a null pointer with count > 0, count < 0: RPT_ERR_ARG. */
+int rpt_orient_objects(const void *objects_in, int count, const float ypr[3], void *objects_out);
+int rpt_orient_matrix(const float lorentz_in[16], const float ypr[3], float lorentz_out[16]);
 
 /* Kernel variant: 0 = default (fastest validated); the others select alternative implementations of the same path for
  * A/B measurement.  All produce identical results.

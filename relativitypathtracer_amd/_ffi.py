@@ -179,6 +179,10 @@ HIP_SYMBOLS = {
     "rpt_projection_tables": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rpt_set_environment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rpt_set_environment_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_orientation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_field_of_view": (C.c_int, [C.c_void_p, C.c_float]),
+    "rpt_orient_objects": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
+    "rpt_orient_matrix": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

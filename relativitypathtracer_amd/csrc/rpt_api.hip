@@ -151,6 +151,13 @@ struct rpt_ctx {
     uint32_t *env_host = nullptr;                     // pinned: what the last upload of the image was copied from
     size_t env_host_capacity = 0;
     hipEvent_t env_copied = nullptr;                  // recorded after that copy: env_host is rewritten only once it has passed
+    // rpt_set_orientation / rpt_set_field_of_view (not in the reference): the free-look camera, per context, never shared
+    bool oriented = false;                            // R != I: host_objects (and the device's Object[]) are the RE-BASED objects
+    double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    std::vector<uint8_t> caller_objects;              // while oriented: the caller's last Object[] as it was given (else host_objects is that)
+    std::vector<uint8_t> given_scratch, turned_scratch;   // rpt_set_objects with an orientation: reused from frame to frame (no allocation per call)
+    float v_fov = 0.0f;                               // 0 = the reference's lens
+    float lens_scale = 1.0f;                          // (float)tan(v_fov / 2)
 };
 
 namespace {
@@ -530,6 +537,61 @@ void build_rects(rpt_ctx *ctx, const rpt_object *objs, int count, rptb::Rect *ou
     ctx->rect_geo_generation = ctx->geo->generation;
 }
 
+// ---- the free-look camera's orientation (rpt_set_orientation, rpt_orient_objects) ---------------------------------------------------
+// R = Ry(yaw) Rx(pitch) Rz(roll) in double from the float angles (include/rpt.h has the three matrices and a worked example of each).
+// false: a non-finite angle.  NULL = three zeros = the exact identity (sin 0 = 0, cos 0 = 1).
+bool orientation_matrix(const float *ypr, double R[3][3]) {
+    const double y = ypr ? (double)ypr[0] : 0.0, p = ypr ? (double)ypr[1] : 0.0, r = ypr ? (double)ypr[2] : 0.0;
+    if (!std::isfinite(y) || !std::isfinite(p) || !std::isfinite(r)) return false;
+    const double cy = std::cos(y), sy = std::sin(y), cp = std::cos(p), sp = std::sin(p), cr = std::cos(r), sr = std::sin(r);
+    const double Ry[3][3] = {{cy, 0, sy}, {0, 1, 0}, {-sy, 0, cy}}, Rx[3][3] = {{1, 0, 0}, {0, cp, sp}, {0, -sp, cp}}, Rz[3][3] = {{cr, sr, 0}, {-sr, cr, 0}, {0, 0, 1}};
+    double T[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) T[i][j] = Rx[i][0] * Rz[0][j] + Rx[i][1] * Rz[1][j] + Rx[i][2] * Rz[2][j];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R[i][j] = Ry[i][0] * T[0][j] + Ry[i][1] * T[1][j] + Ry[i][2] * T[2][j];
+    return true;
+}
+
+bool is_identity(const double R[3][3]) {
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            if (R[i][j] != (i == j ? 1.0 : 0.0)) return false;
+    return true;
+}
+
+// out = m diag(1, R) for a matrix of Object.Lorentz's layout (four rows, t first): column 0 kept, entry (r, 1 + c) the three-term sum in
+// double of the row's float space entries times R's column c, rounded to float once.  out may be m.
+void rebase_columns(const rpt_float4 m[4], const double R[3][3], rpt_float4 out[4]) {
+    for (int r = 0; r < 4; r++) {
+        const double l[3] = {m[r].y, m[r].z, m[r].w};
+        float o[3];
+        for (int c = 0; c < 3; c++) o[c] = (float)(l[0] * R[0][c] + l[1] * R[1][c] + l[2] * R[2][c]);
+        out[r].x = m[r].x; out[r].y = o[0]; out[r].z = o[1]; out[r].w = o[2];
+    }
+}
+
+// out = diag(1, R^T) m: row 0 kept, entry (1 + r, c) the three-term sum in double of R's column r times the float entries of column c
+void rebase_rows(const rpt_float4 m[4], const double R[3][3], rpt_float4 out[4]) {
+    float o[3][4];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++)
+            o[r][c] = (float)(R[0][r] * (double)(&m[1].x)[c] + R[1][r] * (double)(&m[2].x)[c] + R[2][r] * (double)(&m[3].x)[c]);
+    out[0] = m[0];
+    for (int r = 0; r < 3; r++) { out[r + 1].x = o[r][0]; out[r + 1].y = o[r][1]; out[r + 1].z = o[r][2]; out[r + 1].w = o[r][3]; }
+}
+
+// The change of basis of the camera frame on `count` objects: Lorentz' = Lorentz diag(1, R), InvLorentz' = diag(1, R^T) InvLorentz, every
+// other byte copied.  The exact identity copies everything (so -0.0f and non-finite entries keep their bytes).  out may be in.
+void orient_objects(const rpt_object *in, int count, const double R[3][3], rpt_object *out) {
+    if (out != in) std::memmove(out, in, (size_t)count * sizeof(rpt_object));
+    if (is_identity(R)) return;
+    for (int i = 0; i < count; i++) {
+        rebase_columns(out[i].Lorentz, R, out[i].Lorentz);
+        rebase_rows(out[i].InvLorentz, R, out[i].InvLorentz);
+    }
+}
+
 int validate_objects(rpt_ctx *ctx, const rpt_object *objs, int count) {
     for (int i = 0; i < count; i++) {
         const rpt_object &o = objs[i];
@@ -590,6 +652,9 @@ bool mesh_band(const rpt_ctx *ctx, float aspect, int tile_rows, int &ty0, int &t
             v1 = std::max(v1, ctx->rects[i].v1);
         }
     if (!(v0 <= v1)) return false;
+    // under a lens row y looks through v = s (y / H - 1/2).  The band only ORDERS the dispatch of the band-first kernels (a wrong band
+    // renders the same pixels later), and the un-culled lens kernel a wide lens falls back to is not band-first: nothing depends on it
+    if (ctx->v_fov != 0.0f) { v0 /= ctx->lens_scale; v1 /= ctx->lens_scale; }
     const float H = (float)ctx->height;
     auto clampi = [](float x, int lo, int hi) { return x < (float)lo ? lo : (x > (float)hi ? hi : (int)x); };
     ty0 = clampi(std::floor((v0 + 0.5f) * H / 8.0f) - 1, 0, tile_rows - 1);
@@ -764,6 +829,9 @@ int ensure_panorama_tables(rpt_ctx *ctx) {
 // environment  the variant with the sky image (rpt_set_environment; 0: none): the kernels variant 0 can select and the un-culled one, in
 //              pinhole and panorama.  Looked up in the row chosen BEFORE the Doppler column: an environment kernel carries Doppler as a
 //              run-time flag and serves both
+// lens         the variant with the scaled image plane (rpt_set_field_of_view; 0: none): the lens form of what variant 0 can select and of
+//              the un-culled kernel, of their Doppler twins and of their environment forms.  Looked up in the row chosen by every other
+//              column, last
 enum : int { VARIANT_DEFAULT = 0, VARIANT_REF_LAYOUT = 1, VARIANT_UNCULLED = 3, VARIANT_BALLOT = 41, VARIANT_BALLOT_FIRST = 43,
              VARIANT_ANALYTIC = 44, VARIANT_DOPPLER_RECORD = 240, VARIANT_PANORAMA_RECORD = 540 };
 struct VariantRow {
@@ -778,45 +846,59 @@ struct VariantRow {
     int msaa;
     int panorama;
     int environment;
+    int lens;
 };
 #define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
 const VariantRow variant_table[] = {
-    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa  pano env
-    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0, 0, 0},
-    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47, 303, 603},
-    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46, 341, 641},
-    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46, 341, 643},
-    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46, 344, 644},
-    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0, 0, 0},
-    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0, 0, 0},
+    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa  pano env lens
+    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0, 0, 0, 0},
+    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47, 303, 603, 803},
+    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46, 341, 641, 841},
+    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46, 341, 643, 843},
+    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46, 344, 644, 844},
+    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0, 0, 0, 0},
+    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0, 0, 0, 0},
     // 50 / 51 cull with the same regions but keep culling outside their window: a known gap (third item), kept as it is here
-    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0},
-    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0},
-    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0},
-    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0, 0, 0},
-    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0, 0, 0},
-    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0, 0, 0},
-    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0, 0, 0},
-    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0, 0, 0},
-    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0, 0, 0},
-    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0, 0, 0},
-    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0, 0, 0},
+    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0, 0},
+    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0, 0},
+    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0, 0},
+    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0, 0, 0, 0},
+    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0, 0, 0, 813},
+    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0, 0, 0, 0},
+    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0, 0, 0, 851},
+    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0, 0, 0, 853},
+    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0, 0, 0, 854},
+    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0, 0, 0, 0},
+    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0, 0, 0, 0},
     // the panorama kernels: reached through the panorama column only
-    {303, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),               0, nullptr,                                                  503, false, rptd::PanoramaUnculled::band_first,          0, 0, 703},
-    {341, false, RPT_KERNEL(rpt_render_kernel_pano_w5),                        0, RPT_KERNEL(rpt_render_kernel_pano_ieee_w5),               541, false, rptd::PanoramaWalk::band_first,              0, 0, 741},
-    {344, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),               0, nullptr,                                                  544, false, rptd::PanoramaAnalytic::band_first,          0, 0, 744},
-    {503, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaUnculled>::band_first, 0, 0, 0},
-    {540, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),         0, nullptr,                                                  0,   false, rptd::PanoramaRecorded::band_first,          0, 0, 0},
-    {541, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),                0, RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5),       0,   false, rptd::DopplerTwin<rptd::PanoramaWalk>::band_first, 0, 0, 0},
-    {544, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaAnalytic>::band_first, 0, 0, 0},
+    {303, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),               0, nullptr,                                                  503, false, rptd::PanoramaUnculled::band_first,          0, 0, 703, 0},
+    {341, false, RPT_KERNEL(rpt_render_kernel_pano_w5),                        0, RPT_KERNEL(rpt_render_kernel_pano_ieee_w5),               541, false, rptd::PanoramaWalk::band_first,              0, 0, 741, 0},
+    {344, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),               0, nullptr,                                                  544, false, rptd::PanoramaAnalytic::band_first,          0, 0, 744, 0},
+    {503, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaUnculled>::band_first, 0, 0, 0, 0},
+    {540, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),         0, nullptr,                                                  0,   false, rptd::PanoramaRecorded::band_first,          0, 0, 0, 0},
+    {541, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),                0, RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5),       0,   false, rptd::DopplerTwin<rptd::PanoramaWalk>::band_first, 0, 0, 0, 0},
+    {544, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaAnalytic>::band_first, 0, 0, 0, 0},
     // the environment kernels (rpt_set_environment): reached through the environment column only; each serves Doppler off and on
-    {603, false, RPT_KERNEL(rpt_render_kernel_env_unculled_w5),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Unculled>::band_first, 0, 0, 0},
-    {641, false, RPT_KERNEL(rpt_render_kernel_env_ballot_w5),                   0, RPT_KERNEL(rpt_render_kernel_env_ballot_ieee_w5),          0,   false, rptd::Environment<rptd::BallotExact>::band_first, 0, 0, 0},
-    {643, false, RPT_KERNEL(rpt_render_kernel_env_ballot_first_w5),             0, RPT_KERNEL(rpt_render_kernel_env_ballot_first_ieee_w5),    0,   false, rptd::Environment<rptd::BallotFirstExact>::band_first, 0, 0, 0},
-    {644, false, RPT_KERNEL(rpt_render_kernel_env_analytic_w8),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Analytic>::band_first, 0, 0, 0},
-    {703, false, RPT_KERNEL(rpt_render_kernel_env_pano_unculled_w5),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaUnculled>::band_first, 0, 0, 0},
-    {741, false, RPT_KERNEL(rpt_render_kernel_env_pano_w5),                     0, RPT_KERNEL(rpt_render_kernel_env_pano_ieee_w5),            0,   false, rptd::Environment<rptd::PanoramaWalk>::band_first, 0, 0, 0},
-    {744, false, RPT_KERNEL(rpt_render_kernel_env_pano_analytic_w8),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaAnalytic>::band_first, 0, 0, 0},
+    {603, false, RPT_KERNEL(rpt_render_kernel_env_unculled_w5),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Unculled>::band_first, 0, 0, 0, 823},
+    {641, false, RPT_KERNEL(rpt_render_kernel_env_ballot_w5),                   0, RPT_KERNEL(rpt_render_kernel_env_ballot_ieee_w5),          0,   false, rptd::Environment<rptd::BallotExact>::band_first, 0, 0, 0, 861},
+    {643, false, RPT_KERNEL(rpt_render_kernel_env_ballot_first_w5),             0, RPT_KERNEL(rpt_render_kernel_env_ballot_first_ieee_w5),    0,   false, rptd::Environment<rptd::BallotFirstExact>::band_first, 0, 0, 0, 863},
+    {644, false, RPT_KERNEL(rpt_render_kernel_env_analytic_w8),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Analytic>::band_first, 0, 0, 0, 864},
+    {703, false, RPT_KERNEL(rpt_render_kernel_env_pano_unculled_w5),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaUnculled>::band_first, 0, 0, 0, 0},
+    {741, false, RPT_KERNEL(rpt_render_kernel_env_pano_w5),                     0, RPT_KERNEL(rpt_render_kernel_env_pano_ieee_w5),            0,   false, rptd::Environment<rptd::PanoramaWalk>::band_first, 0, 0, 0, 0},
+    {744, false, RPT_KERNEL(rpt_render_kernel_env_pano_analytic_w8),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaAnalytic>::band_first, 0, 0, 0, 0},
+    // the lens kernels (rpt_set_field_of_view): reached through the lens column only, looked up LAST (after the environment and Doppler columns)
+    {803, false, RPT_KERNEL(rpt_render_kernel_lens_unculled_w5), 0, nullptr, 0, false, rptd::Lens<rptd::Unculled>::band_first, 0, 0, 0, 0},
+    {841, false, RPT_KERNEL(rpt_render_kernel_lens_ballot_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_ballot_ieee_w5), 0, false, rptd::Lens<rptd::BallotExact>::band_first, 0, 0, 0, 0},
+    {843, false, RPT_KERNEL(rpt_render_kernel_lens_ballot_first_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_ballot_first_ieee_w5), 0, false, rptd::Lens<rptd::BallotFirstExact>::band_first, 0, 0, 0, 0},
+    {844, false, RPT_KERNEL(rpt_render_kernel_lens_analytic_w8), 0, nullptr, 0, false, rptd::Lens<rptd::Analytic>::band_first, 0, 0, 0, 0},
+    {813, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_unculled_w5), 0, nullptr, 0, false, rptd::Lens<rptd::DopplerTwin<rptd::Unculled>>::band_first, 0, 0, 0, 0},
+    {851, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_ieee_w5), 0, false, rptd::Lens<rptd::DopplerTwin<rptd::BallotExact>>::band_first, 0, 0, 0, 0},
+    {853, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_first_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_first_ieee_w5), 0, false, rptd::Lens<rptd::DopplerTwin<rptd::BallotFirstExact>>::band_first, 0, 0, 0, 0},
+    {854, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_analytic_w8), 0, nullptr, 0, false, rptd::Lens<rptd::DopplerTwin<rptd::Analytic>>::band_first, 0, 0, 0, 0},
+    {823, false, RPT_KERNEL(rpt_render_kernel_lens_env_unculled_w5), 0, nullptr, 0, false, rptd::Lens<rptd::Environment<rptd::Unculled>>::band_first, 0, 0, 0, 0},
+    {861, false, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_ieee_w5), 0, false, rptd::Lens<rptd::Environment<rptd::BallotExact>>::band_first, 0, 0, 0, 0},
+    {863, false, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_ieee_w5), 0, false, rptd::Lens<rptd::Environment<rptd::BallotFirstExact>>::band_first, 0, 0, 0, 0},
+    {864, false, RPT_KERNEL(rpt_render_kernel_lens_env_analytic_w8), 0, nullptr, 0, false, rptd::Lens<rptd::Environment<rptd::Analytic>>::band_first, 0, 0, 0, 0},
 };
 #undef RPT_KERNEL
 
@@ -869,7 +951,12 @@ int launch(rpt_ctx *ctx) {
     a.inv_height = 1.0f / (float)ctx->height;
     // the diagonal slabs hold inside their window only (rpt_screen_bounds.hpp): frames up to 4 : 1, |v| <= 1/2 always
     a.diagonals = 0;
-    if (0.5f * a.aspect + 2.0f * a.inv_height * a.aspect <= (float)rptb::DIAG_WINDOW_U && ctx->rects.size() == (size_t)ctx->object_count)
+    // (under a lens, rpt_set_field_of_view, the tiles' plane coordinates are those of the reference's lens times s <= 1 — a wider lens
+    // gets the un-culled kernel below — so the same rule holds with both sides of the tile scaled)
+    const bool lens = ctx->v_fov != 0.0f;
+    const float lens_scale = lens ? ctx->lens_scale : 1.0f;
+    const float diag_reach = 0.5f * a.aspect + 2.0f * a.inv_height * a.aspect;
+    if ((lens ? lens_scale <= 1.0f && lens_scale * diag_reach <= (float)rptb::DIAG_WINDOW_U : diag_reach <= (float)rptb::DIAG_WINDOW_U) && ctx->rects.size() == (size_t)ctx->object_count)
         for (const rptb::Rect &r : ctx->rects) a.diagonals |= rptb::has_diagonals(r) ? 1 : 0;
     a.object_count = ctx->object_count;
     a.width = ctx->width;
@@ -903,6 +990,18 @@ int launch(rpt_ctx *ctx) {
     // The equirectangular camera (rpt_set_projection): variant 0's choice and variant 3 go to their panorama kernels (341 / 344, 303), whose
     // rays leave the pinhole's proven window anyway; everything else refuses here, at the launch, like the kernels without a Doppler twin.
     const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
+    // A lens (rpt_set_field_of_view): the lens form of the kernel every other setting chooses, looked up last.  What has none refuses here,
+    // at the launch, like the precedents: the setting may precede the others.
+    if (lens) {
+        if (panorama) return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
+        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: MSAA > 1 has no lens kernel");
+        if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED && ctx->variant != VARIANT_BALLOT && ctx->variant != VARIANT_BALLOT_FIRST && ctx->variant != VARIANT_ANALYTIC)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: variant " + std::to_string(ctx->variant) + " has no lens kernel (variants 0, 3, 41, 43 and 44 have)");
+        if (v == VARIANT_REF_LAYOUT)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the lens kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+        if (ctx->doppler && (ctx->external_doppler || ctx->want_owned_doppler))
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the Doppler debug kernel (rpt_set_debug_doppler) has no lens form");
+    }
     if (panorama) {
         if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED)
             return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: variant " + std::to_string(ctx->variant) + " has no panorama kernel (variants 0 and 3 have)");
@@ -915,7 +1014,11 @@ int launch(rpt_ctx *ctx) {
     // The per-object regions are PROVEN for the window |u| <= 2, |v| <= 1/2 (rpt_bounds_certify.hpp): a frame wider than 4 : 1 has
     // pixels outside it, and beyond 2^20 pixels a side a tile's 1.5-pixel skirt is no longer large against float rounding — such
     // frames are rendered by the un-culled kernel (same pixels, every object tested everywhere).
-    const bool window_holds_frame = 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U && ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
+    // Under a lens pixel (x, y) looks through (fl(s fx2), fl(s fy2)): with s <= 1 no larger in magnitude than |fy2| <= 1/2 and than
+    // fl(s fl(aspect / 2)), which is what is compared here (rounding is monotone).  The 2^20 bound covers every s: the skirt and the
+    // rounding it is held against scale with s alike (rpt_kernels.hip.h: wave_object_mask_lens).  A wider lens: the un-culled lens kernel.
+    const bool window_holds_frame = (lens ? lens_scale <= 1.0f && lens_scale * (0.5f * a.aspect) <= (float)rptb::cert::WINDOW_U : 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U) &&
+                                    ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
     if (!window_holds_frame && row && row->window) row = variant_row(v = VARIANT_UNCULLED);
     a.first_h = 0;
     if (row && row->band_first) set_band_first(ctx, a, tiles);
@@ -945,6 +1048,10 @@ int launch(rpt_ctx *ctx) {
                                                                   : "rpt_set_doppler: this kernel variant has no Doppler twin");
         row = variant_row(v = record ? (panorama ? VARIANT_PANORAMA_RECORD : VARIANT_DOPPLER_RECORD) : row->doppler);
     }
+    if (lens) {
+        if (!row || !row->lens) return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: kernel " + std::to_string(v) + " has no lens form");
+        row = variant_row(v = row->lens);
+    }
     rptd::DopplerArgs da;         // (the twins' arguments: this frame's KernelArgs + the two Doppler fields)
     static_cast<rptd::KernelArgs &>(da) = a;
     da.doppler = ctx->doppler;
@@ -960,6 +1067,14 @@ int launch(rpt_ctx *ctx) {
     ea.env_width = ctx->env_width;
     ea.env_height = ctx->env_height;
     std::memcpy(ea.env_frame, ctx->env_frame, sizeof ea.env_frame);
+    if (ctx->oriented) {          // (rpt_set_orientation: E' = E diag(1, R) — a sky at rest in the scene stays at rest when the head turns)
+        rpt_float4 e[4];
+        std::memcpy(e, ctx->env_frame, sizeof e);
+        rebase_columns(e, ctx->R, ea.env_frame);
+    }
+    rptd::LensArgs la;            // (the lens kernels' arguments: the above + the scale of the image plane)
+    static_cast<rptd::EnvironmentArgs &>(la) = ea;
+    la.lens_scale = lens_scale;
     if (!row) {
 #ifdef RPT_DIAGNOSTICS
         if (int rc = launch_diagnostic(ctx, a, grid, tiles, v)) return rc;
@@ -969,7 +1084,7 @@ int launch(rpt_ctx *ctx) {
     } else if (row->relaxed_waves) {
         if (rpt_launch_relaxed_kernel(row->relaxed_waves, &a, sizeof a, grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
     } else {
-        void *args[] = {environment ? (void *)&ea : (panorama ? (void *)&pa : (ctx->doppler ? (void *)&da : (void *)&a))};
+        void *args[] = {lens ? (void *)&la : (environment ? (void *)&ea : (panorama ? (void *)&pa : (ctx->doppler ? (void *)&da : (void *)&a)))};
         (void)hipLaunchKernel(row->ieee && !ctx->geo->exact_rcp_ok ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     }
     RPT_HIP(ctx, hipGetLastError());
@@ -1143,14 +1258,35 @@ int rpt_share_scene(rpt_ctx *ctx, rpt_ctx *owner) {
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->geo = owner->geo;
     ctx->scene_uploaded = true;
-    const int count = (int)(owner->host_objects.size() / sizeof(rpt_object));
-    const int rc = rpt_set_objects(ctx, count ? owner->host_objects.data() : nullptr, count);
+    // (the owner's objects as ITS caller gave them: the orientation is per context, this one applies its own)
+    const std::vector<uint8_t> &given = owner->oriented ? owner->caller_objects : owner->host_objects;
+    const int count = (int)(given.size() / sizeof(rpt_object));
+    const int rc = rpt_set_objects(ctx, count ? given.data() : nullptr, count);
     if (rc) ctx->scene_uploaded = false;
     return rc;
 }
 
+// rpt_set_objects with an orientation set (rpt_set_orientation): the caller's bytes are kept as they came, and what the context
+// derives everything from, uploads and hands its test hooks is the re-based copy
+static int set_objects_as_given(rpt_ctx *ctx, const void *objects, int count);
 int rpt_set_objects(rpt_ctx *ctx, const void *objects, int count) {
     if (!ctx || count < 0 || (count && !objects)) return RPT_ERR_ARG;
+    if (!ctx->oriented) {
+        const int rc = set_objects_as_given(ctx, objects, count);
+        if (rc == RPT_OK) ctx->caller_objects.clear();
+        return rc;
+    }
+    const size_t bytes = (size_t)count * sizeof(rpt_object);
+    std::vector<uint8_t> &given = ctx->given_scratch, &turned = ctx->turned_scratch;
+    given.assign((const uint8_t *)objects, (const uint8_t *)objects + bytes);
+    turned.resize(bytes);
+    orient_objects((const rpt_object *)given.data(), count, ctx->R, (rpt_object *)turned.data());
+    const int rc = set_objects_as_given(ctx, turned.data(), count);
+    if (rc == RPT_OK) ctx->caller_objects.swap(given);      // (the old copy becomes next frame's scratch)
+    return rc;
+}
+
+static int set_objects_as_given(rpt_ctx *ctx, const void *objects, int count) {
     if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_set_objects before rpt_upload_scene");
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = validate_objects(ctx, (const rpt_object *)objects, count)) return rc;
@@ -1211,7 +1347,8 @@ int rpt_set_params(rpt_ctx *ctx, const float white_point[3], float ambient, int 
     ctx->interval = interval;
     ctx->params_set = true;
     if (interval_changed && ctx->scene_uploaded && ctx->object_count > 0) {
-        const std::vector<uint8_t> copy = ctx->host_objects;      // the culling record of DObj uses `interval`
+        const std::vector<uint8_t> copy = ctx->oriented ? ctx->caller_objects : ctx->host_objects;      // the culling record of DObj uses `interval`
+        if (copy.size() != (size_t)ctx->object_count * sizeof(rpt_object)) return fail(ctx, RPT_ERR_STATE, "rpt_set_params: the context holds no copy of the caller's objects");
         return rpt_set_objects(ctx, copy.data(), ctx->object_count);
     }
     return RPT_OK;
@@ -1337,6 +1474,57 @@ int rpt_set_environment_frame(rpt_ctx *ctx, const float lorentz[16]) {
     for (int k = 0; k < 16; k++)
         if (!std::isfinite(m[k])) return fail(ctx, RPT_ERR_ARG, "rpt_set_environment_frame: every entry must be finite");
     std::memcpy(ctx->env_frame, m, sizeof ctx->env_frame);
+    return RPT_OK;
+}
+
+int rpt_set_orientation(rpt_ctx *ctx, const float ypr[3]) {
+    if (!ctx) return RPT_ERR_ARG;
+    double R[3][3];
+    if (!orientation_matrix(ypr, R)) return fail(ctx, RPT_ERR_ARG, "rpt_set_orientation: yaw, pitch and roll must be finite (radians), or NULL");
+    // the caller's last Object[], as given, BEFORE the setting changes (host_objects holds it while no orientation is set)
+    const std::vector<uint8_t> given = ctx->oriented ? ctx->caller_objects : ctx->host_objects;
+    const bool was_oriented = ctx->oriented;
+    double was_R[3][3];
+    std::memcpy(was_R, ctx->R, sizeof was_R);
+    ctx->oriented = !is_identity(R);
+    std::memcpy(ctx->R, R, sizeof R);
+    if (!ctx->scene_uploaded || ctx->object_count <= 0) return RPT_OK;
+    if (given.size() != (size_t)ctx->object_count * sizeof(rpt_object)) {      // (cannot happen: every successful rpt_set_objects leaves the copy that matches `oriented`)
+        ctx->oriented = was_oriented;
+        std::memcpy(ctx->R, was_R, sizeof was_R);
+        return fail(ctx, RPT_ERR_STATE, "rpt_set_orientation: the context holds no copy of the caller's objects to re-derive from");
+    }
+    const int rc = rpt_set_objects(ctx, given.data(), ctx->object_count);      // re-derive regions, proofs, records and the upload at once
+    if (rc != RPT_OK) {          // nothing was taken over: the setting goes back with it, so `oriented`, host_objects and caller_objects still match
+        ctx->oriented = was_oriented;
+        std::memcpy(ctx->R, was_R, sizeof was_R);
+    }
+    return rc;
+}
+
+int rpt_set_field_of_view(rpt_ctx *ctx, float v_fov) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (v_fov != 0.0f && !(v_fov >= 0.01f && v_fov <= 3.0f))
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the vertical field of view is 0 (the reference's lens) or 0.01 <= v_fov <= 3.0 radians");
+    ctx->v_fov = v_fov;
+    ctx->lens_scale = v_fov != 0.0f ? (float)std::tan(0.5 * (double)v_fov) : 1.0f;
+    return RPT_OK;
+}
+
+int rpt_orient_objects(const void *objects_in, int count, const float ypr[3], void *objects_out) {
+    double R[3][3];
+    if (count < 0 || (count && (!objects_in || !objects_out)) || !orientation_matrix(ypr, R)) return RPT_ERR_ARG;
+    orient_objects((const rpt_object *)objects_in, count, R, (rpt_object *)objects_out);
+    return RPT_OK;
+}
+
+int rpt_orient_matrix(const float lorentz_in[16], const float ypr[3], float lorentz_out[16]) {
+    double R[3][3];
+    if (!lorentz_in || !lorentz_out || !orientation_matrix(ypr, R)) return RPT_ERR_ARG;
+    rpt_float4 m[4];
+    std::memcpy(m, lorentz_in, sizeof m);
+    if (!is_identity(R)) rebase_columns(m, R, m);
+    std::memcpy(lorentz_out, m, sizeof m);
     return RPT_OK;
 }
 

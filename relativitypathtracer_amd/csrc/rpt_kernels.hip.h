@@ -161,6 +161,13 @@ struct EnvironmentArgs : PanoramaArgs {
     rpt_float4 env_frame[4];        // E: camera frame -> the sky's rest frame, rows t, x, y, z (rpt_set_environment_frame)
 };
 
+// The lens kernels' arguments (rpt_set_field_of_view; not in the reference): EnvironmentArgs with the scale of the image plane appended, for
+// the same reason once more.  Every lens kernel takes them: the plain ones (doppler = 0 and env_texels unused there), their Doppler
+// twins and the environment forms.
+struct LensArgs : EnvironmentArgs {
+    float lens_scale;               // s = (float)tan(v_fov / 2): pixel (x, y) looks through (s fx2, s fy2, 0.5); 1.0f is the reference's lens
+};
+
 struct Hit {                 // opencl_kernel.cl:38-44
     float dist;
     f3 normal;
@@ -178,6 +185,16 @@ RPT_DEV f3 createCamRayDir(float x_coord, float y_coord, int width, int height, 
     const float fx2 = (fx - 0.5f) * aspect_ratio;
     const float fy2 = fy - 0.5f;
     return normalize(mk3(fx2, fy2, 0.5f));
+}
+
+// The pinhole with a lens (rpt_set_field_of_view; not in the reference): createCamRayDir's fx2, fy2 as it forms them, each times s =
+// (float)tan(v_fov / 2) — two more float products, nothing reassociated.  s = 1.0f makes both products exact: the reference's ray.
+RPT_DEV f3 lensCamRayDir(float x_coord, float y_coord, int width, int height, float aspect_ratio, float s) {
+    const float fx = x_coord / (float)width;
+    const float fy = y_coord / (float)height;
+    const float fx2 = (fx - 0.5f) * aspect_ratio;
+    const float fy2 = fy - 0.5f;
+    return normalize(mk3(s * fx2, s * fy2, 0.5f));
 }
 
 // The equirectangular camera (rpt_set_projection; not in the reference): p = (cos phi sin lambda, sin phi, cos phi cos lambda) from the
@@ -624,6 +641,7 @@ enum class Walk {
 enum class Camera {
     pinhole,         // createCamRayDir: the reference's image plane z = 0.5
     equirect,        // equirectCamDir: the panorama tables (rpt_set_projection); the arguments are a PanoramaArgs
+    lens,            // lensCamRayDir: the pinhole's image plane scaled by LensArgs::lens_scale (rpt_set_field_of_view); the arguments are a LensArgs
 };
 struct KernelPolicy {
     static constexpr Walk walk = Walk::throughput;
@@ -658,6 +676,10 @@ struct PanoramaRecorded : Panorama<DopplerRecorded> {};                         
 // the environment kernels (rpt_set_environment): one family for Doppler off and on — the twin's code with EnvironmentArgs::doppler as a
 // run-time flag; with flags 0 S_f is the identity (doppler_colour returns its colour untouched), so the frame is the plain kernel's
 template <class P> struct Environment : DopplerTwin<P> { static constexpr bool environment = true; };                           // 6xx, 7xx
+// the lens kernels (rpt_set_field_of_view): the pinhole's kernels with the image plane — the camera ray's and the wave's tile in the object
+// mask alike — scaled by LensArgs::lens_scale; everything else is the policy they derive from.  803 / 841 / 843 / 844: Lens<P> for the
+// plain kernels; + 10: Lens<DopplerTwin<P>> for their Doppler twins; + 20: Lens<Environment<P>> for the environment forms
+template <class P> struct Lens : P { static constexpr Camera camera = Camera::lens; };                                          // 8xx
 
 template <class P>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
@@ -1215,6 +1237,35 @@ RPT_DEV unsigned long long wave_object_mask(const KernelArgs &a, int tile_x0, in
     return __ballot(keep);
 }
 
+// The same under a lens (Camera::lens): pixel (x, y) looks through the plane point (fl(s fx2), fl(s fy2)), so the tile's four plane
+// coordinates are scaled by s as well.  What the mask needs is that every pixel's plane point lies inside its tile's grown range; the
+// regions themselves are statements about real plane points of the proven window, whatever rounding produced them
+// (rpt_bounds_certify.hpp, section 1), and the host launches this kernel only while s <= 1 keeps every pixel inside that window.
+// The skirt under s: a pixel x >= x0 of the tile has the exact coordinate U = s (x / W - 1/2) aspect, the tile's lower edge the exact
+// E = s ((x0 - 1.5) / W - 1/2) aspect, U - E >= 1.5 s aspect / W.  The pixel's float chain (divide, subtract, multiply by aspect) is
+// off by at most 3u aspect before the lens and the edge's (multiply by 1 / W rounded, subtract, multiply) by at most 4u aspect, u =
+// 2^-24 — the existing skirt's case; the product with s scales both errors by s and adds one relative rounding of a value of at most
+// s aspect / 2 to each: |fl - exact| <= 3.5u s aspect and 4.5u s aspect.  The pixel stays inside while 8u s aspect < 1.5 s aspect / W,
+// i.e. W < 1.5 / 8u = 3.1 million: s cancels, so the bound of 2^20 pixels a side that launch() enforces covers every lens (no
+// product underflows: s >= 0.005 and the coordinates are multiples of 2^-24 or 0).  The same in v with aspect = 1, and at the upper
+// edges.  At s = 1.0f every product here is exact and the mask is wave_object_mask's.
+RPT_DEV unsigned long long wave_object_mask_lens(const KernelArgs &a, float s, int tile_x0, int tile_y0) {
+    const int lane = threadIdx.x & 63;
+    const int n = a.object_count;
+    const int slot = (lane < n) ? lane : 0;
+    const float4 r = a.rects[2 * slot];
+    const float iw = a.inv_width, ih = a.inv_height;
+    const float tu0 = s * ((((float)tile_x0 - 1.5f) * iw - 0.5f) * a.aspect), tu1 = s * ((((float)tile_x0 + 8.5f) * iw - 0.5f) * a.aspect);
+    const float tv0 = s * (((float)tile_y0 - 1.5f) * ih - 0.5f), tv1 = s * (((float)tile_y0 + 8.5f) * ih - 0.5f);
+    bool outside = (r.z < tu0) | (r.x > tu1) | (r.w < tv0) | (r.y > tv1);
+    if (a.diagonals) {
+        const float4 g = a.rects[2 * slot + 1];
+        outside = outside | (g.y < tu0 + tv0) | (g.x > tu1 + tv1) | (g.w < tu0 - tv1) | (g.z > tu1 - tv0);
+    }
+    const bool keep = (lane < n) & !outside;
+    return __ballot(keep);
+}
+
 // ---------------------------------------------------------------------------------------------
 // One thread per pixel, wave = 8x8 tile, workgroup = one wave or a 32x8 strip; what else the kernel does is its policy P
 // (KernelPolicy above; the product kernels' policies are listed there, the measurement arms' in rpt_diag_kernels.hip.h).
@@ -1254,7 +1305,9 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // the wave's object mask comes from a __ballot over ALL 64 lanes (lane i answers for object i), so it is formed
     // before the lanes of a partial tile leave
     unsigned long long object_mask = ~0ull;
-    if (P::culled && P::object_mask) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    if constexpr (P::camera == Camera::lens) {
+        if (P::culled && P::object_mask) object_mask = wave_object_mask_lens(a, static_cast<const LensArgs &>(a).lens_scale, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    } else if (P::culled && P::object_mask) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
 #ifdef RPT_DIAGNOSTICS
     if (P::diag == 10) object_mask = a.tile_masks[__builtin_amdgcn_readfirstlane(tile_row * a.mask_tiles_x + (int)blockIdx.x * 4 + wave)];   // the prepass's per-tile mask
 #endif
@@ -1271,6 +1324,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
         // straight to the sky (no object loop, no scene load)
         f3 camdir;
         if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(static_cast<const PanoramaArgs &>(a), x_coord, y_coord);
+        else if constexpr (P::camera == Camera::lens) camdir = lensCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect, static_cast<const LensArgs &>(a).lens_scale);
         else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
         if (!masked || object_mask != 0 || a.object_count > 64) traced = trace<P>(a, camdir, object_mask, color);
         if (!traced) color = environment_colour(static_cast<const EnvironmentArgs &>(a), camdir);
@@ -1278,6 +1332,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     } else if (!masked || object_mask != 0 || a.object_count > 64) {
         f3 camdir;
         if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(static_cast<const PanoramaArgs &>(a), x_coord, y_coord);
+        else if constexpr (P::camera == Camera::lens) camdir = lensCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect, static_cast<const LensArgs &>(a).lens_scale);
         else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
         if (trace<P>(a, camdir, object_mask, color, P::drec ? &drec : nullptr)) {
             packed = tonemap_pack(a, color, mapped);
@@ -1416,6 +1471,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_pano_w5(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaWalk>>(a); }                  // 741
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_env_pano_ieee_w5(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaWalkIeee>>(a); }         // (741)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_env_pano_analytic_w8(const EnvironmentArgs a) { render_pixel_body<Environment<PanoramaAnalytic>>(a); }     // 744
+
+// Lens kernels (rpt_set_field_of_view; not in the reference): what variant 0 can select (41 / 43 / 44, with the IEEE forms) and the un-culled
+// kernel (3), with the image plane scaled; then their Doppler twins and their environment forms, as the families above.  Same launch shapes
+// and occupancy attributes as the kernels they stand in for.  DESIGN.md "Free-look camera".
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_unculled_w5(const LensArgs a) { render_pixel_body<Lens<Unculled>>(a); }    // 803
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_ballot_w5(const LensArgs a) { render_pixel_body<Lens<BallotExact>>(a); }    // 841
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_ballot_ieee_w5(const LensArgs a) { render_pixel_body<Lens<Ballot>>(a); }    // (841)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_ballot_first_w5(const LensArgs a) { render_pixel_body<Lens<BallotFirstExact>>(a); }    // 843
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_ballot_first_ieee_w5(const LensArgs a) { render_pixel_body<Lens<BallotFirst>>(a); }    // (843)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_lens_analytic_w8(const LensArgs a) { render_pixel_body<Lens<Analytic>>(a); }    // 844
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_doppler_unculled_w5(const LensArgs a) { render_pixel_body<Lens<DopplerTwin<Unculled>>>(a); }    // 813
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_doppler_ballot_w5(const LensArgs a) { render_pixel_body<Lens<DopplerTwin<BallotExact>>>(a); }    // 851
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_doppler_ballot_ieee_w5(const LensArgs a) { render_pixel_body<Lens<DopplerTwin<Ballot>>>(a); }    // (851)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_doppler_ballot_first_w5(const LensArgs a) { render_pixel_body<Lens<DopplerTwin<BallotFirstExact>>>(a); }    // 853
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_doppler_ballot_first_ieee_w5(const LensArgs a) { render_pixel_body<Lens<DopplerTwin<BallotFirst>>>(a); }    // (853)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_lens_doppler_analytic_w8(const LensArgs a) { render_pixel_body<Lens<DopplerTwin<Analytic>>>(a); }    // 854
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_unculled_w5(const LensArgs a) { render_pixel_body<Lens<Environment<Unculled>>>(a); }    // 823
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_w5(const LensArgs a) { render_pixel_body<Lens<Environment<BallotExact>>>(a); }    // 861
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_ieee_w5(const LensArgs a) { render_pixel_body<Lens<Environment<Ballot>>>(a); }    // (861)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_first_w5(const LensArgs a) { render_pixel_body<Lens<Environment<BallotFirstExact>>>(a); }    // 863
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_first_ieee_w5(const LensArgs a) { render_pixel_body<Lens<Environment<BallotFirst>>>(a); }    // (863)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_lens_env_analytic_w8(const LensArgs a) { render_pixel_body<Lens<Environment<Analytic>>>(a); }    // 864
 
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd

@@ -47,6 +47,80 @@ def projection_tables(width: int, height: int, h_fov: float = 2 * math.pi, v_fov
     return cols, rows
 
 
+def _ypr(yaw: float, pitch: float, roll: float):
+    return (C.c_float * 3)(float(yaw), float(pitch), float(roll))
+
+
+def rotation_matrix(yaw: float = 0.0, pitch: float = 0.0, roll: float = 0.0) -> np.ndarray:
+    """R = Ry(yaw) Rx(pitch) Rz(roll) of rpt_set_orientation (include/rpt.h), float64, from the angles rounded to float32 as the library
+    takes them: a direction n of the turned camera is the direction R n of the un-turned one; the view direction is R (0, 0, 1)."""
+    y, p, r = (float(np.float32(a)) for a in (yaw, pitch, roll))
+    cy, sy, cp, sp, cr, sr = math.cos(y), math.sin(y), math.cos(p), math.sin(p), math.cos(r), math.sin(r)
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    rx = np.array([[1, 0, 0], [0, cp, sp], [0, -sp, cp]])
+    rz = np.array([[cr, sr, 0], [-sr, cr, 0], [0, 0, 1]])
+    return ry @ (rx @ rz)
+
+
+def look_at(direction: Sequence[float], up: Sequence[float] = (0.0, 1.0, 0.0)) -> Tuple[float, float, float]:
+    """(yaw, pitch, roll) for Renderer.set_orientation such that the view direction R (0, 0, 1) is `direction` (any non-zero length) and
+    the image's up, R (0, 1, 0), is `up` made perpendicular to it.  Host arithmetic only.  At the poles (direction parallel to the y
+    axis) the yaw is taken from `up` (for direction = +y: the yaw that puts -up in the image centre's forward half-plane, i.e. the way
+    the head tilted back from); if `up` is parallel to `direction` as well, or zero, the yaw is 0 and the roll is 0."""
+    d = np.asarray(direction, dtype=np.float64)
+    n = float(np.linalg.norm(d))
+    if not (n > 0.0 and math.isfinite(n)):
+        raise ValueError("look_at: the direction must be finite and non-zero")
+    d = d / n
+    u = np.asarray(up, dtype=np.float64)
+    u = u - d * float(u @ d)                       # up, perpendicular to the view
+    un = float(np.linalg.norm(u))
+    pitch = math.asin(max(-1.0, min(1.0, float(d[1]))))
+    horizontal = math.hypot(float(d[0]), float(d[2]))
+    if horizontal > 1e-12:
+        yaw = math.atan2(float(d[0]), float(d[2]))
+    elif un > 1e-12:                               # a pole: with roll 0, R (0, 1, 0) = (-sin yaw sin pitch, cos pitch, -cos yaw sin pitch)
+        sgn = 1.0 if d[1] > 0 else -1.0
+        yaw = math.atan2(-sgn * float(u[0]), -sgn * float(u[2]))
+    else:
+        yaw = 0.0
+    if un <= 1e-12:
+        return yaw, pitch, 0.0
+    u = u / un
+    # roll: R (0, 1, 0) = cos(roll) e_up + sin(roll) e_right, e_up / e_right the image's up / right at roll 0
+    r0 = rotation_matrix(yaw, pitch, 0.0)
+    roll = math.atan2(float(u @ r0[:, 0]), float(u @ r0[:, 1]))
+    return yaw, pitch, roll
+
+
+def orient_objects(objects, yaw: float = 0.0, pitch: float = 0.0, roll: float = 0.0) -> np.ndarray:
+    """rpt_orient_objects (host code, no device needed): the Object[] a context with set_orientation(yaw, pitch, roll) renders — Lorentz and
+    InvLorentz re-based to the turned camera frame, every other byte copied.  objects: a Scene or n x 320 bytes; returns uint8 (n, 320)."""
+    if isinstance(objects, Scene):
+        d = objects.desc()
+        raw = np.ctypeslib.as_array(C.cast(d.objects, C.POINTER(C.c_uint8)), shape=(int(d.object_count) * 320,)).copy() if d.object_count else np.zeros(0, np.uint8)
+    else:
+        raw = np.ascontiguousarray(objects).view(np.uint8).reshape(-1).copy()
+    if raw.size % 320:
+        raise ValueError("objects are 320 bytes each")
+    out = np.empty_like(raw)
+    rc = _ffi.hip().rpt_orient_objects(raw.ctypes.data, raw.size // 320, _ypr(yaw, pitch, roll), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"rpt_orient_objects({yaw}, {pitch}, {roll}) failed ({rc})")
+    return out.reshape(-1, 320)
+
+
+def orient_matrix(matrix, yaw: float = 0.0, pitch: float = 0.0, roll: float = 0.0) -> np.ndarray:
+    """rpt_orient_matrix: E diag(1, R) for a 4 x 4 matrix of Object.Lorentz's layout (the sky's frame as a turned context uses it)."""
+    m = np.ascontiguousarray(matrix, dtype=np.float32).reshape(16).copy()
+    out = np.empty(16, dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    rc = _ffi.hip().rpt_orient_matrix(m.ctypes.data_as(fp), _ypr(yaw, pitch, roll), out.ctypes.data_as(fp))
+    if rc != 0:
+        raise ValueError(f"rpt_orient_matrix({yaw}, {pitch}, {roll}) failed ({rc})")
+    return out.reshape(4, 4)
+
+
 class Renderer:
     def __init__(self, device: int = 0, diag: bool = False):
         self._lib = _ffi.hip_diag() if diag else _ffi.hip()      # diag: librpt_hip_diag.so (measurement arms; tools and tests only)
@@ -146,6 +220,25 @@ class Renderer:
         self._check(self._lib.rpt_set_projection(self._h, m, params), "rpt_set_projection")
 
     projection_tables = staticmethod(projection_tables)
+
+    def set_orientation(self, yaw: float = 0.0, pitch: float = 0.0, roll: float = 0.0):
+        """Turn the camera: R = Ry(yaw) Rx(pitch) Rz(roll) in radians, the view direction R (0, 0, 1) — positive yaw towards +x, positive
+        pitch towards +y, positive roll turns the image counter-clockwise (include/rpt.h, rpt_set_orientation).  Per context, every
+        projection and kernel; takes effect at the next launch.  Three zeros: the reference's camera again."""
+        self._check(self._lib.rpt_set_orientation(self._h, _ypr(yaw, pitch, roll)), "rpt_set_orientation")
+
+    def set_field_of_view(self, v_fov: float = 0.0):
+        """The pinhole's vertical field of view in radians, 0.01 .. 3.0; 0 = the reference's lens (90 degrees, the default).  Pinhole only,
+        MSAA 1, variants 0, 3, 41, 43, 44: anything else refuses at the launch (include/rpt.h, rpt_set_field_of_view)."""
+        self._check(self._lib.rpt_set_field_of_view(self._h, float(v_fov)), "rpt_set_field_of_view")
+
+    def look_at(self, direction: Sequence[float], up: Sequence[float] = (0.0, 1.0, 0.0)) -> Tuple[float, float, float]:
+        """set_orientation(*look_at(direction, up)); returns the angles."""
+        ypr = look_at(direction, up)
+        self.set_orientation(*ypr)
+        return ypr
+
+    orient_objects = staticmethod(orient_objects)
 
     def set_environment(self, image: Optional[np.ndarray]):
         """The sky: an equirectangular H x W x 3 uint8 image (row 0 the top), copied by the library; None switches it off (the constant
@@ -332,12 +425,18 @@ class Renderer:
 
 
 def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
-                 projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None):
+                 projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None,
+                 orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}.  environment: an
-    H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first)."""
+    H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first).
+    orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view)."""
     r = Renderer(device)
     try:
+        if orientation is not None:
+            r.set_orientation(*orientation)
+        if v_fov is not None:
+            r.set_field_of_view(v_fov)
         if projection is not None:
             r.set_projection(**({"mode": projection} if isinstance(projection, str) else dict(projection)))
         if environment is not None:
