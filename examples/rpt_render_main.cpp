@@ -3,11 +3,14 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--events FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
 // context, made once, BEFORE the objects are handed over; the per-frame loop stays the reference's.
+//
+// --events FILE also renders one event pass of the view the PPM shows (rpt_render_events; not in the reference) and writes its raw
+// records: width * height * 32 B (rpt_event, rpt_layout.h), row 0 the bottom row as everywhere.  Without the flag nothing changes.
 //
 // With `frames` > 1 the clock runs (16 ms per frame, as the reference's timer does) and the frames are rendered with
 // `in_flight` of them overlapping on the GPU: rpt::FrameRing (include/rpt_frames.hpp) — one context per frame slot
@@ -34,6 +37,7 @@ int main(int argc, char **argv) {
     // the free-look options (degrees), taken out of argv; what is left is positional
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
+    const char *events_path = nullptr;
     {
         const double deg = 3.14159265358979323846 / 180.0;
         int kept = 1;
@@ -43,7 +47,11 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--pitch")) { ypr[1] = (float)(std::atof(argv[++i]) * deg); turned = true; }
             else if (has_value && !std::strcmp(argv[i], "--roll")) { ypr[2] = (float)(std::atof(argv[++i]) * deg); turned = true; }
             else if (has_value && !std::strcmp(argv[i], "--fov")) v_fov = (float)(std::atof(argv[++i]) * deg);
-            else if (!std::strcmp(argv[i], "--yaw") || !std::strcmp(argv[i], "--pitch") || !std::strcmp(argv[i], "--roll") || !std::strcmp(argv[i], "--fov")) {
+            else if (has_value && !std::strcmp(argv[i], "--events")) events_path = argv[++i];
+            else if (!std::strcmp(argv[i], "--events")) {
+                std::fprintf(stderr, "--events needs a file name\n");
+                return 2;
+            } else if (!std::strcmp(argv[i], "--yaw") || !std::strcmp(argv[i], "--pitch") || !std::strcmp(argv[i], "--roll") || !std::strcmp(argv[i], "--fov")) {
                 std::fprintf(stderr, "%s needs a value (degrees)\n", argv[i]);
                 return 2;
             } else argv[kept++] = argv[i];
@@ -51,7 +59,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--events FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -142,6 +150,20 @@ int main(int argc, char **argv) {
     std::vector<unsigned char> fb((size_t)width * height * 16);
     rpt_read_framebuffer(last, fb.data(), fb.size());
     rc = rpt_write_ppm(argv[3], fb.data(), width, height);       // drawGL()                gl_interop.cpp:51
+    if (!rc && events_path) {                                    // what each pixel of that frame shows, where and when
+        std::vector<rpt_event> records((size_t)width * height);
+        rc = rpt_render_events(last);
+        if (!rc) rc = rpt_read_events(last, records.data(), records.size() * sizeof(rpt_event));
+        if (rc) {
+            std::fprintf(stderr, "events: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::FILE *f = std::fopen(events_path, "wb");
+        if (!f || std::fwrite(records.data(), sizeof(rpt_event), records.size(), f) != records.size() || std::fclose(f) != 0) {
+            std::fprintf(stderr, "events: cannot write %s\n", events_path);
+            return 1;
+        }
+    }
     std::fprintf(stderr, "%dx%d frame in %.3f ms -> %s\n", width, height, ms, argv[3]);
     rpt_destroy(ctx);
     rpt_scene_destroy(scene);

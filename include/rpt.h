@@ -31,7 +31,10 @@
  * rpt_projection_tables (host code, no device needed; DESIGN.md, "Panorama camera"), and the opt-in sky environment map, seen through a
  * Lorentz matrix of its own (the reference paints every miss one constant colour): rpt_set_environment, rpt_set_environment_frame and
  * rpt_probe which = 7 ("Environment map"), and the opt-in free-look camera — an orientation and a pinhole zoom: rpt_set_orientation,
- * rpt_set_field_of_view, and rpt_orient_objects / rpt_orient_matrix (host code, no device needed; DESIGN.md, "Free-look camera").
+ * rpt_set_field_of_view, and rpt_orient_objects / rpt_orient_matrix (host code, no device needed; DESIGN.md, "Free-look camera"), and the
+ * opt-in event pass — per pixel the object hit, the distance, the emission event in the object's rest frame and the surface (u, v), which
+ * the reference computes and discards: rpt_set_events_output, rpt_render_events / rpt_render_events_async, rpt_read_events, rpt_pick,
+ * rpt_last_events_variant and rpt_last_events_exact_rcp ("Event pass").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -310,6 +313,50 @@ int rpt_render(rpt_ctx *ctx);
 /* Enqueue one frame on the context's stream without waiting; rpt_sync waits. */
 int rpt_render_async(rpt_ctx *ctx);
 int rpt_sync(rpt_ctx *ctx);
+
+/* The event pass (not in the reference; DESIGN.md "Event pass"): a second kind of frame that holds, for every pixel, what its primary
+ * ray sees, where and when — one 32-B rpt_event (rpt_layout.h): the index of the closest object hit (-1 = none, every other field 0),
+ * Hit.dist (the camera-frame distance; interval * dist is the look-back time), the emission event stationaryCam + (Lorentz (interval,
+ * n)) * dist of the hit object in ITS rest frame (event[0] is the proper-time coordinate the flash test of opencl_kernel.cl:479 reads)
+ * and Hit.uv.  The closest hit is the frame's own: the same intersectors in the same object order with the same strict <, so the
+ * records agree with the colour frame pixel for pixel.  Opt-in, per context; with it unused nothing changes.
+ *
+ * rpt_set_events_output: the record buffer, a caller-owned device pointer to width * height * 32 B, or NULL (the default) for a
+ * library-owned buffer, allocated (and zeroed) on first use. */
+int rpt_set_events_output(rpt_ctx *ctx, void *device_ptr_or_null);
+/* rpt_render_events renders one event frame and waits; rpt_render_events_async enqueues it on the context's stream (rpt_sync waits).
+ * Preconditions and validation are rpt_render's.  The pass uses the context's CURRENT objects, params, rows or tile pattern,
+ * projection, orientation (the objects are the re-based ones, as everywhere) and lens.  Pixel (x, y) of this context's rows is written
+ * at index y * width + x of the full-frame record buffer whatever colour_plane says; rows that are not this context's are not touched,
+ * nor is the colour framebuffer, rpt_last_variant or rpt_last_frame_ms.  The settings of Doppler, the sky and debug_rgb are ignored:
+ * they act on colour only.  The kernel (rpt_last_events_variant):
+ *
+ *   camera     un-culled                        octree walk + the wave's object mask        no mesh in Object[]
+ *   pinhole    903                              941 (IEEE form as for 41)                   944
+ *   panorama   (none needed: nothing is culled) 911 (IEEE form)                             914
+ *   lens       923                              921 (IEEE form)                             924
+ *
+ * rpt_set_variant(3) selects the un-culled form; variants 0, 41, 43 and 44 the default choice (the walk's row with a mesh in Object[],
+ * else the last column).  Frames outside the window the screen regions are proven for (wider than 4 : 1, a lens with tan(v_fov / 2) >
+ * 1) get the un-culled form, as they get 3 / 803.  Only the throughput walk is built.  Refused at the LAUNCH with RPT_ERR_ARG and a
+ * message that starts "rpt_render_events:" (the context stays usable): MSAA > 1, variants 1 and 48-51 set explicitly, a lens together
+ * with the panorama, and an octree whose children are not consecutive (unless Object[] holds no mesh). */
+int rpt_render_events(rpt_ctx *ctx);
+int rpt_render_events_async(rpt_ctx *ctx);
+/* Copy the first `bytes` (at most width * height * 32) of the last event frame's records to the host, after waiting for the stream.
+ * RPT_ERR_STATE before the first event pass. */
+int rpt_read_events(rpt_ctx *ctx, void *host_dst, size_t bytes);
+/* One record of the last event frame (a host that picks with the mouse): waits for the stream and copies 32 B.  RPT_ERR_STATE before
+ * the first event pass; RPT_ERR_ARG for (x, y) outside that frame and for a row that was not this context's (rpt_set_rows). */
+int rpt_pick(rpt_ctx *ctx, int x, int y, rpt_event *out);
+/* The event kernel (a number of the table above) the last event pass of this context ran with; 0 before the first one.  rpt_last_variant
+ * keeps reporting render kernels only.  A null context: RPT_ERR_ARG, like every call here (no event kernel is numbered 1). */
+int rpt_last_events_variant(const rpt_ctx *ctx);
+/* Which form of that kernel ran, rpt_last_exact_rcp's question for the event pass: *exact_out = 1 if the last event pass tested triangles
+ * with the exact reciprocal (941 / 911 / 921 on a scene inside its domain, rpt_scene_exact_rcp), 0 if it ran their IEEE-division form or
+ * a kernel that has none (903, 923, the forms without a walk), and 0 before the first pass.  A status, like the other calls here:
+ * RPT_ERR_ARG for a null context or a null exact_out. */
+int rpt_last_events_exact_rcp(const rpt_ctx *ctx, int *exact_out);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

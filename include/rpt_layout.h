@@ -64,6 +64,18 @@ typedef struct rpt_pixel {
 } rpt_pixel;
 
 /*
+ * One record of the event pass (rpt_render_events; not in the reference): what a pixel's primary ray sees, where and when.
+ * A miss is {-1, 0, 0, 0, 0, 0, 0, 0}, stored exactly so.
+ */
+typedef struct rpt_event {
+    int32_t object;           /*  0  index into the context's Object[] of the closest hit; -1 = the ray hits nothing */
+    float   dist;             /*  4  Hit.dist of the winner (opencl_kernel.cl:395-397): the camera-frame distance    */
+    float   event[4];         /*  8  stationaryCam + (Lorentz (interval, normalize(dir))) * dist of the hit object:
+                                     t, x, y, z in ITS rest frame, the float operations of :386-388 and :396 in that order */
+    float   uv[2];            /* 24  Hit.uv of the winner, as the texture lookup of :430-431 receives it */
+} rpt_event;
+
+/*
  * The eight read-only scene arrays the reference uploads once (main.cpp:33-55), in the
  * reference's layouts, as {pointer, element count} pairs.  Zero-length arrays are legal and
  * their pointer may be NULL (main.cpp:34 passes NULL for empty vectors).
@@ -111,5 +123,8 @@ RPT_SA(offsetof(rpt_octree, trisCount) == 36, "trisCount");
 RPT_SA(offsetof(rpt_octree, children) == 40, "children");
 RPT_SA(offsetof(rpt_octree, neighbors) == 72, "neighbors");
 RPT_SA(sizeof(rpt_pixel) == 16, "pixel is 16 B");
+RPT_SA(sizeof(rpt_event) == 32, "event record is 32 B");
+RPT_SA(offsetof(rpt_event, event) == 8, "event");
+RPT_SA(offsetof(rpt_event, uv) == 24, "uv");
 
 #endif /* RPT_LAYOUT_H */

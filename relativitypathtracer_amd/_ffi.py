@@ -183,6 +183,13 @@ HIP_SYMBOLS = {
     "rpt_set_field_of_view": (C.c_int, [C.c_void_p, C.c_float]),
     "rpt_orient_objects": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "rpt_orient_matrix": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "rpt_set_events_output": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_render_events": (C.c_int, [C.c_void_p]),
+    "rpt_render_events_async": (C.c_int, [C.c_void_p]),
+    "rpt_read_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_pick": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "rpt_last_events_variant": (C.c_int, [C.c_void_p]),
+    "rpt_last_events_exact_rcp": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -158,6 +158,16 @@ struct rpt_ctx {
     std::vector<uint8_t> given_scratch, turned_scratch;   // rpt_set_objects with an orientation: reused from frame to frame (no allocation per call)
     float v_fov = 0.0f;                               // 0 = the reference's lens
     float lens_scale = 1.0f;                          // (float)tan(v_fov / 2)
+    // rpt_set_events_output / rpt_render_events (not in the reference): the event pass, per context, never shared
+    void *external_events = nullptr;                  // the caller's record buffer (width * height * 32 B), or null: owned_events
+    DeviceBuffer owned_events;                        // allocated on first use
+    hipEvent_t ev_events = nullptr;                   // recorded after every event pass (what last_event names then); created on first use
+    int last_events_variant = 0;                      // the event kernel the last pass ran with (rpt_last_events_variant)
+    bool last_events_exact_rcp = false;               // ... and whether its walk took 1 / det through rcp_exact (rpt_last_events_exact_rcp)
+    bool events_rendered = false;
+    // the last event frame, as rpt_pick and rpt_read_events address it: its buffer, its size and the rows this context wrote
+    void *events_ptr = nullptr;
+    int events_width = 0, events_height = 0, events_first_tile = 0, events_tile_step = 1, events_run_log2 = 0;
 };
 
 namespace {
@@ -908,12 +918,9 @@ const VariantRow *variant_row(int v) {
     return nullptr;
 }
 
-int launch(rpt_ctx *ctx) {
-    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
-    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_set_params");
-    if (int rc = ensure_outputs(ctx)) return rc;
-
-    rptd::KernelArgs a;
+// What every frame's KernelArgs hold whatever kernel renders it: the scene, the outputs, the per-frame constants, the rows (launch()
+// and launch_events() fill the rest).
+void fill_kernel_args(const rpt_ctx *ctx, rptd::KernelArgs &a) {
     std::memset(&a, 0, sizeof a);
     a.dnodes = (const rptd::DNode *)ctx->geo->dnodes.ptr;
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
@@ -965,6 +972,17 @@ int launch(rpt_ctx *ctx) {
     a.first_tile = ctx->first_tile;
     a.tile_step = ctx->tile_step;
     a.run_log2 = ctx->run_log2;
+}
+
+int launch(rpt_ctx *ctx) {
+    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
+    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_set_params");
+    if (int rc = ensure_outputs(ctx)) return rc;
+
+    rptd::KernelArgs a;
+    fill_kernel_args(ctx, a);
+    const bool lens = ctx->v_fov != 0.0f;
+    const float lens_scale = lens ? ctx->lens_scale : 1.0f;
 
     const int tiles = local_tile_count(ctx);
     if (tiles == 0) return RPT_OK;
@@ -1093,6 +1111,103 @@ int launch(rpt_ctx *ctx) {
     return RPT_OK;
 }
 
+// ---- the event kernels (rpt_render_events): one row per kernel, chosen by camera and form --------------------------------------------
+// variant   what rpt_last_events_variant reports
+// camera    the context's: the pinhole, the panorama (rpt_set_projection) or the pinhole under a lens (rpt_set_field_of_view)
+// form      un-culled (rpt_set_variant(3); also what a frame outside the window the regions are proven for gets, the rule 3 and 803
+//           follow), the octree walk with the wave's object mask, or no walk compiled in (an Object[] without a mesh).  The panorama
+//           has no un-culled row: it has no object mask and the pass has no shadow rays, so its other two rows cull nothing
+// ieee      the walk's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp), as for 41
+enum class EventCamera { pinhole, equirect, lens };
+enum class EventForm { unculled, walk, analytic };
+struct EventRow {
+    int variant;
+    EventCamera camera;
+    EventForm form;
+    const void *kernel;
+    const void *ieee;
+};
+#define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
+const EventRow events_table[] = {
+    {903, EventCamera::pinhole,  EventForm::unculled, RPT_KERNEL(rpt_events_kernel_unculled),      nullptr},
+    {941, EventCamera::pinhole,  EventForm::walk,     RPT_KERNEL(rpt_events_kernel_ballot),        RPT_KERNEL(rpt_events_kernel_ballot_ieee)},
+    {944, EventCamera::pinhole,  EventForm::analytic, RPT_KERNEL(rpt_events_kernel_analytic),      nullptr},
+    {911, EventCamera::equirect, EventForm::walk,     RPT_KERNEL(rpt_events_kernel_pano),          RPT_KERNEL(rpt_events_kernel_pano_ieee)},
+    {914, EventCamera::equirect, EventForm::analytic, RPT_KERNEL(rpt_events_kernel_pano_analytic), nullptr},
+    {923, EventCamera::lens,     EventForm::unculled, RPT_KERNEL(rpt_events_kernel_lens_unculled), nullptr},
+    {921, EventCamera::lens,     EventForm::walk,     RPT_KERNEL(rpt_events_kernel_lens_ballot),   RPT_KERNEL(rpt_events_kernel_lens_ballot_ieee)},
+    {924, EventCamera::lens,     EventForm::analytic, RPT_KERNEL(rpt_events_kernel_lens_analytic), nullptr},
+};
+#undef RPT_KERNEL
+
+// One event pass on the context's stream: the record of every pixel of this context's rows, written at y * width + x of the full-frame
+// record buffer.  The settings of Doppler, the sky and debug_rgb are not looked at (they act on colour only); neither the colour
+// framebuffer nor anything rpt_last_variant / rpt_last_frame_ms report is touched.
+int launch_events(rpt_ctx *ctx) {
+    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render_events before rpt_upload_scene");
+    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render_events before rpt_set_params");
+    if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_render_events: MSAA > 1 has no event kernel (one primary ray per pixel)");
+    const int sv = ctx->variant;
+    if (sv != VARIANT_DEFAULT && sv != VARIANT_UNCULLED && sv != VARIANT_BALLOT && sv != VARIANT_BALLOT_FIRST && sv != VARIANT_ANALYTIC)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_events: variant " + std::to_string(sv) + " has no event kernel (variants 0, 3, 41, 43 and 44 have)");
+    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
+    const bool lens = ctx->v_fov != 0.0f;
+    if (lens && panorama) return fail(ctx, RPT_ERR_ARG, "rpt_render_events: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
+
+    rptd::KernelArgs a;
+    fill_kernel_args(ctx, a);
+    a.out16 = nullptr;          // (the pass writes records only)
+    a.plane = nullptr;
+    a.debug_rgb = nullptr;
+    const float lens_scale = lens ? ctx->lens_scale : 1.0f;
+    const EventCamera camera = panorama ? EventCamera::equirect : (lens ? EventCamera::lens : EventCamera::pinhole);
+    EventForm form = !ctx->has_mesh ? EventForm::analytic : EventForm::walk;
+    if (camera != EventCamera::equirect) {
+        // the window the regions are proven for: launch()'s rule, word for word (frames wider than 4 : 1, sides beyond 2^20, a lens with s > 1)
+        const bool window_holds_frame = (lens ? lens_scale <= 1.0f && lens_scale * (0.5f * a.aspect) <= (float)rptb::cert::WINDOW_U : 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U) &&
+                                        ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
+        if (sv == VARIANT_UNCULLED || !window_holds_frame) form = EventForm::unculled;
+    }
+    if (!ctx->geo->compact_ok && form != EventForm::analytic)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_events: the event kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+    const EventRow *row = nullptr;
+    for (const EventRow &r : events_table)
+        if (r.camera == camera && r.form == form) row = &r;
+    if (!row) return fail(ctx, RPT_ERR_ARG, "rpt_render_events: no event kernel for this camera");
+
+    const size_t px = (size_t)ctx->width * ctx->height;
+    if (!ctx->external_events && (px * sizeof(rpt_event) > ctx->owned_events.capacity || ctx->owned_events.bytes != px * sizeof(rpt_event))) {
+        if (int rc = reserve(ctx, ctx->owned_events, px * sizeof(rpt_event))) return rc;
+        RPT_HIP(ctx, hipMemsetAsync(ctx->owned_events.ptr, 0, px * sizeof(rpt_event), ctx->stream));
+    }
+    rptd::EventArgs ea;
+    std::memset(&ea, 0, sizeof ea);
+    static_cast<rptd::KernelArgs &>(ea) = a;
+    if (panorama) {
+        if (int rc = ensure_panorama_tables(ctx)) return rc;
+        ea.pano_cols = (const float2 *)ctx->pano_tables.ptr;
+        ea.pano_rows = (const float2 *)ctx->pano_tables.ptr + ctx->width;
+    }
+    ea.lens_scale = lens_scale;
+    ea.events = (rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
+    ctx->events_ptr = ea.events;
+    ctx->events_width = ctx->width;
+    ctx->events_height = ctx->height;
+    ctx->events_first_tile = ctx->first_tile;
+    ctx->events_tile_step = ctx->tile_step;
+    ctx->events_run_log2 = ctx->run_log2;
+    ctx->last_events_variant = row->variant;
+    const bool exact_rcp = row->ieee && ctx->geo->exact_rcp_ok;      // launch()'s rule: the row's own kernel on a scene inside rcp_exact's domain
+    ctx->last_events_exact_rcp = exact_rcp;
+    const int tiles = local_tile_count(ctx);
+    if (tiles == 0) return RPT_OK;
+    const dim3 grid1(((ctx->width + 31) / 32) * 4, tiles);      // one wave (an 8 x 8 tile) per workgroup, as the product kernels
+    void *args[] = {(void *)&ea};
+    (void)hipLaunchKernel(row->ieee && !exact_rcp ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
+    RPT_HIP(ctx, hipGetLastError());
+    return RPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1157,7 +1272,7 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables, &ctx->env_texels})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables, &ctx->env_texels, &ctx->owned_events})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     if (ctx->pano_host) (void)hipHostFree(ctx->pano_host);
@@ -1167,6 +1282,7 @@ void rpt_destroy(rpt_ctx *ctx) {
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
+    if (ctx->ev_events) (void)hipEventDestroy(ctx->ev_events);
     for (hipEvent_t e : ctx->timing_events) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -1774,6 +1890,60 @@ int rpt_render(rpt_ctx *ctx) {
     ctx->latency_call = false;
     if (rc) return rc;
     return rpt_sync(ctx);
+}
+
+int rpt_set_events_output(rpt_ctx *ctx, void *device_ptr_or_null) {
+    if (!ctx) return RPT_ERR_ARG;
+    ctx->external_events = device_ptr_or_null;
+    return RPT_OK;
+}
+
+int rpt_render_events_async(rpt_ctx *ctx) {
+    if (!ctx) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->ev_events) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
+    if (int rc = launch_events(ctx)) return rc;
+    RPT_HIP(ctx, hipEventRecord(ctx->ev_events, ctx->stream));
+    ctx->last_event = ctx->ev_events;
+    ctx->events_rendered = true;
+    return RPT_OK;
+}
+
+int rpt_render_events(rpt_ctx *ctx) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (int rc = rpt_render_events_async(ctx)) return rc;
+    return rpt_sync(ctx);
+}
+
+int rpt_read_events(rpt_ctx *ctx, void *host_dst, size_t bytes) {
+    if (!ctx || !host_dst) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->events_rendered || !ctx->events_ptr) return fail(ctx, RPT_ERR_STATE, "rpt_read_events: no event frame rendered yet");
+    if (bytes > (size_t)ctx->events_width * ctx->events_height * sizeof(rpt_event)) return fail(ctx, RPT_ERR_ARG, "rpt_read_events: more bytes requested than the event frame holds");
+    RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RPT_HIP(ctx, hipMemcpy(host_dst, ctx->events_ptr, bytes, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_pick(rpt_ctx *ctx, int x, int y, rpt_event *out) {
+    if (!ctx || !out) return RPT_ERR_ARG;
+    if (!ctx->events_rendered || !ctx->events_ptr) return fail(ctx, RPT_ERR_STATE, "rpt_pick: no event frame rendered yet");
+    if (x < 0 || y < 0 || x >= ctx->events_width || y >= ctx->events_height) return fail(ctx, RPT_ERR_ARG, "rpt_pick: the pixel lies outside the last event frame");
+    // the rows of the last event frame that were this context's: tile t is one iff (t - first_tile) mod tile_step < run
+    const int tile = y / RPT_TILE_ROWS, rel = tile - ctx->events_first_tile;
+    if (rel < 0 || rel % ctx->events_tile_step >= (1 << ctx->events_run_log2)) return fail(ctx, RPT_ERR_ARG, "rpt_pick: the row is not one of this context's (rpt_set_rows)");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RPT_HIP(ctx, hipMemcpy(out, (const rpt_event *)ctx->events_ptr + ((size_t)y * ctx->events_width + x), sizeof(rpt_event), hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_last_events_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_events_variant : RPT_ERR_ARG; }      // (no event kernel is numbered 1)
+
+int rpt_last_events_exact_rcp(const rpt_ctx *ctx, int *exact_out) {
+    if (!ctx || !exact_out) return RPT_ERR_ARG;
+    *exact_out = ctx->last_events_exact_rcp ? 1 : 0;
+    return RPT_OK;
 }
 
 void *rpt_output_ptr(rpt_ctx *ctx) {

@@ -1414,6 +1414,108 @@ RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
     }
 }
 
+// ---- The event pass (rpt_render_events; not in the reference; DESIGN.md "Event pass") -----------------------------------------------
+// A second kind of frame: per pixel the object the primary ray hits first, the distance, the emission event in that object's rest
+// frame and the surface (u, v) — what trace() computes on its way to a colour and drops.  The arguments are LensArgs with the
+// record pointer appended (every camera's kernels take them: doppler = 0, env_texels unused), so no other kernel's argument block
+// changes.
+struct EventArgs : LensArgs {
+    rpt_event *events;              // [width * height] full-frame addressing, whatever the context's colour_plane says
+};
+
+// sphere_core leaves (u, v) out for an untextured sphere (only the texture fetch reads it in a frame); the record holds Hit.uv of
+// every winner, so for such a winner the sphere's test is repeated once, after the loop, with want_uv set: the same float
+// operations on the same inputs as intersect_object_primary's, hence the same objPt, and the oracle's two lines on it.
+RPT_DEV f2 primary_sphere_uv(const KernelArgs &a, int i, f4 rayDir) {
+    const rpt_object &obj = a.objects[i];
+    const DObj &pre = a.dobjs[i];
+    const f3 d3 = mk3(dot(ld4(obj.Lorentz[1]), rayDir), dot(ld4(obj.Lorentz[2]), rayDir), dot(ld4(obj.Lorentz[3]), rayDir));
+    f3 dir = transformDirection(obj.InvM, d3);
+    const float scale = length(dir);
+    dir = dir / scale;
+    Hit h;
+    h.dist = 1e20f;
+    h.uv.x = h.uv.y = 0.0f;
+    sphere_core(obj, -mk3(pre.ox, pre.oy, pre.oz), pre.sphere_c, dir, scale, h, true);
+    return h.uv;
+}
+
+// One lane's 32-B record as two 16-byte NON-TEMPORAL stores (store_pixel's reason: written once, never read by these kernels; a
+// 4K event frame is 265 MB against 4 MB of L2 per XCD).  A wave's 8 x 8 tile is eight runs of 256 contiguous bytes.
+RPT_DEV void store_event(rpt_event *events, size_t id, int object, float dist, f4 ev, f2 uv) {
+    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+    v4u lo, hi;
+    lo.x = (unsigned int)object; lo.y = __float_as_uint(dist); lo.z = __float_as_uint(ev.x); lo.w = __float_as_uint(ev.y);
+    hi.x = __float_as_uint(ev.z); hi.y = __float_as_uint(ev.w); hi.z = __float_as_uint(uv.x); hi.w = __float_as_uint(uv.y);
+    v4u *p = reinterpret_cast<v4u *>(events) + 2 * id;
+    __builtin_nontemporal_store(lo, p);
+    __builtin_nontemporal_store(hi, p + 1);
+}
+
+// render_pixel_body's geometry (one wave per workgroup, the 8 x 8 tile, the same row and tile arithmetic, the object mask formed
+// before partial lanes leave, the same three camera-direction functions), then trace()'s closest-hit loop — the same
+// intersect_object_primary<P>, the same strict <, the same object order, so ties break as in the frame — and after it only the
+// four-component event.  No texture fetch, flash, lights, shadow rays or tonemap.  The loop is a SECOND COPY of trace()'s (not
+// factored out of it): trace() and every render kernel stay the source, and the machine code, they were.
+template <class P>
+RPT_DEV void events_pixel_body(const EventArgs &a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (int)blockIdx.x & 3;
+    const int strip = (int)blockIdx.x >> 2;
+    const int tile_row = (int)blockIdx.y;
+    const int row_in_tile = lane >> 3;
+    const int x_coord = strip * 32 + wave * 8 + (lane & 7);
+    const int global_tile = (tile_row >> a.run_log2) * a.tile_step + a.first_tile + (tile_row & ((1 << a.run_log2) - 1));
+    const int y_coord = global_tile * RPT_TILE_ROWS + row_in_tile;
+    unsigned long long object_mask = ~0ull;
+    if constexpr (P::camera == Camera::lens) {
+        if (P::culled && P::object_mask) object_mask = wave_object_mask_lens(a, a.lens_scale, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    } else if (P::culled && P::object_mask) object_mask = wave_object_mask(a, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
+    if (x_coord >= a.width || y_coord >= a.height) return;
+
+    int object = -1;
+    float dist = 0.0f;
+    f4 ev = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    f2 uv;
+    uv.x = uv.y = 0.0f;
+    const bool masked = P::culled && P::object_mask;
+    if (!masked || object_mask != 0 || a.object_count > 64) {       // (a wave whose mask is empty stores miss records without reading the scene)
+        f3 camdir;
+        if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(a, x_coord, y_coord);
+        else if constexpr (P::camera == Camera::lens) camdir = lensCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect, a.lens_scale);
+        else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
+        const float inf = 1e20f;
+        Hit hit;
+        hit.dist = inf;
+        hit.uv.x = hit.uv.y = 0.0f;
+        hit.object = -1;
+        const f3 nd = normalize(camdir);
+        const f4 rayDir = mk4((float)a.interval, nd.x, nd.y, nd.z);
+        for (int i = 0; i < a.object_count; i++) {
+            if (i < 64 && !((object_mask >> i) & 1ull)) continue;
+            Hit newHit;
+            newHit.dist = inf;
+            if (intersect_object_primary<P>(a, i, rayDir, newHit)) {
+                if (newHit.dist < hit.dist) {
+                    hit = newHit;
+                    hit.object = i;
+                }
+            }
+        }
+        if (hit.object >= 0) {
+            const rpt_object &ho = a.objects[hit.object];
+            if (ho.type == RPT_SPHERE && ho.textureIndex == -1) hit.uv = primary_sphere_uv(a, hit.object, rayDir);
+            // opencl_kernel.cl:396: event = newEvent0 + lightDir * newHit.dist, lightDir = Lorentz * (interval, nd) (:386-388)
+            const f4 lightDir = transformPoint4D(ho.Lorentz, rayDir);
+            ev = ld4(ho.stationaryCam) + lightDir * hit.dist;
+            object = hit.object;
+            dist = hit.dist;
+            uv = hit.uv;
+        }
+    }
+    store_event(a.events, (size_t)y_coord * a.width + x_coord, object, dist, ev, uv);
+}
+
 #ifndef RPT_RELAXED_FP    /* rpt_relaxed.hip instantiates its own two kernels and nothing else from here on */
 // Product kernels (rpt_set_variant; the number in the comment is the variant).
 __global__ __launch_bounds__(64) void rpt_render_kernel_v0(const KernelArgs a) { render_pixel_body<RefLayout>(a); }                                                              // 1: any valid octree
@@ -1493,6 +1595,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_first_w5(const LensArgs a) { render_pixel_body<Lens<Environment<BallotFirstExact>>>(a); }    // 863
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_first_ieee_w5(const LensArgs a) { render_pixel_body<Lens<Environment<BallotFirst>>>(a); }    // (863)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_lens_env_analytic_w8(const LensArgs a) { render_pixel_body<Lens<Environment<Analytic>>>(a); }    // 864
+
+// Event kernels (rpt_render_events; not in the reference): the product kernels' launch shape, the record instead of a colour.  The number
+// is what rpt_last_events_variant reports.  Only the throughput walk is built; 941 / 911 / 921 take 1 / det through rcp_exact like 41,
+// with an IEEE form each for scenes outside the domain.  The panorama needs no un-culled form: it has no object mask and the pass has no
+// shadow rays, so nothing is culled there.  DESIGN.md "Event pass".
+// Occupancy (make asm; profiles/r09_events_kernel_resources.txt): the walk forms need 79-81 VGPRs, 102-106 SGPRs and no scratch when
+// asked for five waves per SIMD as the render kernels are — without the shading state they sit one 8-register granule below the
+// 88-register step, so SIX waves fit (512 / 6 = 85 -> 80 VGPRs: 79-80 used, still no scratch); seven would need <= 72 and spill.  The
+// forms without the walk need 44-46 VGPRs, 78 SGPRs, no scratch: EIGHT waves, the most a SIMD holds, as kernel 44.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_unculled(const EventArgs a) { events_pixel_body<Unculled>(a); }    // 903
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_ballot(const EventArgs a) { events_pixel_body<BallotExact>(a); }    // 941
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_ballot_ieee(const EventArgs a) { events_pixel_body<Ballot>(a); }    // (941)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_analytic(const EventArgs a) { events_pixel_body<Analytic>(a); }    // 944
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_pano(const EventArgs a) { events_pixel_body<PanoramaWalk>(a); }    // 911
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_pano_ieee(const EventArgs a) { events_pixel_body<PanoramaWalkIeee>(a); }    // (911)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_pano_analytic(const EventArgs a) { events_pixel_body<PanoramaAnalytic>(a); }    // 914
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_lens_unculled(const EventArgs a) { events_pixel_body<Lens<Unculled>>(a); }    // 923
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_lens_ballot(const EventArgs a) { events_pixel_body<Lens<BallotExact>>(a); }    // 921
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_lens_ballot_ieee(const EventArgs a) { events_pixel_body<Lens<Ballot>>(a); }    // (921)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_lens_analytic(const EventArgs a) { events_pixel_body<Lens<Analytic>>(a); }    // 924
 
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd

@@ -14,6 +14,7 @@ from typing import Mapping, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _ffi
+from .events import EVENT_DTYPE
 from .scene import Scene
 
 PIXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("rgba", "u1", (4,)), ("unspecified", "<u4")])
@@ -133,6 +134,7 @@ class Renderer:
         self.device = device
         self.width = self.height = 0
         self._rows = (0, 1, False)
+        self._events_size = None             # (width, height) of the last event frame: what read_events shapes its result by
         self._run = 1
 
     def close(self):
@@ -296,6 +298,47 @@ class Renderer:
     def sync(self):
         self._check(self._lib.rpt_sync(self._h), "rpt_sync")
 
+    # -- the event pass (include/rpt.h, rpt_render_events; not in the reference) ------------------
+    def set_events_output(self, device_ptr: Optional[int]):
+        """The record buffer of the event pass: a device pointer to width * height * 32 B, or None for a library-owned one."""
+        self._check(self._lib.rpt_set_events_output(self._h, C.c_void_p(device_ptr or 0)), "rpt_set_events_output")
+
+    def render_events(self, async_: bool = False) -> Optional[np.ndarray]:
+        """One event frame with the context's current objects, params, rows, projection, orientation and lens: per pixel the object
+        hit (-1 = none), the distance, the emission event in the hit object's rest frame and the surface (u, v).  Blocking: returns the
+        (H, W) array of EVENT_DTYPE (row 0 = the bottom row).  async_=True: enqueues only and returns None (sync, then read_events)."""
+        if async_:
+            self._check(self._lib.rpt_render_events_async(self._h), "rpt_render_events_async")
+            self._events_size = (self.width, self.height)
+            return None
+        self._check(self._lib.rpt_render_events(self._h), "rpt_render_events")
+        self._events_size = (self.width, self.height)
+        return self.read_events()
+
+    def read_events(self) -> np.ndarray:
+        """The last event frame's records, (H, W) of EVENT_DTYPE with W and H as they were when that frame was rendered (set_scene_params
+        since then does not change them); rows that are not this context's hold what the buffer held."""
+        width, height = self._events_size or (self.width, self.height)      # (before the first pass the call refuses: RPT_ERR_STATE)
+        out = np.empty((height, width), dtype=EVENT_DTYPE)
+        self._check(self._lib.rpt_read_events(self._h, out.ctypes.data, out.nbytes), "rpt_read_events")
+        return out
+
+    def pick(self, x: int, y: int) -> np.void:
+        """One record of the last event frame (rpt_pick): pixel (x, y), y counted from the bottom row."""
+        out = np.zeros(1, dtype=EVENT_DTYPE)
+        self._check(self._lib.rpt_pick(self._h, int(x), int(y), out.ctypes.data), "rpt_pick")
+        return out[0]
+
+    def last_events_variant(self) -> int:
+        """The event kernel (include/rpt.h, rpt_render_events) the last event pass ran with; 0 before the first one."""
+        return int(self._lib.rpt_last_events_variant(self._h))
+
+    def last_events_exact_rcp(self) -> bool:
+        """Whether the last event pass's triangle test took 1 / det through the exact reciprocal (941 / 911 / 921 on a scene in its domain)."""
+        exact = C.c_int(0)
+        self._check(self._lib.rpt_last_events_exact_rcp(self._h, C.byref(exact)), "rpt_last_events_exact_rcp")
+        return bool(exact.value)
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -426,8 +469,9 @@ class Renderer:
 
 def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
                  projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None,
-                 orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None):
-    """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None).  projection: None (the pinhole), a mode name
+                 orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False):
+    """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
+    records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}.  environment: an
     H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first).
     orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view)."""
@@ -448,6 +492,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        return r.read_framebuffer(), (r.read_debug_rgb() if debug_rgb else None)
+        frame = r.read_framebuffer(), (r.read_debug_rgb() if debug_rgb else None)
+        return frame + (r.render_events(),) if events else frame
     finally:
         r.close()
