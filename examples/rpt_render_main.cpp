@@ -3,11 +3,15 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--events FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
 // context, made once, BEFORE the objects are handed over; the per-frame loop stays the reference's.
+//
+// --aa N[:T] switches adaptive anti-aliasing on (rpt_set_adaptive_aa; not in the reference): N x N samples in every pixel whose 8-bit
+// colour differs from a 4-neighbour's by more than T (default 8; -1 = every pixel) in the one-sample frame.  A setting of the render
+// context too; the number of refined pixels goes to stderr.  Without the flag nothing changes.
 //
 // --events FILE also renders one event pass of the view the PPM shows (rpt_render_events; not in the reference) and writes its raw
 // records: width * height * 32 B (rpt_event, rpt_layout.h), row 0 the bottom row as everywhere.  Without the flag nothing changes.
@@ -38,6 +42,7 @@ int main(int argc, char **argv) {
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
     const char *events_path = nullptr;
+    int aa_n = 1, aa_threshold = 8;
     {
         const double deg = 3.14159265358979323846 / 180.0;
         int kept = 1;
@@ -48,6 +53,18 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--roll")) { ypr[2] = (float)(std::atof(argv[++i]) * deg); turned = true; }
             else if (has_value && !std::strcmp(argv[i], "--fov")) v_fov = (float)(std::atof(argv[++i]) * deg);
             else if (has_value && !std::strcmp(argv[i], "--events")) events_path = argv[++i];
+            else if (has_value && !std::strcmp(argv[i], "--aa")) {
+                char *end = nullptr;
+                aa_n = (int)std::strtol(argv[++i], &end, 10);
+                if (end && *end == ':') aa_threshold = (int)std::strtol(end + 1, &end, 10);
+                if (!end || *end != '\0' || end == argv[i]) {
+                    std::fprintf(stderr, "--aa takes N or N:T (samples per axis 1..8, threshold -1..255)\n");
+                    return 2;
+                }
+            } else if (!std::strcmp(argv[i], "--aa")) {
+                std::fprintf(stderr, "--aa needs a value: N or N:T\n");
+                return 2;
+            }
             else if (!std::strcmp(argv[i], "--events")) {
                 std::fprintf(stderr, "--events needs a file name\n");
                 return 2;
@@ -59,7 +76,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--events FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -91,6 +108,7 @@ int main(int argc, char **argv) {
     int rc = RPT_OK;
     if (turned) rc = rpt_set_orientation(ctx, ypr);              // the context's view: before any Object[] is handed over
     if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ctx, v_fov);
+    if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ctx, aa_n, aa_threshold);
     if (!rc) rc = rpt_upload_scene(ctx, &desc);                  // 8x cl::Buffer + write    main.cpp:33-55
     if (!rc) rc = rpt_set_params(ctx, wp, ambient, width, height, interval);   // initCLKernel()  main.cpp:62
     if (!rc) rc = rpt_set_output(ctx, nullptr);                  // BufferGL(vbo)           main.cpp:58
@@ -112,6 +130,7 @@ int main(int argc, char **argv) {
         for (int k = 0; k < ring.frames_in_flight() && !rc; k++) {      // the view is per context: every frame slot gets it
             if (turned) rc = rpt_set_orientation(ring.slot(k), ypr);
             if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ring.slot(k), v_fov);
+            if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ring.slot(k), aa_n, aa_threshold);
         }
         if (!rc) rc = ring.upload(desc);
         if (!rc) rc = ring.set_params(wp, ambient, width, height, interval);
@@ -150,6 +169,12 @@ int main(int argc, char **argv) {
     std::vector<unsigned char> fb((size_t)width * height * 16);
     rpt_read_framebuffer(last, fb.data(), fb.size());
     rc = rpt_write_ppm(argv[3], fb.data(), width, height);       // drawGL()                gl_interop.cpp:51
+    if (!rc && aa_n != 1) {
+        unsigned long long refined = 0;
+        rc = rpt_last_aa_refined(last, &refined);
+        std::fprintf(stderr, "adaptive anti-aliasing %d x %d, threshold %d: %llu of %lld pixels refined (kernel %d)\n", aa_n, aa_n, aa_threshold, refined,
+                     (long long)width * height, rpt_last_aa_variant(last));
+    }
     if (!rc && events_path) {                                    // what each pixel of that frame shows, where and when
         std::vector<rpt_event> records((size_t)width * height);
         rc = rpt_render_events(last);

@@ -34,7 +34,9 @@
  * rpt_set_field_of_view, and rpt_orient_objects / rpt_orient_matrix (host code, no device needed; DESIGN.md, "Free-look camera"), and the
  * opt-in event pass — per pixel the object hit, the distance, the emission event in the object's rest frame and the surface (u, v), which
  * the reference computes and discards: rpt_set_events_output, rpt_render_events / rpt_render_events_async, rpt_read_events, rpt_pick,
- * rpt_last_events_variant and rpt_last_events_exact_rcp ("Event pass").
+ * rpt_last_events_variant and rpt_last_events_exact_rcp ("Event pass"), and opt-in adaptive anti-aliasing in every camera and
+ * colour mode (the reference's MSAASAMPLES is a compile-time constant, 1 as shipped): rpt_set_adaptive_aa, rpt_last_aa_refined and
+ * rpt_last_aa_variant ("Adaptive anti-aliasing").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -357,6 +359,42 @@ int rpt_last_events_variant(const rpt_ctx *ctx);
  * a kernel that has none (903, 923, the forms without a walk), and 0 before the first pass.  A status, like the other calls here:
  * RPT_ERR_ARG for a null context or a null exact_out. */
 int rpt_last_events_exact_rcp(const rpt_ctx *ctx, int *exact_out);
+
+/* Adaptive anti-aliasing (not in the reference; DESIGN.md "Adaptive anti-aliasing"): n x n samples where the picture has an edge, one
+ * where it is flat, in every camera and colour mode.  Opt-in, per context; samples_per_axis = 1 (the default) is off, and with it off
+ * nothing changes.  With n = 2..8 a colour frame (rpt_render, rpt_render_async) is two launches on the context's stream:
+ *   pass A  the one-sample frame exactly as without the setting — the same kernel (rpt_last_variant), the same framebuffer bytes — which
+ *           also writes its packed colours into a context-owned 4 B/pixel plane;
+ *   pass B  a refine kernel (rpt_last_aa_variant) that reads that plane: a pixel is refined iff the largest absolute difference of its
+ *           8-bit R, G, B to those of any of its four neighbours (x +- 1, y +- 1; neighbours outside the frame are ignored) is GREATER
+ *           than `threshold` (-1 refines every pixel: full n x n supersampling; 255 refines none).  A refined pixel is rendered again
+ *           with n^2 camera rays in the order of opencl_kernel.cl:641-648 — sample (sx, sy) at ((float)x + (float)sx / n, (float)y +
+ *           (float)sy / n), colours summed sy outer, sx inner in float, a miss contributing the background (the sky of its own direction
+ *           with rpt_set_environment), divided by n^2, tonemapped, packed — and its 16-B framebuffer pixel (and its debug_rgb triple)
+ *           overwritten.  Every other pixel keeps pass A's bytes.
+ * So adaptive(n, T) = where(mask_T(one-sample frame), supersampled(n), one-sample frame).  In panorama sample (sx, sy) of pixel (x, y)
+ * looks along pixel (n x + sx, n y + sy) of the n W x n H panorama with the same parameters (rpt_projection_tables at that size); under a
+ * lens the scaled image plane is sampled at the fractional coordinates; an orientation needs nothing.  Refine kernels (throughput forms):
+ *
+ *   colour \ camera    pinhole              lens                 panorama
+ *   plain              1001 / 1004 / 1003   1031 / 1034 / 1033   1061 / 1064 / 1063      (octree walk + object mask, IEEE form as for 41
+ *   Doppler            1011 / 1014 / 1013   1041 / 1044 / 1043   1071 / 1074 / 1073       / no mesh in Object[] / un-culled: wherever
+ *   environment        1021 / 1024 / 1023   1051 / 1054 / 1053   1081 / 1084 / 1083       pass A ran un-culled, pass B does)
+ *
+ * Refused at the LAUNCH with RPT_ERR_ARG and a message that starts "rpt_set_adaptive_aa:" (nothing is launched, the context stays
+ * usable): together with rpt_set_msaa > 1; a context restricted by rpt_set_rows / rpt_set_tile_pattern or rendering into a colour plane
+ * (a tile's neighbour rows belong to another rank); the Doppler debug kernels (rpt_set_debug_doppler: 240 / 540); variants other than
+ * 0, 3, 41, 43, 44; an octree the derived layout cannot hold.  rpt_set_msaa's own refusals are unchanged.  rpt_verify_frame keeps
+ * comparing the one-sample pass, rpt_timed_frames keeps timing it, and the event pass is untouched.  The call itself returns RPT_ERR_ARG
+ * for a null context, samples_per_axis outside 1..8 and threshold outside -1..255. */
+int rpt_set_adaptive_aa(rpt_ctx *ctx, int samples_per_axis, int threshold);
+/* The number of pixels pass B refined in this context's last FINISHED adaptive frame (counted on the device, one atomic add per wave,
+ * copied back in stream order and read at rpt_sync or here once that copy has run); 0 before the first one and for a frame rendered with
+ * the setting off.  RPT_ERR_ARG for a null context or a null `pixels`. */
+int rpt_last_aa_refined(rpt_ctx *ctx, unsigned long long *pixels);
+/* The refine kernel (a number of the table above) of this context's last colour frame; 0 if that frame had no pass B (or before the
+ * first).  rpt_last_variant keeps reporting pass A's kernel. */
+int rpt_last_aa_variant(const rpt_ctx *ctx);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

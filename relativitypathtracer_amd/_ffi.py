@@ -190,6 +190,9 @@ HIP_SYMBOLS = {
     "rpt_pick": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rpt_last_events_variant": (C.c_int, [C.c_void_p]),
     "rpt_last_events_exact_rcp": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rpt_set_adaptive_aa": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "rpt_last_aa_refined": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_last_aa_variant": (C.c_int, [C.c_void_p]),
     "rpt_version": (C.c_char_p, []),
 }
 

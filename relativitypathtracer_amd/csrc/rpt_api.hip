@@ -168,6 +168,21 @@ struct rpt_ctx {
     // the last event frame, as rpt_pick and rpt_read_events address it: its buffer, its size and the rows this context wrote
     void *events_ptr = nullptr;
     int events_width = 0, events_height = 0, events_first_tile = 0, events_tile_step = 1, events_run_log2 = 0;
+    // rpt_set_adaptive_aa (not in the reference): adaptive anti-aliasing, per context, never shared
+    int aa_n = 1, aa_threshold = 8;                   // samples per axis (1 = off) and the criterion's threshold
+    DeviceBuffer aa_plane;                            // pass A's packed colours, 4 B/pixel: what pass B decides from
+    DeviceBuffer aa_counter;                          // 8 B: the refined pixels of the frame in flight
+    unsigned long long *aa_host = nullptr;            // pinned: the counter of the last frame whose copy has run
+    hipEvent_t aa_counted = nullptr;                  // recorded after that copy
+    unsigned long long aa_refined = 0;                // rpt_last_aa_refined: aa_host as last read with aa_counted passed
+    bool aa_pending = false;                          // a copy has been enqueued since aa_refined was read
+    int last_aa_variant = 0;                          // the refine kernel of the last colour frame (rpt_last_aa_variant)
+    DeviceBuffer aa_tables;                           // panorama: rpt_projection_tables at aa_n times the frame's size, columns then rows
+    float *aa_tables_host = nullptr;                  // pinned: what the last upload of those tables was copied from
+    size_t aa_tables_host_capacity = 0;
+    hipEvent_t aa_tables_copied = nullptr;            // recorded after that copy: aa_tables_host is rewritten only once it has passed
+    int aa_tables_n = 0, aa_tables_width = 0, aa_tables_height = 0;      // what the device tables were built for (0: nothing yet)
+    float aa_tables_params[3] = {0, 0, 0};
 };
 
 namespace {
@@ -823,6 +838,36 @@ int ensure_panorama_tables(rpt_ctx *ctx) {
     return RPT_OK;
 }
 
+// The same tables at n times the resolution, for the refine pass of an adaptive panorama frame (rpt_set_adaptive_aa): sample (sx, sy) of
+// pixel (x, y) looks along pixel (n x + sx, n y + sy) of the n W x n H panorama.  Held per context, rebuilt when n, the size or the
+// projection changes; the upload follows ensure_panorama_tables' discipline.
+int ensure_aa_tables(rpt_ctx *ctx) {
+    const int n = ctx->aa_n;
+    if (ctx->aa_tables_n == n && ctx->aa_tables_width == ctx->width && ctx->aa_tables_height == ctx->height &&
+        std::memcmp(ctx->aa_tables_params, ctx->projection_params, sizeof ctx->aa_tables_params) == 0) return RPT_OK;
+    const size_t w = (size_t)n * ctx->width, h = (size_t)n * ctx->height;
+    const size_t floats = 2 * (w + h), bytes = floats * sizeof(float);
+    if (!ctx->aa_tables_copied) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->aa_tables_copied, hipEventDisableTiming));
+    else RPT_HIP(ctx, hipEventSynchronize(ctx->aa_tables_copied));
+    if (bytes > ctx->aa_tables_host_capacity) {
+        if (ctx->aa_tables_host) RPT_HIP(ctx, hipHostFree(ctx->aa_tables_host));
+        ctx->aa_tables_host = nullptr;
+        ctx->aa_tables_host_capacity = 0;
+        RPT_HIP(ctx, hipHostMalloc((void **)&ctx->aa_tables_host, bytes, hipHostMallocDefault));
+        ctx->aa_tables_host_capacity = bytes;
+    }
+    if (bytes > ctx->aa_tables.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
+    if (int rc = reserve(ctx, ctx->aa_tables, bytes)) return rc;
+    projection_fill(ctx->projection_params, (int)w, (int)h, ctx->aa_tables_host, ctx->aa_tables_host + 2 * w);
+    RPT_HIP(ctx, hipMemcpyAsync(ctx->aa_tables.ptr, ctx->aa_tables_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(ctx->aa_tables_copied, ctx->stream));
+    ctx->aa_tables_n = n;
+    ctx->aa_tables_width = ctx->width;
+    ctx->aa_tables_height = ctx->height;
+    std::memcpy(ctx->aa_tables_params, ctx->projection_params, sizeof ctx->aa_tables_params);
+    return RPT_OK;
+}
+
 // ---- the product kernels: every fact launch() and rpt_set_variant() know about a variant, one row each ------------------------------
 // variant      what rpt_set_variant takes (settable rows) and rpt_last_variant reports; the other rows are reached through the
 //              msaa and doppler columns only
@@ -918,6 +963,40 @@ const VariantRow *variant_row(int v) {
     return nullptr;
 }
 
+// ---- the refine kernels (rpt_set_adaptive_aa): one row per kernel, chosen by camera, colour family and form ---------------------------
+// variant   what rpt_last_aa_variant reports: 1000 + 10 (3 camera + colour) + {1 walk, 3 un-culled, 4 no walk}
+// form      pass A's: un-culled wherever the one-sample kernel ran un-culled, the walk with the wave's object mask, or no walk compiled in
+// ieee      the walk's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp), as for 41
+enum class RefineCamera { pinhole, lens, equirect };
+enum class RefineColour { plain, doppler, environment };
+enum class RefineForm { unculled, walk, analytic };
+struct RefineRow {
+    int variant;
+    RefineCamera camera;
+    RefineColour colour;
+    RefineForm form;
+    const void *kernel;
+    const void *ieee;
+};
+#define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
+#define RPT_REFINE_ROWS(base, camera, colour, name)                                                                                                       \
+    {base + 3, camera, colour, RefineForm::unculled, RPT_KERNEL(rpt_refine_kernel_##name##_unculled), nullptr},                                          \
+    {base + 1, camera, colour, RefineForm::walk,     RPT_KERNEL(rpt_refine_kernel_##name##_walk),     RPT_KERNEL(rpt_refine_kernel_##name##_walk_ieee)}, \
+    {base + 4, camera, colour, RefineForm::analytic, RPT_KERNEL(rpt_refine_kernel_##name##_analytic), nullptr}
+const RefineRow refine_table[] = {
+    RPT_REFINE_ROWS(1000, RefineCamera::pinhole,  RefineColour::plain,       plain),
+    RPT_REFINE_ROWS(1010, RefineCamera::pinhole,  RefineColour::doppler,     doppler),
+    RPT_REFINE_ROWS(1020, RefineCamera::pinhole,  RefineColour::environment, env),
+    RPT_REFINE_ROWS(1030, RefineCamera::lens,     RefineColour::plain,       lens),
+    RPT_REFINE_ROWS(1040, RefineCamera::lens,     RefineColour::doppler,     lens_doppler),
+    RPT_REFINE_ROWS(1050, RefineCamera::lens,     RefineColour::environment, lens_env),
+    RPT_REFINE_ROWS(1060, RefineCamera::equirect, RefineColour::plain,       pano),
+    RPT_REFINE_ROWS(1070, RefineCamera::equirect, RefineColour::doppler,     pano_doppler),
+    RPT_REFINE_ROWS(1080, RefineCamera::equirect, RefineColour::environment, pano_env),
+};
+#undef RPT_REFINE_ROWS
+#undef RPT_KERNEL
+
 // What every frame's KernelArgs hold whatever kernel renders it: the scene, the outputs, the per-frame constants, the rows (launch()
 // and launch_events() fill the rest).
 void fill_kernel_args(const rpt_ctx *ctx, rptd::KernelArgs &a) {
@@ -974,7 +1053,9 @@ void fill_kernel_args(const rpt_ctx *ctx, rptd::KernelArgs &a) {
     a.run_log2 = ctx->run_log2;
 }
 
-int launch(rpt_ctx *ctx) {
+// colour_frame: the launch renders a frame of rpt_render / rpt_render_async, which is what rpt_set_adaptive_aa acts on (pass A + pass B);
+// rpt_verify_frame and rpt_timed_frames launch the one-sample pass alone.
+int launch(rpt_ctx *ctx, bool colour_frame = false) {
     if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
     if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_set_params");
     if (int rc = ensure_outputs(ctx)) return rc;
@@ -983,6 +1064,27 @@ int launch(rpt_ctx *ctx) {
     fill_kernel_args(ctx, a);
     const bool lens = ctx->v_fov != 0.0f;
     const float lens_scale = lens ? ctx->lens_scale : 1.0f;
+
+    // Adaptive anti-aliasing (rpt_set_adaptive_aa): what it cannot serve refuses here and below, before anything is launched
+    const bool adaptive = colour_frame && ctx->aa_n > 1;
+    if (colour_frame) ctx->last_aa_variant = 0;
+    if (adaptive) {
+        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: rpt_set_msaa > 1 is set as well (full supersampling is threshold -1 here)");
+        if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->run_log2 != 0 || ctx->colour_plane)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: this context renders a share of the frame's rows or a colour plane (rpt_set_rows / rpt_set_tile_pattern): the neighbour rows belong to another rank");
+        if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED && ctx->variant != VARIANT_BALLOT && ctx->variant != VARIANT_BALLOT_FIRST && ctx->variant != VARIANT_ANALYTIC)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: variant " + std::to_string(ctx->variant) + " has no refine kernel (variants 0, 3, 41, 43 and 44 have)");
+        if (ctx->doppler && (ctx->external_doppler || ctx->want_owned_doppler))
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: the Doppler debug kernels (rpt_set_debug_doppler) have no refine pass");
+        if (!ctx->geo->compact_ok && ctx->has_mesh)
+            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: the refine kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+        // pass A writes its packed colours here as well (the kernels honour `plane` next to `out16`; whole-frame contexts: local rows are the frame's)
+        if (int rc = reserve(ctx, ctx->aa_plane, (size_t)local_tile_count(ctx) * RPT_TILE_ROWS * ctx->width * 4)) return rc;
+        if (int rc = reserve(ctx, ctx->aa_counter, 8)) return rc;
+        if (!ctx->aa_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->aa_host, 8, hipHostMallocDefault));
+        if (!ctx->aa_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->aa_counted, hipEventDisableTiming));
+        a.plane = (uint32_t *)ctx->aa_plane.ptr;
+    }
 
     const int tiles = local_tile_count(ctx);
     if (tiles == 0) return RPT_OK;
@@ -1038,6 +1140,8 @@ int launch(rpt_ctx *ctx) {
     const bool window_holds_frame = (lens ? lens_scale <= 1.0f && lens_scale * (0.5f * a.aspect) <= (float)rptb::cert::WINDOW_U : 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U) &&
                                     ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
     if (!window_holds_frame && row && row->window) row = variant_row(v = VARIANT_UNCULLED);
+    // (pass B's form is pass A's at this point: 3 / 303 un-culled, 44 / 344 without the walk, else the walk)
+    const int aa_base = v;
     a.first_h = 0;
     if (row && row->band_first) set_band_first(ctx, a, tiles);
     a.msaa = ctx->msaa;
@@ -1093,6 +1197,32 @@ int launch(rpt_ctx *ctx) {
     rptd::LensArgs la;            // (the lens kernels' arguments: the above + the scale of the image plane)
     static_cast<rptd::EnvironmentArgs &>(la) = ea;
     la.lens_scale = lens_scale;
+    const RefineRow *refine = nullptr;
+    bool refine_exact = false;
+    rptd::RefineArgs ra;
+    if (adaptive) {
+        if (!row || row->relaxed_waves) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: kernel " + std::to_string(v) + " has no refine pass");
+        const RefineCamera camera = panorama ? RefineCamera::equirect : (lens ? RefineCamera::lens : RefineCamera::pinhole);
+        const RefineColour colour = environment ? RefineColour::environment : (ctx->doppler ? RefineColour::doppler : RefineColour::plain);
+        RefineForm form = aa_base == VARIANT_UNCULLED || aa_base == 303 ? RefineForm::unculled : (aa_base == VARIANT_ANALYTIC || aa_base == 344 ? RefineForm::analytic : RefineForm::walk);
+        // under a lens the skirt's proof for the SAMPLE positions reaches 0.98 million pixels a side, not 2^20 (rpt_kernels.hip.h: refine_pixel_body)
+        if (lens && form != RefineForm::unculled && (ctx->width > (1 << 19) || ctx->height > (1 << 19))) form = RefineForm::unculled;
+        for (const RefineRow &r : refine_table)
+            if (r.camera == camera && r.colour == colour && r.form == form) refine = &r;
+        if (!refine) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: no refine kernel for this camera");
+        if (panorama)
+            if (int rc = ensure_aa_tables(ctx)) return rc;
+        refine_exact = refine->ieee && ctx->geo->exact_rcp_ok;
+        std::memset(&ra, 0, sizeof ra);
+        static_cast<rptd::LensArgs &>(ra) = la;
+        ra.plane = nullptr;           // (pass B writes the framebuffer and debug_rgb only: the plane is what its neighbours still read)
+        ra.aa_plane = (const uint32_t *)ctx->aa_plane.ptr;
+        ra.aa_refined = (unsigned long long *)ctx->aa_counter.ptr;
+        ra.aa_cols = panorama ? (const float2 *)ctx->aa_tables.ptr : nullptr;
+        ra.aa_rows = panorama ? (const float2 *)ctx->aa_tables.ptr + (size_t)ctx->aa_n * ctx->width : nullptr;
+        ra.aa_n = ctx->aa_n;
+        ra.aa_threshold = ctx->aa_threshold;
+    }
     if (!row) {
 #ifdef RPT_DIAGNOSTICS
         if (int rc = launch_diagnostic(ctx, a, grid, tiles, v)) return rc;
@@ -1108,7 +1238,28 @@ int launch(rpt_ctx *ctx) {
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = v;
     ctx->last_exact_rcp = row && row->ieee && ctx->geo->exact_rcp_ok;
+    if (refine) {                 // pass B, behind pass A on the same stream; then the counter's way home, in stream order
+        RPT_HIP(ctx, hipMemsetAsync(ctx->aa_counter.ptr, 0, 8, ctx->stream));
+        void *args[] = {(void *)&ra};
+        (void)hipLaunchKernel(refine->ieee && !refine_exact ? refine->ieee : refine->kernel, grid1, dim3(64), args, 0, ctx->stream);
+        RPT_HIP(ctx, hipGetLastError());
+        RPT_HIP(ctx, hipMemcpyAsync(ctx->aa_host, ctx->aa_counter.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
+        RPT_HIP(ctx, hipEventRecord(ctx->aa_counted, ctx->stream));
+        ctx->aa_pending = true;
+        ctx->last_aa_variant = refine->variant;
+    } else if (colour_frame) {    // a frame with the setting off refines nothing
+        ctx->aa_pending = false;
+        ctx->aa_refined = 0;
+    }
     return RPT_OK;
+}
+
+// rpt_last_aa_refined's value: the pinned word, once the copy behind the last adaptive frame has run
+void collect_aa_refined(rpt_ctx *ctx) {
+    if (ctx->aa_pending && ctx->aa_counted && hipEventQuery(ctx->aa_counted) == hipSuccess) {
+        ctx->aa_refined = *ctx->aa_host;
+        ctx->aa_pending = false;
+    }
 }
 
 // ---- the event kernels (rpt_render_events): one row per kernel, chosen by camera and form --------------------------------------------
@@ -1272,13 +1423,17 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables, &ctx->env_texels, &ctx->owned_events})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables, &ctx->env_texels, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->aa_tables})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     if (ctx->pano_host) (void)hipHostFree(ctx->pano_host);
     if (ctx->pano_copied) (void)hipEventDestroy(ctx->pano_copied);
     if (ctx->env_host) (void)hipHostFree(ctx->env_host);
     if (ctx->env_copied) (void)hipEventDestroy(ctx->env_copied);
+    if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
+    if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
+    if (ctx->aa_tables_host) (void)hipHostFree(ctx->aa_tables_host);
+    if (ctx->aa_tables_copied) (void)hipEventDestroy(ctx->aa_tables_copied);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -1801,7 +1956,7 @@ int rpt_render_async(rpt_ctx *ctx) {
         ee = ctx->timing_events[2 * ctx->timing_frames + 1];
     }
     RPT_HIP(ctx, hipEventRecord(eb, ctx->stream));
-    if (int rc = launch(ctx)) return rc;
+    if (int rc = launch(ctx, true)) return rc;
     RPT_HIP(ctx, hipEventRecord(ee, ctx->stream));
     ctx->last_event = ee;
     if (timed) ctx->timing_frames++;
@@ -1880,8 +2035,30 @@ int rpt_sync(rpt_ctx *ctx) {
     if (!ctx) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    collect_aa_refined(ctx);
     return RPT_OK;
 }
+
+int rpt_set_adaptive_aa(rpt_ctx *ctx, int samples_per_axis, int threshold) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (samples_per_axis < 1 || samples_per_axis > 8) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: 1..8 samples per axis (1 = off)");
+    if (threshold < -1 || threshold > 255) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: the threshold is -1 (refine every pixel) .. 255 (refine none)");
+    ctx->aa_n = samples_per_axis;
+    ctx->aa_threshold = threshold;
+    return RPT_OK;
+}
+
+int rpt_last_aa_refined(rpt_ctx *ctx, unsigned long long *pixels) {
+    if (!ctx || !pixels) return RPT_ERR_ARG;
+    if (ctx->aa_pending) {
+        RPT_HIP(ctx, hipSetDevice(ctx->device));
+        collect_aa_refined(ctx);
+    }
+    *pixels = ctx->aa_refined;
+    return RPT_OK;
+}
+
+int rpt_last_aa_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_aa_variant : RPT_ERR_ARG; }
 
 int rpt_render(rpt_ctx *ctx) {
     if (!ctx) return RPT_ERR_ARG;

@@ -1616,6 +1616,169 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_lens_ballot_ieee(const EventArgs a) { events_pixel_body<Lens<Ballot>>(a); }    // (921)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_lens_analytic(const EventArgs a) { events_pixel_body<Lens<Analytic>>(a); }    // 924
 
+// ---- Adaptive anti-aliasing (rpt_set_adaptive_aa; not in the reference; DESIGN.md "Adaptive anti-aliasing") ------------------------------
+// The second launch of an adaptive frame.  The first is the one-sample kernel a frame gets anyway (its source and its code untouched),
+// told to write its packed colours into a context-owned 4 B/pixel plane beside the framebuffer; this kernel reads that plane, decides
+// per pixel whether it lies on an edge, and re-renders the pixels that do with n x n camera rays in the order of opencl_kernel.cl:641-648.
+// The arguments are LensArgs with the pass's own fields appended (every camera's and every colour family's refine kernel takes them),
+// so no other kernel's argument block changes.
+struct RefineArgs : LensArgs {
+    const uint32_t *aa_plane;       // [height][width] the packed colours of the one-sample pass (read only here: a neighbour's tile reads them too)
+    unsigned long long *aa_refined; // the context's counter of refined pixels: one atomic add per wave that refined anything
+    const float2 *aa_cols;          // panorama: rpt_projection_tables at n width x n height, [n width] {sin, cos} of a sample column's longitude
+    const float2 *aa_rows;          // ... and [n height] of a sample row's latitude
+    int aa_n;                       // samples per axis, 2..8
+    int aa_threshold;               // refine where a neighbour's 8-bit R, G or B differs by MORE than this: -1 = everywhere, 255 = nowhere
+};
+
+// the largest of |R - R'|, |G - G'|, |B - B'| of two packed colours
+RPT_DEV int packed_rgb_distance(uint32_t p, uint32_t q) {
+    int d = 0;
+    for (int c = 0; c < 3; c++) {
+        const int e = (int)((p >> (8 * c)) & 255u) - (int)((q >> (8 * c)) & 255u);
+        const int m = e < 0 ? -e : e;
+        d = m > d ? m : d;
+    }
+    return d;
+}
+
+RPT_DEV int max_int(int x, int y) { return x < y ? y : x; }
+
+// the index of the k-th set bit of m (k counted from 0; k < popcount(m)): six halving steps on the population count
+RPT_DEV int nth_set_bit(unsigned long long m, int k) {
+    int pos = 0;
+    for (int width = 32; width >= 1; width >>= 1) {
+        const int below = __popcll((m >> pos) & ((1ull << width) - 1ull));
+        if (k >= below) { k -= below; pos += width; }
+    }
+    return pos;
+}
+
+// One wave per 8 x 8 tile, as every render kernel (whole-frame contexts only: the host refuses rpt_set_rows, so local rows are the frame's).
+//   1. Each lane compares its own packed colour with those of x +- 1 and y +- 1 IN THE PLANE (never the framebuffer this pass rewrites;
+//      neighbours outside the frame are ignored); one __ballot makes the wave's refine set, and a wave whose set is empty ends there —
+//      before it has read a rectangle, an object or a table.
+//   2. The (pixel, sample) pairs of the set are spread over all 64 lanes, floor(64 / n^2) pixels per round: lane L of a round traces
+//      sample L mod n^2 of the round's pixel number L / n^2, found by rank in the ballot (nth_set_bit) — a pixel is never a loop of n^2
+//      traces in one lane while the others idle.  trace<P> and the wave's object mask are the one-sample kernels' own.
+//   3. The n^2 colours of a pixel are handed to the lane that traced its sample 0 through 1 KB of LDS (one 16-B write per lane, n^2
+//      16-B reads per owner; DESIGN.md says why not shuffles); that lane adds them IN THE REFERENCE'S ORDER — sy outer, sx inner, one
+//      float addition after another: a tree or a DPP reduction would change the bits — divides by n^2, maps, packs and stores.
+// The object mask and the sample positions.  Sample (sx, sy) of pixel (x, y) is at xs = fl((float)x + fl(sx / n)), 0 <= sx / n <= 7/8:
+// x <= xs <= x + 1 (rounding is monotone), off its exact place by at most half an ulp of xs, i.e. 2^-5 pixel while the frame is at most
+// 2^20 pixels wide (what launch() enforces before it culls).  wave_object_mask tests the tile grown by 1.5 pixels on every side, proven to
+// hold every PIXEL's plane point against float rounding of at most 7u aspect on the plane (its comment: 3u from the pixel's chain, 4u from
+// the edge's, u = 2^-24).  At the lower edges a sample is no lower than its pixel, so the pixel's margin of 1.5 pixels stands.  At the upper
+// edges the last pixel's samples reach at most one pixel further, leaving 0.5 aspect / W of the skirt against 7u aspect + 2^-5 aspect / W:
+// enough while W < 0.468 / 7u = 1.12 million, and W <= 2^20.  Under a lens (wave_object_mask_lens) both the skirt and every error above are
+// scaled by s alike, with one more relative rounding on each side (3.5u s aspect and 4.5u s aspect): 8u W < 0.468, W < 0.98 million — so the
+// host culls a lens refine pass only up to 2^19 pixels a side (launch(): un-culled above that).  The same in v with aspect = 1.  Wherever
+// the one-sample pass ran un-culled (variant 3, a lens beyond 90 degrees, the panorama, which has no tile mask, a frame outside the
+// proven window) the host launches the un-culled form of this kernel; more than 64 objects are tested everywhere, as in trace().
+template <class P>
+RPT_DEV void refine_pixel_body(const RefineArgs &a) {
+    __shared__ float4 handover[64];
+    const int lane = threadIdx.x & 63;
+    const int wave = (int)blockIdx.x & 3;              // one wave per workgroup, as the one-sample product kernels
+    const int strip = (int)blockIdx.x >> 2;
+    const int tile_x0 = strip * 32 + wave * 8, tile_y0 = (int)blockIdx.y * RPT_TILE_ROWS;
+    const int x_coord = tile_x0 + (lane & 7), y_coord = tile_y0 + (lane >> 3);
+    bool refine = false;
+    if (x_coord < a.width && y_coord < a.height) {
+        const uint32_t *p = a.aa_plane + (size_t)y_coord * a.width + x_coord;
+        const uint32_t mine = *p;
+        int d = 0;
+        if (x_coord > 0) d = max_int(d, packed_rgb_distance(mine, p[-1]));
+        if (x_coord + 1 < a.width) d = max_int(d, packed_rgb_distance(mine, p[1]));
+        if (y_coord > 0) d = max_int(d, packed_rgb_distance(mine, p[-(ptrdiff_t)a.width]));
+        if (y_coord + 1 < a.height) d = max_int(d, packed_rgb_distance(mine, p[a.width]));
+        refine = d > a.aa_threshold;
+    }
+    const unsigned long long set = __ballot(refine);
+    if (set == 0ull) return;                           // wave-uniform: most waves of a frame end here
+    const int count = __popcll(set);
+    if (lane == 0) atomicAdd(a.aa_refined, (unsigned long long)count);
+
+    // all 64 lanes are here (the exit above is the wave's), so the mask's __ballot sees every lane's object
+    unsigned long long object_mask = ~0ull;
+    if constexpr (P::camera == Camera::lens) {
+        if (P::culled && P::object_mask) object_mask = wave_object_mask_lens(a, a.lens_scale, tile_x0, tile_y0);
+    } else if (P::culled && P::object_mask) object_mask = wave_object_mask(a, tile_x0, tile_y0);
+    const bool masked = P::culled && P::object_mask;
+    const bool any = !masked || object_mask != 0 || a.object_count > 64;
+
+    const int n = a.aa_n, n2 = n * n;
+    const int per_round = 64 / n2;                     // 16, 7, 4, 2, 1, 1, 1 pixels for n = 2 .. 8
+    const int slot = lane / n2, sample = lane - slot * n2;
+    const int sy = sample / n, sx = sample - sy * n;
+    for (int first = 0; first < count; first += per_round) {
+        const int rank = first + slot;
+        const bool active = slot < per_round && rank < count;
+        int px = 0, py = 0;
+        f3 c = mk3(0.15f, 0.15f, 0.25f);               // a miss contributes the background of opencl_kernel.cl:565
+        if (active) {
+            const int owner = nth_set_bit(set, rank);
+            px = tile_x0 + (owner & 7);
+            py = tile_y0 + (owner >> 3);
+            if (any || P::environment) {
+                f3 camdir;
+                if constexpr (P::camera == Camera::equirect) {
+                    const float2 col = a.aa_cols[n * px + sx], row = a.aa_rows[n * py + sy];
+                    camdir = normalize(mk3(row.y * col.x, row.x, row.y * col.y));          // equirectCamDir on the n-times tables
+                } else {
+                    const float xs = (float)px + (float)sx / (float)n, ys = (float)py + (float)sy / (float)n;
+                    if constexpr (P::camera == Camera::lens) camdir = lensCamRayDir(xs, ys, a.width, a.height, a.aspect, a.lens_scale);
+                    else camdir = createCamRayDir(xs, ys, a.width, a.height, a.aspect);
+                }
+                f3 traced;
+                if (any && trace<P>(a, camdir, object_mask, traced)) c = traced;
+                else if constexpr (P::environment) c = environment_colour(a, camdir);       // the sky of the sample's own direction
+            }
+        }
+        handover[lane] = make_float4(c.x, c.y, c.z, 0.0f);
+        __syncthreads();
+        if (active && sample == 0) {
+            f3 sum = mk3(0.0f, 0.0f, 0.0f);
+            for (int k = 0; k < n2; k++) {
+                const float4 h = handover[lane + k];
+                sum = sum + mk3(h.x, h.y, h.z);
+            }
+            const float fn2 = (float)n2;
+            sum = mk3(sum.x / fn2, sum.y / fn2, sum.z / fn2);
+            f3 mapped;
+            const uint32_t packed = tonemap_pack(a, sum, mapped);
+            const size_t id = (size_t)py * a.width + px;
+            if (a.out16) store_pixel(a.out16, id, __float_as_uint((float)px), __float_as_uint((float)py), packed, 0u);
+            if (a.debug_rgb) {
+                a.debug_rgb[3 * id + 0] = mapped.x;
+                a.debug_rgb[3 * id + 1] = mapped.y;
+                a.debug_rgb[3 * id + 2] = mapped.z;
+            }
+        }
+        __syncthreads();                               // the next round's writes wait for this round's reads
+    }
+}
+
+// Refine kernels: the throughput forms only, as the event pass — the walk with the wave's object mask and the exact reciprocal (10x1), its
+// IEEE form for scenes outside the domain, no walk compiled in (10x4), un-culled (10x3) — for each camera and colour family.  The tens
+// digit: 0 pinhole, 1 its Doppler twin, 2 its environment form; 3 / 4 / 5 the same under a lens; 6 / 7 / 8 in panorama.  The number is
+// what rpt_last_aa_variant reports.
+#define RPT_REFINE_FAMILY(name, WRAP_OPEN, WRAP_CLOSE, UNCULLED, WALK, WALK_IEEE, ANALYTIC)                                                                                       \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_refine_kernel_##name##_unculled(const RefineArgs a) { refine_pixel_body<WRAP_OPEN UNCULLED WRAP_CLOSE >(a); }   \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_refine_kernel_##name##_walk(const RefineArgs a) { refine_pixel_body<WRAP_OPEN WALK WRAP_CLOSE >(a); }           \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_refine_kernel_##name##_walk_ieee(const RefineArgs a) { refine_pixel_body<WRAP_OPEN WALK_IEEE WRAP_CLOSE >(a); } \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_refine_kernel_##name##_analytic(const RefineArgs a) { refine_pixel_body<WRAP_OPEN ANALYTIC WRAP_CLOSE >(a); }
+RPT_REFINE_FAMILY(plain, , , Unculled, BallotExact, Ballot, Analytic)                                                       // 1003, 1001, (1001), 1004
+RPT_REFINE_FAMILY(doppler, DopplerTwin<, >, Unculled, BallotExact, Ballot, Analytic)                                        // 1013, 1011, (1011), 1014
+RPT_REFINE_FAMILY(env, Environment<, >, Unculled, BallotExact, Ballot, Analytic)                                            // 1023, 1021, (1021), 1024
+RPT_REFINE_FAMILY(lens, Lens<, >, Unculled, BallotExact, Ballot, Analytic)                                                  // 1033, 1031, (1031), 1034
+RPT_REFINE_FAMILY(lens_doppler, Lens<DopplerTwin<, > >, Unculled, BallotExact, Ballot, Analytic)                             // 1043, 1041, (1041), 1044
+RPT_REFINE_FAMILY(lens_env, Lens<Environment<, > >, Unculled, BallotExact, Ballot, Analytic)                                 // 1053, 1051, (1051), 1054
+RPT_REFINE_FAMILY(pano, , , PanoramaUnculled, PanoramaWalk, PanoramaWalkIeee, PanoramaAnalytic)                             // 1063, 1061, (1061), 1064
+RPT_REFINE_FAMILY(pano_doppler, DopplerTwin<, >, PanoramaUnculled, PanoramaWalk, PanoramaWalkIeee, PanoramaAnalytic)        // 1073, 1071, (1071), 1074
+RPT_REFINE_FAMILY(pano_env, Environment<, >, PanoramaUnculled, PanoramaWalk, PanoramaWalkIeee, PanoramaAnalytic)            // 1083, 1081, (1081), 1084
+#undef RPT_REFINE_FAMILY
+
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd
 #include "rpt_diag_kernels.hip.h"    /* librpt_hip_diag.so only: instrumented kernels, round 1's prepass, the A/B arms of rounds 2 and 3 */

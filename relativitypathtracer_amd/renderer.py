@@ -209,6 +209,24 @@ class Renderer:
         """MSAASAMPLES of opencl_kernel.cl:7 (1 = the reference as shipped)."""
         self._check(self._lib.rpt_set_msaa(self._h, int(samples_per_axis)), "rpt_set_msaa")
 
+    def set_adaptive_aa(self, samples: int, threshold: int = 8):
+        """Adaptive anti-aliasing (include/rpt.h, rpt_set_adaptive_aa; not in the reference; off by default): colour frames are the
+        one-sample frame with every pixel whose 8-bit colour differs from a 4-neighbour's by more than `threshold` in some channel
+        rendered again with samples x samples rays.  samples = 1 switches it off; threshold -1 refines every pixel, 255 none (the
+        default of 8 is a knob, not a claim; adaptive.refine_mask previews what a threshold selects).  Every camera and colour mode;
+        what it cannot serve (set_msaa > 1, set_rows, the Doppler debug kernel, variants other than 0, 3, 41, 43, 44) refuses at the launch."""
+        self._check(self._lib.rpt_set_adaptive_aa(self._h, int(samples), int(threshold)), "rpt_set_adaptive_aa")
+
+    def last_aa_refined(self) -> int:
+        """Pixels the refine pass of the last finished adaptive frame re-rendered (0 with the setting off)."""
+        n = C.c_uint64(0)
+        self._check(self._lib.rpt_last_aa_refined(self._h, C.byref(n)), "rpt_last_aa_refined")
+        return int(n.value)
+
+    def last_aa_variant(self) -> int:
+        """The refine kernel (include/rpt.h, rpt_set_adaptive_aa) of the last colour frame; 0 if it had no refine pass."""
+        return int(self._lib.rpt_last_aa_variant(self._h))
+
     def set_doppler(self, shift: bool = True, beaming: bool = True):
         """Relativistic Doppler shift and / or searchlight beaming (not in the reference; off by default).  set_doppler(False, False)
         turns it off again.  Kernels without a Doppler twin (variants 1, 50, 51, MSAA > 1) then refuse at the launch."""
@@ -469,14 +487,18 @@ class Renderer:
 
 def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
                  projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None,
-                 orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False):
+                 orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
+                 adaptive_aa: Optional[Tuple[int, int]] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}.  environment: an
     H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first).
-    orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view)."""
+    orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view).
+    adaptive_aa: (samples per axis, threshold) for Renderer.set_adaptive_aa."""
     r = Renderer(device)
     try:
+        if adaptive_aa is not None:
+            r.set_adaptive_aa(*adaptive_aa)
         if orientation is not None:
             r.set_orientation(*orientation)
         if v_fov is not None:
