@@ -47,6 +47,22 @@ struct DeviceBuffer {
 
 void release(DeviceBuffer &b);
 
+// A device buffer that is (re)written from the host in stream order: staged_host() hands out pinned memory that is safe to rewrite,
+// staged_copy() enqueues the copy and records `copied`.  A frame still in flight reads what it was launched with, a later one the new bytes.
+struct StagedUpload {
+    DeviceBuffer device;
+    void *host = nullptr;                             // pinned: what the last upload was copied from
+    size_t host_capacity = 0;
+    hipEvent_t copied = nullptr;                      // recorded after that copy: `host` is rewritten only once it has passed
+};
+
+// The equirectangular camera's tables (rpt_projection_tables) on the device, and what they were built for (n = 0: nothing yet)
+struct ProjectionTables {
+    StagedUpload upload;                              // [n (width + height)] float2: the column table, then the row table
+    int n = 0, width = 0, height = 0;
+    float params[3] = {0, 0, 0};
+};
+
 // The resident scene geometry: immutable between two rpt_upload_scene calls, so contexts that keep several frames
 // in flight share ONE copy (rpt_share_scene); the last context holding it frees it.
 struct Geometry {
@@ -126,7 +142,6 @@ struct rpt_ctx {
 #endif
     float last_ms = 0.0f;
     bool frame_rendered = false;
-    bool latency_call = false;                        // the launch in progress comes from the blocking rpt_render()
     bool has_mesh = true;                             // the current Object[] holds a mesh object (rpt_set_objects); picks the kernel
     // rpt_set_doppler (not in the reference): RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING, 0 = off; per context, never shared
     int doppler = 0;
@@ -137,20 +152,12 @@ struct rpt_ctx {
     // rpt_set_projection (not in the reference): RPT_PROJECTION_*, per context, never shared
     int projection = RPT_PROJECTION_PINHOLE;
     float projection_params[3] = {0, 0, 0};           // {h_fov, v_fov, yaw} of the equirectangular camera
-    DeviceBuffer pano_tables;                         // [width + height] float2: the column table, then the row table
-    float *pano_host = nullptr;                       // pinned: what the last upload of the tables was copied from
-    size_t pano_host_capacity = 0;
-    hipEvent_t pano_copied = nullptr;                 // recorded after that copy: pano_host is rewritten only once it has passed
-    bool pano_valid = false;                          // the device tables are those of (pano_width, pano_height, projection_params)
-    int pano_width = 0, pano_height = 0;
+    ProjectionTables pano;                            // the frame's tables
     // rpt_set_environment / rpt_set_environment_frame (not in the reference): the sky image, per context, never shared
     bool env_on = false;
     int env_width = 0, env_height = 0;
     float env_frame[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // E, row-major, t first; a kernel ARGUMENT (a frame in flight keeps its own)
-    DeviceBuffer env_texels;                          // [env_width * env_height] dwords R | G << 8 | B << 16
-    uint32_t *env_host = nullptr;                     // pinned: what the last upload of the image was copied from
-    size_t env_host_capacity = 0;
-    hipEvent_t env_copied = nullptr;                  // recorded after that copy: env_host is rewritten only once it has passed
+    StagedUpload env;                                 // [env_width * env_height] dwords R | G << 8 | B << 16
     // rpt_set_orientation / rpt_set_field_of_view (not in the reference): the free-look camera, per context, never shared
     bool oriented = false;                            // R != I: host_objects (and the device's Object[]) are the RE-BASED objects
     double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -177,12 +184,7 @@ struct rpt_ctx {
     unsigned long long aa_refined = 0;                // rpt_last_aa_refined: aa_host as last read with aa_counted passed
     bool aa_pending = false;                          // a copy has been enqueued since aa_refined was read
     int last_aa_variant = 0;                          // the refine kernel of the last colour frame (rpt_last_aa_variant)
-    DeviceBuffer aa_tables;                           // panorama: rpt_projection_tables at aa_n times the frame's size, columns then rows
-    float *aa_tables_host = nullptr;                  // pinned: what the last upload of those tables was copied from
-    size_t aa_tables_host_capacity = 0;
-    hipEvent_t aa_tables_copied = nullptr;            // recorded after that copy: aa_tables_host is rewritten only once it has passed
-    int aa_tables_n = 0, aa_tables_width = 0, aa_tables_height = 0;      // what the device tables were built for (0: nothing yet)
-    float aa_tables_params[3] = {0, 0, 0};
+    ProjectionTables aa_pano;                         // panorama: the tables at aa_n times the frame's size, for the refine pass
 };
 
 namespace {
@@ -222,6 +224,38 @@ int upload(rpt_ctx *ctx, DeviceBuffer &b, const void *src, size_t bytes) {
 void release(DeviceBuffer &b) {
     if (b.ptr) (void)hipFree(b.ptr);
     b = DeviceBuffer();
+}
+
+// `bytes` of u's pinned memory that may be rewritten now, and a device buffer that holds as many: waits for the previous copy, and for
+// the stream before a device buffer that a frame in flight may still read is replaced by a larger one.
+int staged_host(rpt_ctx *ctx, StagedUpload &u, size_t bytes, void **host) {
+    if (!u.copied) RPT_HIP(ctx, hipEventCreateWithFlags(&u.copied, hipEventDisableTiming));
+    else RPT_HIP(ctx, hipEventSynchronize(u.copied));
+    if (bytes > u.host_capacity) {
+        if (u.host) RPT_HIP(ctx, hipHostFree(u.host));
+        u.host = nullptr;
+        u.host_capacity = 0;
+        RPT_HIP(ctx, hipHostMalloc(&u.host, bytes, hipHostMallocDefault));
+        u.host_capacity = bytes;
+    }
+    if (bytes > u.device.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
+    if (int rc = reserve(ctx, u.device, bytes)) return rc;
+    *host = u.host;
+    return RPT_OK;
+}
+
+// ... and its way to the device, behind everything enqueued so far
+int staged_copy(rpt_ctx *ctx, StagedUpload &u) {
+    RPT_HIP(ctx, hipMemcpyAsync(u.device.ptr, u.host, u.device.bytes, hipMemcpyHostToDevice, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(u.copied, ctx->stream));
+    return RPT_OK;
+}
+
+void release(StagedUpload &u) {
+    release(u.device);
+    if (u.host) (void)hipHostFree(u.host);
+    if (u.copied) (void)hipEventDestroy(u.copied);
+    u = StagedUpload();
 }
 
 // opencl_kernel.cl:607-616 on the host (same fp32 expression; this file is built without contraction)
@@ -812,194 +846,349 @@ void projection_fill(const float params[3], int width, int height, float *cols, 
     }
 }
 
-// The context's device tables for this frame's size and parameters.  Rebuilt only when one of them changed, and uploaded in stream order
-// from a pinned buffer that is not rewritten before its previous copy has run: a frame still in flight reads the tables it was launched
-// with, a later one the new ones.
-int ensure_panorama_tables(rpt_ctx *ctx) {
-    if (ctx->pano_valid && ctx->pano_width == ctx->width && ctx->pano_height == ctx->height) return RPT_OK;
-    const size_t floats = 2 * ((size_t)ctx->width + (size_t)ctx->height), bytes = floats * sizeof(float);
-    if (!ctx->pano_copied) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->pano_copied, hipEventDisableTiming));
-    else RPT_HIP(ctx, hipEventSynchronize(ctx->pano_copied));
-    if (bytes > ctx->pano_host_capacity) {
-        if (ctx->pano_host) RPT_HIP(ctx, hipHostFree(ctx->pano_host));
-        ctx->pano_host = nullptr;
-        ctx->pano_host_capacity = 0;
-        RPT_HIP(ctx, hipHostMalloc((void **)&ctx->pano_host, bytes, hipHostMallocDefault));
-        ctx->pano_host_capacity = bytes;
-    }
-    if (bytes > ctx->pano_tables.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
-    if (int rc = reserve(ctx, ctx->pano_tables, bytes)) return rc;
-    projection_fill(ctx->projection_params, ctx->width, ctx->height, ctx->pano_host, ctx->pano_host + 2 * (size_t)ctx->width);
-    RPT_HIP(ctx, hipMemcpyAsync(ctx->pano_tables.ptr, ctx->pano_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RPT_HIP(ctx, hipEventRecord(ctx->pano_copied, ctx->stream));
-    ctx->pano_valid = true;
-    ctx->pano_width = ctx->width;
-    ctx->pano_height = ctx->height;
-    return RPT_OK;
-}
-
-// The same tables at n times the resolution, for the refine pass of an adaptive panorama frame (rpt_set_adaptive_aa): sample (sx, sy) of
-// pixel (x, y) looks along pixel (n x + sx, n y + sy) of the n W x n H panorama.  Held per context, rebuilt when n, the size or the
-// projection changes; the upload follows ensure_panorama_tables' discipline.
-int ensure_aa_tables(rpt_ctx *ctx) {
-    const int n = ctx->aa_n;
-    if (ctx->aa_tables_n == n && ctx->aa_tables_width == ctx->width && ctx->aa_tables_height == ctx->height &&
-        std::memcmp(ctx->aa_tables_params, ctx->projection_params, sizeof ctx->aa_tables_params) == 0) return RPT_OK;
+// The device tables of the context's projection at n times this frame's size: n = 1 the frame's own (ctx->pano), n = aa_n the refine
+// pass's (ctx->aa_pano: sample (sx, sy) of pixel (x, y) looks along pixel (n x + sx, n y + sy) of the n W x n H panorama).  Rebuilt only
+// when n, the size or the parameters changed, and uploaded in stream order (StagedUpload).
+int ensure_projection_tables(rpt_ctx *ctx, ProjectionTables &t, int n) {
+    if (t.n == n && t.width == ctx->width && t.height == ctx->height && std::memcmp(t.params, ctx->projection_params, sizeof t.params) == 0) return RPT_OK;
     const size_t w = (size_t)n * ctx->width, h = (size_t)n * ctx->height;
-    const size_t floats = 2 * (w + h), bytes = floats * sizeof(float);
-    if (!ctx->aa_tables_copied) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->aa_tables_copied, hipEventDisableTiming));
-    else RPT_HIP(ctx, hipEventSynchronize(ctx->aa_tables_copied));
-    if (bytes > ctx->aa_tables_host_capacity) {
-        if (ctx->aa_tables_host) RPT_HIP(ctx, hipHostFree(ctx->aa_tables_host));
-        ctx->aa_tables_host = nullptr;
-        ctx->aa_tables_host_capacity = 0;
-        RPT_HIP(ctx, hipHostMalloc((void **)&ctx->aa_tables_host, bytes, hipHostMallocDefault));
-        ctx->aa_tables_host_capacity = bytes;
-    }
-    if (bytes > ctx->aa_tables.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
-    if (int rc = reserve(ctx, ctx->aa_tables, bytes)) return rc;
-    projection_fill(ctx->projection_params, (int)w, (int)h, ctx->aa_tables_host, ctx->aa_tables_host + 2 * w);
-    RPT_HIP(ctx, hipMemcpyAsync(ctx->aa_tables.ptr, ctx->aa_tables_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RPT_HIP(ctx, hipEventRecord(ctx->aa_tables_copied, ctx->stream));
-    ctx->aa_tables_n = n;
-    ctx->aa_tables_width = ctx->width;
-    ctx->aa_tables_height = ctx->height;
-    std::memcpy(ctx->aa_tables_params, ctx->projection_params, sizeof ctx->aa_tables_params);
+    float *host = nullptr;
+    if (int rc = staged_host(ctx, t.upload, 2 * (w + h) * sizeof(float), (void **)&host)) return rc;
+    projection_fill(ctx->projection_params, (int)w, (int)h, host, host + 2 * w);
+    if (int rc = staged_copy(ctx, t.upload)) return rc;
+    t.n = n;
+    t.width = ctx->width;
+    t.height = ctx->height;
+    std::memcpy(t.params, ctx->projection_params, sizeof t.params);
     return RPT_OK;
 }
 
-// ---- the product kernels: every fact launch() and rpt_set_variant() know about a variant, one row each ------------------------------
-// variant      what rpt_set_variant takes (settable rows) and rpt_last_variant reports; the other rows are reached through the
-//              msaa and doppler columns only
-// kernel       launched with grid (4 ceil(W / 32), row tiles) x 64 threads; null: the relaxed-arithmetic build (rpt_relaxed.hip),
-//              launched through rpt_launch_relaxed_kernel at relaxed_waves waves per SIMD
-// ieee         the kernel's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp); where a
-//              row has one, rpt_last_exact_rcp says whether the row's own kernel ran
-// doppler      the variant of the Doppler twin (0: none; while the record hook is set the debug kernel 240 stands in for every twin)
-// window       outside the window the screen regions are proven for, the un-culled kernel (3) renders the frame instead
-// band_first   the policy's own (rpt_kernels.hip.h): the band of tile rows that holds the meshes is dispatched first
-// msaa         the variant for MSAA > 1 (0: refused)
-// panorama     the variant with the equirectangular camera (rpt_set_projection; 0: none).  Only variant 0's choices and variant 3 have one:
-//              every other variant set explicitly is refused in panorama, whatever this column says
-// environment  the variant with the sky image (rpt_set_environment; 0: none): the kernels variant 0 can select and the un-culled one, in
-//              pinhole and panorama.  Looked up in the row chosen BEFORE the Doppler column: an environment kernel carries Doppler as a
-//              run-time flag and serves both
-// lens         the variant with the scaled image plane (rpt_set_field_of_view; 0: none): the lens form of what variant 0 can select and of
-//              the un-culled kernel, of their Doppler twins and of their environment forms.  Looked up in the row chosen by every other
-//              column, last
-enum : int { VARIANT_DEFAULT = 0, VARIANT_REF_LAYOUT = 1, VARIANT_UNCULLED = 3, VARIANT_BALLOT = 41, VARIANT_BALLOT_FIRST = 43,
-             VARIANT_ANALYTIC = 44, VARIANT_DOPPLER_RECORD = 240, VARIANT_PANORAMA_RECORD = 540 };
-struct VariantRow {
+// ---- the kernels a frame can get: one table shape, one row per kernel, found by (camera, colour, form) ------------------------------
+// variant   what rpt_last_variant (the colour kernels), rpt_last_aa_variant (the refine kernels) and rpt_last_events_variant report
+// camera    the pinhole, the panorama (rpt_set_projection) or the pinhole under a lens (rpt_set_field_of_view)
+// colour    plain, the Doppler twin (rpt_set_doppler) or the sky (rpt_set_environment: carries Doppler as a run-time flag, serves both)
+// form      which walk, which culls, which arithmetic (Form below)
+// kernel    launched with grid (4 ceil(W / 32), row tiles) x 64 threads; null: the relaxed-arithmetic build (rpt_relaxed.hip), launched
+//           through rpt_launch_relaxed_kernel
+// ieee      the kernel's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp); where a row
+//           has one, rpt_last_exact_rcp says whether the row's own kernel ran
+// choose_kernels() below decides the three keys from the settings, in this order: the form from the variant, the call and the scene; the
+// panorama; the proven window; MSAA; then the colour — the sky is looked up BEFORE Doppler, since a sky kernel serves Doppler off and on —
+// and the lens LAST, as the lens form of whatever every other setting chose.  A key without a row is a refusal.
+using rptd::Camera;
+enum class Colour { plain, doppler, sky };
+enum class Form {
+    // what rpt_set_variant takes, by the number of its pinhole / plain row
+    ref_layout,       // 1   the reference's octree layout (any valid octree), un-culled
+    unculled,         // 3   every object tested everywhere
+    walk,             // 41  the wave's object mask, the octree walk one record at a time
+    walk_first,       // 43  ... the walk an iteration ahead, the band of tile rows that holds the meshes dispatched first
+    analytic,         // 44  no walk compiled in (an Object[] without a mesh)
+    ieee,             // 48  41 with the IEEE division whatever the scene (the A/B arm)
+    ieee_first,       // 49  43 likewise
+    relaxed5,         // 50  41's body with OpenCL's default arithmetic, 5 waves per SIMD
+    relaxed6,         // 51  ... 6 waves per SIMD
+    // reached through other settings only
+    msaa,             // 46  MSAASAMPLES > 1 (rpt_set_msaa) of the default kernels
+    msaa_unculled,    // 47  ... of the un-culled one
+    record,           // 240 / 540  the Doppler debug kernel (rpt_set_debug_doppler), un-culled
+    diagnostic,       // a measurement arm of librpt_hip_diag.so (launch_diagnostic): no row here
+};
+constexpr bool settable(Form f) { return f <= Form::relaxed6; }
+// ... dispatches the band of tile rows that holds the meshes first (KernelArgs::first_h): what the kernels' policies say
+constexpr bool band_first(Form f) { return f == Form::walk_first || f == Form::ieee_first; }
+static_assert(rptd::BallotFirstExact::band_first && rptd::BallotFirst::band_first && !rptd::RefLayout::band_first && !rptd::Unculled::band_first &&
+              !rptd::BallotExact::band_first && !rptd::Ballot::band_first && !rptd::Analytic::band_first && !rptd::DopplerRecorded::band_first,
+              "band_first(Form) is the policies' band_first");
+static_assert(rptd::Lens<rptd::Environment<rptd::BallotFirstExact>>::band_first && rptd::Lens<rptd::DopplerTwin<rptd::BallotFirst>>::band_first &&
+              !rptd::Lens<rptd::Environment<rptd::BallotExact>>::band_first && !rptd::PanoramaWalk::band_first,
+              "the camera and colour policies keep the band_first of the form they wrap (the panorama has no band-first form)");
+// ... culls with the per-object screen regions, which are PROVEN inside their window only (the relaxed builds cull with the same regions
+// but keep culling outside the window: a known gap, ADVICE.md, third item, kept as it is here)
+constexpr bool needs_proven_window(Form f) { return f == Form::walk || f == Form::walk_first || f == Form::analytic || f == Form::ieee || f == Form::ieee_first; }
+constexpr int relaxed_waves(Form f) { return f == Form::relaxed5 ? 5 : (f == Form::relaxed6 ? 6 : 0); }
+
+struct KernelRow {
     int variant;
-    bool settable;
+    Camera camera;
+    Colour colour;
+    Form form;
     const void *kernel;
-    int relaxed_waves;
     const void *ieee;
-    int doppler;
-    bool window;
-    bool band_first;
-    int msaa;
-    int panorama;
-    int environment;
-    int lens;
 };
 #define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
-const VariantRow variant_table[] = {
-    // variant set  kernel                                                    waves ieee                                                      doppler window band_first                                  msaa  pano env lens
-    {1,   true,  RPT_KERNEL(rpt_render_kernel_v0),                             0, nullptr,                                                  0,   false, rptd::RefLayout::band_first,                 0, 0, 0, 0},
-    {3,   true,  RPT_KERNEL(rpt_render_kernel_unculled_w5),                    0, nullptr,                                                  203, false, rptd::Unculled::band_first,                  47, 303, 603, 803},
-    {41,  true,  RPT_KERNEL(rpt_render_kernel_ballot_w5),                      0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             241, true,  rptd::BallotExact::band_first,               46, 341, 641, 841},
-    {43,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_w5),                0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       243, true,  rptd::BallotFirstExact::band_first,          46, 341, 643, 843},
-    {44,  true,  RPT_KERNEL(rpt_render_kernel_analytic_w8),                    0, nullptr,                                                  244, true,  rptd::Analytic::band_first,                  46, 344, 644, 844},
-    {48,  true,  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),                 0, nullptr,                                                  248, true,  rptd::Ballot::band_first,                    0, 0, 0, 0},
-    {49,  true,  RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),           0, nullptr,                                                  249, true,  rptd::BallotFirst::band_first,               0, 0, 0, 0},
-    // 50 / 51 cull with the same regions but keep culling outside their window: a known gap (third item), kept as it is here
-    {50,  true,  nullptr,                                                      5, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0, 0},
-    {51,  true,  nullptr,                                                      6, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0, 0},
-    {46,  false, RPT_KERNEL(rpt_render_kernel_msaa_w5),                        0, nullptr,                                                  0,   false, rptd::Ballot::band_first,                    0, 0, 0, 0},
-    {47,  false, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),               0, nullptr,                                                  0,   false, rptd::Unculled::band_first,                  0, 0, 0, 0},
-    {203, false, RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Unculled>::band_first, 0, 0, 0, 813},
-    {240, false, RPT_KERNEL(rpt_render_kernel_doppler_record_w5),              0, nullptr,                                                  0,   false, rptd::DopplerRecorded::band_first,           0, 0, 0, 0},
-    {241, false, RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),              0, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     0,   false, rptd::DopplerTwin<rptd::BallotExact>::band_first, 0, 0, 0, 851},
-    {243, false, RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),        0, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), 0, false, rptd::DopplerTwin<rptd::BallotFirstExact>::band_first, 0, 0, 0, 853},
-    {244, false, RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),            0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Analytic>::band_first, 0, 0, 0, 854},
-    {248, false, RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),         0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::Ballot>::band_first, 0, 0, 0, 0},
-    {249, false, RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5),   0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::BallotFirst>::band_first, 0, 0, 0, 0},
-    // the panorama kernels: reached through the panorama column only
-    {303, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),               0, nullptr,                                                  503, false, rptd::PanoramaUnculled::band_first,          0, 0, 703, 0},
-    {341, false, RPT_KERNEL(rpt_render_kernel_pano_w5),                        0, RPT_KERNEL(rpt_render_kernel_pano_ieee_w5),               541, false, rptd::PanoramaWalk::band_first,              0, 0, 741, 0},
-    {344, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),               0, nullptr,                                                  544, false, rptd::PanoramaAnalytic::band_first,          0, 0, 744, 0},
-    {503, false, RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaUnculled>::band_first, 0, 0, 0, 0},
-    {540, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),         0, nullptr,                                                  0,   false, rptd::PanoramaRecorded::band_first,          0, 0, 0, 0},
-    {541, false, RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),                0, RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5),       0,   false, rptd::DopplerTwin<rptd::PanoramaWalk>::band_first, 0, 0, 0, 0},
-    {544, false, RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),       0, nullptr,                                                  0,   false, rptd::DopplerTwin<rptd::PanoramaAnalytic>::band_first, 0, 0, 0, 0},
-    // the environment kernels (rpt_set_environment): reached through the environment column only; each serves Doppler off and on
-    {603, false, RPT_KERNEL(rpt_render_kernel_env_unculled_w5),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Unculled>::band_first, 0, 0, 0, 823},
-    {641, false, RPT_KERNEL(rpt_render_kernel_env_ballot_w5),                   0, RPT_KERNEL(rpt_render_kernel_env_ballot_ieee_w5),          0,   false, rptd::Environment<rptd::BallotExact>::band_first, 0, 0, 0, 861},
-    {643, false, RPT_KERNEL(rpt_render_kernel_env_ballot_first_w5),             0, RPT_KERNEL(rpt_render_kernel_env_ballot_first_ieee_w5),    0,   false, rptd::Environment<rptd::BallotFirstExact>::band_first, 0, 0, 0, 863},
-    {644, false, RPT_KERNEL(rpt_render_kernel_env_analytic_w8),                 0, nullptr,                                                   0,   false, rptd::Environment<rptd::Analytic>::band_first, 0, 0, 0, 864},
-    {703, false, RPT_KERNEL(rpt_render_kernel_env_pano_unculled_w5),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaUnculled>::band_first, 0, 0, 0, 0},
-    {741, false, RPT_KERNEL(rpt_render_kernel_env_pano_w5),                     0, RPT_KERNEL(rpt_render_kernel_env_pano_ieee_w5),            0,   false, rptd::Environment<rptd::PanoramaWalk>::band_first, 0, 0, 0, 0},
-    {744, false, RPT_KERNEL(rpt_render_kernel_env_pano_analytic_w8),            0, nullptr,                                                   0,   false, rptd::Environment<rptd::PanoramaAnalytic>::band_first, 0, 0, 0, 0},
-    // the lens kernels (rpt_set_field_of_view): reached through the lens column only, looked up LAST (after the environment and Doppler columns)
-    {803, false, RPT_KERNEL(rpt_render_kernel_lens_unculled_w5), 0, nullptr, 0, false, rptd::Lens<rptd::Unculled>::band_first, 0, 0, 0, 0},
-    {841, false, RPT_KERNEL(rpt_render_kernel_lens_ballot_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_ballot_ieee_w5), 0, false, rptd::Lens<rptd::BallotExact>::band_first, 0, 0, 0, 0},
-    {843, false, RPT_KERNEL(rpt_render_kernel_lens_ballot_first_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_ballot_first_ieee_w5), 0, false, rptd::Lens<rptd::BallotFirstExact>::band_first, 0, 0, 0, 0},
-    {844, false, RPT_KERNEL(rpt_render_kernel_lens_analytic_w8), 0, nullptr, 0, false, rptd::Lens<rptd::Analytic>::band_first, 0, 0, 0, 0},
-    {813, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_unculled_w5), 0, nullptr, 0, false, rptd::Lens<rptd::DopplerTwin<rptd::Unculled>>::band_first, 0, 0, 0, 0},
-    {851, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_ieee_w5), 0, false, rptd::Lens<rptd::DopplerTwin<rptd::BallotExact>>::band_first, 0, 0, 0, 0},
-    {853, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_first_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_first_ieee_w5), 0, false, rptd::Lens<rptd::DopplerTwin<rptd::BallotFirstExact>>::band_first, 0, 0, 0, 0},
-    {854, false, RPT_KERNEL(rpt_render_kernel_lens_doppler_analytic_w8), 0, nullptr, 0, false, rptd::Lens<rptd::DopplerTwin<rptd::Analytic>>::band_first, 0, 0, 0, 0},
-    {823, false, RPT_KERNEL(rpt_render_kernel_lens_env_unculled_w5), 0, nullptr, 0, false, rptd::Lens<rptd::Environment<rptd::Unculled>>::band_first, 0, 0, 0, 0},
-    {861, false, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_ieee_w5), 0, false, rptd::Lens<rptd::Environment<rptd::BallotExact>>::band_first, 0, 0, 0, 0},
-    {863, false, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_w5), 0, RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_ieee_w5), 0, false, rptd::Lens<rptd::Environment<rptd::BallotFirstExact>>::band_first, 0, 0, 0, 0},
-    {864, false, RPT_KERNEL(rpt_render_kernel_lens_env_analytic_w8), 0, nullptr, 0, false, rptd::Lens<rptd::Environment<rptd::Analytic>>::band_first, 0, 0, 0, 0},
+const KernelRow colour_table[] = {
+    {1,   Camera::pinhole,  Colour::plain,   Form::ref_layout,    RPT_KERNEL(rpt_render_kernel_v0),                         nullptr},
+    {3,   Camera::pinhole,  Colour::plain,   Form::unculled,      RPT_KERNEL(rpt_render_kernel_unculled_w5),                nullptr},
+    {41,  Camera::pinhole,  Colour::plain,   Form::walk,          RPT_KERNEL(rpt_render_kernel_ballot_w5),                  RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5)},
+    {43,  Camera::pinhole,  Colour::plain,   Form::walk_first,    RPT_KERNEL(rpt_render_kernel_ballot_first_w5),            RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5)},
+    {44,  Camera::pinhole,  Colour::plain,   Form::analytic,      RPT_KERNEL(rpt_render_kernel_analytic_w8),                nullptr},
+    {48,  Camera::pinhole,  Colour::plain,   Form::ieee,          RPT_KERNEL(rpt_render_kernel_ballot_ieee_w5),             nullptr},
+    {49,  Camera::pinhole,  Colour::plain,   Form::ieee_first,    RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_w5),       nullptr},
+    {50,  Camera::pinhole,  Colour::plain,   Form::relaxed5,      nullptr,                                                  nullptr},
+    {51,  Camera::pinhole,  Colour::plain,   Form::relaxed6,      nullptr,                                                  nullptr},
+    {46,  Camera::pinhole,  Colour::plain,   Form::msaa,          RPT_KERNEL(rpt_render_kernel_msaa_w5),                    nullptr},
+    {47,  Camera::pinhole,  Colour::plain,   Form::msaa_unculled, RPT_KERNEL(rpt_render_kernel_msaa_unculled_w5),           nullptr},
+    {203, Camera::pinhole,  Colour::doppler, Form::unculled,      RPT_KERNEL(rpt_render_kernel_unculled_doppler_w5),        nullptr},
+    {240, Camera::pinhole,  Colour::doppler, Form::record,        RPT_KERNEL(rpt_render_kernel_doppler_record_w5),          nullptr},
+    {241, Camera::pinhole,  Colour::doppler, Form::walk,          RPT_KERNEL(rpt_render_kernel_ballot_doppler_w5),          RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5)},
+    {243, Camera::pinhole,  Colour::doppler, Form::walk_first,    RPT_KERNEL(rpt_render_kernel_ballot_first_doppler_w5),    RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5)},
+    {244, Camera::pinhole,  Colour::doppler, Form::analytic,      RPT_KERNEL(rpt_render_kernel_analytic_doppler_w8),        nullptr},
+    {248, Camera::pinhole,  Colour::doppler, Form::ieee,          RPT_KERNEL(rpt_render_kernel_ballot_ieee_doppler_w5),     nullptr},
+    {249, Camera::pinhole,  Colour::doppler, Form::ieee_first,    RPT_KERNEL(rpt_render_kernel_ballot_first_ieee_doppler_w5), nullptr},
+    {603, Camera::pinhole,  Colour::sky,     Form::unculled,      RPT_KERNEL(rpt_render_kernel_env_unculled_w5),            nullptr},
+    {641, Camera::pinhole,  Colour::sky,     Form::walk,          RPT_KERNEL(rpt_render_kernel_env_ballot_w5),              RPT_KERNEL(rpt_render_kernel_env_ballot_ieee_w5)},
+    {643, Camera::pinhole,  Colour::sky,     Form::walk_first,    RPT_KERNEL(rpt_render_kernel_env_ballot_first_w5),        RPT_KERNEL(rpt_render_kernel_env_ballot_first_ieee_w5)},
+    {644, Camera::pinhole,  Colour::sky,     Form::analytic,      RPT_KERNEL(rpt_render_kernel_env_analytic_w8),            nullptr},
+    // the panorama: no object mask, so no band-first form (a walk_first choice gets the walk) and no forced-IEEE arms
+    {303, Camera::equirect, Colour::plain,   Form::unculled,      RPT_KERNEL(rpt_render_kernel_pano_unculled_w5),           nullptr},
+    {341, Camera::equirect, Colour::plain,   Form::walk,          RPT_KERNEL(rpt_render_kernel_pano_w5),                    RPT_KERNEL(rpt_render_kernel_pano_ieee_w5)},
+    {344, Camera::equirect, Colour::plain,   Form::analytic,      RPT_KERNEL(rpt_render_kernel_pano_analytic_w8),           nullptr},
+    {503, Camera::equirect, Colour::doppler, Form::unculled,      RPT_KERNEL(rpt_render_kernel_pano_unculled_doppler_w5),   nullptr},
+    {540, Camera::equirect, Colour::doppler, Form::record,        RPT_KERNEL(rpt_render_kernel_pano_doppler_record_w5),     nullptr},
+    {541, Camera::equirect, Colour::doppler, Form::walk,          RPT_KERNEL(rpt_render_kernel_pano_doppler_w5),            RPT_KERNEL(rpt_render_kernel_pano_ieee_doppler_w5)},
+    {544, Camera::equirect, Colour::doppler, Form::analytic,      RPT_KERNEL(rpt_render_kernel_pano_analytic_doppler_w8),   nullptr},
+    {703, Camera::equirect, Colour::sky,     Form::unculled,      RPT_KERNEL(rpt_render_kernel_env_pano_unculled_w5),       nullptr},
+    {741, Camera::equirect, Colour::sky,     Form::walk,          RPT_KERNEL(rpt_render_kernel_env_pano_w5),                RPT_KERNEL(rpt_render_kernel_env_pano_ieee_w5)},
+    {744, Camera::equirect, Colour::sky,     Form::analytic,      RPT_KERNEL(rpt_render_kernel_env_pano_analytic_w8),       nullptr},
+    {803, Camera::lens,     Colour::plain,   Form::unculled,      RPT_KERNEL(rpt_render_kernel_lens_unculled_w5),           nullptr},
+    {841, Camera::lens,     Colour::plain,   Form::walk,          RPT_KERNEL(rpt_render_kernel_lens_ballot_w5),             RPT_KERNEL(rpt_render_kernel_lens_ballot_ieee_w5)},
+    {843, Camera::lens,     Colour::plain,   Form::walk_first,    RPT_KERNEL(rpt_render_kernel_lens_ballot_first_w5),       RPT_KERNEL(rpt_render_kernel_lens_ballot_first_ieee_w5)},
+    {844, Camera::lens,     Colour::plain,   Form::analytic,      RPT_KERNEL(rpt_render_kernel_lens_analytic_w8),           nullptr},
+    {813, Camera::lens,     Colour::doppler, Form::unculled,      RPT_KERNEL(rpt_render_kernel_lens_doppler_unculled_w5),   nullptr},
+    {851, Camera::lens,     Colour::doppler, Form::walk,          RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_w5),     RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_ieee_w5)},
+    {853, Camera::lens,     Colour::doppler, Form::walk_first,    RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_first_w5), RPT_KERNEL(rpt_render_kernel_lens_doppler_ballot_first_ieee_w5)},
+    {854, Camera::lens,     Colour::doppler, Form::analytic,      RPT_KERNEL(rpt_render_kernel_lens_doppler_analytic_w8),   nullptr},
+    {823, Camera::lens,     Colour::sky,     Form::unculled,      RPT_KERNEL(rpt_render_kernel_lens_env_unculled_w5),       nullptr},
+    {861, Camera::lens,     Colour::sky,     Form::walk,          RPT_KERNEL(rpt_render_kernel_lens_env_ballot_w5),         RPT_KERNEL(rpt_render_kernel_lens_env_ballot_ieee_w5)},
+    {863, Camera::lens,     Colour::sky,     Form::walk_first,    RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_w5),   RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_ieee_w5)},
+    {864, Camera::lens,     Colour::sky,     Form::analytic,      RPT_KERNEL(rpt_render_kernel_lens_env_analytic_w8),       nullptr},
+};
+
+// The refine kernels (rpt_set_adaptive_aa), variant 1000 + 10 (3 camera + colour) + {1 walk, 3 un-culled, 4 no walk}.  The form is pass
+// A's: un-culled wherever the one-sample kernel ran un-culled, the walk with the wave's object mask, or no walk compiled in.
+#define RPT_REFINE_ROWS(base, camera, colour, name)                                                                                                 \
+    {base + 3, camera, colour, Form::unculled, RPT_KERNEL(rpt_refine_kernel_##name##_unculled), nullptr},                                          \
+    {base + 1, camera, colour, Form::walk,     RPT_KERNEL(rpt_refine_kernel_##name##_walk),     RPT_KERNEL(rpt_refine_kernel_##name##_walk_ieee)}, \
+    {base + 4, camera, colour, Form::analytic, RPT_KERNEL(rpt_refine_kernel_##name##_analytic), nullptr}
+const KernelRow refine_table[] = {
+    RPT_REFINE_ROWS(1000, Camera::pinhole,  Colour::plain,   plain),
+    RPT_REFINE_ROWS(1010, Camera::pinhole,  Colour::doppler, doppler),
+    RPT_REFINE_ROWS(1020, Camera::pinhole,  Colour::sky,     env),
+    RPT_REFINE_ROWS(1030, Camera::lens,     Colour::plain,   lens),
+    RPT_REFINE_ROWS(1040, Camera::lens,     Colour::doppler, lens_doppler),
+    RPT_REFINE_ROWS(1050, Camera::lens,     Colour::sky,     lens_env),
+    RPT_REFINE_ROWS(1060, Camera::equirect, Colour::plain,   pano),
+    RPT_REFINE_ROWS(1070, Camera::equirect, Colour::doppler, pano_doppler),
+    RPT_REFINE_ROWS(1080, Camera::equirect, Colour::sky,     pano_env),
+};
+#undef RPT_REFINE_ROWS
+
+// The event kernels (rpt_render_events): colour does not exist there.  Un-culled is rpt_set_variant(3) and what a frame outside the proven
+// window gets; the panorama has no un-culled row: it has no object mask and the pass has no shadow rays, so its two rows cull nothing.
+const KernelRow events_table[] = {
+    {903, Camera::pinhole,  Colour::plain, Form::unculled, RPT_KERNEL(rpt_events_kernel_unculled),      nullptr},
+    {941, Camera::pinhole,  Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_ballot),        RPT_KERNEL(rpt_events_kernel_ballot_ieee)},
+    {944, Camera::pinhole,  Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_analytic),      nullptr},
+    {911, Camera::equirect, Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_pano),          RPT_KERNEL(rpt_events_kernel_pano_ieee)},
+    {914, Camera::equirect, Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_pano_analytic), nullptr},
+    {923, Camera::lens,     Colour::plain, Form::unculled, RPT_KERNEL(rpt_events_kernel_lens_unculled), nullptr},
+    {921, Camera::lens,     Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_lens_ballot),   RPT_KERNEL(rpt_events_kernel_lens_ballot_ieee)},
+    {924, Camera::lens,     Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_lens_analytic), nullptr},
 };
 #undef RPT_KERNEL
 
-const VariantRow *variant_row(int v) {
-    for (const VariantRow &r : variant_table)
-        if (r.variant == v) return &r;
+template <size_t N>
+const KernelRow *find_row(const KernelRow (&table)[N], Camera camera, Colour colour, Form form) {
+    for (const KernelRow &r : table)
+        if (r.camera == camera && r.colour == colour && r.form == form) return &r;
     return nullptr;
 }
 
-// ---- the refine kernels (rpt_set_adaptive_aa): one row per kernel, chosen by camera, colour family and form ---------------------------
-// variant   what rpt_last_aa_variant reports: 1000 + 10 (3 camera + colour) + {1 walk, 3 un-culled, 4 no walk}
-// form      pass A's: un-culled wherever the one-sample kernel ran un-culled, the walk with the wave's object mask, or no walk compiled in
-// ieee      the walk's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp), as for 41
-enum class RefineCamera { pinhole, lens, equirect };
-enum class RefineColour { plain, doppler, environment };
-enum class RefineForm { unculled, walk, analytic };
-struct RefineRow {
-    int variant;
-    RefineCamera camera;
-    RefineColour colour;
-    RefineForm form;
-    const void *kernel;
-    const void *ieee;
-};
-#define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
-#define RPT_REFINE_ROWS(base, camera, colour, name)                                                                                                       \
-    {base + 3, camera, colour, RefineForm::unculled, RPT_KERNEL(rpt_refine_kernel_##name##_unculled), nullptr},                                          \
-    {base + 1, camera, colour, RefineForm::walk,     RPT_KERNEL(rpt_refine_kernel_##name##_walk),     RPT_KERNEL(rpt_refine_kernel_##name##_walk_ieee)}, \
-    {base + 4, camera, colour, RefineForm::analytic, RPT_KERNEL(rpt_refine_kernel_##name##_analytic), nullptr}
-const RefineRow refine_table[] = {
-    RPT_REFINE_ROWS(1000, RefineCamera::pinhole,  RefineColour::plain,       plain),
-    RPT_REFINE_ROWS(1010, RefineCamera::pinhole,  RefineColour::doppler,     doppler),
-    RPT_REFINE_ROWS(1020, RefineCamera::pinhole,  RefineColour::environment, env),
-    RPT_REFINE_ROWS(1030, RefineCamera::lens,     RefineColour::plain,       lens),
-    RPT_REFINE_ROWS(1040, RefineCamera::lens,     RefineColour::doppler,     lens_doppler),
-    RPT_REFINE_ROWS(1050, RefineCamera::lens,     RefineColour::environment, lens_env),
-    RPT_REFINE_ROWS(1060, RefineCamera::equirect, RefineColour::plain,       pano),
-    RPT_REFINE_ROWS(1070, RefineCamera::equirect, RefineColour::doppler,     pano_doppler),
-    RPT_REFINE_ROWS(1080, RefineCamera::equirect, RefineColour::environment, pano_env),
-};
-#undef RPT_REFINE_ROWS
-#undef RPT_KERNEL
+// the form rpt_set_variant(v) asks for; Form::diagnostic: not a number the product library takes
+Form settable_form(int v) {
+    for (const KernelRow &r : colour_table)
+        if (r.variant == v && r.camera == Camera::pinhole && r.colour == Colour::plain && settable(r.form)) return r.form;
+    return Form::diagnostic;
+}
 
-// What every frame's KernelArgs hold whatever kernel renders it: the scene, the outputs, the per-frame constants, the rows (launch()
-// and launch_events() fill the rest).
-void fill_kernel_args(const rpt_ctx *ctx, rptd::KernelArgs &a) {
+// ---- the rules over the settings that more than one choice follows -------------------------------------------------------------------
+// The variants that exist for every camera and colour, as refine kernels and as event kernels: 0 and the forms it can resolve to
+bool has_product_forms(int variant) { return variant == 0 || variant == 3 || variant == 41 || variant == 43 || variant == 44; }
+
+// The per-object regions are PROVEN for the window |u| <= 2, |v| <= 1/2 (rpt_bounds_certify.hpp): a frame wider than 4 : 1 has pixels
+// outside it, and beyond 2^20 pixels a side a tile's 1.5-pixel skirt is no longer large against float rounding — such frames are rendered
+// un-culled (same pixels, every object tested everywhere).
+// Under a lens pixel (x, y) looks through (fl(s fx2), fl(s fy2)): with s <= 1 no larger in magnitude than |fy2| <= 1/2 and than
+// fl(s fl(aspect / 2)), which is what is compared here (rounding is monotone).  The 2^20 bound covers every s: the skirt and the rounding
+// it is held against scale with s alike (rpt_kernels.hip.h: wave_object_mask_lens).  A wider lens: un-culled as well.
+bool window_holds_frame(const rpt_ctx *ctx) {
+    const float half_aspect = 0.5f * ((float)ctx->width / (float)ctx->height);
+    const bool lens = ctx->v_fov != 0.0f;
+    return (lens ? ctx->lens_scale <= 1.0f && ctx->lens_scale * half_aspect <= (float)rptb::cert::WINDOW_U : half_aspect <= (float)rptb::cert::WINDOW_U) &&
+           ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
+}
+
+// Frames in flight that are too small to fill the chip with walks wait for latency as the blocking call does
+// (profiles/r03_latency_walk_ab.txt: 43 ahead of 41 up to 1920x1080 — bunny -6 %, shadows -19 % — level at 2560x1440, behind from
+// 3200x1800).  A rank's share of a sharded frame counts, not the frame.
+bool small_frame(const rpt_ctx *ctx) {
+    return (size_t)local_tile_count(ctx) * RPT_TILE_ROWS * (size_t)ctx->width <= (size_t)RPT_LATENCY_KERNEL_MAX_PIXELS;
+}
+
+// the Doppler debug kernel stands in for every twin while the record hook is set (rpt_set_debug_doppler)
+bool doppler_recording(const rpt_ctx *ctx) { return ctx->doppler && (ctx->external_doppler || ctx->want_owned_doppler); }
+
+// ---- the choice: everything a launch decides, from the settings alone ----------------------------------------------------------------
+// colour_frame: the launch renders a frame of rpt_render / rpt_render_async, which is what rpt_set_adaptive_aa acts on (pass A + pass B);
+// rpt_verify_frame and rpt_timed_frames launch the one-sample pass alone, in flight.
+enum class CallKind { blocking, in_flight, events };
+struct Call {
+    CallKind kind;
+    bool colour_frame;
+};
+struct Choice {
+    int code = RPT_OK;                  // != RPT_OK: the refusal, with its text
+    std::string text;
+    bool nothing = false;               // this context holds no row of the frame (rpt_set_rows): nothing to launch, nothing refused
+    const KernelRow *colour = nullptr;  // the colour kernel (the event kernel of an event pass); null with `variant` set: a measurement arm
+    const KernelRow *refine = nullptr;  // pass B of an adaptive frame, or null
+    int variant = 0;                    // colour->variant, or the measurement arm's number (librpt_hip_diag.so)
+    bool exact_rcp = false;             // the scene lies in rcp_exact's domain: a row that has an `ieee` sibling runs its own kernel
+    bool band_first = false;            // the band of tile rows that holds the meshes goes first
+    const void *kernel(const KernelRow *row) const { return row->ieee && !exact_rcp ? row->ieee : row->kernel; }
+    bool ran_exact(const KernelRow *row) const { return row && row->ieee && exact_rcp; }
+};
+
+Choice refuse(int code, std::string text) {
+    Choice c;
+    c.code = code;
+    c.text = std::move(text);
+    return c;
+}
+
+Choice choose_event_kernel(const rpt_ctx *ctx) {
+    if (!ctx->scene_uploaded) return refuse(RPT_ERR_STATE, "rpt_render_events before rpt_upload_scene");
+    if (!ctx->params_set) return refuse(RPT_ERR_STATE, "rpt_render_events before rpt_set_params");
+    if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_render_events: MSAA > 1 has no event kernel (one primary ray per pixel)");
+    if (!has_product_forms(ctx->variant))
+        return refuse(RPT_ERR_ARG, "rpt_render_events: variant " + std::to_string(ctx->variant) + " has no event kernel (variants 0, 3, 41, 43 and 44 have)");
+    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE, lens = ctx->v_fov != 0.0f;
+    if (lens && panorama) return refuse(RPT_ERR_ARG, "rpt_render_events: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
+    const Camera camera = panorama ? Camera::equirect : (lens ? Camera::lens : Camera::pinhole);
+    Form form = !ctx->has_mesh ? Form::analytic : Form::walk;
+    if (camera != Camera::equirect && (ctx->variant == 3 || !window_holds_frame(ctx))) form = Form::unculled;
+    if (!ctx->geo->compact_ok && form != Form::analytic)
+        return refuse(RPT_ERR_ARG, "rpt_render_events: the event kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+    Choice c;
+    c.colour = find_row(events_table, camera, Colour::plain, form);
+    if (!c.colour) return refuse(RPT_ERR_ARG, "rpt_render_events: no event kernel for this camera");
+    c.variant = c.colour->variant;
+    c.exact_rcp = ctx->geo->exact_rcp_ok;
+    return c;
+}
+
+// Calls nothing in HIP and changes nothing in the context.  Where several refusals apply, the first one here is what the caller sees.
+Choice choose_kernels(const rpt_ctx *ctx, Call call) {
+    if (call.kind == CallKind::events) return choose_event_kernel(ctx);
+    if (!ctx->scene_uploaded) return refuse(RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
+    if (!ctx->params_set) return refuse(RPT_ERR_STATE, "rpt_render before rpt_set_params");
+    const int sv = ctx->variant;
+    const bool lens = ctx->v_fov != 0.0f, panorama = ctx->projection != RPT_PROJECTION_PINHOLE, recording = doppler_recording(ctx);
+    // Adaptive anti-aliasing (rpt_set_adaptive_aa): what it cannot serve refuses first
+    const bool adaptive = call.colour_frame && ctx->aa_n > 1;
+    if (adaptive) {
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: rpt_set_msaa > 1 is set as well (full supersampling is threshold -1 here)");
+        if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->run_log2 != 0 || ctx->colour_plane)
+            return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: this context renders a share of the frame's rows or a colour plane (rpt_set_rows / rpt_set_tile_pattern): the neighbour rows belong to another rank");
+        if (!has_product_forms(sv))
+            return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: variant " + std::to_string(sv) + " has no refine kernel (variants 0, 3, 41, 43 and 44 have)");
+        if (recording) return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: the Doppler debug kernels (rpt_set_debug_doppler) have no refine pass");
+        if (!ctx->geo->compact_ok && ctx->has_mesh)
+            return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: the refine kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+    }
+    Choice c;
+    c.exact_rcp = ctx->geo->exact_rcp_ok;
+    if (local_tile_count(ctx) == 0) {
+        c.nothing = true;
+        return c;
+    }
+    // The form.  Variant 0 = default: rpt_render_async() is a throughput call (frames in flight fill each other's gaps): the in-wave cull
+    // kernel in natural order (41).  The blocking rpt_render() is a latency call — its caller waits for this frame, and the frame is as
+    // long as its longest wave — so the band of tile rows that holds the meshes is dispatched first and the walk asks for its triangle
+    // records an iteration ahead (43); small frames in flight likewise.  A frame whose Object[] holds no mesh gets the kernel without the
+    // octree walk (44): 8 waves per SIMD instead of 5.  An octree the derived layout cannot hold gets the general kernel (1).
+    // Kernels 41 and 43 take the triangle test's 1 / det through rcp_exact when the scene's triangles allow it and the IEEE division
+    // otherwise (KernelRow::ieee); rpt_last_variant reports 41 / 43 either way, rpt_last_exact_rcp which ran.
+    c.variant = sv;
+    Form form = sv == 0 ? (!ctx->has_mesh ? Form::analytic : (call.kind == CallKind::blocking || small_frame(ctx) ? Form::walk_first : Form::walk)) : settable_form(sv);
+    if (form == Form::analytic && ctx->has_mesh) form = Form::walk;          // (asked for explicitly on a scene with meshes: the full kernel)
+    if (!ctx->geo->compact_ok && form != Form::analytic) form = Form::ref_layout;
+    // A lens (rpt_set_field_of_view), the panorama (rpt_set_projection), MSAA, Doppler and the sky: what has no kernel refuses here, at
+    // the launch, so that the settings may be made in any order
+    if (lens) {
+        if (panorama) return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: MSAA > 1 has no lens kernel");
+        if (!has_product_forms(sv))
+            return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: variant " + std::to_string(sv) + " has no lens kernel (variants 0, 3, 41, 43 and 44 have)");
+        if (form == Form::ref_layout)
+            return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: the lens kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+        if (recording) return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: the Doppler debug kernel (rpt_set_debug_doppler) has no lens form");
+    }
+    Camera camera = Camera::pinhole;
+    if (panorama) {      // variant 0's choice and variant 3 only; its rays leave the pinhole's proven window anyway
+        if (sv != 0 && sv != 3) return refuse(RPT_ERR_ARG, "rpt_set_projection: variant " + std::to_string(sv) + " has no panorama kernel (variants 0 and 3 have)");
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_projection: MSAA > 1 has no panorama kernel");
+        if (form == Form::walk_first) form = Form::walk;
+        camera = Camera::equirect;
+        if (!find_row(colour_table, camera, Colour::plain, form))
+            return refuse(RPT_ERR_ARG, "rpt_set_projection: the panorama kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+    } else if (needs_proven_window(form) && !window_holds_frame(ctx)) {
+        form = Form::unculled;
+    }
+    // (pass B's form is pass A's at this point: un-culled, without the walk, else the walk)
+    const Form refine_form = form == Form::unculled || form == Form::analytic ? form : Form::walk;
+    c.band_first = band_first(form);
+    if (ctx->msaa > 1) {       // MSAASAMPLES > 1: the multi-sample form of the default kernel (46), or of the un-culled one (47)
+        form = form == Form::unculled ? Form::msaa_unculled : (form == Form::walk || form == Form::walk_first || form == Form::analytic ? Form::msaa : Form::diagnostic);
+        if (!find_row(colour_table, camera, Colour::plain, form))
+            return refuse(RPT_ERR_ARG, "rpt_set_msaa > 1 is implemented for the default kernels and variant 3 (derived octree layouts)");
+    }
+    Colour colour = Colour::plain;
+    if (ctx->env_on) {         // looked up before Doppler: a sky kernel carries Doppler as a run-time flag and serves both
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_environment: MSAA > 1 has no environment kernel");
+        if (recording) return refuse(RPT_ERR_ARG, "rpt_set_environment: the Doppler debug kernels (rpt_set_debug_doppler) have no environment form");
+        colour = Colour::sky;
+        if (!find_row(colour_table, camera, colour, form))
+            return refuse(RPT_ERR_ARG, form == Form::ref_layout && sv != 1
+                                           ? "rpt_set_environment: the environment kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)"
+                                           : "rpt_set_environment: variant " + std::to_string(sv) + " has no environment kernel (variants 0, 3, 41, 43 and 44 have)");
+    } else if (ctx->doppler) {
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_doppler: MSAA > 1 has no Doppler kernel");
+        colour = Colour::doppler;
+        if (!find_row(colour_table, camera, colour, form))
+            return refuse(RPT_ERR_ARG, form == Form::ref_layout ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
+                                                                : "rpt_set_doppler: this kernel variant has no Doppler twin");
+        if (recording) form = Form::record;
+    }
+    if (lens) camera = Camera::lens;         // last: the lens form of what every other setting chose
+    c.colour = find_row(colour_table, camera, colour, form);
+    if (c.colour) c.variant = c.colour->variant;
+#ifndef RPT_DIAGNOSTICS
+    if (!c.colour) return refuse(RPT_ERR_ARG, "unknown kernel variant");
+#endif
+    if (adaptive) {
+        // under a lens the skirt's proof for the SAMPLE positions reaches 0.98 million pixels a side, not 2^20 (rpt_kernels.hip.h: refine_pixel_body)
+        const bool beyond_samples = lens && (ctx->width > (1 << 19) || ctx->height > (1 << 19));
+        c.refine = find_row(refine_table, camera, colour, beyond_samples ? Form::unculled : refine_form);
+        if (!c.refine) return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: no refine kernel for this camera");
+    }
+    return c;
+}
+
+// What every frame's arguments hold whatever kernel renders it: the scene, the outputs, the per-frame constants, the rows and the camera
+// (launch() adds the colour, launch_events() the records).  One LensArgs serves every kernel: each reads its own prefix of it.
+void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
     std::memset(&a, 0, sizeof a);
     a.dnodes = (const rptd::DNode *)ctx->geo->dnodes.ptr;
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
@@ -1038,11 +1227,11 @@ void fill_kernel_args(const rpt_ctx *ctx, rptd::KernelArgs &a) {
     // the diagonal slabs hold inside their window only (rpt_screen_bounds.hpp): frames up to 4 : 1, |v| <= 1/2 always
     a.diagonals = 0;
     // (under a lens, rpt_set_field_of_view, the tiles' plane coordinates are those of the reference's lens times s <= 1 — a wider lens
-    // gets the un-culled kernel below — so the same rule holds with both sides of the tile scaled)
+    // gets the un-culled kernel — so the same rule holds with both sides of the tile scaled)
     const bool lens = ctx->v_fov != 0.0f;
-    const float lens_scale = lens ? ctx->lens_scale : 1.0f;
+    a.lens_scale = lens ? ctx->lens_scale : 1.0f;
     const float diag_reach = 0.5f * a.aspect + 2.0f * a.inv_height * a.aspect;
-    if ((lens ? lens_scale <= 1.0f && lens_scale * diag_reach <= (float)rptb::DIAG_WINDOW_U : diag_reach <= (float)rptb::DIAG_WINDOW_U) && ctx->rects.size() == (size_t)ctx->object_count)
+    if ((lens ? a.lens_scale <= 1.0f && a.lens_scale * diag_reach <= (float)rptb::DIAG_WINDOW_U : diag_reach <= (float)rptb::DIAG_WINDOW_U) && ctx->rects.size() == (size_t)ctx->object_count)
         for (const rptb::Rect &r : ctx->rects) a.diagonals |= rptb::has_diagonals(r) ? 1 : 0;
     a.object_count = ctx->object_count;
     a.width = ctx->width;
@@ -1051,203 +1240,87 @@ void fill_kernel_args(const rpt_ctx *ctx, rptd::KernelArgs &a) {
     a.first_tile = ctx->first_tile;
     a.tile_step = ctx->tile_step;
     a.run_log2 = ctx->run_log2;
+    if (ctx->projection != RPT_PROJECTION_PINHOLE) {      // (the caller has made them this frame's: ensure_projection_tables)
+        a.pano_cols = (const float2 *)ctx->pano.upload.device.ptr;
+        a.pano_rows = a.pano_cols + ctx->width;
+    }
 }
 
-// colour_frame: the launch renders a frame of rpt_render / rpt_render_async, which is what rpt_set_adaptive_aa acts on (pass A + pass B);
-// rpt_verify_frame and rpt_timed_frames launch the one-sample pass alone.
-int launch(rpt_ctx *ctx, bool colour_frame = false) {
-    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
-    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render before rpt_set_params");
+// One colour frame on the context's stream: the choice, then buffers, arguments and the launch (pass A + pass B of an adaptive frame).
+int launch(rpt_ctx *ctx, Call call) {
+    const Choice c = choose_kernels(ctx, call);
+    if (call.colour_frame && ctx->scene_uploaded && ctx->params_set) ctx->last_aa_variant = 0;
+    if (c.code != RPT_OK) return fail(ctx, c.code, c.text);
     if (int rc = ensure_outputs(ctx)) return rc;
-
-    rptd::KernelArgs a;
-    fill_kernel_args(ctx, a);
-    const bool lens = ctx->v_fov != 0.0f;
-    const float lens_scale = lens ? ctx->lens_scale : 1.0f;
-
-    // Adaptive anti-aliasing (rpt_set_adaptive_aa): what it cannot serve refuses here and below, before anything is launched
-    const bool adaptive = colour_frame && ctx->aa_n > 1;
-    if (colour_frame) ctx->last_aa_variant = 0;
-    if (adaptive) {
-        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: rpt_set_msaa > 1 is set as well (full supersampling is threshold -1 here)");
-        if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->run_log2 != 0 || ctx->colour_plane)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: this context renders a share of the frame's rows or a colour plane (rpt_set_rows / rpt_set_tile_pattern): the neighbour rows belong to another rank");
-        if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED && ctx->variant != VARIANT_BALLOT && ctx->variant != VARIANT_BALLOT_FIRST && ctx->variant != VARIANT_ANALYTIC)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: variant " + std::to_string(ctx->variant) + " has no refine kernel (variants 0, 3, 41, 43 and 44 have)");
-        if (ctx->doppler && (ctx->external_doppler || ctx->want_owned_doppler))
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: the Doppler debug kernels (rpt_set_debug_doppler) have no refine pass");
-        if (!ctx->geo->compact_ok && ctx->has_mesh)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: the refine kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+    const int tiles = local_tile_count(ctx);
+    if (call.colour_frame && ctx->aa_n > 1) {
         // pass A writes its packed colours here as well (the kernels honour `plane` next to `out16`; whole-frame contexts: local rows are the frame's)
-        if (int rc = reserve(ctx, ctx->aa_plane, (size_t)local_tile_count(ctx) * RPT_TILE_ROWS * ctx->width * 4)) return rc;
+        if (int rc = reserve(ctx, ctx->aa_plane, (size_t)tiles * RPT_TILE_ROWS * ctx->width * 4)) return rc;
         if (int rc = reserve(ctx, ctx->aa_counter, 8)) return rc;
         if (!ctx->aa_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->aa_host, 8, hipHostMallocDefault));
         if (!ctx->aa_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->aa_counted, hipEventDisableTiming));
-        a.plane = (uint32_t *)ctx->aa_plane.ptr;
+    }
+    if (c.nothing) return RPT_OK;
+    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
+    if (panorama) {
+        if (int rc = ensure_projection_tables(ctx, ctx->pano, 1)) return rc;
+        if (c.refine)
+            if (int rc = ensure_projection_tables(ctx, ctx->aa_pano, ctx->aa_n)) return rc;
     }
 
-    const int tiles = local_tile_count(ctx);
-    if (tiles == 0) return RPT_OK;
-    const dim3 grid((ctx->width + 31) / 32, tiles);         // the measurement arms: four waves (a 32 x 8 strip) per workgroup
-    const dim3 grid1(((ctx->width + 31) / 32) * 4, tiles);  // the product kernels: one wave (an 8 x 8 tile) per workgroup
-    // variant 0 = default.  rpt_render_async() is a throughput call (frames in flight fill each other's gaps): the in-wave
-    // cull kernel in natural order (41).  The blocking rpt_render() is a latency call — its caller waits for this frame, and the
-    // frame is as long as its longest wave — so the band of tile rows that holds the meshes is dispatched first and the walk asks
-    // for its triangle records an iteration ahead (43).  A frame whose Object[] holds no mesh gets the kernel without the octree
-    // walk (44): 8 waves per SIMD instead of 5.  An octree the derived layout cannot hold gets the general kernel (1).
-    // Frames in flight that are too small to fill the chip with walks wait for latency as well (profiles/r03_latency_walk_ab.txt:
-    // 43 ahead of 41 up to 1920x1080 — bunny -6 %, shadows -19 % — level at 2560x1440, behind from 3200x1800): 43 for those too.
-    const bool small_frame = (size_t)tiles * RPT_TILE_ROWS * (size_t)ctx->width <= (size_t)RPT_LATENCY_KERNEL_MAX_PIXELS;
-    // Kernels 41 and 43 take the triangle test's 1 / det through rcp_exact when the scene's triangles allow it (exact_rcp_ok,
-    // rpt_scene_exact_rcp: the same floats as the IEEE division there) and the IEEE division otherwise; 48 / 49 are 41 / 43 with the
-    // IEEE division whatever the scene (the A/B arm).  rpt_last_variant reports 41 / 43 either way, rpt_last_exact_rcp which ran.
-    int v = ctx->variant == VARIANT_DEFAULT ? (!ctx->has_mesh ? VARIANT_ANALYTIC : (ctx->latency_call || small_frame ? VARIANT_BALLOT_FIRST : VARIANT_BALLOT))
-                                            : ctx->variant;
-    if (v == VARIANT_ANALYTIC && ctx->has_mesh) v = VARIANT_BALLOT;          // (asked for explicitly on a scene with meshes: the full kernel)
-    if (!ctx->geo->compact_ok && v != VARIANT_ANALYTIC) v = VARIANT_REF_LAYOUT;
-    const VariantRow *row = variant_row(v);
-    if (row && !row->settable) row = nullptr;          // (the diagnostics library takes any number: the MSAA and Doppler forms are reached below only)
-    // The equirectangular camera (rpt_set_projection): variant 0's choice and variant 3 go to their panorama kernels (341 / 344, 303), whose
-    // rays leave the pinhole's proven window anyway; everything else refuses here, at the launch, like the kernels without a Doppler twin.
-    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
-    // A lens (rpt_set_field_of_view): the lens form of the kernel every other setting chooses, looked up last.  What has none refuses here,
-    // at the launch, like the precedents: the setting may precede the others.
-    if (lens) {
-        if (panorama) return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
-        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: MSAA > 1 has no lens kernel");
-        if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED && ctx->variant != VARIANT_BALLOT && ctx->variant != VARIANT_BALLOT_FIRST && ctx->variant != VARIANT_ANALYTIC)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: variant " + std::to_string(ctx->variant) + " has no lens kernel (variants 0, 3, 41, 43 and 44 have)");
-        if (v == VARIANT_REF_LAYOUT)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the lens kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
-        if (ctx->doppler && (ctx->external_doppler || ctx->want_owned_doppler))
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the Doppler debug kernel (rpt_set_debug_doppler) has no lens form");
-    }
-    if (panorama) {
-        if (ctx->variant != VARIANT_DEFAULT && ctx->variant != VARIANT_UNCULLED)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: variant " + std::to_string(ctx->variant) + " has no panorama kernel (variants 0 and 3 have)");
-        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: MSAA > 1 has no panorama kernel");
-        if (v == VARIANT_REF_LAYOUT || !row || !row->panorama)
-            return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: the panorama kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
-        row = variant_row(v = row->panorama);
-        if (int rc = ensure_panorama_tables(ctx)) return rc;
-    }
-    // The per-object regions are PROVEN for the window |u| <= 2, |v| <= 1/2 (rpt_bounds_certify.hpp): a frame wider than 4 : 1 has
-    // pixels outside it, and beyond 2^20 pixels a side a tile's 1.5-pixel skirt is no longer large against float rounding — such
-    // frames are rendered by the un-culled kernel (same pixels, every object tested everywhere).
-    // Under a lens pixel (x, y) looks through (fl(s fx2), fl(s fy2)): with s <= 1 no larger in magnitude than |fy2| <= 1/2 and than
-    // fl(s fl(aspect / 2)), which is what is compared here (rounding is monotone).  The 2^20 bound covers every s: the skirt and the
-    // rounding it is held against scale with s alike (rpt_kernels.hip.h: wave_object_mask_lens).  A wider lens: the un-culled lens kernel.
-    const bool window_holds_frame = (lens ? lens_scale <= 1.0f && lens_scale * (0.5f * a.aspect) <= (float)rptb::cert::WINDOW_U : 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U) &&
-                                    ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
-    if (!window_holds_frame && row && row->window) row = variant_row(v = VARIANT_UNCULLED);
-    // (pass B's form is pass A's at this point: 3 / 303 un-culled, 44 / 344 without the walk, else the walk)
-    const int aa_base = v;
-    a.first_h = 0;
-    if (row && row->band_first) set_band_first(ctx, a, tiles);
+    rptd::LensArgs a;
+    fill_frame_args(ctx, a);
+    if (c.refine) a.plane = (uint32_t *)ctx->aa_plane.ptr;
+    if (c.band_first) set_band_first(ctx, a, tiles);
     a.msaa = ctx->msaa;
-    if (ctx->msaa > 1) {       // MSAASAMPLES > 1: the multi-sample form of the default kernel (46), or of the un-culled one (47)
-        if (!row || !row->msaa) return fail(ctx, RPT_ERR_ARG, "rpt_set_msaa > 1 is implemented for the default kernels and variant 3 (derived octree layouts)");
-        row = variant_row(v = row->msaa);
-    }
-    // Doppler on (rpt_set_doppler): every kernel chosen above goes to its twin, or to the debug kernel (240, un-culled) while the record
-    // hook is set.  The kernels without a twin refuse here, at the launch: the setting may precede rpt_set_variant.
-    float *const record = ctx->doppler ? (float *)(ctx->external_doppler ? ctx->external_doppler : (ctx->want_owned_doppler ? ctx->owned_doppler.ptr : nullptr)) : nullptr;
-    // The sky image (rpt_set_environment): the kernel chosen above goes to its environment form, which serves Doppler off and on.  What has
-    // none refuses here, at the launch, like the precedents: the setting may precede rpt_set_variant.
-    const bool environment = ctx->env_on;
-    if (environment) {
-        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_environment: MSAA > 1 has no environment kernel");
-        if (record) return fail(ctx, RPT_ERR_ARG, "rpt_set_environment: the Doppler debug kernels (rpt_set_debug_doppler) have no environment form");
-        if (!row || !row->environment)
-            return fail(ctx, RPT_ERR_ARG, v == VARIANT_REF_LAYOUT && ctx->variant != VARIANT_REF_LAYOUT
-                                              ? "rpt_set_environment: the environment kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)"
-                                              : "rpt_set_environment: variant " + std::to_string(ctx->variant) + " has no environment kernel (variants 0, 3, 41, 43 and 44 have)");
-        row = variant_row(v = row->environment);
-    } else if (ctx->doppler) {
-        if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_set_doppler: MSAA > 1 has no Doppler kernel");
-        if (!row || !row->doppler)
-            return fail(ctx, RPT_ERR_ARG, v == VARIANT_REF_LAYOUT ? "rpt_set_doppler: kernel 1 (the reference's octree layout) has no Doppler twin"
-                                                                  : "rpt_set_doppler: this kernel variant has no Doppler twin");
-        row = variant_row(v = record ? (panorama ? VARIANT_PANORAMA_RECORD : VARIANT_DOPPLER_RECORD) : row->doppler);
-    }
-    if (lens) {
-        if (!row || !row->lens) return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: kernel " + std::to_string(v) + " has no lens form");
-        row = variant_row(v = row->lens);
-    }
-    rptd::DopplerArgs da;         // (the twins' arguments: this frame's KernelArgs + the two Doppler fields)
-    static_cast<rptd::KernelArgs &>(da) = a;
-    da.doppler = ctx->doppler;
-    da.debug_doppler = record;
-    ctx->doppler_recorded = record != nullptr;
-    rptd::PanoramaArgs pa;        // (the panorama kernels' arguments: the above + the two tables)
-    static_cast<rptd::DopplerArgs &>(pa) = da;
-    pa.pano_cols = panorama ? (const float2 *)ctx->pano_tables.ptr : nullptr;
-    pa.pano_rows = panorama ? (const float2 *)ctx->pano_tables.ptr + ctx->width : nullptr;
-    rptd::EnvironmentArgs ea;     // (the environment kernels' arguments: the above + the image and its frame)
-    static_cast<rptd::PanoramaArgs &>(ea) = pa;
-    ea.env_texels = environment ? (const uint32_t *)ctx->env_texels.ptr : nullptr;
-    ea.env_width = ctx->env_width;
-    ea.env_height = ctx->env_height;
-    std::memcpy(ea.env_frame, ctx->env_frame, sizeof ea.env_frame);
+    a.doppler = ctx->doppler;
+    a.debug_doppler = doppler_recording(ctx) ? (float *)(ctx->external_doppler ? ctx->external_doppler : ctx->owned_doppler.ptr) : nullptr;
+    ctx->doppler_recorded = a.debug_doppler != nullptr;
+    a.env_texels = ctx->env_on ? (const uint32_t *)ctx->env.device.ptr : nullptr;
+    a.env_width = ctx->env_width;
+    a.env_height = ctx->env_height;
+    std::memcpy(a.env_frame, ctx->env_frame, sizeof a.env_frame);
     if (ctx->oriented) {          // (rpt_set_orientation: E' = E diag(1, R) — a sky at rest in the scene stays at rest when the head turns)
         rpt_float4 e[4];
         std::memcpy(e, ctx->env_frame, sizeof e);
-        rebase_columns(e, ctx->R, ea.env_frame);
+        rebase_columns(e, ctx->R, a.env_frame);
     }
-    rptd::LensArgs la;            // (the lens kernels' arguments: the above + the scale of the image plane)
-    static_cast<rptd::EnvironmentArgs &>(la) = ea;
-    la.lens_scale = lens_scale;
-    const RefineRow *refine = nullptr;
-    bool refine_exact = false;
-    rptd::RefineArgs ra;
-    if (adaptive) {
-        if (!row || row->relaxed_waves) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: kernel " + std::to_string(v) + " has no refine pass");
-        const RefineCamera camera = panorama ? RefineCamera::equirect : (lens ? RefineCamera::lens : RefineCamera::pinhole);
-        const RefineColour colour = environment ? RefineColour::environment : (ctx->doppler ? RefineColour::doppler : RefineColour::plain);
-        RefineForm form = aa_base == VARIANT_UNCULLED || aa_base == 303 ? RefineForm::unculled : (aa_base == VARIANT_ANALYTIC || aa_base == 344 ? RefineForm::analytic : RefineForm::walk);
-        // under a lens the skirt's proof for the SAMPLE positions reaches 0.98 million pixels a side, not 2^20 (rpt_kernels.hip.h: refine_pixel_body)
-        if (lens && form != RefineForm::unculled && (ctx->width > (1 << 19) || ctx->height > (1 << 19))) form = RefineForm::unculled;
-        for (const RefineRow &r : refine_table)
-            if (r.camera == camera && r.colour == colour && r.form == form) refine = &r;
-        if (!refine) return fail(ctx, RPT_ERR_ARG, "rpt_set_adaptive_aa: no refine kernel for this camera");
-        if (panorama)
-            if (int rc = ensure_aa_tables(ctx)) return rc;
-        refine_exact = refine->ieee && ctx->geo->exact_rcp_ok;
+
+    const dim3 grid1(((ctx->width + 31) / 32) * 4, tiles);  // the product kernels: one wave (an 8 x 8 tile) per workgroup
+    if (!c.colour) {
+#ifdef RPT_DIAGNOSTICS
+        const dim3 grid((ctx->width + 31) / 32, tiles);     // the measurement arms: four waves (a 32 x 8 strip) per workgroup
+        if (int rc = launch_diagnostic(ctx, a, grid, tiles, c.variant)) return rc;
+#endif
+    } else if (!c.colour->kernel) {
+        if (rpt_launch_relaxed_kernel(relaxed_waves(c.colour->form), &a, sizeof(rptd::KernelArgs), grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
+    } else {
+        void *args[] = {(void *)&a};
+        (void)hipLaunchKernel(c.kernel(c.colour), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
+    }
+    RPT_HIP(ctx, hipGetLastError());
+    ctx->last_variant = c.variant;
+    ctx->last_exact_rcp = c.ran_exact(c.colour);
+    if (c.refine) {               // pass B, behind pass A on the same stream; then the counter's way home, in stream order
+        rptd::RefineArgs ra;
         std::memset(&ra, 0, sizeof ra);
-        static_cast<rptd::LensArgs &>(ra) = la;
+        static_cast<rptd::LensArgs &>(ra) = a;
         ra.plane = nullptr;           // (pass B writes the framebuffer and debug_rgb only: the plane is what its neighbours still read)
         ra.aa_plane = (const uint32_t *)ctx->aa_plane.ptr;
         ra.aa_refined = (unsigned long long *)ctx->aa_counter.ptr;
-        ra.aa_cols = panorama ? (const float2 *)ctx->aa_tables.ptr : nullptr;
-        ra.aa_rows = panorama ? (const float2 *)ctx->aa_tables.ptr + (size_t)ctx->aa_n * ctx->width : nullptr;
+        ra.aa_cols = panorama ? (const float2 *)ctx->aa_pano.upload.device.ptr : nullptr;
+        ra.aa_rows = panorama ? ra.aa_cols + (size_t)ctx->aa_n * ctx->width : nullptr;
         ra.aa_n = ctx->aa_n;
         ra.aa_threshold = ctx->aa_threshold;
-    }
-    if (!row) {
-#ifdef RPT_DIAGNOSTICS
-        if (int rc = launch_diagnostic(ctx, a, grid, tiles, v)) return rc;
-#else
-        return fail(ctx, RPT_ERR_ARG, "unknown kernel variant");
-#endif
-    } else if (row->relaxed_waves) {
-        if (rpt_launch_relaxed_kernel(row->relaxed_waves, &a, sizeof a, grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
-    } else {
-        void *args[] = {lens ? (void *)&la : (environment ? (void *)&ea : (panorama ? (void *)&pa : (ctx->doppler ? (void *)&da : (void *)&a)))};
-        (void)hipLaunchKernel(row->ieee && !ctx->geo->exact_rcp_ok ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
-    }
-    RPT_HIP(ctx, hipGetLastError());
-    ctx->last_variant = v;
-    ctx->last_exact_rcp = row && row->ieee && ctx->geo->exact_rcp_ok;
-    if (refine) {                 // pass B, behind pass A on the same stream; then the counter's way home, in stream order
         RPT_HIP(ctx, hipMemsetAsync(ctx->aa_counter.ptr, 0, 8, ctx->stream));
         void *args[] = {(void *)&ra};
-        (void)hipLaunchKernel(refine->ieee && !refine_exact ? refine->ieee : refine->kernel, grid1, dim3(64), args, 0, ctx->stream);
+        (void)hipLaunchKernel(c.kernel(c.refine), grid1, dim3(64), args, 0, ctx->stream);
         RPT_HIP(ctx, hipGetLastError());
         RPT_HIP(ctx, hipMemcpyAsync(ctx->aa_host, ctx->aa_counter.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
         RPT_HIP(ctx, hipEventRecord(ctx->aa_counted, ctx->stream));
         ctx->aa_pending = true;
-        ctx->last_aa_variant = refine->variant;
-    } else if (colour_frame) {    // a frame with the setting off refines nothing
+        ctx->last_aa_variant = c.refine->variant;
+    } else if (call.colour_frame) {    // a frame with the setting off refines nothing
         ctx->aa_pending = false;
         ctx->aa_refined = 0;
     }
@@ -1262,84 +1335,25 @@ void collect_aa_refined(rpt_ctx *ctx) {
     }
 }
 
-// ---- the event kernels (rpt_render_events): one row per kernel, chosen by camera and form --------------------------------------------
-// variant   what rpt_last_events_variant reports
-// camera    the context's: the pinhole, the panorama (rpt_set_projection) or the pinhole under a lens (rpt_set_field_of_view)
-// form      un-culled (rpt_set_variant(3); also what a frame outside the window the regions are proven for gets, the rule 3 and 803
-//           follow), the octree walk with the wave's object mask, or no walk compiled in (an Object[] without a mesh).  The panorama
-//           has no un-culled row: it has no object mask and the pass has no shadow rays, so its other two rows cull nothing
-// ieee      the walk's IEEE-division form, launched instead for scenes outside rcp_exact's domain (rpt_scene_exact_rcp), as for 41
-enum class EventCamera { pinhole, equirect, lens };
-enum class EventForm { unculled, walk, analytic };
-struct EventRow {
-    int variant;
-    EventCamera camera;
-    EventForm form;
-    const void *kernel;
-    const void *ieee;
-};
-#define RPT_KERNEL(name) reinterpret_cast<const void *>(&rptd::name)
-const EventRow events_table[] = {
-    {903, EventCamera::pinhole,  EventForm::unculled, RPT_KERNEL(rpt_events_kernel_unculled),      nullptr},
-    {941, EventCamera::pinhole,  EventForm::walk,     RPT_KERNEL(rpt_events_kernel_ballot),        RPT_KERNEL(rpt_events_kernel_ballot_ieee)},
-    {944, EventCamera::pinhole,  EventForm::analytic, RPT_KERNEL(rpt_events_kernel_analytic),      nullptr},
-    {911, EventCamera::equirect, EventForm::walk,     RPT_KERNEL(rpt_events_kernel_pano),          RPT_KERNEL(rpt_events_kernel_pano_ieee)},
-    {914, EventCamera::equirect, EventForm::analytic, RPT_KERNEL(rpt_events_kernel_pano_analytic), nullptr},
-    {923, EventCamera::lens,     EventForm::unculled, RPT_KERNEL(rpt_events_kernel_lens_unculled), nullptr},
-    {921, EventCamera::lens,     EventForm::walk,     RPT_KERNEL(rpt_events_kernel_lens_ballot),   RPT_KERNEL(rpt_events_kernel_lens_ballot_ieee)},
-    {924, EventCamera::lens,     EventForm::analytic, RPT_KERNEL(rpt_events_kernel_lens_analytic), nullptr},
-};
-#undef RPT_KERNEL
-
 // One event pass on the context's stream: the record of every pixel of this context's rows, written at y * width + x of the full-frame
 // record buffer.  The settings of Doppler, the sky and debug_rgb are not looked at (they act on colour only); neither the colour
 // framebuffer nor anything rpt_last_variant / rpt_last_frame_ms report is touched.
 int launch_events(rpt_ctx *ctx) {
-    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render_events before rpt_upload_scene");
-    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render_events before rpt_set_params");
-    if (ctx->msaa > 1) return fail(ctx, RPT_ERR_ARG, "rpt_render_events: MSAA > 1 has no event kernel (one primary ray per pixel)");
-    const int sv = ctx->variant;
-    if (sv != VARIANT_DEFAULT && sv != VARIANT_UNCULLED && sv != VARIANT_BALLOT && sv != VARIANT_BALLOT_FIRST && sv != VARIANT_ANALYTIC)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_events: variant " + std::to_string(sv) + " has no event kernel (variants 0, 3, 41, 43 and 44 have)");
-    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
-    const bool lens = ctx->v_fov != 0.0f;
-    if (lens && panorama) return fail(ctx, RPT_ERR_ARG, "rpt_render_events: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
-
-    rptd::KernelArgs a;
-    fill_kernel_args(ctx, a);
-    a.out16 = nullptr;          // (the pass writes records only)
-    a.plane = nullptr;
-    a.debug_rgb = nullptr;
-    const float lens_scale = lens ? ctx->lens_scale : 1.0f;
-    const EventCamera camera = panorama ? EventCamera::equirect : (lens ? EventCamera::lens : EventCamera::pinhole);
-    EventForm form = !ctx->has_mesh ? EventForm::analytic : EventForm::walk;
-    if (camera != EventCamera::equirect) {
-        // the window the regions are proven for: launch()'s rule, word for word (frames wider than 4 : 1, sides beyond 2^20, a lens with s > 1)
-        const bool window_holds_frame = (lens ? lens_scale <= 1.0f && lens_scale * (0.5f * a.aspect) <= (float)rptb::cert::WINDOW_U : 0.5f * a.aspect <= (float)rptb::cert::WINDOW_U) &&
-                                        ctx->width <= (1 << 20) && ctx->height <= (1 << 20);
-        if (sv == VARIANT_UNCULLED || !window_holds_frame) form = EventForm::unculled;
-    }
-    if (!ctx->geo->compact_ok && form != EventForm::analytic)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_events: the event kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
-    const EventRow *row = nullptr;
-    for (const EventRow &r : events_table)
-        if (r.camera == camera && r.form == form) row = &r;
-    if (!row) return fail(ctx, RPT_ERR_ARG, "rpt_render_events: no event kernel for this camera");
-
+    const Choice c = choose_kernels(ctx, Call{CallKind::events, false});
+    if (c.code != RPT_OK) return fail(ctx, c.code, c.text);
     const size_t px = (size_t)ctx->width * ctx->height;
     if (!ctx->external_events && (px * sizeof(rpt_event) > ctx->owned_events.capacity || ctx->owned_events.bytes != px * sizeof(rpt_event))) {
         if (int rc = reserve(ctx, ctx->owned_events, px * sizeof(rpt_event))) return rc;
         RPT_HIP(ctx, hipMemsetAsync(ctx->owned_events.ptr, 0, px * sizeof(rpt_event), ctx->stream));
     }
+    if (ctx->projection != RPT_PROJECTION_PINHOLE)
+        if (int rc = ensure_projection_tables(ctx, ctx->pano, 1)) return rc;
     rptd::EventArgs ea;
     std::memset(&ea, 0, sizeof ea);
-    static_cast<rptd::KernelArgs &>(ea) = a;
-    if (panorama) {
-        if (int rc = ensure_panorama_tables(ctx)) return rc;
-        ea.pano_cols = (const float2 *)ctx->pano_tables.ptr;
-        ea.pano_rows = (const float2 *)ctx->pano_tables.ptr + ctx->width;
-    }
-    ea.lens_scale = lens_scale;
+    fill_frame_args(ctx, ea);
+    ea.out16 = nullptr;         // (the pass writes records only)
+    ea.plane = nullptr;
+    ea.debug_rgb = nullptr;
     ea.events = (rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
     ctx->events_ptr = ea.events;
     ctx->events_width = ctx->width;
@@ -1347,14 +1361,13 @@ int launch_events(rpt_ctx *ctx) {
     ctx->events_first_tile = ctx->first_tile;
     ctx->events_tile_step = ctx->tile_step;
     ctx->events_run_log2 = ctx->run_log2;
-    ctx->last_events_variant = row->variant;
-    const bool exact_rcp = row->ieee && ctx->geo->exact_rcp_ok;      // launch()'s rule: the row's own kernel on a scene inside rcp_exact's domain
-    ctx->last_events_exact_rcp = exact_rcp;
+    ctx->last_events_variant = c.variant;
+    ctx->last_events_exact_rcp = c.ran_exact(c.colour);
     const int tiles = local_tile_count(ctx);
     if (tiles == 0) return RPT_OK;
     const dim3 grid1(((ctx->width + 31) / 32) * 4, tiles);      // one wave (an 8 x 8 tile) per workgroup, as the product kernels
     void *args[] = {(void *)&ea};
-    (void)hipLaunchKernel(row->ieee && !exact_rcp ? row->ieee : row->kernel, grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
+    (void)hipLaunchKernel(c.kernel(c.colour), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     RPT_HIP(ctx, hipGetLastError());
     return RPT_OK;
 }
@@ -1423,17 +1436,12 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->pano_tables, &ctx->env_texels, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->aa_tables})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    if (ctx->pano_host) (void)hipHostFree(ctx->pano_host);
-    if (ctx->pano_copied) (void)hipEventDestroy(ctx->pano_copied);
-    if (ctx->env_host) (void)hipHostFree(ctx->env_host);
-    if (ctx->env_copied) (void)hipEventDestroy(ctx->env_copied);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env}) release(*u);
     if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
     if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
-    if (ctx->aa_tables_host) (void)hipHostFree(ctx->aa_tables_host);
-    if (ctx->aa_tables_copied) (void)hipEventDestroy(ctx->aa_tables_copied);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -1690,7 +1698,6 @@ int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params) {
         return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: mode is RPT_PROJECTION_PINHOLE or RPT_PROJECTION_EQUIRECT");
     }
     ctx->projection = mode;
-    if (std::memcmp(p, ctx->projection_params, sizeof p) != 0) ctx->pano_valid = false;
     std::memcpy(ctx->projection_params, p, sizeof p);
     return RPT_OK;
 }
@@ -1717,21 +1724,11 @@ int rpt_set_environment(rpt_ctx *ctx, const unsigned char *rgb8, int width, int 
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t texels = (size_t)width * (size_t)height, bytes = texels * sizeof(uint32_t);
     ctx->env_on = false;         // (until the new image is in place)
-    if (!ctx->env_copied) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->env_copied, hipEventDisableTiming));
-    else RPT_HIP(ctx, hipEventSynchronize(ctx->env_copied));
-    if (bytes > ctx->env_host_capacity) {
-        if (ctx->env_host) RPT_HIP(ctx, hipHostFree(ctx->env_host));
-        ctx->env_host = nullptr;
-        ctx->env_host_capacity = 0;
-        RPT_HIP(ctx, hipHostMalloc((void **)&ctx->env_host, bytes, hipHostMallocDefault));
-        ctx->env_host_capacity = bytes;
-    }
-    if (bytes > ctx->env_texels.capacity) RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the old buffer may still be read)
-    if (int rc = reserve(ctx, ctx->env_texels, bytes)) return rc;
+    uint32_t *host = nullptr;
+    if (int rc = staged_host(ctx, ctx->env, bytes, (void **)&host)) return rc;
     for (size_t i = 0; i < texels; i++)
-        ctx->env_host[i] = (uint32_t)rgb8[3 * i] | ((uint32_t)rgb8[3 * i + 1] << 8) | ((uint32_t)rgb8[3 * i + 2] << 16);
-    RPT_HIP(ctx, hipMemcpyAsync(ctx->env_texels.ptr, ctx->env_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RPT_HIP(ctx, hipEventRecord(ctx->env_copied, ctx->stream));
+        host[i] = (uint32_t)rgb8[3 * i] | ((uint32_t)rgb8[3 * i + 1] << 8) | ((uint32_t)rgb8[3 * i + 2] << 16);
+    if (int rc = staged_copy(ctx, ctx->env)) return rc;
     ctx->env_width = width;
     ctx->env_height = height;
     ctx->env_on = true;
@@ -1862,8 +1859,7 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
 int rpt_set_variant(rpt_ctx *ctx, int variant) {
     if (!ctx) return RPT_ERR_ARG;
 #ifndef RPT_DIAGNOSTICS     /* the diagnostics library knows many more (rpt_diag_kernels.hip.h); an unknown number fails at the launch */
-    const VariantRow *row = variant_row(variant);
-    if (variant != VARIANT_DEFAULT && !(row && row->settable))
+    if (variant != 0 && settable_form(variant) == Form::diagnostic)
         return fail(ctx, RPT_ERR_ARG, "rpt_set_variant: unknown variant (measurement arms and instrumented kernels exist in librpt_hip_diag.so only)");
 #endif
     ctx->variant = variant;
@@ -1925,12 +1921,12 @@ int rpt_verify_frame(rpt_ctx *ctx, unsigned long long *differing_pixels) {
     ctx->want_owned_doppler = false;
     int rc = RPT_OK;
     ctx->external_plane = plane_a;
-    rc = launch(ctx);
+    rc = launch(ctx, Call{CallKind::in_flight, false});
     const int verified_variant = ctx->last_variant;      // what rpt_last_variant reports afterwards: the kernel that was CHECKED, not the un-culled one
     if (rc == RPT_OK) {
         ctx->external_plane = plane_b;
-        ctx->variant = VARIANT_UNCULLED;
-        rc = launch(ctx);
+        ctx->variant = 3;
+        rc = launch(ctx, Call{CallKind::in_flight, false});
     }
     ctx->last_variant = verified_variant;
     ctx->external_plane = saved.plane; ctx->external_rgb = saved.rgb; ctx->colour_plane = saved.colour_plane; ctx->want_owned_rgb = saved.want_rgb; ctx->variant = saved.variant;
@@ -1946,7 +1942,8 @@ int rpt_verify_frame(rpt_ctx *ctx, unsigned long long *differing_pixels) {
     return RPT_OK;
 }
 
-int rpt_render_async(rpt_ctx *ctx) {
+// One colour frame between its two events: rpt_render_async, and rpt_render before it waits
+static int render_frame(rpt_ctx *ctx, CallKind kind) {
     if (!ctx) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     hipEvent_t eb = ctx->ev_begin, ee = ctx->ev_end;
@@ -1956,7 +1953,7 @@ int rpt_render_async(rpt_ctx *ctx) {
         ee = ctx->timing_events[2 * ctx->timing_frames + 1];
     }
     RPT_HIP(ctx, hipEventRecord(eb, ctx->stream));
-    if (int rc = launch(ctx, true)) return rc;
+    if (int rc = launch(ctx, Call{kind, true})) return rc;
     RPT_HIP(ctx, hipEventRecord(ee, ctx->stream));
     ctx->last_event = ee;
     if (timed) ctx->timing_frames++;
@@ -1964,6 +1961,8 @@ int rpt_render_async(rpt_ctx *ctx) {
     ctx->frame_rendered = true;
     return RPT_OK;
 }
+
+int rpt_render_async(rpt_ctx *ctx) { return render_frame(ctx, CallKind::in_flight); }
 
 int rpt_timing_begin(rpt_ctx *ctx, int max_frames) {
     if (!ctx || max_frames <= 0 || max_frames > (1 << 20)) return RPT_ERR_ARG;
@@ -2061,11 +2060,7 @@ int rpt_last_aa_refined(rpt_ctx *ctx, unsigned long long *pixels) {
 int rpt_last_aa_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_aa_variant : RPT_ERR_ARG; }
 
 int rpt_render(rpt_ctx *ctx) {
-    if (!ctx) return RPT_ERR_ARG;
-    ctx->latency_call = true;
-    const int rc = rpt_render_async(ctx);
-    ctx->latency_call = false;
-    if (rc) return rc;
+    if (int rc = render_frame(ctx, CallKind::blocking)) return rc;
     return rpt_sync(ctx);
 }
 
@@ -2169,12 +2164,12 @@ int rpt_timed_frames(rpt_ctx *ctx, int frames, float *avg_ms) {
     if (!ctx || frames <= 0 || !avg_ms) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     for (int w = 0; w < 2; w++) {          // untimed: allocate outputs, warm caches, measure the row costs
-        if (int rc = launch(ctx)) return rc;
+        if (int rc = launch(ctx, Call{CallKind::in_flight, false})) return rc;
         RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     RPT_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
     for (int i = 0; i < frames; i++)
-        if (int rc = launch(ctx)) return rc;
+        if (int rc = launch(ctx, Call{CallKind::in_flight, false})) return rc;
     RPT_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
     RPT_HIP(ctx, hipEventSynchronize(ctx->ev_end));
     float ms = 0;
@@ -2284,7 +2279,7 @@ int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int 
     if (hipMemcpy(d_in, host_in, sizeof(float) * in_w[which] * n, hipMemcpyHostToDevice) != hipSuccess) rc = RPT_ERR_DEVICE;
     if (!rc) {
         if (which == 6) hipLaunchKernelGGL(rptd::rpt_probe_doppler_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_in, d_out, n);
-        else if (which == 7) hipLaunchKernelGGL(rptd::rpt_probe_environment_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->env_texels.ptr, ctx->env_width, ctx->env_height, d_in, d_out, n);
+        else if (which == 7) hipLaunchKernelGGL(rptd::rpt_probe_environment_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->env.device.ptr, ctx->env_width, ctx->env_height, d_in, d_out, n);
         else hipLaunchKernelGGL(rptd::rpt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, which, d_in, d_out, n);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
             hipMemcpy(host_out, d_out, sizeof(float) * out_w[which] * n, hipMemcpyDeviceToHost) != hipSuccess)

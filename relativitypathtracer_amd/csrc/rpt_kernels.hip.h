@@ -168,6 +168,18 @@ struct LensArgs : EnvironmentArgs {
     float lens_scale;               // s = (float)tan(v_fov / 2): pixel (x, y) looks through (s fx2, s fy2, 0.5); 1.0f is the reference's lens
 };
 
+// One LensArgs on the host serves every render kernel (rpt_api.hip: launch): each block is a PREFIX of the next — single inheritance,
+// the base at offset 0, the new fields behind it — and a kernel's launch copies its own kernarg size from the block's address.
+// (RefineArgs and EventArgs below extend LensArgs in the same way.)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(__builtin_offsetof(LensArgs, rects) == 0 && __builtin_offsetof(LensArgs, counters) + sizeof(void *) == sizeof(KernelArgs), "KernelArgs first");
+static_assert(__builtin_offsetof(LensArgs, doppler) >= sizeof(KernelArgs) && __builtin_offsetof(LensArgs, debug_doppler) + sizeof(void *) == sizeof(DopplerArgs), "then DopplerArgs' fields");
+static_assert(__builtin_offsetof(LensArgs, pano_cols) >= sizeof(DopplerArgs) && __builtin_offsetof(LensArgs, pano_rows) + sizeof(void *) == sizeof(PanoramaArgs), "then PanoramaArgs' fields");
+static_assert(__builtin_offsetof(LensArgs, env_texels) >= sizeof(PanoramaArgs) && __builtin_offsetof(LensArgs, env_frame) + sizeof(rpt_float4[4]) == sizeof(EnvironmentArgs), "then EnvironmentArgs' fields");
+static_assert(__builtin_offsetof(LensArgs, lens_scale) >= sizeof(EnvironmentArgs), "then LensArgs' own");
+#pragma clang diagnostic pop
+
 struct Hit {                 // opencl_kernel.cl:38-44
     float dist;
     f3 normal;
@@ -631,7 +643,7 @@ namespace rptd {
 
 // ---- what a render kernel is: its policy, a type of static constexpr members that render_pixel_body and everything it calls read.
 // KernelPolicy holds the defaults (kernel 48); each product kernel below derives its own; the diagnostics build adds DiagPolicy<N>
-// (rpt_diag_kernels.hip.h).  rpt_api.hip's table of variants reads band_first from the same types.
+// (rpt_diag_kernels.hip.h).  rpt_api.hip's tables name one kernel per (camera, colour, form) and pin band_first(Form) against these types.
 enum class Walk {
     reference,       // octree_core_ref on the reference's layouts (any valid octree)
     none,            // no octree walk compiled in: for Object[]s without a mesh
