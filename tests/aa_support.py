@@ -65,7 +65,7 @@ def pano_sample_dirs(W, H, n, **kw):
 
 def oracle_supersampled(lib, scene, W, H, n, dirs, objects=None, env=None, flags=0):
     """The family's CPU reference with the sample loop: (pixels, rgb, hits) with hits[H W] = the pixel's samples that hit an object.
-    env: (E 4 x 4, image) or None."""
+    env: (E 4 x 4, image) or None; flags: the Doppler flags, for the rays that hit (tests/native/doppler_oracle.c) and for the sky."""
     d, prm = scene.desc(), scene.params
     a = oracle_ffi.OracleArgs()
     if objects is not None:
@@ -84,7 +84,7 @@ def oracle_supersampled(lib, scene, W, H, n, dirs, objects=None, env=None, flags
     a.out_pixels, a.out_rgb = px.ctypes.data, rgb.ctypes.data
     assert dirs.shape == (W * H * n * n, 3) and dirs.dtype == np.float32
     if env is None:
-        rc = lib.rpt_aa_oracle_render(C.byref(a), dirs.ctypes.data, n, None, None, 0, 0, 0, hits.ctypes.data, THREADS)
+        rc = lib.rpt_aa_oracle_render(C.byref(a), dirs.ctypes.data, n, None, None, 0, 0, int(flags), hits.ctypes.data, THREADS)
     else:
         E, img = np.ascontiguousarray(env[0], dtype=np.float32), np.ascontiguousarray(env[1])
         rc = lib.rpt_aa_oracle_render(C.byref(a), dirs.ctypes.data, n, E.ctypes.data, img.ctypes.data, img.shape[1], img.shape[0], int(flags),

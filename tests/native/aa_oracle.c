@@ -6,8 +6,8 @@
  * rpt_aa_oracle_render: pixel id = y * width + x has n * n samples; sample s = sy * n + sx looks along
  * dirs[3 (id n n + s) .. + 2] (unnormalised: the pinhole's or the lens's plane point at (x + sx / n, y + sy / n), or the panorama's p
  * of pixel (n x + sx, n y + sy) at n times the size — built by the test from the library's own tables).  Each sample's colour is the
- * oracle's trace (a miss is its background) or, with a sky image (rgb8 != NULL), the sky of the sample's own direction where the ray
- * hits nothing; the colours are summed in sample order, one float addition after another, divided by n * n, then tonemapped,
+ * oracle's trace (a miss is its background; with doppler != 0 doppler_oracle.c's trace_doppler, sky image or none) or, with a sky image
+ * (rgb8 != NULL), the sky of the sample's own direction where the ray hits nothing; the colours are summed in sample order, one float addition after another, divided by n * n, then tonemapped,
  * clamped and packed exactly as render_pixel does.  hits_out[id] (if not NULL) = how many of the pixel's samples hit an object.
  */
 #include "environment_oracle.c"
@@ -39,8 +39,10 @@ static void aa_pixel(const AaJob *job, unsigned int id) {
         Hit probe;
         const int hit = intersect_scene(job->scene, &camray, &probe);
         hits += hit ? 1 : 0;
-        const f3 c = hit || !job->use_env ? trace(job->scene, a->ambient, &camray)
-                                          : env_sky(&job->env, job->E, a->interval, job->doppler, camray.dir);
+        f3 c;
+        if (!hit && job->use_env) c = env_sky(&job->env, job->E, a->interval, job->doppler, camray.dir);
+        else if (job->doppler != 0) trace_doppler(job->scene, a->ambient, &camray, job->doppler, NULL, &c);
+        else c = trace(job->scene, a->ambient, &camray);
         finalcolor = add3(finalcolor, c);
     }
     if (job->hits_out) job->hits_out[id] = (uint8_t)hits;

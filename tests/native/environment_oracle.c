@@ -4,11 +4,12 @@
  *
  * rpt_environment_oracle_lookup: n directions {d.x, d.y, d.z} (normalised here) -> {u, v, r, g, b}: what rpt_probe which = 7 returns.
  * rpt_environment_oracle_render: pixel id = y * width + x looks along dirs[3 id .. 3 id + 2] (unnormalised: the pinhole's plane point or
- * the panorama's p); a ray that hits something is the oracle's trace (the reference: NO Doppler), one that hits nothing takes the sky
- * path with Doppler flags `doppler`; then the tonemap, the clamp and the pack of render_pixel.  hit_out[id] = 1 where the ray hit.
- * S_f is restated from DESIGN.md "Doppler and beaming" (the arithmetic order listed there), not from device code.
+ * the panorama's p); a ray that hits something is the oracle's trace, or with doppler != 0 doppler_oracle.c's trace_doppler (the trace
+ * with the light and camera factors); one that hits nothing takes the sky path with Doppler flags `doppler`; then the tonemap, the clamp
+ * and the pack of render_pixel.  hit_out[id] = 1 where the ray hit.
+ * S_f (doppler_colour.h) is restated from DESIGN.md "Doppler and beaming" (the arithmetic order listed there), not from device code.
  */
-#include "../../oracle/rpt_oracle.c"
+#include "doppler_oracle.c"
 
 #define ENV_PI_D 3.14159265358979323846264338327950288
 
@@ -48,32 +49,6 @@ static f3 env_bilinear(const EnvImage *e, f2 uv) {
     result2 = add3(result2, muls3(env_texel(e, x, y), u_opp));
     result2 = muls3(result2, v_ratio);
     return add3(result, result2);
-}
-
-/* DESIGN.md "Doppler and beaming": the emitted spectrum through (K0, 0), (nu_R, r), (1, g), (nu_B, b), (K4, 0) */
-static float env_spectrum(float u, f3 c) {
-    const float nu_r = (float)(546.1 / 700.0), nu_b = (float)(546.1 / 435.8);
-    const float k0 = (float)(2.0 * (546.1 / 700.0) - 1.0), k4 = (float)(2.0 * (546.1 / 435.8) - 1.0);
-    if (!(u > k0) || !(u < k4)) return 0.0f;
-    float xa, xb, ya, yb;
-    if (u < nu_r) { xa = k0; xb = nu_r; ya = 0.0f; yb = c.x; }
-    else if (u < 1.0f) { xa = nu_r; xb = 1.0f; ya = c.x; yb = c.y; }
-    else if (u < nu_b) { xa = 1.0f; xb = nu_b; ya = c.y; yb = c.z; }
-    else { xa = nu_b; xb = k4; ya = c.z; yb = 0.0f; }
-    const float t = (u - xa) / (xb - xa);
-    return ya * (1.0f - t) + yb * t;
-}
-
-static f3 env_doppler(int flags, float D, f3 c) {
-    const float nu_r = (float)(546.1 / 700.0), nu_b = (float)(546.1 / 435.8);
-    if (D == 1.0f) return c;
-    if (flags & 1) {
-        f3 o = F3(env_spectrum(nu_r / D, c), env_spectrum(1.0f / D, c), env_spectrum(nu_b / D, c));
-        if (flags & 2) o = muls3(o, (D * D) * D);
-        return o;
-    }
-    if (flags & 2) return muls3(c, (D * D) * (D * D));
-    return c;
 }
 
 static f3 env_sky(const EnvImage *e, const rpt_float4 E[4], int interval, int doppler, f3 dir) {
@@ -117,7 +92,10 @@ static void env_pixel(const EnvJob *job, unsigned int id) {
     camray.dir = normalize3(F3(job->dirs[3 * (size_t)id], job->dirs[3 * (size_t)id + 1], job->dirs[3 * (size_t)id + 2]));
     Hit probe;
     const int hit = intersect_scene(job->scene, &camray, &probe);
-    f3 finalcolor = hit ? trace(job->scene, a->ambient, &camray) : env_sky(&job->env, job->E, a->interval, job->doppler, camray.dir);
+    f3 finalcolor;
+    if (!hit) finalcolor = env_sky(&job->env, job->E, a->interval, job->doppler, camray.dir);
+    else if (job->doppler != 0) trace_doppler(job->scene, a->ambient, &camray, job->doppler, NULL, &finalcolor);
+    else finalcolor = trace(job->scene, a->ambient, &camray);
     if (job->hit_out) job->hit_out[id] = (uint8_t)hit;
     finalcolor = div3(hable(finalcolor), hable(wp));
     finalcolor = F3(cl_min(finalcolor.x, 1.0f), cl_min(finalcolor.y, 1.0f), cl_min(finalcolor.z, 1.0f));
