@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] [--overlay SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -16,12 +16,19 @@
 // --events FILE also renders one event pass of the view the PPM shows (rpt_render_events; not in the reference) and writes its raw
 // records: width * height * 32 B (rpt_event, rpt_layout.h), row 0 the bottom row as everywhere.  Without the flag nothing changes.
 //
+// --overlay outlines,clock:STEP,delay:STEP,lattice:SX:SY:SZ,tint[:TMAX] draws lines on the picture before it is written (rpt_set_overlay,
+// rpt_render_overlay; not in the reference): any subset of the five layers, in any order — object outlines, contours of the hit object's
+// own clock, of the look-back time and of its rest-frame coordinates (a step of 0 skips that axis), and a tint by light delay (TMAX
+// omitted: the frame's largest).  The host runs the three passes — the colour frame, an event frame of the same view, the overlay — and
+// reports the pixels the overlay changed on stderr.  Without the flag nothing changes.
+//
 // With `frames` > 1 the clock runs (16 ms per frame, as the reference's timer does) and the frames are rendered with
 // `in_flight` of them overlapping on the GPU: rpt::FrameRing (include/rpt_frames.hpp) — one context per frame slot
 // sharing one resident scene (rpt_share_scene), frame f in slot f mod in_flight.  The PPM is the last frame.
 //
 // Textures are read with the library's built-in binary PPM reader (convert the JPEGs first, e.g. with
 // Pillow) — decoding JPEG is the job of CImg/libjpeg in the reference and is outside the render path.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -37,12 +44,66 @@
 #include "rpt_frames.hpp"
 #include "rpt_scene.h"
 
+// --overlay's value into a description with the layers' default colours; false (and a message on stderr) if it cannot be read
+static bool parse_overlay(const char *spec, rpt_overlay_desc *d) {
+    std::memset(d, 0, sizeof *d);
+    const unsigned char white[4] = {255, 255, 255, 255}, yellow[4] = {255, 255, 0, 255}, cyan[4] = {0, 255, 255, 255}, magenta[4] = {255, 0, 255, 255};
+    std::memcpy(d->outline_rgba, white, 4);
+    std::memcpy(d->delay_rgba, yellow, 4);
+    std::memcpy(d->clock_rgba, cyan, 4);
+    std::memcpy(d->lattice_rgba, magenta, 4);
+    d->tint_alpha = 128;
+    const std::string all(spec);
+    size_t pos = 0;
+    while (pos <= all.size()) {
+        const size_t comma = std::min(all.find(',', pos), all.size());
+        const std::string item = all.substr(pos, comma - pos);
+        pos = comma + 1;
+        std::vector<std::string> part;
+        for (size_t q = 0; q <= item.size();) {
+            const size_t colon = std::min(item.find(':', q), item.size());
+            part.push_back(item.substr(q, colon - q));
+            q = colon + 1;
+        }
+        std::vector<float> value;
+        for (size_t k = 1; k < part.size(); k++) {
+            char *end = nullptr;
+            const float v = std::strtof(part[k].c_str(), &end);
+            if (part[k].empty() || *end != '\0' || !std::isfinite(v)) {
+                std::fprintf(stderr, "--overlay: '%s' in '%s' is not a number\n", part[k].c_str(), item.c_str());
+                return false;
+            }
+            value.push_back(v);
+        }
+        const std::string &name = part[0];
+        const size_t want = name == "outlines" ? 0 : name == "clock" || name == "delay" ? 1 : name == "lattice" ? 3 : name == "tint" ? value.size() <= 1 ? value.size() : 1 : ~(size_t)0;
+        if (want == ~(size_t)0) {
+            std::fprintf(stderr, "--overlay: unknown layer '%s' (outlines, clock:STEP, delay:STEP, lattice:SX:SY:SZ, tint[:TMAX])\n", name.c_str());
+            return false;
+        }
+        if (value.size() != want) {
+            std::fprintf(stderr, "--overlay: '%s' takes %s\n", name.c_str(), name == "outlines" ? "no value" : name == "lattice" ? "three steps, lattice:SX:SY:SZ" : name == "tint" ? "at most one value, tint[:TMAX]" : "one step");
+            return false;
+        }
+        if (name == "outlines") d->layers |= RPT_OVERLAY_OUTLINES;
+        else if (name == "clock") { d->layers |= RPT_OVERLAY_ISO_CLOCK; d->clock_step = value[0]; }
+        else if (name == "delay") { d->layers |= RPT_OVERLAY_ISO_DELAY; d->delay_step = value[0]; }
+        else if (name == "lattice") { d->layers |= RPT_OVERLAY_LATTICE; for (int k = 0; k < 3; k++) d->lattice_step[k] = value[k]; }
+        else { d->layers |= RPT_OVERLAY_DELAY_TINT; d->tint_t_max = value.empty() ? 0.0f : value[0]; }
+    }
+    std::fprintf(stderr, "overlay: layers %u, clock step %g, delay step %g, lattice steps %g %g %g, tint range %g\n", d->layers, d->clock_step, d->delay_step,
+                 d->lattice_step[0], d->lattice_step[1], d->lattice_step[2], d->tint_t_max);
+    return true;
+}
+
 int main(int argc, char **argv) {
     // the free-look options (degrees), taken out of argv; what is left is positional
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
     const char *events_path = nullptr;
     int aa_n = 1, aa_threshold = 8;
+    rpt_overlay_desc overlay;
+    std::memset(&overlay, 0, sizeof overlay);
     {
         const double deg = 3.14159265358979323846 / 180.0;
         int kept = 1;
@@ -53,6 +114,12 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--roll")) { ypr[2] = (float)(std::atof(argv[++i]) * deg); turned = true; }
             else if (has_value && !std::strcmp(argv[i], "--fov")) v_fov = (float)(std::atof(argv[++i]) * deg);
             else if (has_value && !std::strcmp(argv[i], "--events")) events_path = argv[++i];
+            else if (has_value && !std::strcmp(argv[i], "--overlay")) {
+                if (!parse_overlay(argv[++i], &overlay)) return 2;
+            } else if (!std::strcmp(argv[i], "--overlay")) {
+                std::fprintf(stderr, "--overlay needs a value: outlines,clock:STEP,delay:STEP,lattice:SX:SY:SZ,tint[:TMAX]\n");
+                return 2;
+            }
             else if (has_value && !std::strcmp(argv[i], "--aa")) {
                 char *end = nullptr;
                 aa_n = (int)std::strtol(argv[++i], &end, 10);
@@ -76,7 +143,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] [--overlay SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -166,6 +233,20 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "%d frames, %d in flight: %.4f ms/frame, %.0f Mrays/s (%d presented while rendering)\n", frames,
                      ring.frames_in_flight(), sec / frames * 1e3, (double)width * height * frames / sec / 1e6, presented);
     }
+    bool events_rendered = false;
+    if (overlay.layers) {                                        // lines on that frame, from an event frame of the same view
+        unsigned long long changed = 0;
+        rc = rpt_render_events(last);
+        events_rendered = !rc;
+        if (!rc) rc = rpt_set_overlay(last, &overlay);
+        if (!rc) rc = rpt_render_overlay(last);
+        if (!rc) rc = rpt_last_overlay_pixels(last, &changed);
+        if (rc) {
+            std::fprintf(stderr, "overlay: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::fprintf(stderr, "overlay: %llu of %lld pixels changed\n", changed, (long long)width * height);
+    }
     std::vector<unsigned char> fb((size_t)width * height * 16);
     rpt_read_framebuffer(last, fb.data(), fb.size());
     rc = rpt_write_ppm(argv[3], fb.data(), width, height);       // drawGL()                gl_interop.cpp:51
@@ -177,7 +258,7 @@ int main(int argc, char **argv) {
     }
     if (!rc && events_path) {                                    // what each pixel of that frame shows, where and when
         std::vector<rpt_event> records((size_t)width * height);
-        rc = rpt_render_events(last);
+        if (!events_rendered) rc = rpt_render_events(last);      // (--overlay has rendered that very frame already)
         if (!rc) rc = rpt_read_events(last, records.data(), records.size() * sizeof(rpt_event));
         if (rc) {
             std::fprintf(stderr, "events: %s\n", rpt_last_error(last));

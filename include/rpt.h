@@ -36,7 +36,9 @@
  * the reference computes and discards: rpt_set_events_output, rpt_render_events / rpt_render_events_async, rpt_read_events, rpt_pick,
  * rpt_last_events_variant and rpt_last_events_exact_rcp ("Event pass"), and opt-in adaptive anti-aliasing in every camera and
  * colour mode (the reference's MSAASAMPLES is a compile-time constant, 1 as shipped): rpt_set_adaptive_aa, rpt_last_aa_refined and
- * rpt_last_aa_variant ("Adaptive anti-aliasing").
+ * rpt_last_aa_variant ("Adaptive anti-aliasing"), and the opt-in overlay pass — outlines, isochrones, rest-frame grids and a tint
+ * by light delay drawn on the rendered frame from the event records: rpt_set_overlay, rpt_render_overlay / rpt_render_overlay_async and
+ * rpt_last_overlay_pixels ("Overlay pass").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -395,6 +397,58 @@ int rpt_last_aa_refined(rpt_ctx *ctx, unsigned long long *pixels);
 /* The refine kernel (a number of the table above) of this context's last colour frame; 0 if that frame had no pass B (or before the
  * first).  rpt_last_variant keeps reporting pass A's kernel. */
 int rpt_last_aa_variant(const rpt_ctx *ctx);
+
+/* The overlay pass (not in the reference; DESIGN.md "Overlay pass"): lines drawn ON the rendered frame from the event records — object
+ * outlines, contours of the look-back time, of the hit object's own clock and of its rest-frame coordinates, and a tint by light delay.
+ * Opt-in, per context, not shared by rpt_share_scene; with layers == 0 or the pass never called nothing changes.  The pass is enqueued
+ * on the context's stream after a colour frame and an event frame of the same view and blends into the R, G, B bytes of the 16-B
+ * framebuffer pixels in place (alpha, bytes 0-7 and 12-15, the debug planes and the record buffer are not written).  Every rule is
+ * float32 and integer arithmetic without fused operations; relativitypathtracer_amd/events.py `overlay` restates them in numpy.
+ *
+ *   contour layers  scalar s per pixel — ISO_DELAY |(float)interval * dist|, ISO_CLOCK event[0], LATTICE event[1], event[2], event[3] per
+ *                   axis with a non-zero step, ORed — and inv = 1.0f / step, computed once on the host.  cell(p) = floorf(s(p) * inv).  A HIT
+ *                   pixel p is on a line iff some neighbour q of (x + 1, y), (x, y + 1) lies inside the frame, has the same object as p
+ *                   and cell(q) != cell(p).  A pixel whose product s * inv is not finite or is >= 2^30 in magnitude is never on a line and
+ *                   never makes its neighbour one.
+ *   OUTLINES        a pixel (hit or miss) is on an outline iff some q of the same two neighbours inside the frame has a different object.
+ *   DELAY_TINT      hit pixels only: d = |(float)interval * dist| (0 if not finite), x = clamp(d / t_max, 0, 1) (0 if t_max is 0), the ramp
+ *                   r = clamp(1 - 2x, 0, 1), g = 1 - |2x - 1|, b = clamp(2x - 1, 0, 1), each lifted to 0.25f + 0.75f * c, times 255.0f,
+ *                   rounded to nearest even, blended with tint_alpha.  tint_t_max == 0: t_max is the frame's largest d over hit pixels,
+ *                   found by a reduction kernel on the same stream (a maximum is exact in any order).
+ *   order           the tint, then LATTICE, ISO_CLOCK, ISO_DELAY, OUTLINES; each blends out = (c * a + old * (255 - a) + 127) / 255 per
+ *                   R, G, B channel in integers, a = the layer's fourth colour byte (tint_alpha for the tint).
+ *
+ * rpt_set_overlay copies the description (NULL = off) and returns RPT_ERR_ARG for unknown layer bits, a step that is <= 0 or not finite for
+ * a layer that is on (a lattice axis may be 0 = skipped; all three 0 is refused), and a tint_t_max that is negative or not finite.
+ * rpt_render_overlay[_async]: RPT_ERR_STATE unless the context has enqueued (or finished) a colour frame and an event frame of the current
+ * width x height, both after the last rpt_set_objects, rpt_set_params, rpt_set_projection, rpt_set_orientation or rpt_set_field_of_view;
+ * RPT_ERR_ARG, with a message that starts "rpt_render_overlay:", for a context restricted by rpt_set_rows / rpt_set_tile_pattern or
+ * rendering a colour plane (a tile's upper neighbour row belongs to another rank).  The context stays usable after either.  The buffers
+ * read and written are those of rpt_set_output / rpt_set_events_output (caller-owned or the library's) that the two frames were rendered
+ * into; naming another buffer after the frames is RPT_ERR_STATE too (it holds no frame).  With layers == 0 the call checks nothing, launches nothing
+ * and succeeds.  Calling the pass twice on one frame blends twice: render the colour frame again for a fresh picture.
+ * rpt_last_overlay_pixels: pixels whose RGBA bytes the last FINISHED overlay pass changed (counted on the device, one atomic add per workgroup,
+ * copied back in stream order, read at rpt_sync or here once the copy has run); 0 before the first. */
+#define RPT_OVERLAY_OUTLINES   1   /* object index differs from a neighbour's */
+#define RPT_OVERLAY_ISO_DELAY  2   /* contours of the look-back time |interval * dist| */
+#define RPT_OVERLAY_ISO_CLOCK  4   /* contours of event[0], the hit object's own time */
+#define RPT_OVERLAY_LATTICE    8   /* contours of event[1..3], a grid at rest with the hit object */
+#define RPT_OVERLAY_DELAY_TINT 16  /* delay_map's red-green-blue ramp, blended over the picture */
+
+typedef struct rpt_overlay_desc {
+    uint32_t layers;             /* OR of the above; 0 = off (default) */
+    float    delay_step;         /* > 0 where its layer is on */
+    float    clock_step;
+    float    lattice_step[3];    /* per axis; 0 skips that axis */
+    float    tint_t_max;         /* > 0, or 0 = this frame's largest delay, found on the device */
+    uint8_t  outline_rgba[4], delay_rgba[4], clock_rgba[4], lattice_rgba[4];
+    uint8_t  tint_alpha, _pad[3];
+} rpt_overlay_desc;
+
+int rpt_set_overlay(rpt_ctx *ctx, const rpt_overlay_desc *desc_or_null);
+int rpt_render_overlay(rpt_ctx *ctx);        /* enqueue and wait */
+int rpt_render_overlay_async(rpt_ctx *ctx);  /* enqueue; rpt_sync waits */
+int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

@@ -43,6 +43,13 @@ class Octree(C.Structure):
     ]
 
 
+class OverlayDesc(C.Structure):
+    """rpt_overlay_desc of include/rpt.h (48 B): the layers of the overlay pass."""
+    _fields_ = [("layers", C.c_uint32), ("delay_step", C.c_float), ("clock_step", C.c_float), ("lattice_step", C.c_float * 3),
+                ("tint_t_max", C.c_float), ("outline_rgba", C.c_uint8 * 4), ("delay_rgba", C.c_uint8 * 4), ("clock_rgba", C.c_uint8 * 4),
+                ("lattice_rgba", C.c_uint8 * 4), ("tint_alpha", C.c_uint8), ("_pad", C.c_uint8 * 3)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -193,6 +200,10 @@ HIP_SYMBOLS = {
     "rpt_set_adaptive_aa": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "rpt_last_aa_refined": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_last_aa_variant": (C.c_int, [C.c_void_p]),
+    "rpt_set_overlay": (C.c_int, [C.c_void_p, C.POINTER(OverlayDesc)]),
+    "rpt_render_overlay": (C.c_int, [C.c_void_p]),
+    "rpt_render_overlay_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_overlay_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_version": (C.c_char_p, []),
 }
 

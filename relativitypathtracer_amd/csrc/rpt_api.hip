@@ -185,6 +185,17 @@ struct rpt_ctx {
     bool aa_pending = false;                          // a copy has been enqueued since aa_refined was read
     int last_aa_variant = 0;                          // the refine kernel of the last colour frame (rpt_last_aa_variant)
     ProjectionTables aa_pano;                         // panorama: the tables at aa_n times the frame's size, for the refine pass
+    // rpt_set_overlay / rpt_render_overlay (not in the reference): the overlay pass, per context, never shared
+    rpt_overlay_desc overlay = {};                    // layers == 0: off
+    unsigned long long view_generation = 1;           // bumped by every call that changes the view (objects, params, projection, orientation, lens)
+    unsigned long long colour_generation = 0, events_generation = 0;     // the view the last colour frame / event frame was enqueued for (0 = none yet)
+    int colour_width = 0, colour_height = 0;          // the last colour frame's size (the last event frame's: events_width, events_height)
+    void *colour_out = nullptr;                       // ... and the framebuffer it was rendered into (the last event frame's records: events_ptr)
+    DeviceBuffer overlay_scratch;                     // 16 B: the changed pixels of the pass in flight, then the bit pattern of the frame's largest delay
+    unsigned long long *overlay_host = nullptr;       // pinned: the counter of the last pass whose copy has run
+    hipEvent_t overlay_counted = nullptr;             // recorded after that copy
+    unsigned long long overlay_pixels = 0;            // rpt_last_overlay_pixels: overlay_host as last read with overlay_counted passed
+    bool overlay_pending = false;                     // a copy has been enqueued since overlay_pixels was read
 };
 
 namespace {
@@ -1372,6 +1383,91 @@ int launch_events(rpt_ctx *ctx) {
     return RPT_OK;
 }
 
+uint32_t packed_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
+
+// One overlay pass on the context's stream (kernel 1100, behind 1101 where the tint's range is the frame's own): the refusals, the
+// counter, the launch, then the counter's way home in stream order, as pass B of an adaptive frame.
+int launch_overlay(rpt_ctx *ctx) {
+    const rpt_overlay_desc &d = ctx->overlay;
+    if (d.layers == 0) {          // off: nothing is checked, launched or changed
+        ctx->overlay_pending = false;
+        ctx->overlay_pixels = 0;
+        return RPT_OK;
+    }
+    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay before rpt_upload_scene");
+    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay before rpt_set_params");
+    if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->colour_plane)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_overlay: the pass reads a pixel's upper neighbour, which on a context restricted by rpt_set_rows / rpt_set_tile_pattern (or rendering a colour plane) belongs to another rank");
+    if (ctx->colour_generation == 0 || !ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: no colour frame rendered yet");
+    if (ctx->events_generation == 0 || !ctx->events_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: no event frame rendered yet (rpt_render_events)");
+    if (ctx->colour_width != ctx->width || ctx->colour_height != ctx->height || ctx->events_width != ctx->width || ctx->events_height != ctx->height)
+        return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: the last colour frame and event frame are not both of the current width x height");
+    if (ctx->colour_generation != ctx->view_generation || ctx->events_generation != ctx->view_generation)
+        return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: the view has changed (objects, params, projection, orientation or lens) since the last colour frame or event frame; render both again");
+    rpt_pixel *out16 = (rpt_pixel *)(ctx->external_out ? ctx->external_out : ctx->owned_out.ptr);
+    const rpt_event *events = (const rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
+    // the buffers the two frames were rendered into are the ones the pass reads and writes: a buffer set since then holds no frame (and
+    // a library-owned one may be smaller than this frame)
+    if (!out16 || !events || (void *)out16 != ctx->colour_out || (const void *)events != ctx->events_ptr)
+        return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: rpt_set_output or rpt_set_events_output has named another buffer since the colour frame and the event frame were rendered");
+    if (int rc = reserve(ctx, ctx->overlay_scratch, 16)) return rc;
+    if (!ctx->overlay_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->overlay_host, 8, hipHostMallocDefault));
+    if (!ctx->overlay_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->overlay_counted, hipEventDisableTiming));
+
+    rptd::OverlayArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.events = events;
+    a.out16 = out16;
+    a.changed = (unsigned long long *)ctx->overlay_scratch.ptr;
+    a.width = ctx->width;
+    a.height = ctx->height;
+    a.layers = d.layers;
+    a.interval = (float)ctx->interval;
+    if (d.layers & RPT_OVERLAY_ISO_DELAY) a.delay_inv = 1.0f / d.delay_step;
+    if (d.layers & RPT_OVERLAY_ISO_CLOCK) a.clock_inv = 1.0f / d.clock_step;
+    if (d.layers & RPT_OVERLAY_LATTICE)
+        for (int k = 0; k < 3; k++)
+            if (d.lattice_step[k] != 0.0f) {
+                a.lattice_inv[k] = 1.0f / d.lattice_step[k];
+                a.layers |= (1u << k) << RPT_OVERLAY_AXIS_SHIFT;
+            }
+    a.tint_t_max = d.tint_t_max;
+    a.outline_rgba = packed_rgba(d.outline_rgba);
+    a.delay_rgba = packed_rgba(d.delay_rgba);
+    a.clock_rgba = packed_rgba(d.clock_rgba);
+    a.lattice_rgba = packed_rgba(d.lattice_rgba);
+    a.tint_alpha = d.tint_alpha;
+
+    const size_t pixels = (size_t)ctx->width * ctx->height;
+    RPT_HIP(ctx, hipMemsetAsync(ctx->overlay_scratch.ptr, 0, 16, ctx->stream));
+    if ((d.layers & RPT_OVERLAY_DELAY_TINT) && d.tint_t_max == 0.0f) {
+        uint32_t *tmax = (uint32_t *)ctx->overlay_scratch.ptr + 2;
+        a.tmax_bits = tmax;
+        const size_t blocks = (pixels + 255) / 256;
+        const float interval = a.interval;
+        void *args[] = {(void *)&events, (void *)&pixels, (void *)&interval, (void *)&tmax};
+        (void)hipLaunchKernel((const void *)rptd::rpt_overlay_tmax_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), args, 0, ctx->stream);
+        RPT_HIP(ctx, hipGetLastError());
+    }
+    const dim3 grid((ctx->width + RPT_OVERLAY_TILE_W - 1) / RPT_OVERLAY_TILE_W, (ctx->height + RPT_OVERLAY_TILE_H - 1) / RPT_OVERLAY_TILE_H);
+    void *args[] = {(void *)&a};
+    (void)hipLaunchKernel((const void *)rptd::rpt_overlay_kernel, grid, dim3(RPT_OVERLAY_TILE_W * RPT_OVERLAY_TILE_H), args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    RPT_HIP(ctx, hipMemcpyAsync(ctx->overlay_host, ctx->overlay_scratch.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(ctx->overlay_counted, ctx->stream));
+    ctx->last_event = ctx->overlay_counted;
+    ctx->overlay_pending = true;
+    return RPT_OK;
+}
+
+// rpt_last_overlay_pixels' value: the pinned word, once the copy behind the last overlay pass has run
+void collect_overlay_pixels(rpt_ctx *ctx) {
+    if (ctx->overlay_pending && ctx->overlay_counted && hipEventQuery(ctx->overlay_counted) == hipSuccess) {
+        ctx->overlay_pixels = *ctx->overlay_host;
+        ctx->overlay_pending = false;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1436,12 +1532,14 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env}) release(*u);
     if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
     if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
+    if (ctx->overlay_host) (void)hipHostFree(ctx->overlay_host);
+    if (ctx->overlay_counted) (void)hipEventDestroy(ctx->overlay_counted);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -1612,6 +1710,7 @@ static int set_objects_as_given(rpt_ctx *ctx, const void *objects, int count) {
     ctx->has_mesh = false;
     for (int i = 0; i < count; i++) ctx->has_mesh = ctx->has_mesh || ((const rpt_object *)objects)[i].type == RPT_MESH;
     ctx->host_objects.assign((const uint8_t *)objects, (const uint8_t *)objects + bytes);
+    ctx->view_generation++;
     return RPT_OK;
 }
 
@@ -1625,6 +1724,7 @@ int rpt_set_params(rpt_ctx *ctx, const float white_point[3], float ambient, int 
     const bool interval_changed = ctx->interval != interval;
     ctx->interval = interval;
     ctx->params_set = true;
+    ctx->view_generation++;
     if (interval_changed && ctx->scene_uploaded && ctx->object_count > 0) {
         const std::vector<uint8_t> copy = ctx->oriented ? ctx->caller_objects : ctx->host_objects;      // the culling record of DObj uses `interval`
         if (copy.size() != (size_t)ctx->object_count * sizeof(rpt_object)) return fail(ctx, RPT_ERR_STATE, "rpt_set_params: the context holds no copy of the caller's objects");
@@ -1699,6 +1799,7 @@ int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params) {
     }
     ctx->projection = mode;
     std::memcpy(ctx->projection_params, p, sizeof p);
+    ctx->view_generation++;
     return RPT_OK;
 }
 
@@ -1756,6 +1857,7 @@ int rpt_set_orientation(rpt_ctx *ctx, const float ypr[3]) {
     std::memcpy(was_R, ctx->R, sizeof was_R);
     ctx->oriented = !is_identity(R);
     std::memcpy(ctx->R, R, sizeof R);
+    ctx->view_generation++;
     if (!ctx->scene_uploaded || ctx->object_count <= 0) return RPT_OK;
     if (given.size() != (size_t)ctx->object_count * sizeof(rpt_object)) {      // (cannot happen: every successful rpt_set_objects leaves the copy that matches `oriented`)
         ctx->oriented = was_oriented;
@@ -1776,6 +1878,7 @@ int rpt_set_field_of_view(rpt_ctx *ctx, float v_fov) {
         return fail(ctx, RPT_ERR_ARG, "rpt_set_field_of_view: the vertical field of view is 0 (the reference's lens) or 0.01 <= v_fov <= 3.0 radians");
     ctx->v_fov = v_fov;
     ctx->lens_scale = v_fov != 0.0f ? (float)std::tan(0.5 * (double)v_fov) : 1.0f;
+    ctx->view_generation++;
     return RPT_OK;
 }
 
@@ -1959,6 +2062,10 @@ static int render_frame(rpt_ctx *ctx, CallKind kind) {
     if (timed) ctx->timing_frames++;
     else if (ctx->timing_frames >= 0) return fail(ctx, RPT_ERR_STATE, "timing region is full");
     ctx->frame_rendered = true;
+    ctx->colour_generation = ctx->view_generation;      // (what rpt_render_overlay asks for)
+    ctx->colour_width = ctx->width;
+    ctx->colour_height = ctx->height;
+    ctx->colour_out = ctx->colour_plane ? nullptr : rpt_output_ptr(ctx);
     return RPT_OK;
 }
 
@@ -2035,6 +2142,7 @@ int rpt_sync(rpt_ctx *ctx) {
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     collect_aa_refined(ctx);
+    collect_overlay_pixels(ctx);
     return RPT_OK;
 }
 
@@ -2078,6 +2186,7 @@ int rpt_render_events_async(rpt_ctx *ctx) {
     RPT_HIP(ctx, hipEventRecord(ctx->ev_events, ctx->stream));
     ctx->last_event = ctx->ev_events;
     ctx->events_rendered = true;
+    ctx->events_generation = ctx->view_generation;      // (what rpt_render_overlay asks for)
     return RPT_OK;
 }
 
@@ -2115,6 +2224,53 @@ int rpt_last_events_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_events_
 int rpt_last_events_exact_rcp(const rpt_ctx *ctx, int *exact_out) {
     if (!ctx || !exact_out) return RPT_ERR_ARG;
     *exact_out = ctx->last_events_exact_rcp ? 1 : 0;
+    return RPT_OK;
+}
+
+int rpt_set_overlay(rpt_ctx *ctx, const rpt_overlay_desc *desc_or_null) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (!desc_or_null) {
+        ctx->overlay = rpt_overlay_desc{};
+        return RPT_OK;
+    }
+    const rpt_overlay_desc &d = *desc_or_null;
+    const uint32_t known = RPT_OVERLAY_OUTLINES | RPT_OVERLAY_ISO_DELAY | RPT_OVERLAY_ISO_CLOCK | RPT_OVERLAY_LATTICE | RPT_OVERLAY_DELAY_TINT;
+    if (d.layers & ~known) return fail(ctx, RPT_ERR_ARG, "rpt_set_overlay: unknown layer bits (the layers are RPT_OVERLAY_*)");
+    const auto step_ok = [](float s) { return std::isfinite(s) && s > 0.0f; };
+    if ((d.layers & RPT_OVERLAY_ISO_DELAY) && !step_ok(d.delay_step)) return fail(ctx, RPT_ERR_ARG, "rpt_set_overlay: delay_step must be finite and > 0 while RPT_OVERLAY_ISO_DELAY is on");
+    if ((d.layers & RPT_OVERLAY_ISO_CLOCK) && !step_ok(d.clock_step)) return fail(ctx, RPT_ERR_ARG, "rpt_set_overlay: clock_step must be finite and > 0 while RPT_OVERLAY_ISO_CLOCK is on");
+    if (d.layers & RPT_OVERLAY_LATTICE) {
+        bool any = false;
+        for (int k = 0; k < 3; k++) {
+            if (d.lattice_step[k] == 0.0f) continue;
+            if (!step_ok(d.lattice_step[k])) return fail(ctx, RPT_ERR_ARG, "rpt_set_overlay: every lattice_step is finite and > 0, or 0 to skip its axis, while RPT_OVERLAY_LATTICE is on");
+            any = true;
+        }
+        if (!any) return fail(ctx, RPT_ERR_ARG, "rpt_set_overlay: RPT_OVERLAY_LATTICE needs a step > 0 on at least one axis");
+    }
+    if (!std::isfinite(d.tint_t_max) || d.tint_t_max < 0.0f) return fail(ctx, RPT_ERR_ARG, "rpt_set_overlay: tint_t_max is > 0, or 0 for the frame's largest delay");
+    ctx->overlay = d;
+    return RPT_OK;
+}
+
+int rpt_render_overlay_async(rpt_ctx *ctx) {
+    if (!ctx) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_overlay(ctx);
+}
+
+int rpt_render_overlay(rpt_ctx *ctx) {
+    if (int rc = rpt_render_overlay_async(ctx)) return rc;
+    return rpt_sync(ctx);
+}
+
+int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels) {
+    if (!ctx || !pixels) return RPT_ERR_ARG;
+    if (ctx->overlay_pending) {
+        RPT_HIP(ctx, hipSetDevice(ctx->device));
+        collect_overlay_pixels(ctx);
+    }
+    *pixels = ctx->overlay_pixels;
     return RPT_OK;
 }
 
@@ -2175,6 +2331,10 @@ int rpt_timed_frames(rpt_ctx *ctx, int frames, float *avg_ms) {
     float ms = 0;
     RPT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
     ctx->frame_rendered = true;
+    ctx->colour_generation = ctx->view_generation;
+    ctx->colour_width = ctx->width;
+    ctx->colour_height = ctx->height;
+    ctx->colour_out = ctx->colour_plane ? nullptr : rpt_output_ptr(ctx);
     ctx->last_ms = ms / frames;
     *avg_ms = ctx->last_ms;
     return RPT_OK;

@@ -1791,6 +1791,170 @@ RPT_REFINE_FAMILY(pano_doppler, DopplerTwin<, >, PanoramaUnculled, PanoramaWalk,
 RPT_REFINE_FAMILY(pano_env, Environment<, >, PanoramaUnculled, PanoramaWalk, PanoramaWalkIeee, PanoramaAnalytic)            // 1083, 1081, (1081), 1084
 #undef RPT_REFINE_FAMILY
 
+// ---- Overlay pass (rpt_set_overlay / rpt_render_overlay; not in the reference; DESIGN.md "Overlay pass") ---------------------------------
+// Lines drawn on the rendered frame from the event records: a bandwidth-bound stencil that reads the records and the framebuffer's packed
+// colour and nothing else, so it serves every camera and colour mode and no render kernel knows of it.  The rules are in include/rpt.h.
+#define RPT_OVERLAY_TILE_W 64
+#define RPT_OVERLAY_TILE_H 8
+#define RPT_OVERLAY_PITCH (RPT_OVERLAY_TILE_W + 1)                          /* a tile row and its right halo pixel */
+#define RPT_OVERLAY_SLOTS ((RPT_OVERLAY_TILE_H + 1) * RPT_OVERLAY_PITCH)   /* ... and the halo row above the tile */
+#define RPT_OVERLAY_OUTSIDE (-2147483647 - 1)    /* `object` of a pixel outside the frame; as a cell: "never on a line" */
+// bits of OverlayArgs::layers above the five of include/rpt.h: the lattice axes with a non-zero step
+#define RPT_OVERLAY_AXIS_SHIFT 8
+
+struct OverlayArgs {
+    const rpt_event *events;        // [height][width] records of the same view
+    rpt_pixel *out16;               // the framebuffer: only the dword at byte 8 of a pixel is read and written
+    unsigned long long *changed;    // the context's counter of pixels whose RGBA changed: one atomic add per workgroup that changed any
+    const uint32_t *tmax_bits;      // tint_t_max == 0: the bit pattern of the frame's largest delay (overlay_tmax_kernel); else null
+    int width, height;
+    uint32_t layers;                // RPT_OVERLAY_* | the lattice axes in use << RPT_OVERLAY_AXIS_SHIFT
+    float interval;                 // (float)interval
+    float delay_inv, clock_inv, lattice_inv[3];     // 1.0f / step, formed on the host
+    float tint_t_max;
+    uint32_t outline_rgba, delay_rgba, clock_rgba, lattice_rgba;    // R | G << 8 | B << 16 | A << 24
+    uint32_t tint_alpha;
+};
+
+// floorf(s * inv) as an integer, or RPT_OVERLAY_OUTSIDE where the product is not finite or is 2^30 or more in magnitude
+RPT_DEV int overlay_cell(float s, float inv) {
+    const float p = s * inv;
+    if (!(fabsf(p) < 1073741824.0f)) return RPT_OVERLAY_OUTSIDE;       // (a NaN fails the comparison too)
+    return (int)floorf(p);
+}
+
+// out = (c * a + old * (255 - a) + 127) / 255 on R, G and B; the alpha byte of `old` stays
+RPT_DEV uint32_t overlay_blend(uint32_t old, uint32_t rgb, uint32_t alpha) {
+    uint32_t out = old & 0xff000000u;
+    for (int k = 0; k < 3; k++) {
+        const uint32_t c = (rgb >> (8 * k)) & 255u, o = (old >> (8 * k)) & 255u;
+        out |= ((c * alpha + o * (255u - alpha) + 127u) / 255u) << (8 * k);
+    }
+    return out;
+}
+
+// |interval * dist|, 0 where that is not finite: the delay of the tint and of its maximum
+RPT_DEV float overlay_delay(float interval, float dist) {
+    const float d = fabsf(interval * dist);
+    return d <= 3.402823466e38f ? d : 0.0f;
+}
+
+// What the rules need of pixel (x, y), put into LDS slot `slot` of the planes that are in use: its object and the cell of every contour
+// layer that is on.  Outside the frame: RPT_OVERLAY_OUTSIDE as the object (no rule looks further).  Returns the record's first 16 bytes.
+RPT_DEV uint4 overlay_reduce_record(const OverlayArgs &a, int x, int y, int slot, int *objects, int (*cells)[RPT_OVERLAY_SLOTS]) {
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u);
+    if (x >= a.width || y >= a.height) {
+        objects[slot] = RPT_OVERLAY_OUTSIDE;
+        return lo;
+    }
+    const uint4 *record = reinterpret_cast<const uint4 *>(a.events + ((size_t)y * a.width + x));
+    lo = record[0];                                                    // object, dist, event[0], event[1]
+    objects[slot] = (int)lo.x;
+    if (a.layers & RPT_OVERLAY_ISO_DELAY) cells[0][slot] = overlay_cell(fabsf(a.interval * __uint_as_float(lo.y)), a.delay_inv);
+    if (a.layers & RPT_OVERLAY_ISO_CLOCK) cells[1][slot] = overlay_cell(__uint_as_float(lo.z), a.clock_inv);
+    if (a.layers & (1u << RPT_OVERLAY_AXIS_SHIFT)) cells[2][slot] = overlay_cell(__uint_as_float(lo.w), a.lattice_inv[0]);
+    if (a.layers & (6u << RPT_OVERLAY_AXIS_SHIFT)) {                   // the second 16 bytes only where a y or z lattice needs them
+        const uint4 hi = record[1];                                    // event[2], event[3], u, v
+        if (a.layers & (2u << RPT_OVERLAY_AXIS_SHIFT)) cells[3][slot] = overlay_cell(__uint_as_float(hi.x), a.lattice_inv[1]);
+        if (a.layers & (4u << RPT_OVERLAY_AXIS_SHIFT)) cells[4][slot] = overlay_cell(__uint_as_float(hi.y), a.lattice_inv[2]);
+    }
+    return lo;
+}
+
+// whether the pixel in `slot` is on a line of the contour plane `cell`: a neighbour (right: slot + 1, upper: slot + pitch) of the same
+// object — a pixel outside the frame has none — whose cell differs, both cells being valid
+RPT_DEV bool overlay_on_contour(const int *objects, const int *cell, int slot, int object) {
+    const int mine = cell[slot];
+    if (mine == RPT_OVERLAY_OUTSIDE) return false;
+    bool on = false;
+    for (int k = 0; k < 2; k++) {
+        const int q = slot + (k ? RPT_OVERLAY_PITCH : 1);
+        const int theirs = cell[q];
+        on = on || (objects[q] == object && theirs != RPT_OVERLAY_OUTSIDE && theirs != mine);
+    }
+    return on;
+}
+
+// 1100: a workgroup of 512 lanes owns a 64 x 8 pixel tile, wave w its row w (a wave's two record loads cover 2 KB of consecutive bytes).
+// Every lane reduces its own record into LDS; the first 64 lanes also reduce the row above the tile, the next 8 the column to its right
+// (72 halo records per 512, most of them still in L2 from the neighbouring workgroup).  After one barrier each lane reads its right and
+// upper neighbour from LDS and blends into its own pixel's RGBA dword: neighbours' colours are never read, so the update in place has no
+// ordering hazard.  LDS: 6 planes of 9 x 65 ints, 14040 B.  Changed pixels: a ballot per wave, the eight waves' counts added in LDS, one
+// global atomic per workgroup — one per wave, 130 000 on one address at 4K, was measured to cost more than the rest of the kernel.
+__global__ __launch_bounds__(512) void rpt_overlay_kernel(const OverlayArgs a) {
+    __shared__ int objects[RPT_OVERLAY_SLOTS];
+    __shared__ int cells[5][RPT_OVERLAY_SLOTS];
+    __shared__ unsigned int tile_changed;
+    const int t = (int)threadIdx.x;
+    if (t == 0) tile_changed = 0u;
+    const int lx = t & (RPT_OVERLAY_TILE_W - 1), ly = t >> 6;
+    const int x0 = (int)blockIdx.x * RPT_OVERLAY_TILE_W, y0 = (int)blockIdx.y * RPT_OVERLAY_TILE_H;
+    const int x = x0 + lx, y = y0 + ly;
+    const int slot = ly * RPT_OVERLAY_PITCH + lx;
+    const uint4 lo = overlay_reduce_record(a, x, y, slot, objects, cells);
+    if (t < RPT_OVERLAY_TILE_W) (void)overlay_reduce_record(a, x0 + t, y0 + RPT_OVERLAY_TILE_H, RPT_OVERLAY_TILE_H * RPT_OVERLAY_PITCH + t, objects, cells);
+    else if (t < RPT_OVERLAY_TILE_W + RPT_OVERLAY_TILE_H)
+        (void)overlay_reduce_record(a, x0 + RPT_OVERLAY_TILE_W, y0 + t - RPT_OVERLAY_TILE_W, (t - RPT_OVERLAY_TILE_W) * RPT_OVERLAY_PITCH + RPT_OVERLAY_TILE_W, objects, cells);
+    __syncthreads();
+
+    bool changed = false;
+    if (x < a.width && y < a.height) {
+        const int object = (int)lo.x;
+        const bool hit = object >= 0;
+        uint32_t *rgba = reinterpret_cast<uint32_t *>(a.out16 + ((size_t)y * a.width + x)) + 2;
+        const uint32_t before = *rgba;
+        uint32_t now = before;
+        if ((a.layers & RPT_OVERLAY_DELAY_TINT) && hit) {
+            const float t_max = a.tmax_bits ? __uint_as_float(*a.tmax_bits) : a.tint_t_max;
+            const float d = overlay_delay(a.interval, __uint_as_float(lo.y));
+            float xr = 0.0f;
+            if (t_max > 0.0f) xr = fminf(fmaxf(d / t_max, 0.0f), 1.0f);
+            const float x2 = 2.0f * xr;
+            const float r = fminf(fmaxf(1.0f - x2, 0.0f), 1.0f);
+            const float g = 1.0f - fabsf(x2 - 1.0f);
+            const float b = fminf(fmaxf(x2 - 1.0f, 0.0f), 1.0f);
+            const uint32_t rb = (uint32_t)rintf((0.25f + 0.75f * r) * 255.0f);
+            const uint32_t gb = (uint32_t)rintf((0.25f + 0.75f * g) * 255.0f);
+            const uint32_t bb = (uint32_t)rintf((0.25f + 0.75f * b) * 255.0f);
+            now = overlay_blend(now, rb | (gb << 8) | (bb << 16), a.tint_alpha);
+        }
+        if (hit) {
+            if (a.layers & RPT_OVERLAY_LATTICE) {
+                bool on = false;
+                for (int k = 0; k < 3; k++)
+                    if (a.layers & ((1u << k) << RPT_OVERLAY_AXIS_SHIFT)) on = on || overlay_on_contour(objects, cells[2 + k], slot, object);
+                if (on) now = overlay_blend(now, a.lattice_rgba, a.lattice_rgba >> 24);
+            }
+            if ((a.layers & RPT_OVERLAY_ISO_CLOCK) && overlay_on_contour(objects, cells[1], slot, object)) now = overlay_blend(now, a.clock_rgba, a.clock_rgba >> 24);
+            if ((a.layers & RPT_OVERLAY_ISO_DELAY) && overlay_on_contour(objects, cells[0], slot, object)) now = overlay_blend(now, a.delay_rgba, a.delay_rgba >> 24);
+        }
+        if (a.layers & RPT_OVERLAY_OUTLINES) {
+            const int right = objects[slot + 1], upper = objects[slot + RPT_OVERLAY_PITCH];
+            if ((right != RPT_OVERLAY_OUTSIDE && right != object) || (upper != RPT_OVERLAY_OUTSIDE && upper != object))
+                now = overlay_blend(now, a.outline_rgba, a.outline_rgba >> 24);
+        }
+        changed = now != before;
+        if (changed) *rgba = now;
+    }
+    const unsigned long long set = __ballot(changed);
+    if ((t & 63) == 0 && set) atomicAdd(&tile_changed, (unsigned int)__popcll(set));
+    __syncthreads();
+    if (t == 0 && tile_changed) atomicAdd(a.changed, (unsigned long long)tile_changed);
+}
+
+// 1101: the frame's largest delay over hit pixels, for tint_t_max == 0.  A grid-stride loop over the records' first 8 bytes, the wave's
+// maximum by six butterfly shuffles, then one atomic max per wave on the bit pattern — the delays are non-negative floats,
+// whose order is that of their bit patterns as unsigned integers.  *out is zeroed by the host before the launch.
+__global__ __launch_bounds__(256) void rpt_overlay_tmax_kernel(const rpt_event *events, size_t pixels, float interval, uint32_t *out) {
+    float mine = 0.0f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (size_t)gridDim.x * 256) {
+        const uint2 head = *reinterpret_cast<const uint2 *>(events + i);      // object, dist
+        if ((int)head.x >= 0) mine = fmaxf(mine, overlay_delay(interval, __uint_as_float(head.y)));
+    }
+    for (int offset = 32; offset >= 1; offset >>= 1) mine = fmaxf(mine, __shfl_xor(mine, offset, 64));
+    if ((threadIdx.x & 63) == 0 && mine > 0.0f) atomicMax(out, __float_as_uint(mine));
+}
+
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd
 #include "rpt_diag_kernels.hip.h"    /* librpt_hip_diag.so only: instrumented kernels, round 1's prepass, the A/B arms of rounds 2 and 3 */

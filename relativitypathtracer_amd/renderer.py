@@ -357,6 +357,39 @@ class Renderer:
         self._check(self._lib.rpt_last_events_exact_rcp(self._h, C.byref(exact)), "rpt_last_events_exact_rcp")
         return bool(exact.value)
 
+    # -- the overlay pass (include/rpt.h, rpt_set_overlay; not in the reference) -------------------
+    def set_overlay(self, **layers):
+        """The layers of the overlay pass, as keywords (events.overlay_settings): outlines=True, outline_rgba=(R, G, B, A);
+        delay_step=..., delay_rgba; clock_step=..., clock_rgba; lattice_step=one step or (sx, sy, sz), lattice_rgba; tint=True,
+        tint_t_max (0 = the frame's largest delay, found on the device), tint_alpha.  No keyword at all switches the pass off.  A
+        description the library refuses (a step <= 0 for a layer that is on, ...) raises RenderError."""
+        from .events import overlay_settings
+        s = overlay_settings(**layers)
+        d = _ffi.OverlayDesc()
+        d.layers = s["layers"]
+        d.delay_step = s["delay_step"] if s["delay_step"] is not None else 0.0
+        d.clock_step = s["clock_step"] if s["clock_step"] is not None else 0.0
+        d.lattice_step[:] = s["lattice_step"] if s["lattice_step"] is not None else (0.0, 0.0, 0.0)
+        d.tint_t_max = s["tint_t_max"]
+        d.outline_rgba[:], d.delay_rgba[:], d.clock_rgba[:], d.lattice_rgba[:] = s["outline_rgba"], s["delay_rgba"], s["clock_rgba"], s["lattice_rgba"]
+        d.tint_alpha = int(s["tint_alpha"])
+        self._check(self._lib.rpt_set_overlay(self._h, C.byref(d) if s["layers"] else None), "rpt_set_overlay")
+
+    def render_overlay(self, async_: bool = False):
+        """Blend the layers of set_overlay into the framebuffer, in place, from the records of the last event frame.  The context must
+        have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice blends twice.
+        async_=True enqueues only (sync waits)."""
+        if async_:
+            self._check(self._lib.rpt_render_overlay_async(self._h), "rpt_render_overlay_async")
+        else:
+            self._check(self._lib.rpt_render_overlay(self._h), "rpt_render_overlay")
+
+    def last_overlay_pixels(self) -> int:
+        """Pixels whose RGBA the last finished overlay pass changed (0 before the first)."""
+        n = C.c_uint64(0)
+        self._check(self._lib.rpt_last_overlay_pixels(self._h, C.byref(n)), "rpt_last_overlay_pixels")
+        return int(n.value)
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -488,13 +521,15 @@ class Renderer:
 def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
                  projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None,
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
-                 adaptive_aa: Optional[Tuple[int, int]] = None):
+                 adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}.  environment: an
     H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first).
     orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view).
-    adaptive_aa: (samples per axis, threshold) for Renderer.set_adaptive_aa."""
+    adaptive_aa: (samples per axis, threshold) for Renderer.set_adaptive_aa.  overlay: the keywords of Renderer.set_overlay, e.g.
+    dict(outlines=True, clock_step=0.5); it implies events=True and runs the three passes — the colour frame, the event frame, the
+    overlay — so the pixels returned carry the lines (rgb, the float colours before packing, does not)."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -514,6 +549,11 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
+        if overlay is not None:
+            records = r.render_events()
+            r.set_overlay(**overlay)
+            r.render_overlay()
+            return r.read_framebuffer(), (r.read_debug_rgb() if debug_rgb else None), records
         frame = r.read_framebuffer(), (r.read_debug_rgb() if debug_rgb else None)
         return frame + (r.render_events(),) if events else frame
     finally:
