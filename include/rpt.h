@@ -311,6 +311,23 @@ int rpt_object_screen_bounds(const void *object, int interval, const float *root
 int rpt_mesh_segment_cull_record(rpt_ctx *ctx, int object_index, float out[10]);
 int rpt_object_screen_bounds_proposed(const void *object, int interval, const float *root_bounds_or_null, float bounds_out[8]);
 int rpt_certify_screen_bounds(const void *object, int interval, const float *root_bounds_or_null, const float bounds[8], int stats_out[4]);
+/* The tile bitmap of a still mesh (csrc/rpt_tile_bitmap.hpp; not in the reference): one bit per 8x8-pixel tile of the frame, 0 = no
+ * primary ray of the tile can report a hit of the mesh — proven from the boxes of at most `max_boxes` (64 in a context) sub-trees of
+ * its octree, for meshes whose triangles are small enough for the bound to be provable (bunny.obj is, pear.obj is not).  A context
+ * builds it for an object once its record has been byte-identical in two consecutive rpt_set_objects calls, and drops it with the
+ * first call in which it is not; the culled pinhole and lens kernels then skip the mesh in tiles whose bit is 0.
+ * rpt_tile_bitmap_host (host code, no device): the bitmap of mesh object `object_index` of `scene` for a width x height frame under
+ * lens_scale (1.0f: the reference's lens) into bits_out[words], bit ty * ceil(width / 8) + tx; boxes_or_null: n_boxes boxes (min.xyz,
+ * max.xyz) to use instead of the mesh's own (tests).  1: built, 0: this object gets no bitmap, < 0: -RPT_ERR_*.  stats_out, if not
+ * NULL: {boxes, boxes proven, tiles set, tiles, depth of the cut}.
+ * rpt_tile_bitmap_state: out = {bit i = object i has a bitmap on the device for the current frame, bitmaps built so far, host
+ * microseconds of the last build, dwords per bitmap}; bits_or_null receives the bitmap of `object_index` (an error if it has none). */
+int rpt_tile_bitmap_host(const rpt_scene_desc *scene, int object_index, int interval, int width, int height, float lens_scale, int max_boxes,
+                         const float *boxes_or_null, int n_boxes, uint32_t *bits_out, size_t words, int stats_out[5]);
+int rpt_tile_bitmap_state(rpt_ctx *ctx, unsigned long long out[4], int object_index, uint32_t *bits_or_null, size_t words);
+/* Device probe: the object mask of every 8x8 tile of the current pinhole or lens frame as kernel 41 / 841 forms it, out[2 t] before and
+ * out[2 t + 1] after the tile bitmaps (t = ty * ceil(width / 8) + tx; tiles = the number of tiles).  Prepares the frame as a launch does. */
+int rpt_probe_tile_masks(rpt_ctx *ctx, unsigned long long *out, size_t tiles);
 
 /* Render one frame and wait for it (the reference's runKernel + finish). */
 int rpt_render(rpt_ctx *ctx);

@@ -144,6 +144,10 @@ HIP_SYMBOLS = {
     "rpt_mesh_segment_cull_record": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "rpt_object_screen_bounds_proposed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rpt_certify_screen_bounds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "rpt_tile_bitmap_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_int)]),
+    "rpt_tile_bitmap_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_void_p, C.c_size_t]),
+    "rpt_probe_tile_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_verify_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_last_variant": (C.c_int, [C.c_void_p]),
     "rpt_last_exact_rcp": (C.c_int, [C.c_void_p]),

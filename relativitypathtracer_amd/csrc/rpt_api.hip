@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <atomic>
 #include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <utility>
@@ -21,6 +22,7 @@
 #include "rpt_octree_build.hip.h"
 #include "rpt_screen_bounds.hpp"
 #include "rpt_bounds_certify.hpp"
+#include "rpt_tile_bitmap.hpp"
 #include "rpt_workers.hpp"
 
 #pragma clang fp contract(off)
@@ -79,8 +81,12 @@ struct Geometry {
     std::vector<float> node_tri_K, node_tri_L;       // per node: the largest |e1| |e2| and the longest edge of the triangles its list names (mesh_segment_apart's margin)
     std::vector<uint8_t> node_holds_its_triangles;   // per node: every triangle of its list lies inside its box (true of a mesh's root
                                                      // unless its list also holds an earlier mesh's triangles, Mesh.cpp:16-19)
+    std::map<int, std::vector<float>> mesh_boxes;    // per mesh root (reference node index): the sub-tree boxes of rpt_tile_bitmap.hpp, six floats each
     size_t vertex_count = 0, normal_count = 0, uv_count = 0, triangle_words = 0, octree_count = 0, octree_tri_count = 0;
     ~Geometry() {
+        bool any = false;
+        for (const DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst}) any = any || b->ptr;
+        if (!any) return;                        // (a host-only copy, rpt_tile_bitmap_host: nothing of the device's to free)
         (void)hipSetDevice(device);
         for (DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst}) release(*b);
     }
@@ -196,6 +202,16 @@ struct rpt_ctx {
     hipEvent_t overlay_counted = nullptr;             // recorded after that copy
     unsigned long long overlay_pixels = 0;            // rpt_last_overlay_pixels: overlay_host as last read with overlay_counted passed
     bool overlay_pending = false;                     // a copy has been enqueued since overlay_pixels was read
+    // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
+    StagedUpload tile_bits;
+    unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
+    unsigned long long bits_tried = 0;                // ... of which a build has been attempted for the key below
+    unsigned long long bits_has = 0;                  // ... of which a bitmap is on the device (behind everything enqueued so far)
+    int bits_width = 0, bits_height = 0, bits_slots = 0;      // the key: what the bitmaps on the device were built for
+    float bits_lens = 0.0f;
+    bool bits_diagonals = false;
+    unsigned long long bits_builds = 0;               // bitmaps built so far (rpt_tile_bitmap_state)
+    double bits_last_build_us = 0.0;                  // host time of the last build
 };
 
 namespace {
@@ -437,6 +453,56 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
     return RPT_OK;
 }
 
+// What the host keeps of a scene's meshes: every node's box, which nodes hold their triangles inside it, how large those triangles
+// are, and the sub-tree boxes of the meshes the scene's objects name.  Host only (rpt_upload_scene; rpt_tile_bitmap_host); `s` is valid
+// (validate_geometry) and g.compact_ok is set.
+void host_mesh_facts(Geometry &g, const rpt_scene_desc *s, int max_boxes) {
+    g.host_node_bounds.resize(s->octree_count * 6);
+    for (size_t i = 0; i < s->octree_count; i++) {
+        float *b = &g.host_node_bounds[6 * i];
+        b[0] = s->octrees[i].min.x; b[1] = s->octrees[i].min.y; b[2] = s->octrees[i].min.z;
+        b[3] = s->octrees[i].max.x; b[4] = s->octrees[i].max.y; b[5] = s->octrees[i].max.z;
+    }
+    // Which nodes hold all of their triangles inside their own box?  (Asked of mesh roots by the shadow-segment cull: a hit on a
+    // triangle is a point of that triangle.)  Indices were validated above.
+    // ... and how large are those triangles?  K = max |e1| |e2|, L = the longest edge, with e1 = fl(B - A), e2 = fl(C - A) as the walk
+    // uses them: the float error of an accepted triangle hit is bounded through them (mesh_segment_apart, rpt_kernels.hip.h).
+    g.node_holds_its_triangles.assign(s->octree_count, 0);
+    g.node_tri_K.assign(s->octree_count, 0.0f);
+    g.node_tri_L.assign(s->octree_count, 0.0f);
+    for (size_t i = 0; i < s->octree_count; i++) {
+        const rpt_octree &o = s->octrees[i];
+        bool inside = o.trisCount >= 0;
+        double K = 0.0, L = 0.0;
+        for (int k = o.trisIndex; inside && k < o.trisIndex + o.trisCount; k++) {
+            const int t = s->octreeTris[k];
+            const rpt_float3 *vv[3];
+            for (int c = 0; c < 3 && inside; c++) {
+                const rpt_float3 &v = s->vertices[s->triangles[9 * t + 3 * c]];
+                vv[c] = &v;
+                inside = v.x >= o.min.x && v.x <= o.max.x && v.y >= o.min.y && v.y <= o.max.y && v.z >= o.min.z && v.z <= o.max.z;
+            }
+            if (!inside) break;
+            const float e1[3] = {vv[1]->x - vv[0]->x, vv[1]->y - vv[0]->y, vv[1]->z - vv[0]->z}, e2[3] = {vv[2]->x - vv[0]->x, vv[2]->y - vv[0]->y, vv[2]->z - vv[0]->z};
+            const double l1 = std::sqrt((double)e1[0] * e1[0] + (double)e1[1] * e1[1] + (double)e1[2] * e1[2]);
+            const double l2 = std::sqrt((double)e2[0] * e2[0] + (double)e2[1] * e2[1] + (double)e2[2] * e2[2]);
+            K = std::max(K, l1 * l2);
+            L = std::max(L, std::max(l1, l2));
+        }
+        g.node_holds_its_triangles[i] = inside ? 1 : 0;
+        g.node_tri_K[i] = std::nextafter((float)K, INFINITY);
+        g.node_tri_L[i] = std::nextafter((float)L, INFINITY);
+    }
+    // the sub-tree boxes of every mesh the scene's objects name (rpt_tile_bitmap.hpp; a mesh that only a later Object[] names gets none)
+    for (size_t i = 0; i < s->object_count && g.compact_ok; i++) {
+        const rpt_object &o = s->objects[i];
+        if (o.type != RPT_MESH || o.meshIndex < 0 || (size_t)o.meshIndex >= s->octree_count || g.mesh_boxes.count(o.meshIndex)) continue;
+        if (!g.node_holds_its_triangles[(size_t)o.meshIndex] || !(16.2 * (double)g.node_tri_K[(size_t)o.meshIndex] <= 0.25)) continue;
+        std::vector<float> boxes;
+        if (rptb::tiles::subtree_boxes(*s, o.meshIndex, max_boxes, boxes)) g.mesh_boxes[o.meshIndex].swap(boxes);
+    }
+}
+
 // The constants of mesh_segment_apart (rpt_kernels.hip.h, where the derivation is): may a shadow ray's segment to the light be
 // dropped for mesh object `o` when it stays beyond a plane of the root box, and with which margins?  Everything the argument
 // assumes about THIS object in THIS frame is checked here, in double, on the float matrices the kernel reads; if anything fails
@@ -605,6 +671,21 @@ void build_rects(rpt_ctx *ctx, const rpt_object *objs, int count, rptb::Rect *ou
     else for (int k = 0; k < n_todo; k++) rect_batch_item(&batch, k);
     ctx->rect_interval = ctx->interval;
     ctx->rect_geo_generation = ctx->geo->generation;
+}
+
+// Which objects stand still?  (Before build_rects, which moves the cache's key.)  A tile bitmap (rpt_tile_bitmap.hpp) is built for an
+// object only once its record has been byte-identical in two consecutive calls, and is dropped with the first call in which it is not:
+// an animated frame pays a memcmp it pays for the rectangles anyway and keeps today's mask, a still view pays for the build once.
+void note_still_objects(rpt_ctx *ctx, const rpt_object *objs, int count) {
+    const bool comparable = ctx->rect_interval == ctx->interval && ctx->rect_geo_generation == ctx->geo->generation &&
+                            ctx->rects.size() == (size_t)count && ctx->host_objects.size() == (size_t)count * sizeof(rpt_object);
+    const rpt_object *prev = comparable ? (const rpt_object *)ctx->host_objects.data() : nullptr;
+    unsigned long long still = 0;
+    for (int i = 0; prev && i < count && i < 64; i++)
+        if (std::memcmp(&prev[i], &objs[i], sizeof objs[i]) == 0) still |= 1ull << i;
+    ctx->bits_still = still;
+    ctx->bits_tried &= still;
+    ctx->bits_has &= still;
 }
 
 // ---- the free-look camera's orientation (rpt_set_orientation, rpt_orient_objects) ---------------------------------------------------
@@ -1197,6 +1278,77 @@ Choice choose_kernels(const rpt_ctx *ctx, Call call) {
     return c;
 }
 
+// The diagonal slabs hold inside their window only (rpt_screen_bounds.hpp): frames up to 4 : 1, |v| <= 1/2 always.  Under a lens
+// (rpt_set_field_of_view) the tiles' plane coordinates are those of the reference's lens times s <= 1 — a wider lens gets the un-culled
+// kernel — so the same rule holds with both sides of the tile scaled.
+bool frame_inside_diagonal_window(const rpt_ctx *ctx) {
+    const bool lens = ctx->v_fov != 0.0f;
+    const float aspect = (float)ctx->width / (float)ctx->height, s = lens ? ctx->lens_scale : 1.0f;
+    const float diag_reach = 0.5f * aspect + 2.0f * (1.0f / (float)ctx->height) * aspect;
+    return lens ? s <= 1.0f && s * diag_reach <= (float)rptb::DIAG_WINDOW_U : diag_reach <= (float)rptb::DIAG_WINDOW_U;
+}
+
+// do the bitmaps on the device belong to this frame?  (its size, its lens, its objects)
+bool tile_bits_current(const rpt_ctx *ctx) {
+    const int slots = ctx->object_count < 64 ? ctx->object_count : 64;
+    return ctx->bits_width == ctx->width && ctx->bits_height == ctx->height && ctx->bits_slots == slots &&
+           ctx->bits_lens == (ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f) && ctx->bits_diagonals == frame_inside_diagonal_window(ctx);
+}
+
+// The tile bitmap of one mesh object for this frame, into `bits`; false: this object gets none (not a mesh with sub-tree boxes, or
+// outside the rule 16.2 K + 3.2u <= 0.25 that DObj::mslope >= 0 stands for, or a box's region could not be proven)
+bool build_tile_bitmap(const rpt_ctx *ctx, const rpt_object &o, uint32_t *bits, rptb::tiles::Stats *stats) {
+    if (o.type != RPT_MESH) return false;
+    const auto it = ctx->geo->mesh_boxes.find(o.meshIndex);
+    if (it == ctx->geo->mesh_boxes.end() || it->second.empty() || (size_t)o.meshIndex >= ctx->geo->node_tri_K.size()) return false;
+    rptd::DObj d;
+    build_dobjs(ctx, &o, 1, &d);
+    if (!(d.mslope >= 0.0f)) return false;
+    const double slope = 16.2 * (double)ctx->geo->node_tri_K[(size_t)o.meshIndex] + 3.2 * rptb::cert::U24;
+    const rptb::tiles::Frame f{ctx->width, ctx->height, ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f, frame_inside_diagonal_window(ctx)};
+    return rptb::tiles::build(o, ctx->interval, it->second.data(), (int)(it->second.size() / 6), slope, (double)ctx->geo->node_tri_L[(size_t)o.meshIndex], f, bits, stats);
+}
+
+// Before a colour frame's launch: every still mesh that has no bitmap for this frame yet gets one (or is marked as tried), behind
+// everything enqueued so far — a frame in flight reads what it was launched with.  Here and not in rpt_set_objects because the bitmap
+// also depends on the frame's size and lens, which may be set after the objects.  Frames the culled kernels refuse (beyond 4 : 1,
+// beyond 2^20 pixels a side, a wide lens), the panorama, variant 3 and MSAA get none.
+int ensure_tile_bits(rpt_ctx *ctx) {
+    if (ctx->projection != RPT_PROJECTION_PINHOLE || ctx->variant == 3 || ctx->msaa > 1 || !ctx->geo->compact_ok || !ctx->has_mesh || !window_holds_frame(ctx) ||
+        ctx->host_objects.size() != (size_t)ctx->object_count * sizeof(rpt_object))
+        return RPT_OK;
+    const int slots = ctx->object_count < 64 ? ctx->object_count : 64;
+    if (!tile_bits_current(ctx)) {
+        ctx->bits_has = ctx->bits_tried = 0;
+        ctx->bits_width = ctx->width; ctx->bits_height = ctx->height; ctx->bits_slots = slots;
+        ctx->bits_lens = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
+        ctx->bits_diagonals = frame_inside_diagonal_window(ctx);
+    }
+    const rpt_object *objs = (const rpt_object *)ctx->host_objects.data();
+    unsigned long long todo = 0;
+    for (int i = 0; i < slots; i++)
+        if (((ctx->bits_still & ~ctx->bits_tried) >> i & 1ull) && objs[i].type == RPT_MESH) todo |= 1ull << i;
+    ctx->bits_tried |= ctx->bits_still;
+    if (!todo) return RPT_OK;
+    const size_t words = rptb::tiles::bitmap_words(ctx->width, ctx->height), bytes = (size_t)slots * words * 4;
+    if (bytes > ctx->tile_bits.host_capacity) ctx->bits_has = 0;      // (the pinned copy is replaced: the others' bitmaps go with it)
+    if (ctx->bits_has == 0) todo = ctx->bits_still;
+    void *host = nullptr;
+    if (int rc = staged_host(ctx, ctx->tile_bits, bytes, &host)) return rc;
+    bool any = false;
+    for (int i = 0; i < slots; i++) {
+        if (!(todo >> i & 1ull)) continue;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!build_tile_bitmap(ctx, objs[i], (uint32_t *)host + (size_t)i * words, nullptr)) continue;
+        ctx->bits_last_build_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        ctx->bits_has |= 1ull << i;
+        ctx->bits_builds++;
+        any = true;
+    }
+    if (any) return staged_copy(ctx, ctx->tile_bits);
+    return RPT_OK;
+}
+
 // What every frame's arguments hold whatever kernel renders it: the scene, the outputs, the per-frame constants, the rows and the camera
 // (launch() adds the colour, launch_events() the records).  One LensArgs serves every kernel: each reads its own prefix of it.
 void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
@@ -1235,15 +1387,16 @@ void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
     a.aspect = (float)ctx->width / (float)ctx->height;
     a.inv_width = 1.0f / (float)ctx->width;
     a.inv_height = 1.0f / (float)ctx->height;
-    // the diagonal slabs hold inside their window only (rpt_screen_bounds.hpp): frames up to 4 : 1, |v| <= 1/2 always
     a.diagonals = 0;
-    // (under a lens, rpt_set_field_of_view, the tiles' plane coordinates are those of the reference's lens times s <= 1 — a wider lens
-    // gets the un-culled kernel — so the same rule holds with both sides of the tile scaled)
     const bool lens = ctx->v_fov != 0.0f;
     a.lens_scale = lens ? ctx->lens_scale : 1.0f;
-    const float diag_reach = 0.5f * a.aspect + 2.0f * a.inv_height * a.aspect;
-    if ((lens ? a.lens_scale <= 1.0f && a.lens_scale * diag_reach <= (float)rptb::DIAG_WINDOW_U : diag_reach <= (float)rptb::DIAG_WINDOW_U) && ctx->rects.size() == (size_t)ctx->object_count)
+    if (frame_inside_diagonal_window(ctx) && ctx->rects.size() == (size_t)ctx->object_count)
         for (const rptb::Rect &r : ctx->rects) a.diagonals |= rptb::has_diagonals(r) ? 1 : 0;
+    // the tile bitmaps of the still meshes (ensure_tile_bits; the kernels of render_pixel_body that take the wave's object mask read them)
+    if (ctx->bits_has && ctx->tile_bits.device.ptr && tile_bits_current(ctx)) {
+        a.tile_bits = (const uint32_t *)ctx->tile_bits.device.ptr;
+        a.tile_bits_objects = ctx->bits_has;
+    }
     a.object_count = ctx->object_count;
     a.width = ctx->width;
     a.height = ctx->height;
@@ -1279,6 +1432,7 @@ int launch(rpt_ctx *ctx, Call call) {
             if (int rc = ensure_projection_tables(ctx, ctx->aa_pano, ctx->aa_n)) return rc;
     }
 
+    if (int rc = ensure_tile_bits(ctx)) return rc;
     rptd::LensArgs a;
     fill_frame_args(ctx, a);
     if (c.refine) a.plane = (uint32_t *)ctx->aa_plane.ptr;
@@ -1535,7 +1689,7 @@ void rpt_destroy(rpt_ctx *ctx) {
     for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits}) release(*u);
     if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
     if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
     if (ctx->overlay_host) (void)hipHostFree(ctx->overlay_host);
@@ -1585,42 +1739,8 @@ int rpt_upload_scene(rpt_ctx *ctx, const rpt_scene_desc *s) {
     ctx->geo->octree_tri_count = s->octree_tri_count;
     if (int rc = build_derived_geometry(ctx, *s)) return rc;
     ctx->geo->exact_rcp_ok = rpt_scene_exact_rcp(s) == 1;
-    ctx->geo->host_node_bounds.resize(s->octree_count * 6);
-    for (size_t i = 0; i < s->octree_count; i++) {
-        float *b = &ctx->geo->host_node_bounds[6 * i];
-        b[0] = s->octrees[i].min.x; b[1] = s->octrees[i].min.y; b[2] = s->octrees[i].min.z;
-        b[3] = s->octrees[i].max.x; b[4] = s->octrees[i].max.y; b[5] = s->octrees[i].max.z;
-    }
-    // Which nodes hold all of their triangles inside their own box?  (Asked of mesh roots by the shadow-segment cull: a hit on a
-    // triangle is a point of that triangle.)  Indices were validated above.
-    // ... and how large are those triangles?  K = max |e1| |e2|, L = the longest edge, with e1 = fl(B - A), e2 = fl(C - A) as the walk
-    // uses them: the float error of an accepted triangle hit is bounded through them (mesh_segment_apart, rpt_kernels.hip.h).
-    ctx->geo->node_holds_its_triangles.assign(s->octree_count, 0);
-    ctx->geo->node_tri_K.assign(s->octree_count, 0.0f);
-    ctx->geo->node_tri_L.assign(s->octree_count, 0.0f);
-    for (size_t i = 0; i < s->octree_count; i++) {
-        const rpt_octree &o = s->octrees[i];
-        bool inside = o.trisCount >= 0;
-        double K = 0.0, L = 0.0;
-        for (int k = o.trisIndex; inside && k < o.trisIndex + o.trisCount; k++) {
-            const int t = s->octreeTris[k];
-            const rpt_float3 *vv[3];
-            for (int c = 0; c < 3 && inside; c++) {
-                const rpt_float3 &v = s->vertices[s->triangles[9 * t + 3 * c]];
-                vv[c] = &v;
-                inside = v.x >= o.min.x && v.x <= o.max.x && v.y >= o.min.y && v.y <= o.max.y && v.z >= o.min.z && v.z <= o.max.z;
-            }
-            if (!inside) break;
-            const float e1[3] = {vv[1]->x - vv[0]->x, vv[1]->y - vv[0]->y, vv[1]->z - vv[0]->z}, e2[3] = {vv[2]->x - vv[0]->x, vv[2]->y - vv[0]->y, vv[2]->z - vv[0]->z};
-            const double l1 = std::sqrt((double)e1[0] * e1[0] + (double)e1[1] * e1[1] + (double)e1[2] * e1[2]);
-            const double l2 = std::sqrt((double)e2[0] * e2[0] + (double)e2[1] * e2[1] + (double)e2[2] * e2[2]);
-            K = std::max(K, l1 * l2);
-            L = std::max(L, std::max(l1, l2));
-        }
-        ctx->geo->node_holds_its_triangles[i] = inside ? 1 : 0;
-        ctx->geo->node_tri_K[i] = std::nextafter((float)K, INFINITY);
-        ctx->geo->node_tri_L[i] = std::nextafter((float)L, INFINITY);
-    }
+    host_mesh_facts(*ctx->geo, s, rptb::tiles::MAX_BOXES);
+    ctx->bits_still = ctx->bits_tried = ctx->bits_has = 0;
     ctx->scene_uploaded = true;
     const int rc = rpt_set_objects(ctx, s->objects, (int)s->object_count);
     if (rc) ctx->scene_uploaded = false;
@@ -1696,6 +1816,7 @@ static int set_objects_as_given(rpt_ctx *ctx, const void *objects, int count) {
         std::memcpy(slot, objects, bytes);
         build_dobjs(ctx, (const rpt_object *)objects, count, (rptd::DObj *)(slot + bytes));
         RPT_HOST_MARK(2);
+        note_still_objects(ctx, (const rpt_object *)objects, count);
         build_rects(ctx, (const rpt_object *)objects, count, (rptb::Rect *)(slot + bytes + (size_t)count * sizeof(rptd::DObj)));
         RPT_HOST_MARK(3);
         RPT_HIP(ctx, hipMemcpyAsync(ctx->objects.ptr, slot, bytes + dbytes, hipMemcpyHostToDevice, ctx->stream));
@@ -1706,6 +1827,7 @@ static int set_objects_as_given(rpt_ctx *ctx, const void *objects, int count) {
         ctx->staging_used |= 1u << k;
         ctx->staging_next++;
     }
+    if (!bytes) ctx->bits_still = ctx->bits_tried = ctx->bits_has = 0;
     ctx->object_count = count;
     ctx->has_mesh = false;
     for (int i = 0; i < count; i++) ctx->has_mesh = ctx->has_mesh || ((const rpt_object *)objects)[i].type == RPT_MESH;
@@ -1957,6 +2079,81 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
     const bool ok = rptb::cert::certify(*(const rpt_object *)object, interval, root_bounds_or_null, r, &st);
     if (stats_out) { stats_out[0] = st.reason; stats_out[1] = st.tests; stats_out[2] = st.max_depth; stats_out[3] = st.segments; }
     return ok ? 1 : 0;
+}
+
+// The tile bitmap of mesh object `object_index` of `scene` (its Object[] as it stands) for a frame, on the host alone: what a context
+// would put on the device for the same object, frame and lens.  boxes_or_null: n_boxes sub-tree boxes to use INSTEAD of the mesh's own
+// (tests: a broken box must never clear a tile).  1: built; 0: this object gets no bitmap; < 0: an error.
+// stats_out: boxes, boxes proven, tiles set, tiles, the depth of the cut.
+int rpt_tile_bitmap_host(const rpt_scene_desc *s, int object_index, int interval, int width, int height, float lens_scale, int max_boxes,
+                         const float *boxes_or_null, int n_boxes, uint32_t *bits_out, size_t words, int stats_out[5]) {
+    if (!s || !bits_out || object_index < 0 || (size_t)object_index >= s->object_count || width < 1 || height < 1 || max_boxes < 1) return -RPT_ERR_ARG;
+    if (words < rptb::tiles::bitmap_words(width, height)) return -RPT_ERR_ARG;
+    rpt_ctx tmp;
+    if (validate_geometry(&tmp, *s) != RPT_OK) return -RPT_ERR_SCENE;
+    const rpt_object &o = s->objects[object_index];
+    if (o.type == RPT_MESH && (o.meshIndex < 0 || (size_t)o.meshIndex >= s->octree_count)) return -RPT_ERR_SCENE;
+    tmp.geo = std::make_shared<Geometry>();
+    tmp.geo->compact_ok = true;
+    tmp.geo->octree_count = s->octree_count;
+    host_mesh_facts(*tmp.geo, s, max_boxes);
+    int depth = -1;
+    if (o.type == RPT_MESH) {
+        std::vector<float> own;
+        if (tmp.geo->mesh_boxes.count(o.meshIndex)) rptb::tiles::subtree_boxes(*s, o.meshIndex, max_boxes, own, &depth);
+        if (boxes_or_null && n_boxes > 0 && tmp.geo->mesh_boxes.count(o.meshIndex)) tmp.geo->mesh_boxes[o.meshIndex].assign(boxes_or_null, boxes_or_null + 6 * (size_t)n_boxes);
+    }
+    tmp.interval = interval;
+    tmp.width = width;
+    tmp.height = height;
+    tmp.v_fov = lens_scale == 1.0f ? 0.0f : 1.0f;       // (only "a lens is set" is read from it)
+    tmp.lens_scale = lens_scale;
+    rptb::tiles::Stats st{0, 0, 0, 0};
+    if (!window_holds_frame(&tmp)) return 0;
+    const bool ok = build_tile_bitmap(&tmp, o, bits_out, &st);
+    if (stats_out) { stats_out[0] = st.boxes; stats_out[1] = st.proven; stats_out[2] = st.tiles_set; stats_out[3] = st.tiles; stats_out[4] = depth; }
+    return ok ? 1 : 0;
+}
+
+// The context's tile bitmaps: out = {objects that have one on the device for the current frame, bitmaps built so far, host
+// microseconds of the last build, dwords per bitmap}; bits_or_null: the bitmap of `object_index` (the pinned copy the device's was made from)
+int rpt_tile_bitmap_state(rpt_ctx *ctx, unsigned long long out[4], int object_index, uint32_t *bits_or_null, size_t words) {
+    if (!ctx || !out) return RPT_ERR_ARG;
+    const bool current = ctx->params_set && tile_bits_current(ctx);
+    const size_t w = ctx->params_set ? rptb::tiles::bitmap_words(ctx->width, ctx->height) : 0;
+    out[0] = current ? ctx->bits_has : 0ull;
+    out[1] = ctx->bits_builds;
+    out[2] = (unsigned long long)(ctx->bits_last_build_us + 0.5);
+    out[3] = w;
+    if (bits_or_null) {
+        if (!current || object_index < 0 || object_index >= 64 || !(ctx->bits_has >> object_index & 1ull) || words < w || !ctx->tile_bits.host) return fail(ctx, RPT_ERR_ARG, "rpt_tile_bitmap_state: no bitmap for this object");
+        RPT_HIP(ctx, hipEventSynchronize(ctx->tile_bits.copied));
+        std::memcpy(bits_or_null, (const uint32_t *)ctx->tile_bits.host + (size_t)object_index * w, w * 4);
+    }
+    return RPT_OK;
+}
+
+// The object mask of every 8x8 tile of the current frame as the device forms it: out[2 t] before and out[2 t + 1] after the tile
+// bitmaps, t = ty * ceil(width / 8) + tx.  Prepares the frame as a launch does (a still mesh gets its bitmap here as there).
+int rpt_probe_tile_masks(rpt_ctx *ctx, unsigned long long *out, size_t tiles) {
+    if (!ctx || !out) return RPT_ERR_ARG;
+    if (!ctx->scene_uploaded || !ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_probe_tile_masks before rpt_upload_scene / rpt_set_params");
+    if (ctx->projection != RPT_PROJECTION_PINHOLE || !window_holds_frame(ctx)) return fail(ctx, RPT_ERR_ARG, "rpt_probe_tile_masks: this frame is not rendered with the object mask");
+    const int tx = (ctx->width + 7) / 8, ty = (ctx->height + 7) / 8;
+    if (tiles != (size_t)tx * ty) return fail(ctx, RPT_ERR_ARG, "rpt_probe_tile_masks: tiles != ceil(width / 8) * ceil(height / 8)");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure_tile_bits(ctx)) return rc;
+    rptd::LensArgs a;
+    fill_frame_args(ctx, a);
+    unsigned long long *d_out = nullptr;
+    RPT_HIP(ctx, hipMalloc((void **)&d_out, tiles * 16));
+    hipLaunchKernelGGL(rptd::rpt_probe_tile_masks_kernel, dim3(tx, ty), dim3(64), 0, ctx->stream, a, ctx->v_fov != 0.0f ? 1 : 0, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, tiles * 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(ctx, RPT_ERR_DEVICE, std::string("rpt_probe_tile_masks: ") + hipGetErrorString(e));
+    return RPT_OK;
 }
 
 int rpt_set_variant(rpt_ctx *ctx, int variant) {

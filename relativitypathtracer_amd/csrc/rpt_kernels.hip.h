@@ -111,7 +111,12 @@ struct KernelArgs {
     const DObj *dobjs;
     const int *links;               // DNode::link of every node again, 4 B apart: what a descent reads per level
     const DTri *first_tris;         // per node: the first triangle record of its leaf list again, addressable by the NODE's index
-    alignas(8) char reserved[20];   // unused (held two tables of removed measurement arms): keeps the fields below, and the kernels' code, in place
+    // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp; in the place of two tables of removed measurement arms, so that the
+    // fields below keep their offsets): bit i of tile_bits_objects = object i has one, at tile_bits + i * ceil(tiles / 32) dwords,
+    // bit ty * ceil(width / 8) + tx of it = 0: no primary ray of that 8x8 tile can report a hit of object i.  Null / 0: none.
+    const uint32_t *tile_bits;
+    unsigned long long tile_bits_objects;
+    int reserved;                   // unused
     int top_count;                  // nodes [0, top_count) are the forest's top levels (whole levels, <= RPT_TOP_MAX)
     // persistent kernels (rpt_persistent.hip.h): the band of tile rows that holds the meshes (first_ty, first_h above) is
     // claimed tile by tile from per-queue counters, the other rows are dealt statically in runs of RPT_SKY_RUN tiles
@@ -661,6 +666,7 @@ struct KernelPolicy {
     static constexpr bool exact_rcp = false;     // the triangle test's 1 / det through rcp_exact (the host picks it per scene)
     static constexpr bool culled = true;         // the wave's object mask (wave_object_mask) and the shadow-segment culls
     static constexpr bool object_mask = true;    // ... of which the object mask, proven on the pinhole's image plane only (culled && object_mask)
+    static constexpr bool tile_bits = true;      // ... which the tile bitmaps of the still meshes thin out further (clear_empty_tiles; needs culled && object_mask)
     static constexpr bool band_first = false;    // the band of tile rows that holds the meshes is dispatched first (KernelArgs::first_h)
     static constexpr bool one_wave = true;       // one wave (an 8x8 tile) per workgroup, not four (a 32x8 strip)
     static constexpr bool doppler = false;       // the Doppler twin (rpt_set_doppler; the arguments are a DopplerArgs)
@@ -674,7 +680,7 @@ struct Ballot : KernelPolicy {};                                                
 struct BallotExact : Ballot { static constexpr bool exact_rcp = true; };                                                        // 41
 struct BallotFirst : KernelPolicy { static constexpr Walk walk = Walk::latency; static constexpr bool band_first = true; };     // 49
 struct BallotFirstExact : BallotFirst { static constexpr bool exact_rcp = true; };                                              // 43
-struct Analytic : KernelPolicy { static constexpr Walk walk = Walk::none; };                                                    // 44
+struct Analytic : KernelPolicy { static constexpr Walk walk = Walk::none; static constexpr bool tile_bits = false; };           // 44 (no mesh, no bitmap)
 template <class P> struct DopplerTwin : P { static constexpr bool doppler = true; };                                            // 2xx, 5xx
 struct DopplerRecorded : DopplerTwin<Unculled> { static constexpr bool drec = true; };                                          // 240
 // the panorama kernels (rpt_set_projection): the equirectangular camera, no object mask (its regions live on the pinhole's plane), the
@@ -1249,6 +1255,35 @@ RPT_DEV unsigned long long wave_object_mask(const KernelArgs &a, int tile_x0, in
     return __ballot(keep);
 }
 
+// The tile bitmaps (rpt_tile_bitmap.hpp, where the proof is): a mesh the mask keeps for this tile is dropped where its bitmap says
+// that no primary ray of the tile can report a hit of it — the tiles between the mesh's silhouette and the octagon around its root box,
+// whose lanes would all walk the octree through empty leaves and miss.  Called only by a wave whose mask is not empty, with lanes
+// inside the frame (so the tile exists in the bitmap); everything here is wave-uniform: scalar loads of one dword per kept object.
+RPT_DEV unsigned long long clear_empty_tiles(const KernelArgs &a, unsigned long long object_mask, int tile_x0, int tile_y0) {
+    unsigned long long cand = object_mask & a.tile_bits_objects;
+    if (cand == 0) return object_mask;
+    const unsigned int tiles_x = (unsigned int)(a.width + 7) >> 3, tiles_y = (unsigned int)(a.height + 7) >> 3;
+    const unsigned int t = (unsigned int)(tile_y0 >> 3) * tiles_x + (unsigned int)(tile_x0 >> 3);
+    const unsigned int words = (tiles_x * tiles_y + 31u) >> 5;
+    while (cand) {
+        const int i = __builtin_ctzll(cand);
+        cand &= cand - 1;
+        const uint32_t w = a.tile_bits[(size_t)i * words + (t >> 5)];
+        if (!((w >> (t & 31u)) & 1u)) object_mask &= ~(1ull << i);
+    }
+    return object_mask;
+}
+
+// ... for the kernels whose policy says so (KernelPolicy::tile_bits), and only in a wave whose mask is not empty: every other wave
+// executes nothing new.  render_pixel_body and the probe of rpt_probe_tile_masks go through this one function.
+template <class P>
+RPT_DEV unsigned long long thin_object_mask(const KernelArgs &a, unsigned long long object_mask, int tile_x0, int tile_y0) {
+    if constexpr (P::culled && P::object_mask && P::tile_bits && P::camera != Camera::equirect && P::diag == 0) {
+        if (object_mask != 0) object_mask = clear_empty_tiles(a, object_mask, tile_x0, tile_y0);
+    }
+    return object_mask;
+}
+
 // The same under a lens (Camera::lens): pixel (x, y) looks through the plane point (fl(s fx2), fl(s fy2)), so the tile's four plane
 // coordinates are scaled by s as well.  What the mask needs is that every pixel's plane point lies inside its tile's grown range; the
 // regions themselves are statements about real plane points of the proven window, whatever rounding produced them
@@ -1324,6 +1359,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     if (P::diag == 10) object_mask = a.tile_masks[__builtin_amdgcn_readfirstlane(tile_row * a.mask_tiles_x + (int)blockIdx.x * 4 + wave)];   // the prepass's per-tile mask
 #endif
     if (x_coord >= a.width || y_coord >= a.height) return;   // the reference has no guard (UB)
+    object_mask = thin_object_mask<P>(a, object_mask, strip * 32 + wave * 8, global_tile * RPT_TILE_ROWS);
 
     f3 color;
     f3 mapped = mk3(0.0f, 0.0f, 0.0f);
@@ -2032,6 +2068,19 @@ __global__ __launch_bounds__(256) void rpt_scatter_helper_planes3_kernel(const u
 }
 
 // rpt_verify_frame: how many packed colours differ between two colour planes (one ballot + popcount per wave-iteration)
+// rpt_probe_tile_masks: one wave per 8x8 tile of the whole frame forms the object mask as kernel 41 (under a lens: 841) does — the
+// ballot over the regions, then thin_object_mask with the same policy — and writes it before and after the tile bitmaps.
+__global__ __launch_bounds__(64) void rpt_probe_tile_masks_kernel(const LensArgs a, int lens, unsigned long long *out) {
+    const int x0 = (int)blockIdx.x * 8, y0 = (int)blockIdx.y * RPT_TILE_ROWS;
+    const unsigned long long before = lens ? wave_object_mask_lens(a, a.lens_scale, x0, y0) : wave_object_mask(a, x0, y0);
+    const unsigned long long after = lens ? thin_object_mask<Lens<BallotExact>>(a, before, x0, y0) : thin_object_mask<BallotExact>(a, before, x0, y0);
+    if (threadIdx.x == 0) {
+        const size_t t = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+        out[2 * t] = before;
+        out[2 * t + 1] = after;
+    }
+}
+
 __global__ __launch_bounds__(256) void rpt_count_differences_kernel(const uint32_t *p, const uint32_t *q, size_t words, unsigned long long *out) {
     unsigned long long mine = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) mine += __popcll(__ballot(p[i] != q[i]));
