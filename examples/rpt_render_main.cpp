@@ -3,11 +3,17 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] [--overlay SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
 // context, made once, BEFORE the objects are handed over; the per-frame loop stays the reference's.
+//
+// --projection fisheye[:FOV_DEG[:fit]] | equisolid[:FOV_DEG[:fit]] | stereographic[:FOV_DEG[:fit]] | cube_strip renders through a ray map
+// (rpt_raymap_fill, rpt_set_raymap, RPT_PROJECTION_RAYMAP; not in the reference): an equidistant or equisolid fisheye or the stereographic
+// view, FOV_DEG degrees across the image circle (default 180), which fit = 0 (the default) inscribes in the frame and fit = 1 stretches to
+// its diagonal; or the six faces of a cube side by side (width = 6 height).  Pixels outside the image circle are black.  A setting of
+// the render context like the others; it composes with --yaw / --pitch / --roll and excludes --fov and --aa.
 //
 // --aa N[:T] switches adaptive anti-aliasing on (rpt_set_adaptive_aa; not in the reference): N x N samples in every pixel whose 8-bit
 // colour differs from a 4-neighbour's by more than T (default 8; -1 = every pixel) in the one-sample frame.  A setting of the render
@@ -96,11 +102,54 @@ static bool parse_overlay(const char *spec, rpt_overlay_desc *d) {
     return true;
 }
 
+// --projection's value into a filled ray map of width x height; false (and a message on stderr) if it cannot be read or filled
+static bool parse_projection(const char *spec, int width, int height, std::vector<float> *dirs) {
+    static const char *const usage = "fisheye[:FOV_DEG[:fit]], equisolid[:FOV_DEG[:fit]], stereographic[:FOV_DEG[:fit]] or cube_strip";
+    std::vector<std::string> part;
+    const std::string all(spec);
+    for (size_t q = 0; q <= all.size();) {
+        const size_t colon = std::min(all.find(':', q), all.size());
+        part.push_back(all.substr(q, colon - q));
+        q = colon + 1;
+    }
+    const std::string &name = part[0];
+    const int kind = name == "fisheye" ? RPT_RAYMAP_FISHEYE : name == "equisolid" ? RPT_RAYMAP_FISHEYE_EQUISOLID : name == "stereographic" ? RPT_RAYMAP_STEREOGRAPHIC : name == "cube_strip" ? RPT_RAYMAP_CUBE_STRIP : -1;
+    if (kind < 0) {
+        std::fprintf(stderr, "--projection: unknown projection '%s' (%s)\n", name.c_str(), usage);
+        return false;
+    }
+    if (part.size() > (kind == RPT_RAYMAP_CUBE_STRIP ? 1u : 3u)) {
+        std::fprintf(stderr, "--projection: '%s' has too many values (%s)\n", spec, usage);
+        return false;
+    }
+    float params[2] = {(float)3.14159265358979323846, 0.0f};
+    for (size_t k = 1; k < part.size(); k++) {
+        char *end = nullptr;
+        const double v = std::strtod(part[k].c_str(), &end);
+        if (part[k].empty() || *end != '\0' || !std::isfinite(v)) {
+            std::fprintf(stderr, "--projection: '%s' in '%s' is not a number\n", part[k].c_str(), spec);
+            return false;
+        }
+        params[k - 1] = k == 1 ? (float)(v * 3.14159265358979323846 / 180.0) : (float)v;
+    }
+    if (width < 1 || height < 1 || 3ll * width * height >= (1ll << 31)) {
+        std::fprintf(stderr, "--projection: no ray map of %d x %d\n", width, height);
+        return false;
+    }
+    dirs->resize((size_t)width * height * 3);
+    if (rpt_raymap_fill(kind, kind == RPT_RAYMAP_CUBE_STRIP ? nullptr : params, width, height, dirs->data()) != RPT_OK) {
+        if (kind == RPT_RAYMAP_CUBE_STRIP) std::fprintf(stderr, "--projection: cube_strip needs width = 6 height, not %d x %d\n", width, height);
+        else std::fprintf(stderr, "--projection: '%s' is out of range (FOV_DEG in (0, 360], below 360 for stereographic; fit 0 or 1)\n", spec);
+        return false;
+    }
+    return true;
+}
+
 int main(int argc, char **argv) {
     // the free-look options (degrees), taken out of argv; what is left is positional
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
-    const char *events_path = nullptr;
+    const char *events_path = nullptr, *projection_spec = nullptr;
     int aa_n = 1, aa_threshold = 8;
     rpt_overlay_desc overlay;
     std::memset(&overlay, 0, sizeof overlay);
@@ -114,6 +163,11 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--roll")) { ypr[2] = (float)(std::atof(argv[++i]) * deg); turned = true; }
             else if (has_value && !std::strcmp(argv[i], "--fov")) v_fov = (float)(std::atof(argv[++i]) * deg);
             else if (has_value && !std::strcmp(argv[i], "--events")) events_path = argv[++i];
+            else if (has_value && !std::strcmp(argv[i], "--projection")) projection_spec = argv[++i];
+            else if (!std::strcmp(argv[i], "--projection")) {
+                std::fprintf(stderr, "--projection needs a value: fisheye[:FOV_DEG[:fit]], equisolid[:FOV_DEG[:fit]], stereographic[:FOV_DEG[:fit]] or cube_strip\n");
+                return 2;
+            }
             else if (has_value && !std::strcmp(argv[i], "--overlay")) {
                 if (!parse_overlay(argv[++i], &overlay)) return 2;
             } else if (!std::strcmp(argv[i], "--overlay")) {
@@ -143,10 +197,12 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--aa N[:T]] [--events FILE] [--overlay SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
+    std::vector<float> raymap;                                   // --projection: the map, filled on the host (no device needed)
+    if (projection_spec && !parse_projection(projection_spec, width, height, &raymap)) return 2;
     const std::string text((std::istreambuf_iterator<char>(std::cin)), std::istreambuf_iterator<char>());
 
     rpt_scene *scene = rpt_scene_create();                       // inputScene()            main.cpp:31
@@ -176,6 +232,8 @@ int main(int argc, char **argv) {
     if (turned) rc = rpt_set_orientation(ctx, ypr);              // the context's view: before any Object[] is handed over
     if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ctx, v_fov);
     if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ctx, aa_n, aa_threshold);
+    if (!rc && !raymap.empty()) rc = rpt_set_raymap(ctx, raymap.data(), width, height);
+    if (!rc && !raymap.empty()) rc = rpt_set_projection(ctx, RPT_PROJECTION_RAYMAP, nullptr);
     if (!rc) rc = rpt_upload_scene(ctx, &desc);                  // 8x cl::Buffer + write    main.cpp:33-55
     if (!rc) rc = rpt_set_params(ctx, wp, ambient, width, height, interval);   // initCLKernel()  main.cpp:62
     if (!rc) rc = rpt_set_output(ctx, nullptr);                  // BufferGL(vbo)           main.cpp:58
@@ -198,6 +256,8 @@ int main(int argc, char **argv) {
             if (turned) rc = rpt_set_orientation(ring.slot(k), ypr);
             if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ring.slot(k), v_fov);
             if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ring.slot(k), aa_n, aa_threshold);
+            if (!rc && !raymap.empty()) rc = rpt_set_raymap(ring.slot(k), raymap.data(), width, height);      // (the map is per context: every slot its copy)
+            if (!rc && !raymap.empty()) rc = rpt_set_projection(ring.slot(k), RPT_PROJECTION_RAYMAP, nullptr);
         }
         if (!rc) rc = ring.upload(desc);
         if (!rc) rc = ring.set_params(wp, ambient, width, height, interval);

@@ -38,7 +38,9 @@
  * colour mode (the reference's MSAASAMPLES is a compile-time constant, 1 as shipped): rpt_set_adaptive_aa, rpt_last_aa_refined and
  * rpt_last_aa_variant ("Adaptive anti-aliasing"), and the opt-in overlay pass — outlines, isochrones, rest-frame grids and a tint
  * by light delay drawn on the rendered frame from the event records: rpt_set_overlay, rpt_render_overlay / rpt_render_overlay_async and
- * rpt_last_overlay_pixels ("Overlay pass").
+ * rpt_last_overlay_pixels ("Overlay pass"), and the opt-in ray-map camera — one direction per pixel, for fisheyes, the
+ * stereographic view, cube strips and calibrated lenses: rpt_set_raymap, RPT_PROJECTION_RAYMAP and rpt_raymap_fill (host code, no device
+ * needed; DESIGN.md, "Ray-map camera").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -165,6 +167,60 @@ int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params);
  * cos lambda_x}, rows_out 2 H floats {sin phi_y, cos phi_y}.  mode must be RPT_PROJECTION_EQUIRECT (the pinhole has no tables), params
  * as for rpt_set_projection, 1 <= W, H and W H < 2^31; anything else is RPT_ERR_ARG. */
 int rpt_projection_tables(int mode, const float *params, int width, int height, float *cols_out, float *rows_out);
+
+/* The ray-map camera (not in the reference; DESIGN.md "Ray-map camera"): one direction per pixel, for the views that are not a function
+ * of the column times a function of the row — fisheyes and dome masters, the stereographic view, a cube strip, a calibrated lens.
+ * rpt_set_projection(ctx, RPT_PROJECTION_RAYMAP, NULL) selects it (params must be NULL); the directions are the context's map, which is
+ * set FIRST: on a context that holds no map the call is RPT_ERR_ARG, as it was for every context before this camera existed.  (A map
+ * dropped afterwards, or one of another size than the frame, is refused at the launch, below.)
+ *
+ * rpt_set_raymap: dirs3 holds width * height * 3 floats, row-major, row 0 the bottom as everywhere.  The map is COPIED and uploaded in
+ * stream order (a frame in flight keeps the map it was launched with; the next launch sees the new one); it is per context and not shared
+ * by rpt_share_scene; NULL drops it.  Pixel (x, y) looks along normalize(p), p = dirs3[3 (y W + x) ..], the float normalize of the
+ * pinhole and the panorama.  p == (0, 0, 0), and only that, means the pixel has NO RAY: it is written as {x, y, rgba = 0, 0, 0, 1} —
+ * black, with the constant alpha byte of every pixel — with a zero debug_rgb triple, whatever the colour mode, and it is a miss record in
+ * the event pass.  A non-finite component, width < 1, height < 1 or 3 width height >= 2^31 is RPT_ERR_ARG at the call.
+ * With RPT_PROJECTION_RAYMAP set, rpt_render / rpt_render_async / rpt_verify_frame / rpt_render_events[_async] return RPT_ERR_ARG at the
+ * LAUNCH, with a message that starts "rpt_set_raymap:", while no map is set or the map's size is not the frame's; nothing is launched and
+ * the context stays usable.  A turned camera composes as in panorama (p looks along R p); the sky's matrix, rows, tile patterns, the
+ * colour plane, frames in flight and external streams need nothing: the map is addressed by global pixel.
+ * Kernels (rpt_last_variant), each the panorama kernel of the same place with the direction read from the map — no object mask, the
+ * shadow-ray culls kept:
+ *
+ *   colour \ form     un-culled   octree walk (IEEE form as for 41)   no mesh in Object[]
+ *   plain              1203        1241                                1244
+ *   Doppler twins      1213        1251                                1254
+ *   environment        1223        1261                                1264
+ *   event pass         (none)      1291                                1294               (rpt_last_events_variant)
+ *
+ * Variants 0, 41, 43 and 44 get the walk (or the last column without a mesh), variant 3 the un-culled form, which is what rpt_verify_frame
+ * compares with.  Refused at the LAUNCH with RPT_ERR_ARG: a lens (rpt_set_field_of_view: the map has its own field of view), MSAA > 1,
+ * adaptive anti-aliasing (message "rpt_set_adaptive_aa: ...": a map has no directions between its pixels), every other variant, the
+ * Doppler debug kernel, and an octree whose children are not consecutive (unless Object[] holds no mesh). */
+#define RPT_PROJECTION_RAYMAP 2
+int rpt_set_raymap(rpt_ctx *ctx, const float *dirs3, int width, int height);
+/* Host code, no device: fills dirs3_out (width * height * 3 floats, the layout above) with a standard map, everything evaluated in
+ * double from the float parameters and rounded to float once per component.  With X = (2 (x + 0.5) - W) / S, Y = (2 (y + 0.5) - H) / S
+ * and rho = sqrt(X^2 + Y^2), the azimuthal kinds take params = {fov, fit}: fit = 0 puts the image circle inside the frame, S = min(W, H);
+ * fit = 1 makes it the frame's diagonal, S = sqrt(W^2 + H^2).  rho > 1 has no ray, (0, 0, 0); rho = 0 is (0, 0, 1); otherwise
+ * p = (sin theta X / rho, sin theta Y / rho, cos theta) with
+ *   RPT_RAYMAP_FISHEYE            theta = rho fov / 2                      (equidistant)      fov in (0, 2 pi]
+ *   RPT_RAYMAP_FISHEYE_EQUISOLID  theta = 2 asin(rho sin(fov / 4))                            fov in (0, 2 pi]
+ *   RPT_RAYMAP_STEREOGRAPHIC      theta = 2 atan(rho tan(fov / 4))                            fov in (0, 2 pi), the float nearest 2 pi excluded
+ * RPT_RAYMAP_CUBE_STRIP (params NULL, W = 6 H): six square faces side by side, from the left +x, -x, +y, -y, +z, -z, each a 90-degree
+ * pinhole: with a = (2 (x - f H + 0.5) - H) / H, b = (2 (y + 0.5) - H) / H pixel (x, y) of face f has p = forward + a right + b up,
+ *   face      +x          -x          +y          -y          +z          -z
+ *   forward   ( 1, 0, 0)  (-1, 0, 0)  ( 0, 1, 0)  ( 0,-1, 0)  ( 0, 0, 1)  ( 0, 0,-1)
+ *   right     ( 0, 0,-1)  ( 0, 0, 1)  ( 1, 0, 0)  ( 1, 0, 0)  ( 1, 0, 0)  (-1, 0, 0)
+ *   up        ( 0, 1, 0)  ( 0, 1, 0)  ( 0, 0,-1)  ( 0, 0, 1)  ( 0, 1, 0)  ( 0, 1, 0)
+ * (the frame of a viewer standing inside the cube with +y up; the library's axes are left-handed: +x is on the right of +z).  A kind that
+ * is none of these, a fov outside its range, a fit that is neither 0 nor 1, params where NULL is asked for (or the reverse), W != 6 H for
+ * the strip, width < 1, height < 1, 3 W H >= 2^31 or a null output: RPT_ERR_ARG. */
+#define RPT_RAYMAP_FISHEYE 0
+#define RPT_RAYMAP_FISHEYE_EQUISOLID 1
+#define RPT_RAYMAP_STEREOGRAPHIC 2
+#define RPT_RAYMAP_CUBE_STRIP 3
+int rpt_raymap_fill(int kind, const float *params, int width, int height, float *dirs3_out);
 
 /* The sky (not in the reference; DESIGN.md "Environment map"), per context, off by default, not shared by rpt_share_scene.
  * rgb8 is an equirectangular image of width x height interleaved R, G, B bytes, row 0 the top (+y), as object textures are; it is

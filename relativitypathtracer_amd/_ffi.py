@@ -188,6 +188,8 @@ HIP_SYMBOLS = {
     "rpt_read_debug_doppler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_set_projection": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "rpt_projection_tables": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rpt_set_raymap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "rpt_raymap_fill": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
     "rpt_set_environment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "rpt_set_environment_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_set_orientation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),

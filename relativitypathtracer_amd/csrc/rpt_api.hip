@@ -159,6 +159,10 @@ struct rpt_ctx {
     int projection = RPT_PROJECTION_PINHOLE;
     float projection_params[3] = {0, 0, 0};           // {h_fov, v_fov, yaw} of the equirectangular camera
     ProjectionTables pano;                            // the frame's tables
+    // rpt_set_raymap (not in the reference): the ray-map camera's directions, per context, never shared
+    bool raymap_on = false;
+    int raymap_width = 0, raymap_height = 0, raymap_pitch = 0;
+    StagedUpload raymap;                              // [raymap_pitch * raymap_height] float4 {p.x, p.y, p.z, 0}, pitch = width rounded up to 8
     // rpt_set_environment / rpt_set_environment_frame (not in the reference): the sky image, per context, never shared
     bool env_on = false;
     int env_width = 0, env_height = 0;
@@ -995,6 +999,9 @@ static_assert(rptd::BallotFirstExact::band_first && rptd::BallotFirst::band_firs
 static_assert(rptd::Lens<rptd::Environment<rptd::BallotFirstExact>>::band_first && rptd::Lens<rptd::DopplerTwin<rptd::BallotFirst>>::band_first &&
               !rptd::Lens<rptd::Environment<rptd::BallotExact>>::band_first && !rptd::PanoramaWalk::band_first,
               "the camera and colour policies keep the band_first of the form they wrap (the panorama has no band-first form)");
+static_assert(!rptd::Raymap<rptd::BallotExact>::band_first && !rptd::Raymap<rptd::BallotExact>::object_mask && !rptd::Raymap<rptd::Ballot>::tile_bits &&
+              rptd::DopplerTwin<rptd::Raymap<rptd::Ballot>>::culled && !rptd::Environment<rptd::Raymap<rptd::Unculled>>::culled,
+              "the ray-map policies: no band-first form, no object mask, no tile bitmaps; the shadow-segment culls of the form they wrap");
 // ... culls with the per-object screen regions, which are PROVEN inside their window only (the relaxed builds cull with the same regions
 // but keep culling outside the window: a known gap, ADVICE.md, third item, kept as it is here)
 constexpr bool needs_proven_window(Form f) { return f == Form::walk || f == Form::walk_first || f == Form::analytic || f == Form::ieee || f == Form::ieee_first; }
@@ -1055,6 +1062,16 @@ const KernelRow colour_table[] = {
     {861, Camera::lens,     Colour::sky,     Form::walk,          RPT_KERNEL(rpt_render_kernel_lens_env_ballot_w5),         RPT_KERNEL(rpt_render_kernel_lens_env_ballot_ieee_w5)},
     {863, Camera::lens,     Colour::sky,     Form::walk_first,    RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_w5),   RPT_KERNEL(rpt_render_kernel_lens_env_ballot_first_ieee_w5)},
     {864, Camera::lens,     Colour::sky,     Form::analytic,      RPT_KERNEL(rpt_render_kernel_lens_env_analytic_w8),       nullptr},
+    // the ray-map camera (rpt_set_raymap): as the panorama, no band-first form and no forced-IEEE arms; no record form
+    {1203, Camera::raymap,  Colour::plain,   Form::unculled,      RPT_KERNEL(rpt_render_kernel_raymap_unculled_w5),         nullptr},
+    {1241, Camera::raymap,  Colour::plain,   Form::walk,          RPT_KERNEL(rpt_render_kernel_raymap_walk_w5),             RPT_KERNEL(rpt_render_kernel_raymap_walk_ieee_w5)},
+    {1244, Camera::raymap,  Colour::plain,   Form::analytic,      RPT_KERNEL(rpt_render_kernel_raymap_analytic_w8),         nullptr},
+    {1213, Camera::raymap,  Colour::doppler, Form::unculled,      RPT_KERNEL(rpt_render_kernel_raymap_doppler_unculled_w5), nullptr},
+    {1251, Camera::raymap,  Colour::doppler, Form::walk,          RPT_KERNEL(rpt_render_kernel_raymap_doppler_walk_w5),     RPT_KERNEL(rpt_render_kernel_raymap_doppler_walk_ieee_w5)},
+    {1254, Camera::raymap,  Colour::doppler, Form::analytic,      RPT_KERNEL(rpt_render_kernel_raymap_doppler_analytic_w8), nullptr},
+    {1223, Camera::raymap,  Colour::sky,     Form::unculled,      RPT_KERNEL(rpt_render_kernel_raymap_env_unculled_w5),     nullptr},
+    {1261, Camera::raymap,  Colour::sky,     Form::walk,          RPT_KERNEL(rpt_render_kernel_raymap_env_walk_w5),         RPT_KERNEL(rpt_render_kernel_raymap_env_walk_ieee_w5)},
+    {1264, Camera::raymap,  Colour::sky,     Form::analytic,      RPT_KERNEL(rpt_render_kernel_raymap_env_analytic_w8),     nullptr},
 };
 
 // The refine kernels (rpt_set_adaptive_aa), variant 1000 + 10 (3 camera + colour) + {1 walk, 3 un-culled, 4 no walk}.  The form is pass
@@ -1087,6 +1104,8 @@ const KernelRow events_table[] = {
     {923, Camera::lens,     Colour::plain, Form::unculled, RPT_KERNEL(rpt_events_kernel_lens_unculled), nullptr},
     {921, Camera::lens,     Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_lens_ballot),   RPT_KERNEL(rpt_events_kernel_lens_ballot_ieee)},
     {924, Camera::lens,     Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_lens_analytic), nullptr},
+    {1291, Camera::raymap,  Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_raymap),        RPT_KERNEL(rpt_events_kernel_raymap_ieee)},
+    {1294, Camera::raymap,  Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_raymap_analytic), nullptr},
 };
 #undef RPT_KERNEL
 
@@ -1128,6 +1147,15 @@ bool small_frame(const rpt_ctx *ctx) {
     return (size_t)local_tile_count(ctx) * RPT_TILE_ROWS * (size_t)ctx->width <= (size_t)RPT_LATENCY_KERNEL_MAX_PIXELS;
 }
 
+// The ray-map camera (rpt_set_projection with RPT_PROJECTION_RAYMAP): what a launch needs of the map; "" = nothing is missing
+std::string raymap_missing(const rpt_ctx *ctx) {
+    if (!ctx->raymap_on) return "rpt_set_raymap: RPT_PROJECTION_RAYMAP is set but the context has no ray map";
+    if (ctx->raymap_width != ctx->width || ctx->raymap_height != ctx->height)
+        return "rpt_set_raymap: the map is " + std::to_string(ctx->raymap_width) + " x " + std::to_string(ctx->raymap_height) + ", the frame " +
+               std::to_string(ctx->width) + " x " + std::to_string(ctx->height);
+    return "";
+}
+
 // the Doppler debug kernel stands in for every twin while the record hook is set (rpt_set_debug_doppler)
 bool doppler_recording(const rpt_ctx *ctx) { return ctx->doppler && (ctx->external_doppler || ctx->want_owned_doppler); }
 
@@ -1165,11 +1193,16 @@ Choice choose_event_kernel(const rpt_ctx *ctx) {
     if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_render_events: MSAA > 1 has no event kernel (one primary ray per pixel)");
     if (!has_product_forms(ctx->variant))
         return refuse(RPT_ERR_ARG, "rpt_render_events: variant " + std::to_string(ctx->variant) + " has no event kernel (variants 0, 3, 41, 43 and 44 have)");
-    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE, lens = ctx->v_fov != 0.0f;
+    const bool panorama = ctx->projection == RPT_PROJECTION_EQUIRECT, raymap = ctx->projection == RPT_PROJECTION_RAYMAP, lens = ctx->v_fov != 0.0f;
     if (lens && panorama) return refuse(RPT_ERR_ARG, "rpt_render_events: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
-    const Camera camera = panorama ? Camera::equirect : (lens ? Camera::lens : Camera::pinhole);
+    if (lens && raymap) return refuse(RPT_ERR_ARG, "rpt_render_events: the ray map has a field of view of its own (rpt_set_raymap); a lens needs the pinhole");
+    if (raymap) {
+        const std::string missing = raymap_missing(ctx);
+        if (!missing.empty()) return refuse(RPT_ERR_ARG, missing);
+    }
+    const Camera camera = panorama ? Camera::equirect : (raymap ? Camera::raymap : (lens ? Camera::lens : Camera::pinhole));
     Form form = !ctx->has_mesh ? Form::analytic : Form::walk;
-    if (camera != Camera::equirect && (ctx->variant == 3 || !window_holds_frame(ctx))) form = Form::unculled;
+    if (camera != Camera::equirect && camera != Camera::raymap && (ctx->variant == 3 || !window_holds_frame(ctx))) form = Form::unculled;
     if (!ctx->geo->compact_ok && form != Form::analytic)
         return refuse(RPT_ERR_ARG, "rpt_render_events: the event kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
     Choice c;
@@ -1186,10 +1219,11 @@ Choice choose_kernels(const rpt_ctx *ctx, Call call) {
     if (!ctx->scene_uploaded) return refuse(RPT_ERR_STATE, "rpt_render before rpt_upload_scene");
     if (!ctx->params_set) return refuse(RPT_ERR_STATE, "rpt_render before rpt_set_params");
     const int sv = ctx->variant;
-    const bool lens = ctx->v_fov != 0.0f, panorama = ctx->projection != RPT_PROJECTION_PINHOLE, recording = doppler_recording(ctx);
+    const bool lens = ctx->v_fov != 0.0f, panorama = ctx->projection == RPT_PROJECTION_EQUIRECT, raymap = ctx->projection == RPT_PROJECTION_RAYMAP, recording = doppler_recording(ctx);
     // Adaptive anti-aliasing (rpt_set_adaptive_aa): what it cannot serve refuses first
     const bool adaptive = call.colour_frame && ctx->aa_n > 1;
     if (adaptive) {
+        if (raymap) return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: the ray-map camera (rpt_set_raymap) has no refine pass: a map holds one direction per pixel, none between them");
         if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: rpt_set_msaa > 1 is set as well (full supersampling is threshold -1 here)");
         if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->run_log2 != 0 || ctx->colour_plane)
             return refuse(RPT_ERR_ARG, "rpt_set_adaptive_aa: this context renders a share of the frame's rows or a colour plane (rpt_set_rows / rpt_set_tile_pattern): the neighbour rows belong to another rank");
@@ -1220,6 +1254,7 @@ Choice choose_kernels(const rpt_ctx *ctx, Call call) {
     // the launch, so that the settings may be made in any order
     if (lens) {
         if (panorama) return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: the panorama has fields of view of its own (rpt_set_projection); a lens needs the pinhole");
+        if (raymap) return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: the ray map has a field of view of its own (rpt_set_raymap); a lens needs the pinhole");
         if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: MSAA > 1 has no lens kernel");
         if (!has_product_forms(sv))
             return refuse(RPT_ERR_ARG, "rpt_set_field_of_view: variant " + std::to_string(sv) + " has no lens kernel (variants 0, 3, 41, 43 and 44 have)");
@@ -1235,6 +1270,17 @@ Choice choose_kernels(const rpt_ctx *ctx, Call call) {
         camera = Camera::equirect;
         if (!find_row(colour_table, camera, Colour::plain, form))
             return refuse(RPT_ERR_ARG, "rpt_set_projection: the panorama kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+    } else if (raymap) {  // variant 0's choice, the forms it can resolve to, and variant 3; nothing of the pinhole's window applies
+        const std::string missing = raymap_missing(ctx);
+        if (!missing.empty()) return refuse(RPT_ERR_ARG, missing);
+        if (!has_product_forms(sv))
+            return refuse(RPT_ERR_ARG, "rpt_set_raymap: variant " + std::to_string(sv) + " has no ray-map kernel (variants 0, 3, 41, 43 and 44 have)");
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_raymap: MSAA > 1 has no ray-map kernel");
+        if (recording) return refuse(RPT_ERR_ARG, "rpt_set_raymap: the Doppler debug kernel (rpt_set_debug_doppler) has no ray-map form");
+        if (form == Form::walk_first) form = Form::walk;
+        camera = Camera::raymap;
+        if (!find_row(colour_table, camera, Colour::plain, form))
+            return refuse(RPT_ERR_ARG, "rpt_set_raymap: the ray-map kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
     } else if (needs_proven_window(form) && !window_holds_frame(ctx)) {
         form = Form::unculled;
     }
@@ -1352,7 +1398,7 @@ int ensure_tile_bits(rpt_ctx *ctx) {
 // What every frame's arguments hold whatever kernel renders it: the scene, the outputs, the per-frame constants, the rows and the camera
 // (launch() adds the colour, launch_events() the records).  One LensArgs serves every kernel: each reads its own prefix of it.
 void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
-    std::memset(&a, 0, sizeof a);
+    std::memset((void *)&a, 0, sizeof a);
     a.dnodes = (const rptd::DNode *)ctx->geo->dnodes.ptr;
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
     a.links = (const int *)ctx->geo->dlinks.ptr;
@@ -1404,7 +1450,7 @@ void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
     a.first_tile = ctx->first_tile;
     a.tile_step = ctx->tile_step;
     a.run_log2 = ctx->run_log2;
-    if (ctx->projection != RPT_PROJECTION_PINHOLE) {      // (the caller has made them this frame's: ensure_projection_tables)
+    if (ctx->projection == RPT_PROJECTION_EQUIRECT) {     // (the caller has made them this frame's: ensure_projection_tables)
         a.pano_cols = (const float2 *)ctx->pano.upload.device.ptr;
         a.pano_rows = a.pano_cols + ctx->width;
     }
@@ -1425,7 +1471,7 @@ int launch(rpt_ctx *ctx, Call call) {
         if (!ctx->aa_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->aa_counted, hipEventDisableTiming));
     }
     if (c.nothing) return RPT_OK;
-    const bool panorama = ctx->projection != RPT_PROJECTION_PINHOLE;
+    const bool panorama = ctx->projection == RPT_PROJECTION_EQUIRECT;
     if (panorama) {
         if (int rc = ensure_projection_tables(ctx, ctx->pano, 1)) return rc;
         if (c.refine)
@@ -1433,8 +1479,10 @@ int launch(rpt_ctx *ctx, Call call) {
     }
 
     if (int rc = ensure_tile_bits(ctx)) return rc;
-    rptd::LensArgs a;
+    rptd::RaymapArgs a;         // (one block serves every render kernel: each reads its own prefix of it)
     fill_frame_args(ctx, a);
+    a.raymap = c.colour && c.colour->camera == Camera::raymap ? (const float4 *)ctx->raymap.device.ptr : nullptr;     // (choose_kernels has checked it against the frame)
+    a.raymap_pitch = ctx->raymap_pitch;
     if (c.refine) a.plane = (uint32_t *)ctx->aa_plane.ptr;
     if (c.band_first) set_band_first(ctx, a, tiles);
     a.msaa = ctx->msaa;
@@ -1469,7 +1517,7 @@ int launch(rpt_ctx *ctx, Call call) {
     if (c.refine) {               // pass B, behind pass A on the same stream; then the counter's way home, in stream order
         rptd::RefineArgs ra;
         std::memset(&ra, 0, sizeof ra);
-        static_cast<rptd::LensArgs &>(ra) = a;
+        static_cast<rptd::LensArgs &>(ra) = static_cast<const rptd::LensArgs &>(a);
         ra.plane = nullptr;           // (pass B writes the framebuffer and debug_rgb only: the plane is what its neighbours still read)
         ra.aa_plane = (const uint32_t *)ctx->aa_plane.ptr;
         ra.aa_refined = (unsigned long long *)ctx->aa_counter.ptr;
@@ -1511,11 +1559,13 @@ int launch_events(rpt_ctx *ctx) {
         if (int rc = reserve(ctx, ctx->owned_events, px * sizeof(rpt_event))) return rc;
         RPT_HIP(ctx, hipMemsetAsync(ctx->owned_events.ptr, 0, px * sizeof(rpt_event), ctx->stream));
     }
-    if (ctx->projection != RPT_PROJECTION_PINHOLE)
+    if (ctx->projection == RPT_PROJECTION_EQUIRECT)
         if (int rc = ensure_projection_tables(ctx, ctx->pano, 1)) return rc;
-    rptd::EventArgs ea;
-    std::memset(&ea, 0, sizeof ea);
+    rptd::RaymapEventArgs ea;   // (every event kernel reads its own prefix: EventArgs, or all of it)
+    std::memset((void *)&ea, 0, sizeof ea);
     fill_frame_args(ctx, ea);
+    ea.raymap = c.colour->camera == Camera::raymap ? (const float4 *)ctx->raymap.device.ptr : nullptr;
+    ea.raymap_pitch = ctx->raymap_pitch;
     ea.out16 = nullptr;         // (the pass writes records only)
     ea.plane = nullptr;
     ea.debug_rgb = nullptr;
@@ -1689,7 +1739,7 @@ void rpt_destroy(rpt_ctx *ctx) {
     for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap}) release(*u);
     if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
     if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
     if (ctx->overlay_host) (void)hipHostFree(ctx->overlay_host);
@@ -1916,8 +1966,13 @@ int rpt_set_projection(rpt_ctx *ctx, int mode, const float *params) {
     } else if (mode == RPT_PROJECTION_EQUIRECT) {
         if (!projection_params(params, p))
             return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: equirect parameters are {h_fov in (0, 2 pi], v_fov in (0, pi], finite yaw} in radians, or NULL");
+    } else if (mode == RPT_PROJECTION_RAYMAP) {
+        if (params) return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: RPT_PROJECTION_RAYMAP takes no parameters (NULL): the directions are the context's map (rpt_set_raymap)");
+        // (the number was no mode before the ray map existed, and a context that has no map still has no such camera; a map that is
+        // dropped LATER, or one of another size, is what the launch refuses)
+        if (!ctx->raymap_on) return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: RPT_PROJECTION_RAYMAP needs the context's ray map: call rpt_set_raymap first");
     } else {
-        return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: mode is RPT_PROJECTION_PINHOLE or RPT_PROJECTION_EQUIRECT");
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_projection: mode is RPT_PROJECTION_PINHOLE, RPT_PROJECTION_EQUIRECT or RPT_PROJECTION_RAYMAP");
     }
     ctx->projection = mode;
     std::memcpy(ctx->projection_params, p, sizeof p);
@@ -1930,6 +1985,103 @@ int rpt_projection_tables(int mode, const float *params, int width, int height, 
     if (mode != RPT_PROJECTION_EQUIRECT || !projection_params(params, p)) return RPT_ERR_ARG;
     if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 31) - 1 || !cols_out || !rows_out) return RPT_ERR_ARG;
     projection_fill(p, width, height, cols_out, rows_out);
+    return RPT_OK;
+}
+
+// ---- the ray-map camera (rpt_set_raymap, rpt_raymap_fill) ----------------------------------------------------------------------------
+// The map goes to the device as one float4 per pixel in rows of the width rounded up to 8 pixels (rpt_kernels.hip.h: RaymapArgs), in
+// stream order from a pinned buffer that is not rewritten before its previous copy has run (the sky image's discipline): a frame still
+// in flight reads the map it was launched with, a later one the new map.  Dropping the map frees nothing (rpt_destroy does).
+int rpt_set_raymap(rpt_ctx *ctx, const float *dirs3, int width, int height) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (!dirs3) {
+        ctx->raymap_on = false;
+        ctx->view_generation++;
+        return RPT_OK;
+    }
+    if (width < 1 || height < 1 || 3ll * width * height >= (1ll << 31))
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_raymap: width and height are >= 1 and 3 width height < 2^31");
+    const size_t n = 3 * (size_t)width * (size_t)height;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(dirs3[i])) return fail(ctx, RPT_ERR_ARG, "rpt_set_raymap: component " + std::to_string(i) + " of the map is not finite");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t pitch = ((size_t)width + 7) & ~(size_t)7, bytes = pitch * (size_t)height * 4 * sizeof(float);
+    ctx->raymap_on = false;      // (until the new map is in place)
+    float *host = nullptr;
+    if (int rc = staged_host(ctx, ctx->raymap, bytes, (void **)&host)) return rc;
+    for (int y = 0; y < height; y++) {
+        float *row = host + (size_t)y * pitch * 4;
+        const float *src = dirs3 + 3 * (size_t)y * (size_t)width;
+        for (int x = 0; x < width; x++) {
+            row[4 * (size_t)x] = src[3 * (size_t)x];
+            row[4 * (size_t)x + 1] = src[3 * (size_t)x + 1];
+            row[4 * (size_t)x + 2] = src[3 * (size_t)x + 2];
+            row[4 * (size_t)x + 3] = 0.0f;
+        }
+        for (size_t k = 4 * (size_t)width; k < 4 * pitch; k++) row[k] = 0.0f;
+    }
+    if (int rc = staged_copy(ctx, ctx->raymap)) return rc;
+    ctx->raymap_width = width;
+    ctx->raymap_height = height;
+    ctx->raymap_pitch = (int)pitch;
+    ctx->raymap_on = true;
+    ctx->view_generation++;
+    return RPT_OK;
+}
+
+// Host code, no device.  Everything in double from the float parameters, one rounding to float per component.
+int rpt_raymap_fill(int kind, const float *params, int width, int height, float *dirs3_out) {
+    if (width < 1 || height < 1 || 3ll * width * height >= (1ll << 31) || !dirs3_out) return RPT_ERR_ARG;
+    const double W = width, H = height;
+    if (kind == RPT_RAYMAP_CUBE_STRIP) {
+        if (params || (long long)width != 6ll * height) return RPT_ERR_ARG;
+        // face f: p = forward + a right + b up, a and b the face's pinhole coordinates in (-1, 1) — a 90-degree lens
+        static const double forward[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+        static const double right[6][3] = {{0, 0, -1}, {0, 0, 1}, {1, 0, 0}, {1, 0, 0}, {1, 0, 0}, {-1, 0, 0}};
+        static const double up[6][3] = {{0, 1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}, {0, 1, 0}, {0, 1, 0}};
+        for (int y = 0; y < height; y++) {
+            const double b = (2.0 * ((double)y + 0.5) - H) / H;
+            for (int x = 0; x < width; x++) {
+                const int f = x / height;
+                const double a = (2.0 * ((double)(x - f * height) + 0.5) - H) / H;
+                float *o = dirs3_out + 3 * ((size_t)y * (size_t)width + (size_t)x);
+                for (int k = 0; k < 3; k++) o[k] = (float)(forward[f][k] + a * right[f][k] + b * up[f][k]);
+            }
+        }
+        return RPT_OK;
+    }
+    if (kind != RPT_RAYMAP_FISHEYE && kind != RPT_RAYMAP_FISHEYE_EQUISOLID && kind != RPT_RAYMAP_STEREOGRAPHIC) return RPT_ERR_ARG;
+    if (!params) return RPT_ERR_ARG;
+    const float fov_f = params[0], fit_f = params[1];
+    const float two_pi = (float)(2.0 * RPT_PI_D);
+    if (!(fov_f > 0.0f && fov_f <= two_pi) || (kind == RPT_RAYMAP_STEREOGRAPHIC && !(fov_f < two_pi))) return RPT_ERR_ARG;
+    if (fit_f != 0.0f && fit_f != 1.0f) return RPT_ERR_ARG;
+    const double fov = fov_f, S = fit_f == 0.0f ? (W < H ? W : H) : std::sqrt(W * W + H * H);
+    for (int y = 0; y < height; y++) {
+        const double Y = (2.0 * ((double)y + 0.5) - H) / S;
+        for (int x = 0; x < width; x++) {
+            const double X = (2.0 * ((double)x + 0.5) - W) / S;
+            const double rho = std::sqrt(X * X + Y * Y);
+            float *o = dirs3_out + 3 * ((size_t)y * (size_t)width + (size_t)x);
+            if (rho > 1.0) {
+                o[0] = o[1] = o[2] = 0.0f;
+                continue;
+            }
+            if (rho == 0.0) {
+                o[0] = o[1] = 0.0f;
+                o[2] = 1.0f;
+                continue;
+            }
+            double theta;
+            if (kind == RPT_RAYMAP_FISHEYE) theta = rho * fov / 2.0;
+            else if (kind == RPT_RAYMAP_FISHEYE_EQUISOLID) theta = 2.0 * std::asin(rho * std::sin(fov / 4.0));
+            else theta = 2.0 * std::atan(rho * std::tan(fov / 4.0));
+            const double st = std::sin(theta);
+            o[0] = (float)(st * X / rho);
+            o[1] = (float)(st * Y / rho);
+            o[2] = (float)std::cos(theta);
+        }
+    }
     return RPT_OK;
 }
 

@@ -185,6 +185,20 @@ static_assert(__builtin_offsetof(LensArgs, env_texels) >= sizeof(PanoramaArgs) &
 static_assert(__builtin_offsetof(LensArgs, lens_scale) >= sizeof(EnvironmentArgs), "then LensArgs' own");
 #pragma clang diagnostic pop
 
+// The ray-map kernels' arguments (rpt_set_raymap; not in the reference): LensArgs with the map appended, for the same reason once more.
+// Every ray-map render kernel takes them (doppler = 0 in the plain ones, lens_scale unused); the event form has a block of its own
+// behind EventArgs (RaymapEventArgs below).  The map holds one float4 {p.x, p.y, p.z, 0} per pixel, row-major, row 0 the bottom, rows
+// raymap_pitch pixels apart (the width rounded up to a multiple of 8): the 8 pixels a wave's tile has in one row are one aligned
+// 128-byte line, read by one 16-byte-aligned vector load a lane.  p == (0, 0, 0): the pixel has no ray.  DESIGN.md "Ray-map camera".
+struct RaymapArgs : LensArgs {
+    const float4 *raymap;           // [raymap_pitch * height]; addressed by GLOBAL pixel (row tiles and tile patterns need nothing else)
+    int raymap_pitch;
+};
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(__builtin_offsetof(RaymapArgs, raymap) >= sizeof(LensArgs), "RaymapArgs' own fields lie behind LensArgs");
+#pragma clang diagnostic pop
+
 struct Hit {                 // opencl_kernel.cl:38-44
     float dist;
     f3 normal;
@@ -222,6 +236,11 @@ RPT_DEV f3 equirectCamDir(const PanoramaArgs &a, int x, int y) {
     const float2 r = a.pano_rows[y];
     return normalize(mk3(r.y * c.x, r.x, r.y * c.y));
 }
+
+// The ray-map camera (rpt_set_raymap; not in the reference): the map's entry of pixel (x, y), then the pinhole's normalize.  The load is
+// one 16-byte read per lane; a wave's 8 x 8 tile reads eight whole 128-byte lines.  (0, 0, 0) = no ray: the caller must not normalise it.
+RPT_DEV float4 raymapLoad(const float4 *map, int pitch, int x, int y) { return map[(size_t)y * (size_t)pitch + (size_t)x]; }
+RPT_DEV bool raymapHasRay(float4 p) { return !(p.x == 0.0f && p.y == 0.0f && p.z == 0.0f); }
 
 // opencl_kernel.cl:106-126
 RPT_DEV bool intersect_triangle(f3 A, f3 B, f3 C, const Ray &ray, float &dist, f2 &uv) {
@@ -659,6 +678,7 @@ enum class Camera {
     pinhole,         // createCamRayDir: the reference's image plane z = 0.5
     equirect,        // equirectCamDir: the panorama tables (rpt_set_projection); the arguments are a PanoramaArgs
     lens,            // lensCamRayDir: the pinhole's image plane scaled by LensArgs::lens_scale (rpt_set_field_of_view); the arguments are a LensArgs
+    raymap,          // raymapLoad: one direction per pixel from the context's map (rpt_set_raymap); the arguments are a RaymapArgs (events: RaymapEventArgs)
 };
 struct KernelPolicy {
     static constexpr Walk walk = Walk::throughput;
@@ -698,6 +718,10 @@ template <class P> struct Environment : DopplerTwin<P> { static constexpr bool e
 // mask alike — scaled by LensArgs::lens_scale; everything else is the policy they derive from.  803 / 841 / 843 / 844: Lens<P> for the
 // plain kernels; + 10: Lens<DopplerTwin<P>> for their Doppler twins; + 20: Lens<Environment<P>> for the environment forms
 template <class P> struct Lens : P { static constexpr Camera camera = Camera::lens; };                                          // 8xx
+// the ray-map kernels (rpt_set_raymap): a per-pixel direction read from the map; like the panorama no object mask (the regions live on the
+// pinhole's plane) and with it no tile bitmaps, the shadow-segment culls kept.  1203 / 1241 / 1244: Raymap<P> for the plain kernels; + 10:
+// DopplerTwin<Raymap<P>>; + 20: Environment<Raymap<P>>
+template <class P> struct Raymap : P { static constexpr Camera camera = Camera::raymap; static constexpr bool object_mask = false; static constexpr bool tile_bits = false; };   // 12xx
 
 template <class P>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
@@ -1366,8 +1390,31 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     bool traced = false;
     [[maybe_unused]] DopplerRecord drec;
     uint32_t packed = a.bg_packed;
+    [[maybe_unused]] bool no_ray = false;        // the ray-map camera only: this pixel's entry of the map is (0, 0, 0)
     const bool masked = (P::culled && P::object_mask) || P::diag == 10;
-    if constexpr (P::environment) {
+    if constexpr (P::camera == Camera::raymap) {
+        // The direction is asked for first, next to the scalar load of the arguments' first line (nothing above reads memory: this
+        // policy has no object mask), so its round trip overlaps everything up to its first use.  A pixel without a ray is {x, y, rgba =
+        // 0, 0, 0, 1} with a zero debug_rgb triple, whatever the colour mode; a wave none of whose lanes has a ray stores that and ends
+        // without reading the scene, as a wave with an empty object mask does.
+        static_assert(!P::object_mask && !P::drec && P::diag == 0, "the ray-map kernels have no object mask, no Doppler record and no measurement arm");
+        const RaymapArgs &ra = static_cast<const RaymapArgs &>(a);
+        const float4 p = raymapLoad(ra.raymap, ra.raymap_pitch, x_coord, y_coord);
+        const bool has_ray = raymapHasRay(p);
+        no_ray = !has_ray;
+        if (__ballot(has_ray) != 0ull && has_ray) {
+            const f3 camdir = normalize(mk3(p.x, p.y, p.z));
+            traced = trace<P>(a, camdir, object_mask, color);
+            if constexpr (P::environment) {
+                if (!traced) color = environment_colour(static_cast<const EnvironmentArgs &>(a), camdir);
+                packed = tonemap_pack(a, color, mapped);
+            } else if (traced) {
+                packed = tonemap_pack(a, color, mapped);
+            }
+        } else {
+            packed = 1u << 24;
+        }
+    } else if constexpr (P::environment) {
         // every pixel has a colour of its own: the camera direction is formed for all, and a wave whose object mask is empty goes
         // straight to the sky (no object loop, no scene load)
         f3 camdir;
@@ -1405,7 +1452,7 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // (the 4-byte plane likewise: measured against the default policy on a rank's share of the frame, bunny 4K 0.0581 -> 0.0566 ms, shadows the same)
     if (a.plane) __builtin_nontemporal_store(packed, a.plane + (size_t)local_row * a.width + x_coord);
     if (a.debug_rgb) {
-        if (!traced && !P::environment) mapped = mk3(a.bg_mapped[0], a.bg_mapped[1], a.bg_mapped[2]);      // (read here only: a miss pixel's store needs nothing beyond the first line of the arguments)
+        if (!traced && !P::environment && !no_ray) mapped = mk3(a.bg_mapped[0], a.bg_mapped[1], a.bg_mapped[2]);      // (read here only: a miss pixel's store needs nothing beyond the first line of the arguments)
         a.debug_rgb[3 * id + 0] = mapped.x;
         a.debug_rgb[3 * id + 1] = mapped.y;
         a.debug_rgb[3 * id + 2] = mapped.z;
@@ -1470,6 +1517,12 @@ RPT_DEV void render_pixel_body_msaa(const KernelArgs &a) {
 struct EventArgs : LensArgs {
     rpt_event *events;              // [width * height] full-frame addressing, whatever the context's colour_plane says
 };
+// ... and the ray-map camera's event kernels (rpt_set_raymap): EventArgs with the map appended (RaymapArgs' two fields), a block of its own
+// so that EventArgs, and every event kernel that takes it, stays what it was
+struct RaymapEventArgs : EventArgs {
+    const float4 *raymap;
+    int raymap_pitch;
+};
 
 // sphere_core leaves (u, v) out for an untextured sphere (only the texture fetch reads it in a frame); the record holds Hit.uv of
 // every winner, so for such a winner the sphere's test is repeated once, after the loop, with want_uv set: the same float
@@ -1527,9 +1580,18 @@ RPT_DEV void events_pixel_body(const EventArgs &a) {
     f2 uv;
     uv.x = uv.y = 0.0f;
     const bool masked = P::culled && P::object_mask;
-    if (!masked || object_mask != 0 || a.object_count > 64) {       // (a wave whose mask is empty stores miss records without reading the scene)
+    [[maybe_unused]] float4 map_p;
+    bool has_ray = true;
+    if constexpr (P::camera == Camera::raymap) {        // (asked for first; a pixel without a ray is a miss record, and a wave without any reads no scene)
+        const RaymapEventArgs &ra = static_cast<const RaymapEventArgs &>(a);
+        map_p = raymapLoad(ra.raymap, ra.raymap_pitch, x_coord, y_coord);
+        has_ray = raymapHasRay(map_p);
+        has_ray = __ballot(has_ray) != 0ull && has_ray;
+    }
+    if (has_ray && (!masked || object_mask != 0 || a.object_count > 64)) {       // (a wave whose mask is empty stores miss records without reading the scene)
         f3 camdir;
-        if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(a, x_coord, y_coord);
+        if constexpr (P::camera == Camera::raymap) camdir = normalize(mk3(map_p.x, map_p.y, map_p.z));
+        else if constexpr (P::camera == Camera::equirect) camdir = equirectCamDir(a, x_coord, y_coord);
         else if constexpr (P::camera == Camera::lens) camdir = lensCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect, a.lens_scale);
         else camdir = createCamRayDir((float)x_coord, (float)y_coord, a.width, a.height, a.aspect);
         const float inf = 1e20f;
@@ -1644,6 +1706,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_lens_env_ballot_first_ieee_w5(const LensArgs a) { render_pixel_body<Lens<Environment<BallotFirst>>>(a); }    // (863)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_lens_env_analytic_w8(const LensArgs a) { render_pixel_body<Lens<Environment<Analytic>>>(a); }    // 864
 
+// Ray-map kernels (rpt_set_raymap with RPT_PROJECTION_RAYMAP; not in the reference): the panorama kernels' shapes and occupancies with the
+// direction of every pixel read from the context's map.  No band-first form and no forced-IEEE arms, as in panorama; the walk takes 1 / det
+// through rcp_exact like 41, with its IEEE form for scenes outside the domain.  12xx plain, + 10 the Doppler twins, + 20 the environment
+// forms.  DESIGN.md "Ray-map camera".
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_unculled_w5(const RaymapArgs a) { render_pixel_body<Raymap<Unculled>>(a); }    // 1203
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_walk_w5(const RaymapArgs a) { render_pixel_body<Raymap<BallotExact>>(a); }    // 1241
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_walk_ieee_w5(const RaymapArgs a) { render_pixel_body<Raymap<Ballot>>(a); }    // (1241)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_raymap_analytic_w8(const RaymapArgs a) { render_pixel_body<Raymap<Analytic>>(a); }    // 1244
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_doppler_unculled_w5(const RaymapArgs a) { render_pixel_body<DopplerTwin<Raymap<Unculled>>>(a); }    // 1213
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_doppler_walk_w5(const RaymapArgs a) { render_pixel_body<DopplerTwin<Raymap<BallotExact>>>(a); }    // 1251
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_doppler_walk_ieee_w5(const RaymapArgs a) { render_pixel_body<DopplerTwin<Raymap<Ballot>>>(a); }    // (1251)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_raymap_doppler_analytic_w8(const RaymapArgs a) { render_pixel_body<DopplerTwin<Raymap<Analytic>>>(a); }    // 1254
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_env_unculled_w5(const RaymapArgs a) { render_pixel_body<Environment<Raymap<Unculled>>>(a); }    // 1223
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_env_walk_w5(const RaymapArgs a) { render_pixel_body<Environment<Raymap<BallotExact>>>(a); }    // 1261
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_raymap_env_walk_ieee_w5(const RaymapArgs a) { render_pixel_body<Environment<Raymap<Ballot>>>(a); }    // (1261)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_raymap_env_analytic_w8(const RaymapArgs a) { render_pixel_body<Environment<Raymap<Analytic>>>(a); }    // 1264
+
 // Event kernels (rpt_render_events; not in the reference): the product kernels' launch shape, the record instead of a colour.  The number
 // is what rpt_last_events_variant reports.  Only the throughput walk is built; 941 / 911 / 921 take 1 / det through rcp_exact like 41,
 // with an IEEE form each for scenes outside the domain.  The panorama needs no un-culled form: it has no object mask and the pass has no
@@ -1663,6 +1742,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_lens_ballot(const EventArgs a) { events_pixel_body<Lens<BallotExact>>(a); }    // 921
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_lens_ballot_ieee(const EventArgs a) { events_pixel_body<Lens<Ballot>>(a); }    // (921)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_lens_analytic(const EventArgs a) { events_pixel_body<Lens<Analytic>>(a); }    // 924
+
+// ... and the ray-map camera's (no un-culled form either: nothing is masked)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_raymap(const RaymapEventArgs a) { events_pixel_body<Raymap<BallotExact>>(a); }    // 1291
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_raymap_ieee(const RaymapEventArgs a) { events_pixel_body<Raymap<Ballot>>(a); }    // (1291)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_raymap_analytic(const RaymapEventArgs a) { events_pixel_body<Raymap<Analytic>>(a); }    // 1294
 
 // ---- Adaptive anti-aliasing (rpt_set_adaptive_aa; not in the reference; DESIGN.md "Adaptive anti-aliasing") ------------------------------
 // The second launch of an adaptive frame.  The first is the one-sample kernel a frame gets anyway (its source and its code untouched),

@@ -21,7 +21,8 @@ PIXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("rgba", "u1", (4,)), ("unsp
 TILE_ROWS = 8
 DOPPLER_SHIFT, DOPPLER_BEAMING = 1, 2     # rpt_set_doppler flags (include/rpt.h)
 DOPPLER_RECORD = 11                       # floats per pixel of the Doppler debug record
-PROJECTIONS = {"pinhole": 0, "equirect": 1}   # RPT_PROJECTION_* (include/rpt.h)
+PROJECTIONS = {"pinhole": 0, "equirect": 1, "raymap": 2}   # RPT_PROJECTION_* (include/rpt.h)
+RAYMAP_KINDS = {"fisheye": 0, "equisolid": 1, "stereographic": 2, "cube_strip": 3}   # RPT_RAYMAP_* (include/rpt.h)
 
 
 class RenderError(RuntimeError):
@@ -31,7 +32,7 @@ class RenderError(RuntimeError):
 def _projection_args(mode: str, h_fov: float, v_fov: float, yaw: float):
     if mode not in PROJECTIONS:
         raise ValueError(f"projection is one of {sorted(PROJECTIONS)}, not {mode!r}")
-    params = None if mode == "pinhole" else (C.c_float * 3)(h_fov, v_fov, yaw)
+    params = (C.c_float * 3)(h_fov, v_fov, yaw) if mode == "equirect" else None
     return PROJECTIONS[mode], params
 
 
@@ -46,6 +47,21 @@ def projection_tables(width: int, height: int, h_fov: float = 2 * math.pi, v_fov
     if rc != 0:
         raise ValueError(f"rpt_projection_tables({mode!r}, {h_fov}, {v_fov}, {yaw}, {width}x{height}) failed ({rc})")
     return cols, rows
+
+
+def raymap(kind: str, width: int, height: int, fov: float = math.pi, fit: int = 0) -> np.ndarray:
+    """A standard ray map for a width x height frame (rpt_raymap_fill; host code, no device needed): (height, width, 3) float32, row 0
+    the bottom, (0, 0, 0) where a pixel has no ray.  kind: "fisheye" (equidistant), "equisolid" or "stereographic" with the full angle
+    fov in radians across the image circle, which fit = 0 inscribes in the frame and fit = 1 stretches to its diagonal; or "cube_strip"
+    (width = 6 height; faces +x, -x, +y, -y, +z, -z from the left; fov and fit are not used)."""
+    if kind not in RAYMAP_KINDS:
+        raise ValueError(f"a ray map's kind is one of {sorted(RAYMAP_KINDS)}, not {kind!r}")
+    params = None if kind == "cube_strip" else (C.c_float * 2)(float(fov), float(fit))
+    dirs = np.empty((max(int(height), 0), max(int(width), 0), 3), dtype=np.float32)
+    rc = _ffi.hip().rpt_raymap_fill(RAYMAP_KINDS[kind], params, int(width), int(height), dirs.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"rpt_raymap_fill({kind!r}, fov={fov}, fit={fit}, {width}x{height}) failed ({rc})")
+    return dirs
 
 
 def _ypr(yaw: float, pitch: float, roll: float):
@@ -234,12 +250,28 @@ class Renderer:
         self._check(self._lib.rpt_set_doppler(self._h, flags), "rpt_set_doppler")
 
     def set_projection(self, mode: str = "pinhole", h_fov: float = 2 * math.pi, v_fov: float = math.pi, yaw: float = 0.0):
-        """The camera: "pinhole" (the reference's, the default) or "equirect", a panorama of h_fov x v_fov radians centred on longitude
-        yaw (0 = +z; include/rpt.h, rpt_set_projection).  Per context.  In panorama only variants 0 and 3 render, at MSAA 1."""
+        """The camera: "pinhole" (the reference's, the default), "equirect", a panorama of h_fov x v_fov radians centred on longitude
+        yaw (0 = +z; include/rpt.h, rpt_set_projection), or "raymap", the directions of set_raymap (the angles are not used).  Per
+        context.  In panorama only variants 0 and 3 render, at MSAA 1; under a ray map variants 0, 3, 41, 43 and 44, at MSAA 1."""
         m, params = _projection_args(mode, h_fov, v_fov, yaw)
         self._check(self._lib.rpt_set_projection(self._h, m, params), "rpt_set_projection")
 
     projection_tables = staticmethod(projection_tables)
+    raymap = staticmethod(raymap)
+
+    def set_raymap(self, dirs: Optional[np.ndarray], width: Optional[int] = None, height: Optional[int] = None):
+        """The ray map (include/rpt.h, rpt_set_raymap): one direction per pixel, (H, W, 3) float32 with row 0 the bottom — or (H W, 3)
+        with width and height given — copied by the library; (0, 0, 0) = the pixel has no ray and is written black.  None drops the
+        map.  Per context; used while set_projection("raymap") is set, and its size must then be the frame's at every launch."""
+        if dirs is None:
+            self._check(self._lib.rpt_set_raymap(self._h, None, 0, 0), "rpt_set_raymap")
+            return
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        if d.ndim == 3 and d.shape[2] == 3 and width is None and height is None:
+            height, width = d.shape[0], d.shape[1]
+        elif not (d.ndim == 2 and d.shape[1] == 3 and width is not None and height is not None and d.shape[0] == int(width) * int(height)):
+            raise ValueError(f"a ray map is an (H, W, 3) array, or an (H W, 3) array with width and height given, not {d.shape}")
+        self._check(self._lib.rpt_set_raymap(self._h, d.ctypes.data, int(width), int(height)), "rpt_set_raymap")
 
     def set_orientation(self, yaw: float = 0.0, pitch: float = 0.0, roll: float = 0.0):
         """Turn the camera: R = Ry(yaw) Rx(pitch) Rz(roll) in radians, the view direction R (0, 0, 1) — positive yaw towards +x, positive
@@ -519,12 +551,15 @@ class Renderer:
 
 
 def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_rgb: bool = False,
-                 projection: Union[None, str, Mapping] = None, environment: Optional[np.ndarray] = None,
+                 projection: Union[None, str, Mapping, np.ndarray] = None, environment: Optional[np.ndarray] = None,
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
-                 adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None):
+                 adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
+                 fov: float = math.pi, fit: int = 0):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
-    for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}.  environment: an
+    for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
+    "fisheye", "equisolid", "stereographic" (with fov, the full angle in radians, and fit: renderer.raymap) or "cube_strip" (width = 6
+    height), or an (H, W, 3) float32 array of directions for Renderer.set_raymap.  environment: an
     H x W x 3 uint8 sky image at rest in the scene's frame (its frame is set from the scene's camera; call update_objects() first).
     orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view).
     adaptive_aa: (samples per axis, threshold) for Renderer.set_adaptive_aa.  overlay: the keywords of Renderer.set_overlay, e.g.
@@ -538,7 +573,10 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
             r.set_orientation(*orientation)
         if v_fov is not None:
             r.set_field_of_view(v_fov)
-        if projection is not None:
+        if isinstance(projection, np.ndarray) or (isinstance(projection, str) and projection in RAYMAP_KINDS):
+            r.set_raymap(projection if isinstance(projection, np.ndarray) else raymap(projection, width, height, fov=fov, fit=fit))
+            r.set_projection("raymap")
+        elif projection is not None:
             r.set_projection(**({"mode": projection} if isinstance(projection, str) else dict(projection)))
         if environment is not None:
             r.set_environment(environment)
