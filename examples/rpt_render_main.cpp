@@ -234,6 +234,16 @@ int main(int argc, char **argv) {
     if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ctx, aa_n, aa_threshold);
     if (!rc && !raymap.empty()) rc = rpt_set_raymap(ctx, raymap.data(), width, height);
     if (!rc && !raymap.empty()) rc = rpt_set_projection(ctx, RPT_PROJECTION_RAYMAP, nullptr);
+    {   // the scene's `wT0,T1` commands (not in the reference): objects and lights that begin and end; a scene without any sets nothing
+        size_t n_objects = 0;
+        int any_window = 0;
+        rpt_scene_get_windows(scene, nullptr, 0, &n_objects, &any_window);
+        if (!rc && any_window) {
+            std::vector<float> windows(2 * n_objects);
+            rpt_scene_get_windows(scene, windows.data(), n_objects, &n_objects, &any_window);
+            rc = rpt_set_object_windows(ctx, windows.data(), (int)n_objects);
+        }
+    }
     if (!rc) rc = rpt_upload_scene(ctx, &desc);                  // 8x cl::Buffer + write    main.cpp:33-55
     if (!rc) rc = rpt_set_params(ctx, wp, ambient, width, height, interval);   // initCLKernel()  main.cpp:62
     if (!rc) rc = rpt_set_output(ctx, nullptr);                  // BufferGL(vbo)           main.cpp:58

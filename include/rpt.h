@@ -40,7 +40,8 @@
  * by light delay drawn on the rendered frame from the event records: rpt_set_overlay, rpt_render_overlay / rpt_render_overlay_async and
  * rpt_last_overlay_pixels ("Overlay pass"), and the opt-in ray-map camera — one direction per pixel, for fisheyes, the
  * stereographic view, cube strips and calibrated lenses: rpt_set_raymap, RPT_PROJECTION_RAYMAP and rpt_raymap_fill (host code, no device
- * needed; DESIGN.md, "Ray-map camera").
+ * needed; DESIGN.md, "Ray-map camera"), and opt-in per-object time windows — objects and lights that begin and end, from which
+ * piecewise-inertial worldlines are built: rpt_set_object_windows ("Time windows").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -523,6 +524,21 @@ int rpt_render_overlay(rpt_ctx *ctx);        /* enqueue and wait */
 int rpt_render_overlay_async(rpt_ctx *ctx);  /* enqueue; rpt_sync waits */
 int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels);
 
+/* Per-object time windows (not in the reference; DESIGN.md, "Time windows"): objects and lights that begin and end.  t0t1 holds count
+ * pairs {t0, t1}, one per entry of Object[]; object i exists for emission times t IN ITS OWN REST FRAME with !(t < t0) && !(t >= t1) —
+ * the coordinate the flash term uses and the event pass stores in event[0].  A primary hit, a shadow ray's occluder and a light's emission
+ * event outside the window are not there (a primary ray that meets only the rejected surface of an object does not see that object:
+ * no later surface is searched for).  -inf / +inf are legal and are the default; t0 >= t1 means never; a NaN bound is RPT_ERR_ARG.
+ * The array is COPIED; the setting is per context and is NOT taken over by rpt_share_scene.  NULL (or count 0) clears it: the context then
+ * launches exactly the kernels it launched before the setting existed.
+ * While set, frames and event frames are rendered by the windowed kernels: rpt_last_variant / rpt_last_events_variant report 2000 + the
+ * variant of the row of the same camera and colour whose form ran (2041, 2044, 2003; 2241.. with Doppler, 2641.. with the sky; 28xx
+ * under a lens, 23xx / 25xx / 27xx in the panorama, 32xx through a ray map; events 2941.., 2921.., 2911.., 3291..).  A band-first
+ * choice (43) gets the walk (2041).  With every window at its default the frame is the un-windowed frame in all 16 bytes of every pixel.
+ * Refused at the LAUNCH with RPT_ERR_ARG, message "rpt_set_object_windows: ...", nothing launched: a count that is not the Object[]'s,
+ * MSAA > 1, adaptive anti-aliasing, variants 1 / 50 / 51, the Doppler debug kernels, an octree whose children are not consecutive. */
+int rpt_set_object_windows(rpt_ctx *ctx, const float *t0t1_or_null, int count);
+
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);
 void *rpt_colour_plane_ptr(rpt_ctx *ctx);    /* device pointer of the compact plane (rpt_set_rows) */
@@ -623,7 +639,6 @@ int rpt_probe_reciprocal(rpt_ctx *ctx, float lo, float hi, unsigned long long co
  * {hit, dist, normal.xyz, uv.xy, 0} per walk, the distance re-measured from the object's origin as :303-305 does.  The three
  * must agree bit for bit (tests/test_gpu_kat.py). */
 int rpt_probe_walk(rpt_ctx *ctx, int object_index, const float *host_rays, float *host_out, int n);
-
 #ifdef __cplusplus
 }
 #endif

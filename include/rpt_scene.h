@@ -80,6 +80,9 @@ int rpt_scene_get_desc(const rpt_scene *s, rpt_scene_desc *out);
 int rpt_scene_get_params(const rpt_scene *s, float white_point[3], float *ambient, int *interval);
 int rpt_scene_get_velocities(const rpt_scene *s, const rpt_float3 **velocities, size_t *count);
 int rpt_scene_get_mesh_roots(const rpt_scene *s, const int **roots, size_t *count);
+/* The time windows of the DSL's `wT0,T1` command (rpt_set_object_windows takes them): *count = the number of objects, *any = 1 when some
+ * object has a window; t0t1_out (may be NULL) receives {t0, t1} of the first min(capacity, *count) objects, (-inf, +inf) where none was given. */
+int rpt_scene_get_windows(const rpt_scene *s, float *t0t1_out, size_t capacity, size_t *count, int *any);
 
 /* framebuffer consumer: write a 16 B/pixel framebuffer (row 0 = bottom, as GL draws it) as a binary
  * PPM with the top row first */

@@ -114,6 +114,7 @@ def scene_lib() -> C.CDLL:
             "rpt_scene_get_params": (I, [P, FP, FP, C.POINTER(C.c_int)]),
             "rpt_scene_get_velocities": (I, [P, C.POINTER(P), C.POINTER(C.c_size_t)]),
             "rpt_scene_get_mesh_roots": (I, [P, C.POINTER(P), C.POINTER(C.c_size_t)]),
+            "rpt_scene_get_windows": (I, [P, P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
             "rpt_write_ppm": (I, [S, P, I, I]),
             "rpt_write_png": (I, [S, P, I, I]),
         }
@@ -210,6 +211,7 @@ HIP_SYMBOLS = {
     "rpt_render_overlay": (C.c_int, [C.c_void_p]),
     "rpt_render_overlay_async": (C.c_int, [C.c_void_p]),
     "rpt_last_overlay_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_object_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "rpt_version": (C.c_char_p, []),
 }
 

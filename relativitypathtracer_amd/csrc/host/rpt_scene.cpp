@@ -249,9 +249,9 @@ bool Scene::inputScene(std::istream &in) {
         for (char *tok = strtok_r(buf.data(), " ", &save); !done && tok; tok = strtok_r(nullptr, " ", &save)) {
             float args[10];
             const size_t len = std::strlen(tok);
-            const bool needObject = std::strchr("pctlvf", tok[0]) != nullptr;
+            const bool needObject = std::strchr("pctlvfw", tok[0]) != nullptr;
             if (needObject && cpu_objects.empty()) { warn(std::string("Object must be defined before \"") + tok + "\""); continue; }
-            if (std::strchr("OpctlvfTMAW", tok[0]) && len < 2) { warn(std::string("command missing argument: \"") + tok + "\""); continue; }
+            if (std::strchr("OpctlvfwTMAW", tok[0]) && len < 2) { warn(std::string("command missing argument: \"") + tok + "\""); continue; }
             switch (tok[0]) {
             case 'O': {
                 int type = -1;
@@ -287,6 +287,16 @@ bool Scene::inputScene(std::istream &in) {
                 cpu_objects.back().flashPeriod = args[0];
                 cpu_objects.back().flashDuration = args[1];
                 break;
+            case 'w':       // wT0,T1 (not in the reference): the current object exists for rest-frame times t0 <= t < t1; inf and -inf are accepted
+            {       // (both numbers must be there: parseArgs would read a missing one as 0, and (5, 0) means "never there")
+                char *end0 = nullptr, *end1 = nullptr;
+                const float t0 = (float)std::strtod(tok + 1, &end0);
+                const bool first = end0 != tok + 1 && *end0 == ',';
+                const float t1 = first ? (float)std::strtod(end0 + 1, &end1) : 0.0f;
+                if (!first || end1 == end0 + 1 || *end1 != '\0' || t0 != t0 || t1 != t1) { warn(std::string("window command needs two numbers: \"") + tok + "\""); break; }
+                windows[cpu_objects.size() - 1] = std::make_pair(t0, t1);
+                break;
+            }
             case 'T': if (!ReadTexture(tok + 1)) return false; break;
             case 'M': if (!ReadOBJ(tok + 1)) return false; break;
             case 'A': ambient = (float)std::atof(tok + 1); break;

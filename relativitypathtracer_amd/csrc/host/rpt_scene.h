@@ -8,6 +8,7 @@
 #include <functional>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rpt_vector.h"
@@ -41,6 +42,9 @@ struct Scene {
     // Object.h:23-24
     std::vector<rpt_object> cpu_objects;
     std::vector<rpt_float3> velocities;
+    // the `w` command (not in the reference): {t0, t1} of the objects that have a time window, by object index; the others have the
+    // default (-inf, +inf).  Empty: a scene without windows (rpt_scene_get_windows)
+    std::map<size_t, std::pair<float, float>> windows;
     // Render.cpp:8-22
     rpt_float3 cameraVelocity = make_float3(0, 0, 0);
     rpt_float4 cameraPos = make_float4(0, 0, 0, 0);   // (t, x, y, z)

@@ -1,4 +1,5 @@
 // rpt_scene_capi.cpp — extern "C" entry points of librpt_scene.so (include/rpt_scene.h).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -196,6 +197,20 @@ int rpt_scene_get_velocities(const rpt_scene *s, const rpt_float3 **v, size_t *c
     if (!s || !v || !count) return -1;
     *v = s->scene.velocities.empty() ? nullptr : s->scene.velocities.data();
     *count = s->scene.velocities.size();
+    return 0;
+}
+
+int rpt_scene_get_windows(const rpt_scene *s, float *t0t1_out, size_t capacity, size_t *count, int *any) {
+    if (!s || !count || !any) return -1;
+    const size_t n = s->scene.cpu_objects.size();
+    *count = n;
+    *any = s->scene.windows.empty() ? 0 : 1;
+    if (!t0t1_out) return 0;
+    for (size_t i = 0; i < n && i < capacity; i++) {
+        const auto it = s->scene.windows.find(i);
+        t0t1_out[2 * i] = it == s->scene.windows.end() ? -INFINITY : it->second.first;
+        t0t1_out[2 * i + 1] = it == s->scene.windows.end() ? INFINITY : it->second.second;
+    }
     return 0;
 }
 

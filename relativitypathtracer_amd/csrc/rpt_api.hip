@@ -138,6 +138,8 @@ struct rpt_ctx {
     bool colour_plane = false;
     int variant = 0;
     int last_variant = 0;                             // the kernel the last launch was made with (rpt_last_variant)
+    // rpt_set_object_windows (not in the reference): {t0, t1} per object, per context, never shared; empty = none (today's kernels)
+    std::vector<float> windows;
     bool last_exact_rcp = false;                      // ... and whether its walk took 1 / det through rcp_exact (rpt_last_exact_rcp)
     int msaa = 1;                                     // MSAASAMPLES (rpt_set_msaa)
     int serial = 0;                                   // creation index of this context in the process (diagnostics output)
@@ -515,7 +517,7 @@ void mesh_segment_cull_record(const rpt_ctx *ctx, const rpt_object &o, rptd::DOb
     d.mslope = -1.0f;
     d.mcw = d.mconst = d.ms0 = 0.0f;
     d.mh[0] = d.mh[1] = d.mh[2] = -1.0f;
-    d.pad2 = 0.0f;
+    d.win_t1 = 0.0f;
     if (o.type != RPT_MESH || !ctx->geo->compact_ok) return;
     const size_t mi = (size_t)o.meshIndex;
     if (o.meshIndex < 0 || mi * 6 + 5 >= ctx->geo->host_node_bounds.size() || mi >= ctx->geo->node_tri_K.size()) return;
@@ -1074,6 +1076,35 @@ const KernelRow colour_table[] = {
     {1264, Camera::raymap,  Colour::sky,     Form::analytic,      RPT_KERNEL(rpt_render_kernel_raymap_env_analytic_w8),     nullptr},
 };
 
+// The windowed kernels (rpt_set_object_windows): looked up AFTER everything else has chosen a row, by that row's camera (the pinhole's rows
+// are served by the lens kernels at lens_scale 1.0f), its colour (plain and Doppler share the twin with the run-time flag) and its form
+// (a band-first form gets the walk, a forced-IEEE arm the walk's IEEE kernel).  The variant here is an offset only: what is reported is
+// 2000 + the variant of the row of the context's own camera and colour whose form ran.
+#define RPT_WINDOWED_ROWS(camera, colour, name)                                                                                                                     \
+    {2000, camera, colour, Form::unculled, RPT_KERNEL(rpt_render_kernel_win_##name##_unculled_w5),  nullptr},                                                        \
+    {2000, camera, colour, Form::walk,     RPT_KERNEL(rpt_render_kernel_win_##name##_walk_w5),      RPT_KERNEL(rpt_render_kernel_win_##name##_walk_ieee_w5)},        \
+    {2000, camera, colour, Form::analytic, RPT_KERNEL(rpt_render_kernel_win_##name##_analytic_w8),  nullptr}
+const KernelRow windowed_table[] = {
+    RPT_WINDOWED_ROWS(Camera::lens,     Colour::doppler, lens),
+    RPT_WINDOWED_ROWS(Camera::lens,     Colour::sky,     lens_env),
+    RPT_WINDOWED_ROWS(Camera::equirect, Colour::doppler, pano),
+    RPT_WINDOWED_ROWS(Camera::equirect, Colour::sky,     pano_env),
+    RPT_WINDOWED_ROWS(Camera::raymap,   Colour::doppler, raymap),
+    RPT_WINDOWED_ROWS(Camera::raymap,   Colour::sky,     raymap_env),
+    // the pinhole's forced-IEEE arms (48 / 49, 248 / 249; the other cameras and the sky refuse them): the walk's IEEE kernel whatever the scene
+    {2000, Camera::lens, Colour::doppler, Form::ieee, RPT_KERNEL(rpt_render_kernel_win_lens_walk_ieee_w5), nullptr},
+};
+#undef RPT_WINDOWED_ROWS
+const KernelRow windowed_events_table[] = {
+    {2000, Camera::lens,     Colour::plain, Form::unculled, RPT_KERNEL(rpt_events_kernel_win_lens_unculled),   nullptr},
+    {2000, Camera::lens,     Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_win_lens_walk),       RPT_KERNEL(rpt_events_kernel_win_lens_walk_ieee)},
+    {2000, Camera::lens,     Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_win_lens_analytic),   nullptr},
+    {2000, Camera::equirect, Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_win_pano_walk),       RPT_KERNEL(rpt_events_kernel_win_pano_walk_ieee)},
+    {2000, Camera::equirect, Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_win_pano_analytic),   nullptr},
+    {2000, Camera::raymap,   Colour::plain, Form::walk,     RPT_KERNEL(rpt_events_kernel_win_raymap_walk),     RPT_KERNEL(rpt_events_kernel_win_raymap_walk_ieee)},
+    {2000, Camera::raymap,   Colour::plain, Form::analytic, RPT_KERNEL(rpt_events_kernel_win_raymap_analytic), nullptr},
+};
+
 // The refine kernels (rpt_set_adaptive_aa), variant 1000 + 10 (3 camera + colour) + {1 walk, 3 un-culled, 4 no walk}.  The form is pass
 // A's: un-culled wherever the one-sample kernel ran un-culled, the walk with the wave's object mask, or no walk compiled in.
 #define RPT_REFINE_ROWS(base, camera, colour, name)                                                                                                 \
@@ -1176,8 +1207,10 @@ struct Choice {
     int variant = 0;                    // colour->variant, or the measurement arm's number (librpt_hip_diag.so)
     bool exact_rcp = false;             // the scene lies in rcp_exact's domain: a row that has an `ieee` sibling runs its own kernel
     bool band_first = false;            // the band of tile rows that holds the meshes goes first
+    const KernelRow *windowed = nullptr;// rpt_set_object_windows: the row that is launched in `colour`'s place (`variant` is 2000 + the row's it stands for)
     const void *kernel(const KernelRow *row) const { return row->ieee && !exact_rcp ? row->ieee : row->kernel; }
     bool ran_exact(const KernelRow *row) const { return row && row->ieee && exact_rcp; }
+    const KernelRow *launched() const { return windowed ? windowed : colour; }
 };
 
 Choice refuse(int code, std::string text) {
@@ -1185,6 +1218,12 @@ Choice refuse(int code, std::string text) {
     c.code = code;
     c.text = std::move(text);
     return c;
+}
+
+// rpt_set_object_windows: "" = the windows fit this launch's Object[]
+std::string windows_mismatch(const rpt_ctx *ctx) {
+    if (ctx->windows.size() == 2 * (size_t)ctx->object_count) return "";
+    return "rpt_set_object_windows: " + std::to_string(ctx->windows.size() / 2) + " windows are set, the Object[] holds " + std::to_string(ctx->object_count);
 }
 
 Choice choose_event_kernel(const rpt_ctx *ctx) {
@@ -1210,6 +1249,13 @@ Choice choose_event_kernel(const rpt_ctx *ctx) {
     if (!c.colour) return refuse(RPT_ERR_ARG, "rpt_render_events: no event kernel for this camera");
     c.variant = c.colour->variant;
     c.exact_rcp = ctx->geo->exact_rcp_ok;
+    if (!ctx->windows.empty()) {       // the windowed form of the same row (the pinhole's: the lens kernel, lens_scale 1.0f)
+        const std::string mismatch = windows_mismatch(ctx);
+        if (!mismatch.empty()) return refuse(RPT_ERR_ARG, mismatch);
+        c.windowed = find_row(windowed_events_table, camera == Camera::pinhole ? Camera::lens : camera, Colour::plain, form);
+        if (!c.windowed) return refuse(RPT_ERR_ARG, "rpt_set_object_windows: no windowed event kernel for this camera");
+        c.variant = 2000 + c.colour->variant;
+    }
     return c;
 }
 
@@ -1315,6 +1361,27 @@ Choice choose_kernels(const rpt_ctx *ctx, Call call) {
 #ifndef RPT_DIAGNOSTICS
     if (!c.colour) return refuse(RPT_ERR_ARG, "unknown kernel variant");
 #endif
+    if (!ctx->windows.empty()) {
+        // Time windows (rpt_set_object_windows): the windowed form of the row everything above chose.  What has none refuses here.
+        if (adaptive) return refuse(RPT_ERR_ARG, "rpt_set_object_windows: adaptive anti-aliasing (rpt_set_adaptive_aa) has no windowed refine pass");
+        if (ctx->msaa > 1) return refuse(RPT_ERR_ARG, "rpt_set_object_windows: MSAA > 1 has no windowed kernel");
+        if (recording) return refuse(RPT_ERR_ARG, "rpt_set_object_windows: the Doppler debug kernels (rpt_set_debug_doppler) have no windowed form");
+#ifdef RPT_DIAGNOSTICS
+        if (!c.colour) return refuse(RPT_ERR_ARG, "rpt_set_object_windows: the measurement arms have no windowed form");
+#endif
+        if (form == Form::ref_layout || form == Form::relaxed5 || form == Form::relaxed6)
+            return refuse(RPT_ERR_ARG, sv == 1 || sv == 50 || sv == 51 ? "rpt_set_object_windows: variant " + std::to_string(sv) + " has no windowed kernel"
+                                                                      : "rpt_set_object_windows: the windowed kernels need the derived octree layout, which this scene's octree does not fit (children not consecutive)");
+        const std::string mismatch = windows_mismatch(ctx);
+        if (!mismatch.empty()) return refuse(RPT_ERR_ARG, mismatch);
+        const Form wform = form == Form::walk_first ? Form::walk : (form == Form::ieee_first ? Form::ieee : form);      // (no band-first form: the walk)
+        const Camera own = camera;
+        c.windowed = find_row(windowed_table, own == Camera::pinhole ? Camera::lens : own, colour == Colour::sky ? Colour::sky : Colour::doppler, wform);
+        const KernelRow *stands_for = find_row(colour_table, own, colour, wform);
+        if (!c.windowed || !stands_for) return refuse(RPT_ERR_ARG, "rpt_set_object_windows: this kernel variant has no windowed form");
+        c.variant = 2000 + stands_for->variant;
+        c.band_first = false;
+    }
     if (adaptive) {
         // under a lens the skirt's proof for the SAMPLE positions reaches 0.98 million pixels a side, not 2^20 (rpt_kernels.hip.h: refine_pixel_body)
         const bool beyond_samples = lens && (ctx->width > (1 << 19) || ctx->height > (1 << 19));
@@ -1509,11 +1576,11 @@ int launch(rpt_ctx *ctx, Call call) {
         if (rpt_launch_relaxed_kernel(relaxed_waves(c.colour->form), &a, sizeof(rptd::KernelArgs), grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
     } else {
         void *args[] = {(void *)&a};
-        (void)hipLaunchKernel(c.kernel(c.colour), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
+        (void)hipLaunchKernel(c.kernel(c.launched()), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     }
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = c.variant;
-    ctx->last_exact_rcp = c.ran_exact(c.colour);
+    ctx->last_exact_rcp = c.ran_exact(c.launched());
     if (c.refine) {               // pass B, behind pass A on the same stream; then the counter's way home, in stream order
         rptd::RefineArgs ra;
         std::memset(&ra, 0, sizeof ra);
@@ -1577,12 +1644,12 @@ int launch_events(rpt_ctx *ctx) {
     ctx->events_tile_step = ctx->tile_step;
     ctx->events_run_log2 = ctx->run_log2;
     ctx->last_events_variant = c.variant;
-    ctx->last_events_exact_rcp = c.ran_exact(c.colour);
+    ctx->last_events_exact_rcp = c.ran_exact(c.launched());
     const int tiles = local_tile_count(ctx);
     if (tiles == 0) return RPT_OK;
     const dim3 grid1(((ctx->width + 31) / 32) * 4, tiles);      // one wave (an 8 x 8 tile) per workgroup, as the product kernels
     void *args[] = {(void *)&ea};
-    (void)hipLaunchKernel(c.kernel(c.colour), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
+    (void)hipLaunchKernel(c.kernel(c.launched()), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
     RPT_HIP(ctx, hipGetLastError());
     return RPT_OK;
 }
@@ -1865,6 +1932,12 @@ static int set_objects_as_given(rpt_ctx *ctx, const void *objects, int count) {
         char *slot = (char *)ctx->pinned_objects + (ctx->pinned_capacity / RPT_STAGING_SLOTS) * k;
         std::memcpy(slot, objects, bytes);
         build_dobjs(ctx, (const rpt_object *)objects, count, (rptd::DObj *)(slot + bytes));
+        if (ctx->windows.size() == 2 * (size_t)count)       // (another count: refused at the launch, choose_kernels)
+            for (int i = 0; i < count; i++) {
+                rptd::DObj &d = ((rptd::DObj *)(slot + bytes))[i];
+                d.win_t0 = ctx->windows[2 * (size_t)i];
+                d.win_t1 = ctx->windows[2 * (size_t)i + 1];
+            }
         RPT_HOST_MARK(2);
         note_still_objects(ctx, (const rpt_object *)objects, count);
         build_rects(ctx, (const rpt_object *)objects, count, (rptb::Rect *)(slot + bytes + (size_t)count * sizeof(rptd::DObj)));
@@ -1902,6 +1975,31 @@ int rpt_set_params(rpt_ctx *ctx, const float white_point[3], float ambient, int 
         if (copy.size() != (size_t)ctx->object_count * sizeof(rpt_object)) return fail(ctx, RPT_ERR_STATE, "rpt_set_params: the context holds no copy of the caller's objects");
         return rpt_set_objects(ctx, copy.data(), ctx->object_count);
     }
+    return RPT_OK;
+}
+
+// The windows ride in DObj::win_t0 / win_t1, which the context uploads with its Object[]: the caller's last objects are taken over again
+// so that frames launched from here on see the new windows (frames in flight keep theirs: the upload is in stream order).  If that
+// upload fails the setting is as it was before the call.
+int rpt_set_object_windows(rpt_ctx *ctx, const float *t0t1_or_null, int count) {
+    if (!ctx || count < 0) return RPT_ERR_ARG;
+    if (count == 0) t0t1_or_null = nullptr;
+    if (t0t1_or_null)
+        for (int i = 0; i < 2 * count; i++)
+            if (t0t1_or_null[i] != t0t1_or_null[i]) return fail(ctx, RPT_ERR_ARG, "rpt_set_object_windows: a bound is NaN");
+    if (!t0t1_or_null && ctx->windows.empty()) return RPT_OK;
+    std::vector<float> before(t0t1_or_null, t0t1_or_null ? t0t1_or_null + 2 * (size_t)count : t0t1_or_null);
+    before.swap(ctx->windows);          // (`before` now holds the old setting)
+    if (ctx->scene_uploaded && ctx->object_count > 0) {
+        const std::vector<uint8_t> copy = ctx->oriented ? ctx->caller_objects : ctx->host_objects;
+        int rc = copy.size() == (size_t)ctx->object_count * sizeof(rpt_object) ? rpt_set_objects(ctx, copy.data(), ctx->object_count)
+                                                                                : fail(ctx, RPT_ERR_STATE, "rpt_set_object_windows: the context holds no copy of the caller's objects");
+        if (rc != RPT_OK) {
+            ctx->windows.swap(before);
+            return rc;
+        }
+    }
+    ctx->view_generation++;
     return RPT_OK;
 }
 

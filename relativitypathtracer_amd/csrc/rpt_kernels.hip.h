@@ -64,7 +64,8 @@ struct alignas(16) DObj {
     float b[3];
     float mesh_in_box;                       // mesh objects: 1 = every triangle the octree can report lies inside the root's box
     int root;                                // mesh objects: the root's index in the derived (breadth-first) node numbering
-    float pad;
+    float win_t0;                            // the object's time window (rpt_set_object_windows; the Windowed kernels only): a hit whose emission time t in
+                                             // the object's rest frame has t < win_t0 or t >= win_t1 (below) does not exist.  0, 0 while the context has none
     // the shadow-ray culls of a mesh object (mesh_ray_misses_root, mesh_segment_apart below; build_dobjs derives them per frame):
     // half extents of the root box about (cbx, cby, cbz) grown by 8u max(|lo|, |hi|) (mh[0] < 0: no cull of this object at all);
     // the segment cull's margin = mconst + mslope * (L1 distance of the ray origin from the centre) (mslope < 0: no segment cull);
@@ -72,7 +73,7 @@ struct alignas(16) DObj {
     float mh[3];
     float mconst, mslope, mcw;
     float ms0;                               // the constant part of that allowance (1e-4 + what the object's own translation costs)
-    float pad2;
+    float win_t1;
 };
 static_assert(sizeof(DObj) == 128, "DObj");
 
@@ -692,6 +693,7 @@ struct KernelPolicy {
     static constexpr bool doppler = false;       // the Doppler twin (rpt_set_doppler; the arguments are a DopplerArgs)
     static constexpr bool drec = false;          // ... that also writes the per-pixel Doppler record (the debug kernel only)
     static constexpr bool environment = false;   // a pixel that hits nothing looks the sky image up (rpt_set_environment; the arguments are an EnvironmentArgs)
+    static constexpr bool windowed = false;      // every hit, occluder and light is held against its object's time window (rpt_set_object_windows; DObj::win_t0, win_t1)
     static constexpr int diag = 0;               // the measurement arm's number (diagnostics build only); 0 in every product policy
 };
 struct RefLayout : KernelPolicy { static constexpr Walk walk = Walk::reference; static constexpr bool culled = false; };        // 1
@@ -722,6 +724,15 @@ template <class P> struct Lens : P { static constexpr Camera camera = Camera::le
 // pinhole's plane) and with it no tile bitmaps, the shadow-segment culls kept.  1203 / 1241 / 1244: Raymap<P> for the plain kernels; + 10:
 // DopplerTwin<Raymap<P>>; + 20: Environment<Raymap<P>>
 template <class P> struct Raymap : P { static constexpr Camera camera = Camera::raymap; static constexpr bool object_mask = false; static constexpr bool tile_bits = false; };   // 12xx
+
+// the windowed kernels (rpt_set_object_windows): the policy they wrap with the three window tests compiled in (trace, sample_light_occluded,
+// events_pixel_body).  Wrapped are the lens kernels (which serve the pinhole at lens_scale 1.0f: the same bytes), the panorama's and the
+// ray map's; the colour is the Doppler twin with DopplerArgs::doppler as a run-time flag (0: the plain kernel's frame, as in the sky
+// family) or the sky.  2000 + the wrapped row's variant.  DESIGN.md "Time windows".
+template <class P> struct Windowed : P { static constexpr bool windowed = true; };                                              // 2xxx
+
+// in(W, t) of DESIGN.md "Time windows": written with two negated compares so that a NaN time, and the default (-inf, +inf), accept
+RPT_DEV bool window_accepts(const DObj &pre, float t) { return !(t < pre.win_t0) && !(t >= pre.win_t1); }
 
 template <class P>
 RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const Ray &newRay, f3 world_origin, float world_dirlen, Hit &hit) {
@@ -1000,7 +1011,11 @@ RPT_DEV bool sample_light_occluded(const KernelArgs &a, f4 origin4, f4 dir4, flo
             const f4 newEvent0 = transformPoint4D(a.objects[i].Lorentz, origin4);
             const f4 lightDir = transformPoint4D(a.objects[i].Lorentz, lightDir0);
             if (intersect_object<P>(a, i, newEvent0, lightDir, newHit, lightDist)) {
-                if (newHit.dist < lightDist) return true;
+                if constexpr (P::windowed) {     // the occluder's event in its own rest frame: the two products above, nothing new
+                    if (newHit.dist < lightDist && window_accepts(a.dobjs[i], newEvent0.x + lightDir.x * newHit.dist)) return true;
+                } else {
+                    if (newHit.dist < lightDist) return true;
+                }
             }
         }
     }
@@ -1130,7 +1145,12 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
         if (P::walk == Walk::reference) got = intersect_object<P>(a, i, ld4(a.objects[i].stationaryCam), transformPoint4D(a.objects[i].Lorentz, rayDir), newHit);
         else got = intersect_object_primary<P>(a, i, rayDir, newHit);
         if (got) {
-            if (newHit.dist < hit.dist) {
+            if constexpr (P::windowed) {         // the flash term's expression below, on the candidate: the emission time in object i's rest frame
+                if (newHit.dist < hit.dist && window_accepts(a.dobjs[i], a.objects[i].stationaryCam.x + dot(ld4(a.objects[i].Lorentz[0]), rayDir) * newHit.dist)) {
+                    hit = newHit;
+                    hit.object = i;
+                }
+            } else if (newHit.dist < hit.dist) {
                 hit = newHit;
                 hit.object = i;
             }
@@ -1172,6 +1192,9 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
                 const f3 lightDir3_LightFrame = lightPos3_LightFrame - yzw(hitPos_LightFrame);
                 const f4 lightDir_LightFrame = mk4(a.interval * length(lightDir3_LightFrame), lightDir3_LightFrame.x,
                                                    lightDir3_LightFrame.y, lightDir3_LightFrame.z);
+                if constexpr (P::windowed) {     // the emission event in the light's rest frame: a light outside its window is dark, and shoots no shadow ray
+                    if (!window_accepts(a.dobjs[i], hitPos_LightFrame.x + lightDir_LightFrame.x)) continue;
+                }
                 const f4 lightDir = transformPoint4D(lo.InvLorentz, lightDir_LightFrame);
                 const f4 lightDir_ObjFrame = transformPoint4D(ho.Lorentz, lightDir);
                 const f3 lightDir3_ObjFrame = yzw(lightDir_ObjFrame);
@@ -1606,7 +1629,12 @@ RPT_DEV void events_pixel_body(const EventArgs &a) {
             Hit newHit;
             newHit.dist = inf;
             if (intersect_object_primary<P>(a, i, rayDir, newHit)) {
-                if (newHit.dist < hit.dist) {
+                if constexpr (P::windowed) {     // (trace()'s own test: the winner's event[0] below is this float)
+                    if (newHit.dist < hit.dist && window_accepts(a.dobjs[i], a.objects[i].stationaryCam.x + dot(ld4(a.objects[i].Lorentz[0]), rayDir) * newHit.dist)) {
+                        hit = newHit;
+                        hit.object = i;
+                    }
+                } else if (newHit.dist < hit.dist) {
                     hit = newHit;
                     hit.object = i;
                 }
@@ -1747,6 +1775,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_raymap(const RaymapEventArgs a) { events_pixel_body<Raymap<BallotExact>>(a); }    // 1291
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_raymap_ieee(const RaymapEventArgs a) { events_pixel_body<Raymap<Ballot>>(a); }    // (1291)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_raymap_analytic(const RaymapEventArgs a) { events_pixel_body<Raymap<Analytic>>(a); }    // 1294
+
+// Windowed kernels (rpt_set_object_windows; not in the reference): Windowed<P> over the lens kernels (the pinhole's too, at lens_scale
+// 1.0f), the panorama's and the ray map's, each as the Doppler twin with the run-time flag (plain: doppler = 0) and as the sky form; un-culled,
+// the walk with its IEEE form, and without the walk.  No band-first form: such a choice gets the walk.  Same launch shapes, argument
+// blocks and occupancy attributes as the kernels they wrap.  DESIGN.md "Time windows".
+#define RPT_WINDOWED_FAMILY(name, ARGS, UNC, WALK, IEEE, ANA)                                                                                              \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_win_##name##_unculled_w5(const ARGS a) { render_pixel_body<Windowed<UNC>>(a); }    \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_win_##name##_walk_w5(const ARGS a) { render_pixel_body<Windowed<WALK>>(a); }       \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_win_##name##_walk_ieee_w5(const ARGS a) { render_pixel_body<Windowed<IEEE>>(a); }  \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_win_##name##_analytic_w8(const ARGS a) { render_pixel_body<Windowed<ANA>>(a); }
+RPT_WINDOWED_FAMILY(lens, LensArgs, Lens<DopplerTwin<Unculled>>, Lens<DopplerTwin<BallotExact>>, Lens<DopplerTwin<Ballot>>, Lens<DopplerTwin<Analytic>>)                        // 2803.. / 2813..
+RPT_WINDOWED_FAMILY(lens_env, LensArgs, Lens<Environment<Unculled>>, Lens<Environment<BallotExact>>, Lens<Environment<Ballot>>, Lens<Environment<Analytic>>)                    // 2823..
+RPT_WINDOWED_FAMILY(pano, PanoramaArgs, DopplerTwin<PanoramaUnculled>, DopplerTwin<PanoramaWalk>, DopplerTwin<PanoramaWalkIeee>, DopplerTwin<PanoramaAnalytic>)                 // 2303.. / 2503..
+RPT_WINDOWED_FAMILY(pano_env, EnvironmentArgs, Environment<PanoramaUnculled>, Environment<PanoramaWalk>, Environment<PanoramaWalkIeee>, Environment<PanoramaAnalytic>)          // 2703..
+RPT_WINDOWED_FAMILY(raymap, RaymapArgs, DopplerTwin<Raymap<Unculled>>, DopplerTwin<Raymap<BallotExact>>, DopplerTwin<Raymap<Ballot>>, DopplerTwin<Raymap<Analytic>>)             // 3203.. / 3213..
+RPT_WINDOWED_FAMILY(raymap_env, RaymapArgs, Environment<Raymap<Unculled>>, Environment<Raymap<BallotExact>>, Environment<Raymap<Ballot>>, Environment<Raymap<Analytic>>)         // 3223..
+#undef RPT_WINDOWED_FAMILY
+// ... and the windowed event kernels: the event kernels' policies wrapped (the lens forms serve the pinhole), their occupancies kept
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_lens_unculled(const EventArgs a) { events_pixel_body<Windowed<Lens<Unculled>>>(a); }    // 2903 / 2923
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_lens_walk(const EventArgs a) { events_pixel_body<Windowed<Lens<BallotExact>>>(a); }    // 2941 / 2921
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_lens_walk_ieee(const EventArgs a) { events_pixel_body<Windowed<Lens<Ballot>>>(a); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_win_lens_analytic(const EventArgs a) { events_pixel_body<Windowed<Lens<Analytic>>>(a); }    // 2944 / 2924
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_pano_walk(const EventArgs a) { events_pixel_body<Windowed<PanoramaWalk>>(a); }    // 2911
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_pano_walk_ieee(const EventArgs a) { events_pixel_body<Windowed<PanoramaWalkIeee>>(a); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_win_pano_analytic(const EventArgs a) { events_pixel_body<Windowed<PanoramaAnalytic>>(a); }    // 2914
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_raymap_walk(const RaymapEventArgs a) { events_pixel_body<Windowed<Raymap<BallotExact>>>(a); }    // 3291
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_events_kernel_win_raymap_walk_ieee(const RaymapEventArgs a) { events_pixel_body<Windowed<Raymap<Ballot>>>(a); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_events_kernel_win_raymap_analytic(const RaymapEventArgs a) { events_pixel_body<Windowed<Raymap<Analytic>>>(a); }    // 3294
 
 // ---- Adaptive anti-aliasing (rpt_set_adaptive_aa; not in the reference; DESIGN.md "Adaptive anti-aliasing") ------------------------------
 // The second launch of an adaptive frame.  The first is the one-sample kernel a frame gets anyway (its source and its code untouched),

@@ -26,7 +26,8 @@ RAYMAP_KINDS = {"fisheye": 0, "equisolid": 1, "stereographic": 2, "cube_strip": 
 
 
 class RenderError(RuntimeError):
-    pass
+    """A call of the library failed; `code` is its return code (include/rpt.h: RPT_ERR_*), None where no call is behind it."""
+    code = None
 
 
 def _projection_args(mode: str, h_fov: float, v_fov: float, yaw: float):
@@ -162,7 +163,9 @@ class Renderer:
 
     def _check(self, rc: int, what: str):
         if rc != 0:
-            raise RenderError(f"{what} failed ({rc}): {self._lib.rpt_last_error(self._h).decode()}")
+            e = RenderError(f"{what} failed ({rc}): {self._lib.rpt_last_error(self._h).decode()}")
+            e.code = int(rc)
+            raise e
 
     # -- reference enqueue sequence ------------------------------------------------------------
     def upload_scene(self, scene: Scene):
@@ -176,10 +179,33 @@ class Renderer:
     def upload_desc(self, desc: _ffi.SceneDesc):
         self._check(self._lib.rpt_upload_scene(self._h, C.byref(desc)), "rpt_upload_scene")
 
+    def set_object_windows(self, windows):
+        """Per-object time windows (include/rpt.h, rpt_set_object_windows): an (object_count, 2) array of {t0, t1} in each object's own
+        rest frame — the object, as a surface, an occluder and a light, exists for t0 <= t < t1; -inf / +inf are the defaults — copied
+        by the library.  None clears the setting.  Per context.  While set, the windowed kernels render (last_variant() >= 2000)."""
+        self._scene_windows = None          # (what set_objects(scene) last passed on is no longer what the context holds)
+        if windows is None:
+            self._check(self._lib.rpt_set_object_windows(self._h, None, 0), "rpt_set_object_windows")
+            return
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if not (w.ndim == 2 and w.shape[1] == 2):
+            raise ValueError(f"windows are an (object_count, 2) array, not {w.shape}")
+        self._check(self._lib.rpt_set_object_windows(self._h, w.ctypes.data, int(w.shape[0])), "rpt_set_object_windows")
+
     def set_objects(self, scene_or_bytes):
         if isinstance(scene_or_bytes, Scene):
             d = scene_or_bytes.desc()
             self._check(self._lib.rpt_set_objects(self._h, d.objects, d.object_count), "rpt_set_objects")
+            # the scene's `w` commands (Scene.windows() is cached by the scene): passed on when they are not what this call passed on
+            # last — behind the objects, so that the upload the library repeats for them is of these objects — and cleared when a
+            # scene without any follows one that had some.  Windows set by hand (set_object_windows) are left alone.
+            w, last = scene_or_bytes.windows(), getattr(self, "_scene_windows", None)
+            if w is None:
+                if last is not None:
+                    self.set_object_windows(None)
+            elif last is None or not np.array_equal(w, last):
+                self.set_object_windows(w)
+                self._scene_windows = w
         else:
             raw = np.ascontiguousarray(scene_or_bytes).view(np.uint8)
             assert raw.size % 320 == 0
@@ -582,6 +608,8 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
             r.set_environment(environment)
             r.set_environment_frame(scene.camera_lorentz()[1])
         r.upload_scene(scene)
+        if scene.windows() is not None:       # (the scene's `w` commands)
+            r.set_object_windows(scene.windows())
         r.set_scene_params(scene, width, height)
         r.set_output(None)
         if debug_rgb:

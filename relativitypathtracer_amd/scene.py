@@ -66,6 +66,7 @@ class Scene:
             self._lib.rpt_scene_add_alias(self._h, k.encode(), v.encode())
         self._lib.rpt_scene_set_texture_decoder(self._h, _PIL_DECODER, None)
         self.asset_root = asset_root
+        self._windows = False               # windows(): not asked yet
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -79,6 +80,7 @@ class Scene:
 
     def inputScene(self, text: str) -> str:
         """Parse a whole scene description (what the reference reads from stdin). Returns diagnostics."""
+        self._windows = False
         self._check(self._lib.rpt_scene_input(self._h, text.encode()), "inputScene")
         return self._lib.rpt_scene_last_error(self._h).decode()
 
@@ -214,6 +216,21 @@ class Scene:
         n = C.c_size_t()
         self._lib.rpt_scene_get_velocities(self._h, C.byref(p), C.byref(n))
         return self._view(p.value, n.value, np.float32, 4).copy()
+
+    def windows(self):
+        """The time windows of the scene's `wT0,T1` commands: an (object_count, 2) float32 array of {t0, t1} in each object's rest frame,
+        (-inf, +inf) where none was given — what Renderer.set_object_windows takes; read-only — or None for a scene without any `w`."""
+        if self._windows is False:          # (only inputScene changes them: asked of the library once per parse)
+            n = C.c_size_t()
+            any_ = C.c_int()
+            self._lib.rpt_scene_get_windows(self._h, None, 0, C.byref(n), C.byref(any_))
+            self._windows = None
+            if any_.value:
+                out = np.empty((n.value, 2), dtype=np.float32)
+                self._lib.rpt_scene_get_windows(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(any_))
+                out.setflags(write=False)
+                self._windows = out
+        return self._windows
 
     def mesh_roots(self):
         p = C.c_void_p()
