@@ -382,6 +382,23 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
 int rpt_tile_bitmap_host(const rpt_scene_desc *scene, int object_index, int interval, int width, int height, float lens_scale, int max_boxes,
                          const float *boxes_or_null, int n_boxes, uint32_t *bits_out, size_t words, int stats_out[5]);
 int rpt_tile_bitmap_state(rpt_ctx *ctx, unsigned long long out[4], int object_index, uint32_t *bits_or_null, size_t words);
+/* The derived layouts of a scene as rpt_upload_scene would put them on the device, built on the host alone (no device; tests).
+ * which = RPT_LAYOUT_NODES: one 64-B record per octree node in the derived, breadth-first numbering — {min.xyz, link, max.xyz, begin
+ *   word, leafCount, nb[6], 0}: link = -1 for a leaf, else first child | leaf mask << 24; begin word = leafBegin | min(leafCount, 255)
+ *   << 24; nb[] in the derived numbering;
+ * RPT_LAYOUT_EXITS: one 32-B record per (node, side), record 6 node + side — {min.xyz, a, max.xyz, b} of the node nb[side] names: a
+ *   leaf gives its box, a = its index and b = its begin word; an inner node its box, a = its link and b = RPT_EXIT_INNER; no neighbour
+ *   gives zeros, a = -1 and b = RPT_EXIT_INNER (no leaf's begin word);
+ * RPT_LAYOUT_HITS: one 64-B record per triangle id — normals A, B, C (9 floats), uvs A, B, C (6 floats), one spare word (0);
+ * RPT_LAYOUT_NODE_INDEX: one int per node: the reference's node index -> the derived one.
+ * *bytes_needed (if not NULL) receives the array's size; it is copied to `out` if out is not NULL and `bytes` holds it.
+ * 1: built; 0: this scene has no derived layout (it renders with the reference-layout kernel); < 0: -RPT_ERR_*. */
+#define RPT_LAYOUT_NODES 0
+#define RPT_LAYOUT_EXITS 1
+#define RPT_LAYOUT_HITS 2
+#define RPT_LAYOUT_NODE_INDEX 3
+#define RPT_EXIT_INNER 0x01ffffff
+int rpt_derived_layout_host(const rpt_scene_desc *scene, int which, void *out, size_t bytes, size_t *bytes_needed);
 /* Device probe: the object mask of every 8x8 tile of the current pinhole or lens frame as kernel 41 / 841 forms it, out[2 t] before and
  * out[2 t + 1] after the tile bitmaps (t = ty * ceil(width / 8) + tx; tiles = the number of tiles).  Prepares the frame as a launch does. */
 int rpt_probe_tile_masks(rpt_ctx *ctx, unsigned long long *out, size_t tiles);

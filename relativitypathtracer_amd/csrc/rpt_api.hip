@@ -72,6 +72,7 @@ struct Geometry {
     DeviceBuffer vertices, normals, uvs, triangles, octrees, octreeTris, textures;
     DeviceBuffer dnodes, dtris, dlinks;       // derived layouts (rpt_kernels.hip.h)
     DeviceBuffer dfirst;                      // first triangle record of every node's list, by node index (the latency walk)
+    DeviceBuffer dexits, dhits;               // exit records by (node, side), hit records by triangle id (rpt_kernels.hip.h: DExit, DHit)
     bool compact_ok = false;                  // derived octree layout usable (children consecutive)
     bool exact_rcp_ok = false;                // every triangle a walk tests lies in the exact reciprocal's domain (rpt_scene_exact_rcp)
     unsigned long long generation = 0;        // unique per upload (the rectangle cache of a context names its geometry by this, not by address)
@@ -85,10 +86,10 @@ struct Geometry {
     size_t vertex_count = 0, normal_count = 0, uv_count = 0, triangle_words = 0, octree_count = 0, octree_tri_count = 0;
     ~Geometry() {
         bool any = false;
-        for (const DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst}) any = any || b->ptr;
+        for (const DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst, &dexits, &dhits}) any = any || b->ptr;
         if (!any) return;                        // (a host-only copy, rpt_tile_bitmap_host: nothing of the device's to free)
         (void)hipSetDevice(device);
-        for (DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst}) release(*b);
+        for (DeviceBuffer *b : {&vertices, &normals, &uvs, &triangles, &octrees, &octreeTris, &textures, &dnodes, &dtris, &dlinks, &dfirst, &dexits, &dhits}) release(*b);
     }
 };
 
@@ -363,26 +364,28 @@ int validate_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
 // (a) the eight children of a node stay consecutive (they are one block in the reference's numbering too, Octree.cpp:191-269)
 // and (b) the top levels of every octree are the first `top_count` records: the persistent kernels keep those nodes' links
 // in LDS.  Geometry::node_new_index maps the reference's node index (Object::meshIndex) to the derived one (DObj::root).
-int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
-    Geometry &g = *ctx->geo;
-    g.compact_ok = false;
-    g.top_count = 0;
-    g.node_new_index.clear();
-    if (s.octree_count == 0) {
-        g.compact_ok = true;
-        if (int rc = reserve(ctx, g.dnodes, 0)) return rc;
-        if (int rc = reserve(ctx, g.dlinks, 0)) return rc;
-        return reserve(ctx, g.dtris, 0);
-    }
+// The exit records (DExit) and the hit records (DHit) are derived here too, from the finished DNodes and from triangles[] /
+// normals[] / uvs[]: copies of floats and words the library already holds, nothing computed.
+// derive_layouts is the host half (rpt_derived_layout_host hands its arrays out as they are); false = this scene has no derived
+// layout, and keeps the reference-layout kernel.  `s` is valid (validate_geometry) and has at least one octree node.
+struct DerivedLayouts {
+    std::vector<rptd::DNode> nodes;
+    std::vector<int32_t> links;
+    std::vector<rptd::DTri> tris, first;
+    std::vector<rptd::DExit> exits;
+    std::vector<rptd::DHit> hits;
+};
+
+bool derive_layouts(Geometry &g, const rpt_scene_desc &s, DerivedLayouts &L) {
     const size_t n = s.octree_count;
-    if (n > (size_t)RPT_LINK_CHILD_MASK) return RPT_OK;                // a link holds 24 bits of child index
+    if (n > (size_t)RPT_LINK_CHILD_MASK) return false;                 // a link holds 24 bits of child index
     std::vector<uint8_t> is_child(n, 0);
     for (size_t i = 0; i < n; i++) {
         const rpt_octree &o = s.octrees[i];
         if (o.children[0] == -1) continue;
         for (int c = 0; c < 8; c++) {
-            if (o.children[c] != o.children[0] + c) return RPT_OK;     // not consecutive: keep the general kernel
-            if (is_child[(size_t)o.children[c]]) return RPT_OK;        // a node with two parents: not a forest of trees
+            if (o.children[c] != o.children[0] + c) return false;     // not consecutive: keep the general kernel
+            if (is_child[(size_t)o.children[c]]) return false;        // a node with two parents: not a forest of trees
             is_child[(size_t)o.children[c]] = 1;
         }
     }
@@ -403,10 +406,13 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
         if (order.size() <= (size_t)RPT_TOP_MAX) g.top_count = (int)order.size();    // whole levels only
         level.swap(next);
     }
-    if (order.size() != n) return RPT_OK;                              // (cannot happen after validate_geometry: every node is a root or a child)
-    std::vector<rptd::DNode> nodes(n);
-    std::vector<int32_t> links(n);
-    std::vector<rptd::DTri> tris;
+    if (order.size() != n) return false;                              // (cannot happen after validate_geometry: every node is a root or a child)
+    std::vector<rptd::DNode> &nodes = L.nodes;
+    std::vector<int32_t> &links = L.links;
+    std::vector<rptd::DTri> &tris = L.tris;
+    nodes.assign(n, rptd::DNode());
+    links.assign(n, 0);
+    tris.clear();
     for (size_t k = 0; k < n; k++) {
         const rpt_octree &o = s.octrees[order[k]];
         rptd::DNode &d = nodes[k];
@@ -418,7 +424,7 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
             unsigned int leaf_mask = 0;
             for (int c = 0; c < 8; c++) leaf_mask |= (s.octrees[o.children[c]].children[0] == -1 ? 1u : 0u) << c;
             d.link = (int)((unsigned int)new_index[(size_t)o.children[0]] | (leaf_mask << 24));
-            if (d.link == -1) return RPT_OK;                            // (first child 0xffffff with eight leaf children: reserved for "leaf")
+            if (d.link == -1) return false;                            // (first child 0xffffff with eight leaf children: reserved for "leaf")
         }
         links[k] = d.link;
         for (int c = 0; c < 6; c++) d.nb[c] = o.neighbors[c] == -1 ? -1 : new_index[(size_t)o.neighbors[c]];
@@ -441,20 +447,75 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
             }
         }
     }
-    if (tris.size() > (size_t)RPT_NODE_BEGIN_MASK) return RPT_OK;      // (16.7 M triangle references: the general kernel takes such a scene)
+    if (tris.size() > (size_t)RPT_NODE_BEGIN_MASK) return false;      // (16.7 M triangle references: the general kernel takes such a scene)
     {   // the first record of every list again, by node index (load_first_tri) — before leafBegin gets the count packed into it
-        std::vector<rptd::DTri> first(n);
+        std::vector<rptd::DTri> &first = L.first;
+        first.resize(n);
         std::memset(first.data(), 0, first.size() * sizeof(rptd::DTri));
         for (size_t k = 0; k < n; k++) if (nodes[k].leafCount > 0) first[k] = tris[(size_t)nodes[k].leafBegin];
-        if (int rc = upload(ctx, g.dfirst, first.data(), first.size() * sizeof(rptd::DTri))) return rc;
     }
     for (size_t k = 0; k < n; k++)          // leafBegin | min(leafCount, 255) << 24: see load_node_rec
         nodes[k].leafBegin = (int)((unsigned int)nodes[k].leafBegin | ((unsigned int)(nodes[k].leafCount < 255 ? nodes[k].leafCount : 255) << 24));
+    // the exit records: (k, side) -> the box, and the index and begin word (a leaf) or the link (inner), of nodes[nodes[k].nb[side]]
+    L.exits.resize(6 * n);
+    for (size_t k = 0; k < n; k++)
+        for (int c = 0; c < 6; c++) {
+            rptd::DExit &e = L.exits[6 * k + (size_t)c];
+            std::memset(&e, 0, sizeof e);
+            e.a = -1;
+            e.b = RPT_EXIT_INNER;
+            const int nb = nodes[k].nb[c];
+            if (nb == -1) continue;
+            const rptd::DNode &d = nodes[(size_t)nb];
+            e.minx = d.minx; e.miny = d.miny; e.minz = d.minz;
+            e.maxx = d.maxx; e.maxy = d.maxy; e.maxz = d.maxz;
+            if (d.link == -1) {
+                e.a = nb;
+                e.b = d.leafBegin;
+                // (cannot happen: a count below 255 is the list's own, and the list ends inside the 0xffffff records checked above)
+                if (e.b == RPT_EXIT_INNER || nb < 0 || nb > RPT_LINK_CHILD_MASK) return false;
+            } else {
+                e.a = d.link;                                           // (never -1: checked where the link was made)
+            }
+        }
+    // the hit records: the floats that triangles[9 t + 3 c + 2] / [+ 1] name in normals[] / uvs[]
+    const size_t n_tris = s.triangle_words / RPT_TRI_STRIDE;
+    L.hits.resize(n_tris);
+    for (size_t t = 0; t < n_tris; t++) {
+        rptd::DHit &h = L.hits[t];
+        std::memset(&h, 0, sizeof h);
+        float *nrm[3] = {h.nA, h.nB, h.nC}, *tex[3] = {h.uvA, h.uvB, h.uvC};
+        for (int c = 0; c < 3; c++) {
+            const rpt_float3 &nv = s.normals[s.triangles[9 * t + 3 * (size_t)c + 2]];
+            const rpt_float2 &tv = s.uvs[s.triangles[9 * t + 3 * (size_t)c + 1]];
+            nrm[c][0] = nv.x; nrm[c][1] = nv.y; nrm[c][2] = nv.z;
+            tex[c][0] = tv.x; tex[c][1] = tv.y;
+        }
+    }
+    return true;
+}
+
+int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
+    Geometry &g = *ctx->geo;
+    g.compact_ok = false;
+    g.top_count = 0;
+    g.node_new_index.clear();
+    if (s.octree_count == 0) {
+        g.compact_ok = true;
+        if (int rc = reserve(ctx, g.dnodes, 0)) return rc;
+        if (int rc = reserve(ctx, g.dlinks, 0)) return rc;
+        return reserve(ctx, g.dtris, 0);
+    }
+    DerivedLayouts L;
+    if (!derive_layouts(g, s, L)) return RPT_OK;
+    if (int rc = upload(ctx, g.dfirst, L.first.data(), L.first.size() * sizeof(rptd::DTri))) return rc;
     // (16 B of slack behind the triangle records: the cooperative 16-B staging loads of the persistent kernels never start past the
     // last record, but keep the buffer's end away from them all the same)
-    if (int rc = upload(ctx, g.dnodes, nodes.data(), nodes.size() * sizeof(rptd::DNode))) return rc;
-    if (int rc = upload(ctx, g.dlinks, links.data(), links.size() * sizeof(int32_t))) return rc;
-    if (int rc = upload(ctx, g.dtris, tris.data(), tris.size() * sizeof(rptd::DTri))) return rc;
+    if (int rc = upload(ctx, g.dnodes, L.nodes.data(), L.nodes.size() * sizeof(rptd::DNode))) return rc;
+    if (int rc = upload(ctx, g.dlinks, L.links.data(), L.links.size() * sizeof(int32_t))) return rc;
+    if (int rc = upload(ctx, g.dtris, L.tris.data(), L.tris.size() * sizeof(rptd::DTri))) return rc;
+    if (int rc = upload(ctx, g.dexits, L.exits.data(), L.exits.size() * sizeof(rptd::DExit))) return rc;
+    if (int rc = upload(ctx, g.dhits, L.hits.data(), L.hits.size() * sizeof(rptd::DHit))) return rc;
     g.compact_ok = true;
     return RPT_OK;
 }
@@ -1470,6 +1531,8 @@ void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
     a.links = (const int *)ctx->geo->dlinks.ptr;
     a.first_tris = (const rptd::DTri *)ctx->geo->dfirst.ptr;
+    a.exits = (const rptd::DExit *)ctx->geo->dexits.ptr;
+    a.hits = (const rptd::DHit *)ctx->geo->dhits.ptr;
     a.top_count = ctx->geo->top_count;
     a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
     a.objects = (const rpt_object *)ctx->objects.ptr;
@@ -2365,6 +2428,27 @@ int rpt_tile_bitmap_host(const rpt_scene_desc *s, int object_index, int interval
     return ok ? 1 : 0;
 }
 
+// The derived layouts of `scene` on the host alone: what build_derived_geometry uploads, array by array (include/rpt.h).
+int rpt_derived_layout_host(const rpt_scene_desc *s, int which, void *out, size_t bytes, size_t *bytes_needed) {
+    if (!s || which < RPT_LAYOUT_NODES || which > RPT_LAYOUT_NODE_INDEX) return -RPT_ERR_ARG;
+    rpt_ctx tmp;
+    if (validate_geometry(&tmp, *s) != RPT_OK) return -RPT_ERR_SCENE;
+    if (s->octree_count == 0) return 0;
+    Geometry g;
+    DerivedLayouts L;
+    if (!derive_layouts(g, *s, L)) return 0;
+    const void *src = which == RPT_LAYOUT_NODES ? (const void *)L.nodes.data() : which == RPT_LAYOUT_EXITS ? (const void *)L.exits.data()
+                    : which == RPT_LAYOUT_HITS ? (const void *)L.hits.data() : (const void *)g.node_new_index.data();
+    const size_t need = which == RPT_LAYOUT_NODES ? L.nodes.size() * sizeof(rptd::DNode) : which == RPT_LAYOUT_EXITS ? L.exits.size() * sizeof(rptd::DExit)
+                      : which == RPT_LAYOUT_HITS ? L.hits.size() * sizeof(rptd::DHit) : g.node_new_index.size() * sizeof(int);
+    if (bytes_needed) *bytes_needed = need;
+    if (out) {
+        if (bytes < need) return -RPT_ERR_ARG;
+        if (need) std::memcpy(out, src, need);
+    }
+    return 1;
+}
+
 // The context's tile bitmaps: out = {objects that have one on the device for the current frame, bitmaps built so far, host
 // microseconds of the last build, dwords per bitmap}; bits_or_null: the bitmap of `object_index` (the pinned copy the device's was made from)
 int rpt_tile_bitmap_state(rpt_ctx *ctx, unsigned long long out[4], int object_index, uint32_t *bits_or_null, size_t words) {
@@ -2904,6 +2988,8 @@ static void probe_kernel_args(rpt_ctx *ctx, rptd::KernelArgs &a) {
     a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
     a.links = (const int *)ctx->geo->dlinks.ptr;
     a.first_tris = (const rptd::DTri *)ctx->geo->dfirst.ptr;
+    a.exits = (const rptd::DExit *)ctx->geo->dexits.ptr;
+    a.hits = (const rptd::DHit *)ctx->geo->dhits.ptr;
     a.top_count = ctx->geo->top_count;
     a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
     a.objects = (const rpt_object *)ctx->objects.ptr;

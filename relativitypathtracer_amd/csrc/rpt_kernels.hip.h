@@ -52,6 +52,26 @@ static_assert(sizeof(DNode) == 64, "DNode is one 64-B line");
 // octreeTris -> triangles -> vertices chain of three dependent loads.
 struct alignas(16) DTri { float ax, ay, az, e1x; float e1y, e1z, e2x, e2y; float e2z; int tri; int pad0, pad1; };
 static_assert(sizeof(DTri) == 48, "DTri is three 16-B loads");
+// What a walk that leaves node n through side s stands on next, by (n, s): record 6 n + s, two 16-B loads from ONE address instead of
+// nb[s] and then the neighbour's node record from the address it returned.  The box is the very floats of the neighbour's DNode;
+//   the neighbour is a leaf:  a = its index (24 bits),          b = its leafBegin word (leafBegin | min(leafCount, 255) << 24);
+//   the neighbour is inner:   a = its link (any 32 bits but -1), b = RPT_EXIT_INNER;
+//   there is no neighbour:    a = -1,                            b = RPT_EXIT_INNER, the box zeros.
+// RPT_EXIT_INNER is no leaf's word: a top byte of 1 says the list has exactly one record, which would end at 0x1000000, and the derived
+// layout holds at most 0xffffff records (rpt_api.hip: derive_layouts checks both).  So no bit that a link or a begin word can set is taken.
+#ifndef RPT_EXIT_RECORDS
+#define RPT_EXIT_RECORDS 1      /* 0: the throughput walk reads nb[] and the node record, as before (tools/exit_hit_ab.py builds that arm) */
+#endif
+#ifndef RPT_HIT_RECORDS
+#define RPT_HIT_RECORDS 1       /* 0: a hit's normals and uvs through triangles[] -> normals[] / uvs[], as before (likewise) */
+#endif
+#define RPT_EXIT_INNER 0x01ffffff
+struct alignas(32) DExit { float minx, miny, minz; int a; float maxx, maxy, maxz; int b; };
+static_assert(sizeof(DExit) == 32, "DExit is two 16-B loads");
+// What mesh_hit_finish needs of triangle id t, record t: the three normals and the three uvs that triangles[9 t ...] names, the floats
+// of normals[] / uvs[] themselves — one hop and four 16-B loads behind the id instead of two hops and twelve loads.
+struct alignas(64) DHit { float nA[3], nB[3], nC[3]; float uvA[2], uvB[2], uvC[2]; int spare; };
+static_assert(sizeof(DHit) == 64, "DHit is one 64-B line");
 // Per object, per frame: the primary-ray origin in object space (every primary ray of a frame
 // starts at the camera event, opencl_kernel.cl:386-389) and what follows from it alone.
 struct alignas(16) DObj {
@@ -139,6 +159,8 @@ struct KernelArgs {
     unsigned long long *wave_times; // diagnostic build only (variant 11): ten words per wave, {start, end} of s_memrealtime (100 MHz) + loop accounting
     unsigned long long *counters;   // diagnostic builds only (variant 7): [0..2] lane-level leaf/tri/descent
                                     // iterations, [3..5] the same counted once per executing wave
+    const DExit *exits;             // [6 * nodes] where a walk stands after leaving node n through side s (DExit above)
+    const DHit *hits;               // [triangles] the normals and uvs of a triangle id, gathered (DHit above)
 };
 
 // The Doppler kernels' arguments (rpt_set_doppler; not in the reference): KernelArgs with two fields appended at the end.  A struct
@@ -179,7 +201,7 @@ struct LensArgs : EnvironmentArgs {
 // (RefineArgs and EventArgs below extend LensArgs in the same way.)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
-static_assert(__builtin_offsetof(LensArgs, rects) == 0 && __builtin_offsetof(LensArgs, counters) + sizeof(void *) == sizeof(KernelArgs), "KernelArgs first");
+static_assert(__builtin_offsetof(LensArgs, rects) == 0 && __builtin_offsetof(LensArgs, hits) + sizeof(void *) == sizeof(KernelArgs), "KernelArgs first");
 static_assert(__builtin_offsetof(LensArgs, doppler) >= sizeof(KernelArgs) && __builtin_offsetof(LensArgs, debug_doppler) + sizeof(void *) == sizeof(DopplerArgs), "then DopplerArgs' fields");
 static_assert(__builtin_offsetof(LensArgs, pano_cols) >= sizeof(DopplerArgs) && __builtin_offsetof(LensArgs, pano_rows) + sizeof(void *) == sizeof(PanoramaArgs), "then PanoramaArgs' fields");
 static_assert(__builtin_offsetof(LensArgs, env_texels) >= sizeof(PanoramaArgs) && __builtin_offsetof(LensArgs, env_frame) + sizeof(rpt_float4[4]) == sizeof(EnvironmentArgs), "then EnvironmentArgs' fields");
@@ -399,18 +421,34 @@ RPT_DEV bool exit_is_past_hit(f3 v, float hit_dist, bool didHit) {
     return __builtin_sqrtf(s) > hit_dist;
 }
 // opencl_kernel.cl:287-306: normal, texture coordinates and the distance re-measured in the caller's frame, from the walk's
-// closest triangle (hit.dist parametric, hit.uv barycentric on entry)
+// closest triangle (hit.dist parametric, hit.uv barycentric on entry).  HIT_RECORD: the fifteen floats from the triangle's DHit (the
+// derived layouts' walk); otherwise through triangles[] into normals[] / uvs[] (the reference's layouts, the persistent kernels) — the
+// same floats either way, and the same arithmetic on them.
+template <bool HIT_RECORD = false>
 RPT_DEV void mesh_hit_finish(const KernelArgs &a, const rpt_object &obj, f3 origin, f3 dir, int hitTri, f3 world_origin,
                              float world_dirlen, Hit &hit) {
     const float u = hit.uv.x, v = hit.uv.y;
     const float w = 1.0f - u - v;
-    const f3 normA = ld3(a.normals[a.triangles[2 + 9 * hitTri + 3 * 0]]);
-    const f3 normB = ld3(a.normals[a.triangles[2 + 9 * hitTri + 3 * 1]]);
-    const f3 normC = ld3(a.normals[a.triangles[2 + 9 * hitTri + 3 * 2]]);
+    f3 normA, normB, normC;
+    rpt_float2 uvA, uvB, uvC;
+    if (HIT_RECORD) {
+        const v4f *p = reinterpret_cast<const v4f *>(a.hits + hitTri);
+        const v4f h0 = p[0], h1 = p[1], h2 = p[2], h3 = p[3];
+        normA = mk3(h0.x, h0.y, h0.z);
+        normB = mk3(h0.w, h1.x, h1.y);
+        normC = mk3(h1.z, h1.w, h2.x);
+        uvA.x = h2.y; uvA.y = h2.z;
+        uvB.x = h2.w; uvB.y = h3.x;
+        uvC.x = h3.y; uvC.y = h3.z;
+    } else {
+        normA = ld3(a.normals[a.triangles[2 + 9 * hitTri + 3 * 0]]);
+        normB = ld3(a.normals[a.triangles[2 + 9 * hitTri + 3 * 1]]);
+        normC = ld3(a.normals[a.triangles[2 + 9 * hitTri + 3 * 2]]);
+        uvA = a.uvs[a.triangles[1 + 9 * hitTri + 3 * 0]];
+        uvB = a.uvs[a.triangles[1 + 9 * hitTri + 3 * 1]];
+        uvC = a.uvs[a.triangles[1 + 9 * hitTri + 3 * 2]];
+    }
     hit.normal = normalize(applyTranspose(obj.InvM, normA * w + normB * u + normC * v));
-    const rpt_float2 uvA = a.uvs[a.triangles[1 + 9 * hitTri + 3 * 0]];
-    const rpt_float2 uvB = a.uvs[a.triangles[1 + 9 * hitTri + 3 * 1]];
-    const rpt_float2 uvC = a.uvs[a.triangles[1 + 9 * hitTri + 3 * 2]];
     hit.uv.x = w * uvA.x + u * uvB.x + v * uvC.x;
     hit.uv.y = w * uvA.y + u * uvB.y + v * uvC.y;
     const f3 objPoint = origin + dir * hit.dist;
@@ -592,9 +630,14 @@ RPT_DEV int descend_to_leaf(const KernelArgs &a, int link, f3 &uv) {
 //   latency walk 2-4.5 %, whose count then sits behind a shift and a compare instead of arriving beside the box:
 //   profiles/r03_packed_count_ab.txt).
 // EXACT_RCP: the triangle test's 1 / det without the IEEE scaling (intersect_triangle_edges); the host selects it per scene.
-template <bool LATENCY, bool EXACT_RCP>
+// EXITS: a leaf is left through its exit record (DExit: the neighbour's box, index or link and begin word from ONE address, asked for
+// after the triangle loop) instead of nb[] and then the neighbour's node record; the "no neighbour" break moves behind that load.
+// The throughput walk takes it; the latency walk does not: there the record arrives a hop before first_tris can be asked for, and
+// kernel 43 lost 10 % on bunny 1080p in flight with it (profiles/r16_exit_hit_ab.txt).
+template <bool LATENCY, bool EXACT_RCP, bool EXITS = (RPT_EXIT_RECORDS != 0) && !LATENCY>
 RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, const Ray &newRay, f3 world_origin,
                          float world_dirlen, Hit &hit) {
+    static_assert(!(EXITS && LATENCY), "exit records: the throughput walk only");
     int curr = root;
     NodeRec rec = load_node_rec<!LATENCY>(a, curr);
     f2 d;
@@ -633,7 +676,8 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
         int i = __float_as_int(rec.hi.w) & RPT_NODE_BEGIN_MASK;
         const int trisEnd = i + rec.count;
         farSide = getOppositeBoxSide(plan, uv);             // the way out, before the triangles
-        const int next = a.dnodes[curr].nb[farSide];
+        int next = 0;
+        if (!EXITS) next = a.dnodes[curr].nb[farSide];
         if (LATENCY) {
             if (i < trisEnd) {
                 TriRec cur = first;
@@ -649,6 +693,20 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
             for (; i < trisEnd; i++) test_tri_rec<EXACT_RCP>(load_tri_rec<true>(a, i), newRay, hit, hitTri, didHit);
         }
         uv = nmin + uv * (nmax - nmin);
+        if (EXITS) {
+            const v4f *p = reinterpret_cast<const v4f *>(a.exits + (curr * 6 + farSide));
+            const v4f lo = p[0], hi = p[1];
+            const int ea = __float_as_int(lo.w), eb = __float_as_int(hi.w);
+            if (exit_is_past_hit(uv - newRay.origin, hit.dist, didHit) || ea == -1) break;
+            const bool inner = eb == RPT_EXIT_INNER;
+            curr = ea;                                      // (an inner neighbour: its link, until the descent above names the leaf)
+            rec.lo = lo;
+            rec.hi = hi;
+            rec.lo.w = __int_as_float(inner ? ea : -1);
+            rec.count = (int)((unsigned int)eb >> 24);      // (RPT_EXIT_INNER: 1, and the descent loads the leaf's own record)
+            if (rec.count == 255) rec.count = a.dnodes[curr].leafCount;
+            continue;
+        }
         if (exit_is_past_hit(uv - newRay.origin, hit.dist, didHit) || next == -1) break;
         curr = next;
         rec = load_node_rec<!LATENCY>(a, curr);
@@ -656,7 +714,7 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
     }
     if (!didHit) return false;
     hitTri = a.dtris[hitTri].tri;
-    mesh_hit_finish(a, obj, newRay.origin, newRay.dir, hitTri, world_origin, world_dirlen, hit);
+    mesh_hit_finish<RPT_HIT_RECORDS != 0>(a, obj, newRay.origin, newRay.dir, hitTri, world_origin, world_dirlen, hit);
     return true;
 }
 
