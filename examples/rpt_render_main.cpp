@@ -28,6 +28,9 @@
 // omitted: the frame's largest).  The host runs the three passes — the colour frame, an event frame of the same view, the overlay — and
 // reports the pixels the overlay changed on stderr.  Without the flag nothing changes.
 //
+// A scene with `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands gets its displays drawn too (rpt_set_readouts, rpt_render_readouts;
+// not in the reference): seven-segment digits on those objects that show their own time, after the overlay, before the picture is written.
+//
 // With `frames` > 1 the clock runs (16 ms per frame, as the reference's timer does) and the frames are rendered with
 // `in_flight` of them overlapping on the GPU: rpt::FrameRing (include/rpt_frames.hpp) — one context per frame slot
 // sharing one resident scene (rpt_share_scene), frame f in slot f mod in_flight.  The PPM is the last frame.
@@ -317,6 +320,27 @@ int main(int argc, char **argv) {
         }
         std::fprintf(stderr, "overlay: %llu of %lld pixels changed\n", changed, (long long)width * height);
     }
+    {   // the scene's `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands (not in the reference): objects that display their own time,
+        // drawn on that frame from an event frame of the same view (rpt_set_readouts, rpt_render_readouts); a scene without any sets nothing
+        size_t n_objects = 0;
+        int any_readout = 0;
+        rpt_scene_get_readouts(scene, nullptr, 0, &n_objects, &any_readout);
+        if (any_readout) {
+            std::vector<rpt_readout> readouts(n_objects);
+            unsigned long long changed = 0;
+            rpt_scene_get_readouts(scene, readouts.data(), n_objects, &n_objects, &any_readout);
+            rc = events_rendered ? 0 : rpt_render_events(last);
+            events_rendered = !rc;
+            if (!rc) rc = rpt_set_readouts(last, readouts.data(), (int)n_objects);
+            if (!rc) rc = rpt_render_readouts(last);
+            if (!rc) rc = rpt_last_readout_pixels(last, &changed);
+            if (rc) {
+                std::fprintf(stderr, "readouts: %s\n", rpt_last_error(last));
+                return 1;
+            }
+            std::fprintf(stderr, "readouts: %llu of %lld pixels changed\n", changed, (long long)width * height);
+        }
+    }
     std::vector<unsigned char> fb((size_t)width * height * 16);
     rpt_read_framebuffer(last, fb.data(), fb.size());
     rc = rpt_write_ppm(argv[3], fb.data(), width, height);       // drawGL()                gl_interop.cpp:51
@@ -328,7 +352,7 @@ int main(int argc, char **argv) {
     }
     if (!rc && events_path) {                                    // what each pixel of that frame shows, where and when
         std::vector<rpt_event> records((size_t)width * height);
-        if (!events_rendered) rc = rpt_render_events(last);      // (--overlay has rendered that very frame already)
+        if (!events_rendered) rc = rpt_render_events(last);      // (--overlay or the scene's readouts have rendered that very frame already)
         if (!rc) rc = rpt_read_events(last, records.data(), records.size() * sizeof(rpt_event));
         if (rc) {
             std::fprintf(stderr, "events: %s\n", rpt_last_error(last));

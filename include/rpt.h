@@ -41,7 +41,9 @@
  * rpt_last_overlay_pixels ("Overlay pass"), and the opt-in ray-map camera — one direction per pixel, for fisheyes, the
  * stereographic view, cube strips and calibrated lenses: rpt_set_raymap, RPT_PROJECTION_RAYMAP and rpt_raymap_fill (host code, no device
  * needed; DESIGN.md, "Ray-map camera"), and opt-in per-object time windows — objects and lights that begin and end, from which
- * piecewise-inertial worldlines are built: rpt_set_object_windows ("Time windows").
+ * piecewise-inertial worldlines are built: rpt_set_object_windows ("Time windows"), and the opt-in readout pass — seven-segment
+ * displays on the objects' surfaces that show each object's own proper time: rpt_set_readouts, rpt_render_readouts /
+ * rpt_render_readouts_async and rpt_last_readout_pixels ("Readout pass").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -555,6 +557,51 @@ int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels);
  * Refused at the LAUNCH with RPT_ERR_ARG, message "rpt_set_object_windows: ...", nothing launched: a count that is not the Object[]'s,
  * MSAA > 1, adaptive anti-aliasing, variants 1 / 50 / 51, the Doppler debug kernels, an octree whose children are not consecutive. */
 int rpt_set_object_windows(rpt_ctx *ctx, const float *t0t1_or_null, int count);
+
+/* The readout pass (not in the reference; DESIGN.md "Readout pass"): objects that display their own time.  A seven-segment display on an
+ * object's surface shows offset + rate * event[0] — event[0] of the event pass: the hit object's rest-frame time at which it emitted the
+ * light the pixel receives, the coordinate the flash term and the time windows act on.  A sibling of the overlay pass with the same
+ * discipline: opt-in, per context, not shared by rpt_share_scene; enqueued on the context's stream after a colour frame and an event
+ * frame of the same view; it blends into the R, G, B bytes of the 16-B framebuffer pixels in place (alpha, bytes 0-7 and 12-15, the debug
+ * planes and the record buffer are not written).  The display is drawn OVER the picture; it is not lit or shaded.  Every rule is float32
+ * and integer arithmetic, every float operation rounded on its own; relativitypathtracer_amd/events.py `readout` restates them in numpy.
+ * They apply to a HIT pixel p whose object o has digits != 0; (u, v) = p's record's uv, e = its event[0].
+ *
+ *   value        sv = (rate * e + offset) * scale, scale = (float)10^decimals formed on the host.  neg = sv < 0.  !(fabsf(sv) < 1e9f)
+ *                overflows (a NaN too); otherwise mag = (int)floorf(fabsf(sv)), and mag >= 10^(digits - neg) overflows as well.  Cell k
+ *                (0 = leftmost) shows: on overflow segment g alone in every cell and no decimal point; when neg, g alone in cell 0;
+ *                otherwise the digit (mag / 10^(digits-1-k)) % 10 (leading zeros are shown).  The decimal point is lit in cell
+ *                digits-1-decimals when decimals > 0.  The value is per PIXEL, from p's own record: across a large moving face
+ *                neighbouring pixels may show different values.  That is the relativity of simultaneity, and it is what is wanted.
+ *   footprint    du_x = u(x+1, y) - u and dv_x = v(x+1, y) - v if pixel (x+1, y) is inside the frame and has the same object, else both 0;
+ *                du_y, dv_y likewise from (x, y+1).
+ *   sub-samples  16 of them, (i, j) in 0..3 x 0..3, a = {-0.375, -0.125, 0.125, 0.375}: us = (u + a_i du_x) + a_j du_y,
+ *                vs = (v + a_i dv_x) + a_j dv_y; s = (us - u0) * inv_w, t = (vs - v0) * inv_h with inv_w = 1.0f / (u1 - u0) and inv_h formed
+ *                on the host.  Inside the display iff s >= 0 && s < 1 && t >= 0 && t < 1.  cs = s * (float)digits,
+ *                c = min((int)floorf(cs), digits - 1), lx = cs - (float)c.  Lit iff (lx, t) lies in [x0, x1) x [y0, y1) of a segment that
+ *                cell c's mask lights.
+ *   segments     in sixteenths of the cell (x0, x1; y0, y1):  a 3, 11; 13, 15   b 10, 12; 8, 14   c 10, 12; 2, 8   d 3, 11; 1, 3
+ *                e 2, 4; 2, 8   f 2, 4; 8, 14   g 3, 11; 7, 9   point 13, 15; 1, 3.  Digit masks, a = bit 0 .. g = bit 6:
+ *                0x3f 0x06 0x5b 0x4f 0x66 0x6d 0x7d 0x07 0x7f 0x6f.
+ *   blend        n_in / n_on = the inside / the lit sub-samples.  now = blend(now, off_rgb, (off_a * n_in + 8) / 16), then
+ *                now = blend(now, on_rgb, (on_a * n_on + 8) / 16); blend is the overlay's (c * a + old * (255 - a) + 127) / 255.
+ *
+ * rpt_set_readouts copies the array — one entry per entry of Object[] — and writes it to the device once, not per frame; NULL or count 0
+ * clears the setting.  RPT_ERR_ARG, message "rpt_set_readouts: ...", the previous setting kept: a float of any entry that is not finite,
+ * digits > 9, and in an entry with digits != 0: decimals > 6 or decimals >= digits, u0 == u1 or v0 == v1.
+ * (A call that fails on the device, RPT_ERR_DEVICE, leaves NO setting: the table may no longer match the previous one.)
+ * rpt_render_readouts[_async] follows rpt_render_overlay's rules: RPT_ERR_STATE unless the context has enqueued a colour frame and an
+ * event frame of the current width x height, view (rpt_set_object_windows changes the view too) and buffers; RPT_ERR_ARG, message
+ * "rpt_render_readouts: ...", for a context restricted by rpt_set_rows / rpt_set_tile_pattern or rendering a colour plane, and for a
+ * count that is not the Object[]'s.  The context stays usable after either.  With nothing set the call checks nothing, launches nothing
+ * and succeeds.  The pass is independent of rpt_render_overlay: either may run first and each blends over what is there; calling it twice
+ * blends twice.  rpt_last_readout_pixels: pixels whose RGBA bytes the last FINISHED readout pass changed, as rpt_last_overlay_pixels. */
+/* rpt_readout: include/rpt_layout.h (36 B; the scene front-end fills the same record, rpt_scene_get_readouts) */
+
+int rpt_set_readouts(rpt_ctx *ctx, const rpt_readout *per_object_or_null, int count);
+int rpt_render_readouts(rpt_ctx *ctx);         /* enqueue and wait */
+int rpt_render_readouts_async(rpt_ctx *ctx);   /* enqueue; rpt_sync waits */
+int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

@@ -75,6 +75,16 @@ typedef struct rpt_event {
     float   uv[2];            /* 24  Hit.uv of the winner, as the texture lookup of :430-431 receives it */
 } rpt_event;
 
+/* One object's display in the readout pass (not in the reference; include/rpt.h, rpt_set_readouts, states the rules) */
+typedef struct rpt_readout {      /* 36 B, one per entry of Object[] */
+    float   rate, offset;         /* value shown: offset + rate * event[0] */
+    float   u0, v0, u1, v1;       /* the display's rectangle in the hit's (u, v); u0 > u1 or v0 > v1 mirrors it */
+    uint8_t digits;               /* 0 = this object has no display; else 1..9 character cells */
+    uint8_t decimals;             /* 0..6 and < digits */
+    uint8_t _pad[2];
+    uint8_t on_rgba[4], off_rgba[4];   /* lit segments / the rest of the rectangle; alpha 0 leaves the picture */
+} rpt_readout;
+
 /*
  * The eight read-only scene arrays the reference uploads once (main.cpp:33-55), in the
  * reference's layouts, as {pointer, element count} pairs.  Zero-length arrays are legal and
@@ -126,5 +136,8 @@ RPT_SA(sizeof(rpt_pixel) == 16, "pixel is 16 B");
 RPT_SA(sizeof(rpt_event) == 32, "event record is 32 B");
 RPT_SA(offsetof(rpt_event, event) == 8, "event");
 RPT_SA(offsetof(rpt_event, uv) == 24, "uv");
+RPT_SA(sizeof(rpt_readout) == 36, "readout is 36 B");
+RPT_SA(offsetof(rpt_readout, digits) == 24, "digits");
+RPT_SA(offsetof(rpt_readout, on_rgba) == 28, "on_rgba");
 
 #endif /* RPT_LAYOUT_H */

@@ -83,6 +83,10 @@ int rpt_scene_get_mesh_roots(const rpt_scene *s, const int **roots, size_t *coun
 /* The time windows of the DSL's `wT0,T1` command (rpt_set_object_windows takes them): *count = the number of objects, *any = 1 when some
  * object has a window; t0t1_out (may be NULL) receives {t0, t1} of the first min(capacity, *count) objects, (-inf, +inf) where none was given. */
 int rpt_scene_get_windows(const rpt_scene *s, float *t0t1_out, size_t capacity, size_t *count, int *any);
+/* The displays of the DSL's `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` command (rpt_set_readouts takes them): *count = the number of
+ * objects, *any = 1 when some object has a display; readouts_out (may be NULL) receives the first min(capacity, *count) objects' records,
+ * all zero (digits 0: no display) where none was given.  Rectangle 0.1, 0.25, 0.9, 0.75 unless given; red on black, alpha 255 and 160. */
+int rpt_scene_get_readouts(const rpt_scene *s, rpt_readout *readouts_out, size_t capacity, size_t *count, int *any);
 
 /* framebuffer consumer: write a 16 B/pixel framebuffer (row 0 = bottom, as GL draws it) as a binary
  * PPM with the top row first */

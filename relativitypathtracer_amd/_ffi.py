@@ -50,6 +50,12 @@ class OverlayDesc(C.Structure):
                 ("lattice_rgba", C.c_uint8 * 4), ("tint_alpha", C.c_uint8), ("_pad", C.c_uint8 * 3)]
 
 
+class Readout(C.Structure):
+    """rpt_readout of include/rpt_layout.h (36 B; include/rpt.h, rpt_set_readouts, states the rules): one object's display in the readout pass."""
+    _fields_ = [("rate", C.c_float), ("offset", C.c_float), ("u0", C.c_float), ("v0", C.c_float), ("u1", C.c_float), ("v1", C.c_float),
+                ("digits", C.c_uint8), ("decimals", C.c_uint8), ("_pad", C.c_uint8 * 2), ("on_rgba", C.c_uint8 * 4), ("off_rgba", C.c_uint8 * 4)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -115,6 +121,7 @@ def scene_lib() -> C.CDLL:
             "rpt_scene_get_velocities": (I, [P, C.POINTER(P), C.POINTER(C.c_size_t)]),
             "rpt_scene_get_mesh_roots": (I, [P, C.POINTER(P), C.POINTER(C.c_size_t)]),
             "rpt_scene_get_windows": (I, [P, P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+            "rpt_scene_get_readouts": (I, [P, P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
             "rpt_write_ppm": (I, [S, P, I, I]),
             "rpt_write_png": (I, [S, P, I, I]),
         }
@@ -213,6 +220,10 @@ HIP_SYMBOLS = {
     "rpt_render_overlay_async": (C.c_int, [C.c_void_p]),
     "rpt_last_overlay_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_set_object_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "rpt_set_readouts": (C.c_int, [C.c_void_p, C.POINTER(Readout), C.c_int]),
+    "rpt_render_readouts": (C.c_int, [C.c_void_p]),
+    "rpt_render_readouts_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_readout_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -15,6 +15,7 @@
 #include <dirent.h>
 #include <strings.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -249,9 +250,9 @@ bool Scene::inputScene(std::istream &in) {
         for (char *tok = strtok_r(buf.data(), " ", &save); !done && tok; tok = strtok_r(nullptr, " ", &save)) {
             float args[10];
             const size_t len = std::strlen(tok);
-            const bool needObject = std::strchr("pctlvfw", tok[0]) != nullptr;
+            const bool needObject = std::strchr("pctlvfwd", tok[0]) != nullptr;
             if (needObject && cpu_objects.empty()) { warn(std::string("Object must be defined before \"") + tok + "\""); continue; }
-            if (std::strchr("OpctlvfwTMAW", tok[0]) && len < 2) { warn(std::string("command missing argument: \"") + tok + "\""); continue; }
+            if (std::strchr("OpctlvfwdTMAW", tok[0]) && len < 2) { warn(std::string("command missing argument: \"") + tok + "\""); continue; }
             switch (tok[0]) {
             case 'O': {
                 int type = -1;
@@ -295,6 +296,39 @@ bool Scene::inputScene(std::istream &in) {
                 const float t1 = first ? (float)std::strtod(end0 + 1, &end1) : 0.0f;
                 if (!first || end1 == end0 + 1 || *end1 != '\0' || t0 != t0 || t1 != t1) { warn(std::string("window command needs two numbers: \"") + tok + "\""); break; }
                 windows[cpu_objects.size() - 1] = std::make_pair(t0, t1);
+                break;
+            }
+            case 'd':       // dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1] (not in the reference): the current object shows offset + rate * its own time
+            {       // (what rpt_set_readouts would refuse is refused here: a warning, and the object keeps what it had)
+                double value[8] = {0, 0, 0, 0, 0.1, 0.25, 0.9, 0.75};
+                int n = 0;
+                bool ok = true;
+                for (const char *q = tok + 1; ok; n++) {
+                    char *end = nullptr;
+                    const double x = std::strtod(q, &end);
+                    ok = n < 8 && end != q && std::isfinite(x) && std::fabs(x) <= (double)FLT_MAX && (*end == ',' || *end == '\0');
+                    if (!ok) break;
+                    value[n] = x;
+                    if (*end == '\0') { n++; break; }
+                    q = end + 1;
+                }
+                ok = ok && (n == 4 || n == 8) && value[2] == std::floor(value[2]) && value[2] >= 1 && value[2] <= 9 && value[3] == std::floor(value[3])
+                     && value[3] >= 0 && value[3] <= 6 && value[3] < value[2] && (float)value[4] != (float)value[6] && (float)value[5] != (float)value[7];
+                if (!ok) { warn(std::string("readout command needs RATE,OFFSET,DIGITS (1..9),DECIMALS (0..6, below DIGITS) and no or four rectangle numbers: \"") + tok + "\""); break; }
+                rpt_readout r;
+                std::memset(&r, 0, sizeof r);
+                r.rate = (float)value[0];
+                r.offset = (float)value[1];
+                r.digits = (uint8_t)value[2];
+                r.decimals = (uint8_t)value[3];
+                r.u0 = (float)value[4];
+                r.v0 = (float)value[5];
+                r.u1 = (float)value[6];
+                r.v1 = (float)value[7];
+                r.on_rgba[0] = 255;       // red on black, the rest of the rectangle dimmed
+                r.on_rgba[3] = 255;
+                r.off_rgba[3] = 160;
+                readouts[cpu_objects.size() - 1] = r;
                 break;
             }
             case 'T': if (!ReadTexture(tok + 1)) return false; break;

@@ -45,6 +45,8 @@ struct Scene {
     // the `w` command (not in the reference): {t0, t1} of the objects that have a time window, by object index; the others have the
     // default (-inf, +inf).  Empty: a scene without windows (rpt_scene_get_windows)
     std::map<size_t, std::pair<float, float>> windows;
+    // the `d` command (not in the reference): the display of the objects that have one, by object index (rpt_scene_get_readouts)
+    std::map<size_t, rpt_readout> readouts;
     // Render.cpp:8-22
     rpt_float3 cameraVelocity = make_float3(0, 0, 0);
     rpt_float4 cameraPos = make_float4(0, 0, 0, 0);   // (t, x, y, z)

@@ -214,6 +214,20 @@ int rpt_scene_get_windows(const rpt_scene *s, float *t0t1_out, size_t capacity, 
     return 0;
 }
 
+int rpt_scene_get_readouts(const rpt_scene *s, rpt_readout *readouts_out, size_t capacity, size_t *count, int *any) {
+    if (!s || !count || !any) return -1;
+    const size_t n = s->scene.cpu_objects.size();
+    *count = n;
+    *any = s->scene.readouts.empty() ? 0 : 1;
+    if (!readouts_out) return 0;
+    for (size_t i = 0; i < n && i < capacity; i++) {
+        const auto it = s->scene.readouts.find(i);
+        if (it == s->scene.readouts.end()) std::memset(&readouts_out[i], 0, sizeof(rpt_readout));
+        else readouts_out[i] = it->second;
+    }
+    return 0;
+}
+
 int rpt_scene_get_mesh_roots(const rpt_scene *s, const int **roots, size_t *count) {
     if (!s || !roots || !count) return -1;
     *roots = s->scene.theMesh.meshIndices.empty() ? nullptr : s->scene.theMesh.meshIndices.data();

@@ -209,6 +209,15 @@ struct rpt_ctx {
     hipEvent_t overlay_counted = nullptr;             // recorded after that copy
     unsigned long long overlay_pixels = 0;            // rpt_last_overlay_pixels: overlay_host as last read with overlay_counted passed
     bool overlay_pending = false;                     // a copy has been enqueued since overlay_pixels was read
+    // rpt_set_readouts / rpt_render_readouts (not in the reference): the readout pass, per context, never shared; the overlay's discipline
+    std::vector<rpt_readout> readouts;                // one per entry of Object[]; empty = none set
+    unsigned long long readout_low_mask = 0;          // bit o: object o < 64 has a display
+    StagedUpload readout_table;                       // rptd::ReadoutDisplay per object, written once per rpt_set_readouts
+    DeviceBuffer readout_scratch;                     // 8 B: the changed pixels of the pass in flight
+    unsigned long long *readout_host = nullptr;       // pinned: the counter of the last pass whose copy has run
+    hipEvent_t readout_counted = nullptr;             // recorded after that copy
+    unsigned long long readout_pixels = 0;            // rpt_last_readout_pixels
+    bool readout_pending = false;                     // a copy has been enqueued since readout_pixels was read
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -1719,6 +1728,32 @@ int launch_events(rpt_ctx *ctx) {
 
 uint32_t packed_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
 
+// What a pass over a rendered frame and its records (the overlay, the readouts) asks for before it launches, `call` naming it in the
+// messages: a context that renders whole frames, and a colour frame and an event frame of the current size and view in the buffers
+// now set.  *out16 and *events: those buffers.
+int frames_of_this_view(rpt_ctx *ctx, const char *call, rpt_pixel **out16_out, const rpt_event **events_out) {
+    const std::string name(call);
+    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, name + " before rpt_upload_scene");
+    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, name + " before rpt_set_params");
+    if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->colour_plane)
+        return fail(ctx, RPT_ERR_ARG, name + ": the pass reads a pixel's upper neighbour, which on a context restricted by rpt_set_rows / rpt_set_tile_pattern (or rendering a colour plane) belongs to another rank");
+    if (ctx->colour_generation == 0 || !ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, name + ": no colour frame rendered yet");
+    if (ctx->events_generation == 0 || !ctx->events_rendered) return fail(ctx, RPT_ERR_STATE, name + ": no event frame rendered yet (rpt_render_events)");
+    if (ctx->colour_width != ctx->width || ctx->colour_height != ctx->height || ctx->events_width != ctx->width || ctx->events_height != ctx->height)
+        return fail(ctx, RPT_ERR_STATE, name + ": the last colour frame and event frame are not both of the current width x height");
+    if (ctx->colour_generation != ctx->view_generation || ctx->events_generation != ctx->view_generation)
+        return fail(ctx, RPT_ERR_STATE, name + ": the view has changed (objects, time windows, params, projection, orientation or lens) since the last colour frame or event frame; render both again");
+    rpt_pixel *out16 = (rpt_pixel *)(ctx->external_out ? ctx->external_out : ctx->owned_out.ptr);
+    const rpt_event *events = (const rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
+    // the buffers the two frames were rendered into are the ones the pass reads and writes: a buffer set since then holds no frame (and
+    // a library-owned one may be smaller than this frame)
+    if (!out16 || !events || (void *)out16 != ctx->colour_out || (const void *)events != ctx->events_ptr)
+        return fail(ctx, RPT_ERR_STATE, name + ": rpt_set_output or rpt_set_events_output has named another buffer since the colour frame and the event frame were rendered");
+    *out16_out = out16;
+    *events_out = events;
+    return RPT_OK;
+}
+
 // One overlay pass on the context's stream (kernel 1100, behind 1101 where the tint's range is the frame's own): the refusals, the
 // counter, the launch, then the counter's way home in stream order, as pass B of an adaptive frame.
 int launch_overlay(rpt_ctx *ctx) {
@@ -1728,22 +1763,9 @@ int launch_overlay(rpt_ctx *ctx) {
         ctx->overlay_pixels = 0;
         return RPT_OK;
     }
-    if (!ctx->scene_uploaded) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay before rpt_upload_scene");
-    if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay before rpt_set_params");
-    if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->colour_plane)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_overlay: the pass reads a pixel's upper neighbour, which on a context restricted by rpt_set_rows / rpt_set_tile_pattern (or rendering a colour plane) belongs to another rank");
-    if (ctx->colour_generation == 0 || !ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: no colour frame rendered yet");
-    if (ctx->events_generation == 0 || !ctx->events_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: no event frame rendered yet (rpt_render_events)");
-    if (ctx->colour_width != ctx->width || ctx->colour_height != ctx->height || ctx->events_width != ctx->width || ctx->events_height != ctx->height)
-        return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: the last colour frame and event frame are not both of the current width x height");
-    if (ctx->colour_generation != ctx->view_generation || ctx->events_generation != ctx->view_generation)
-        return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: the view has changed (objects, params, projection, orientation or lens) since the last colour frame or event frame; render both again");
-    rpt_pixel *out16 = (rpt_pixel *)(ctx->external_out ? ctx->external_out : ctx->owned_out.ptr);
-    const rpt_event *events = (const rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
-    // the buffers the two frames were rendered into are the ones the pass reads and writes: a buffer set since then holds no frame (and
-    // a library-owned one may be smaller than this frame)
-    if (!out16 || !events || (void *)out16 != ctx->colour_out || (const void *)events != ctx->events_ptr)
-        return fail(ctx, RPT_ERR_STATE, "rpt_render_overlay: rpt_set_output or rpt_set_events_output has named another buffer since the colour frame and the event frame were rendered");
+    rpt_pixel *out16 = nullptr;
+    const rpt_event *events = nullptr;
+    if (int rc = frames_of_this_view(ctx, "rpt_render_overlay", &out16, &events)) return rc;
     if (int rc = reserve(ctx, ctx->overlay_scratch, 16)) return rc;
     if (!ctx->overlay_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->overlay_host, 8, hipHostMallocDefault));
     if (!ctx->overlay_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->overlay_counted, hipEventDisableTiming));
@@ -1799,6 +1821,51 @@ void collect_overlay_pixels(rpt_ctx *ctx) {
     if (ctx->overlay_pending && ctx->overlay_counted && hipEventQuery(ctx->overlay_counted) == hipSuccess) {
         ctx->overlay_pixels = *ctx->overlay_host;
         ctx->overlay_pending = false;
+    }
+}
+
+// One readout pass on the context's stream (kernel 1110): the overlay pass's refusals, counter and way home
+int launch_readouts(rpt_ctx *ctx) {
+    if (ctx->readouts.empty()) {      // nothing set: nothing is checked, launched or changed
+        ctx->readout_pending = false;
+        ctx->readout_pixels = 0;
+        return RPT_OK;
+    }
+    rpt_pixel *out16 = nullptr;
+    const rpt_event *events = nullptr;
+    if (int rc = frames_of_this_view(ctx, "rpt_render_readouts", &out16, &events)) return rc;
+    if (ctx->readouts.size() != (size_t)ctx->object_count)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_readouts: " + std::to_string(ctx->readouts.size()) + " readouts are set, the Object[] holds " + std::to_string(ctx->object_count));
+    if (int rc = reserve(ctx, ctx->readout_scratch, 8)) return rc;
+    if (!ctx->readout_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->readout_host, 8, hipHostMallocDefault));
+    if (!ctx->readout_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->readout_counted, hipEventDisableTiming));
+
+    rptd::ReadoutArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.events = events;
+    a.out16 = out16;
+    a.changed = (unsigned long long *)ctx->readout_scratch.ptr;
+    a.displays = (const rptd::ReadoutDisplay *)ctx->readout_table.device.ptr;
+    a.low_mask = ctx->readout_low_mask;
+    a.width = ctx->width;
+    a.height = ctx->height;
+    a.count = ctx->object_count;
+    RPT_HIP(ctx, hipMemsetAsync(ctx->readout_scratch.ptr, 0, 8, ctx->stream));
+    const dim3 grid((ctx->width + RPT_OVERLAY_TILE_W - 1) / RPT_OVERLAY_TILE_W, (ctx->height + RPT_OVERLAY_TILE_H - 1) / RPT_OVERLAY_TILE_H);
+    void *args[] = {(void *)&a};
+    (void)hipLaunchKernel((const void *)rptd::rpt_readout_kernel, grid, dim3(RPT_OVERLAY_TILE_W * RPT_OVERLAY_TILE_H), args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    RPT_HIP(ctx, hipMemcpyAsync(ctx->readout_host, ctx->readout_scratch.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(ctx->readout_counted, ctx->stream));
+    ctx->last_event = ctx->readout_counted;
+    ctx->readout_pending = true;
+    return RPT_OK;
+}
+
+void collect_readout_pixels(rpt_ctx *ctx) {
+    if (ctx->readout_pending && ctx->readout_counted && hipEventQuery(ctx->readout_counted) == hipSuccess) {
+        ctx->readout_pixels = *ctx->readout_host;
+        ctx->readout_pending = false;
     }
 }
 
@@ -1866,14 +1933,16 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch, &ctx->readout_scratch})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table}) release(*u);
     if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
     if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
     if (ctx->overlay_host) (void)hipHostFree(ctx->overlay_host);
     if (ctx->overlay_counted) (void)hipEventDestroy(ctx->overlay_counted);
+    if (ctx->readout_host) (void)hipHostFree(ctx->readout_host);
+    if (ctx->readout_counted) (void)hipEventDestroy(ctx->readout_counted);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -2674,6 +2743,7 @@ int rpt_sync(rpt_ctx *ctx) {
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     collect_aa_refined(ctx);
     collect_overlay_pixels(ctx);
+    collect_readout_pixels(ctx);
     return RPT_OK;
 }
 
@@ -2802,6 +2872,80 @@ int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels) {
         collect_overlay_pixels(ctx);
     }
     *pixels = ctx->overlay_pixels;
+    return RPT_OK;
+}
+
+// The displays go to the device here, once, in stream order (a pass in flight keeps the table it was launched with); a call refused
+// for its arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no setting.
+int rpt_set_readouts(rpt_ctx *ctx, const rpt_readout *per_object_or_null, int count) {
+    if (!ctx || count < 0) return RPT_ERR_ARG;
+    if (!per_object_or_null || count == 0) {
+        ctx->readouts.clear();
+        ctx->readout_low_mask = 0;
+        return RPT_OK;
+    }
+    static const float pow10[7] = {1.0f, 10.0f, 100.0f, 1000.0f, 10000.0f, 100000.0f, 1000000.0f};
+    std::vector<rptd::ReadoutDisplay> table((size_t)count);
+    unsigned long long low_mask = 0;
+    for (int i = 0; i < count; i++) {
+        const rpt_readout &r = per_object_or_null[i];
+        const std::string which = "rpt_set_readouts: entry " + std::to_string(i) + ": ";
+        for (float f : {r.rate, r.offset, r.u0, r.v0, r.u1, r.v1})
+            if (!std::isfinite(f)) return fail(ctx, RPT_ERR_ARG, which + "rate, offset and the rectangle must be finite");
+        if (r.digits > 9) return fail(ctx, RPT_ERR_ARG, which + "digits is 0 (no display) or 1..9");
+        rptd::ReadoutDisplay &d = table[(size_t)i];
+        std::memset(&d, 0, sizeof d);
+        if (r.digits == 0) continue;
+        if (r.decimals > 6 || r.decimals >= r.digits) return fail(ctx, RPT_ERR_ARG, which + "decimals is 0..6 and below digits");
+        if (r.u0 == r.u1 || r.v0 == r.v1) return fail(ctx, RPT_ERR_ARG, which + "the rectangle is empty (u0 == u1 or v0 == v1)");
+        d.rate = r.rate;
+        d.offset = r.offset;
+        d.scale = pow10[r.decimals];
+        d.digits = (uint32_t)r.digits | ((uint32_t)r.decimals << 8);
+        d.u0 = r.u0;
+        d.v0 = r.v0;
+        d.inv_w = 1.0f / (r.u1 - r.u0);
+        d.inv_h = 1.0f / (r.v1 - r.v0);
+        d.on_rgba = packed_rgba(r.on_rgba);
+        d.off_rgba = packed_rgba(r.off_rgba);
+        if (i < 64) low_mask |= 1ull << i;
+    }
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    void *host = nullptr;
+    const size_t bytes = table.size() * sizeof(rptd::ReadoutDisplay);
+    int rc = staged_host(ctx, ctx->readout_table, bytes, &host);
+    if (!rc) {
+        std::memcpy(host, table.data(), bytes);
+        rc = staged_copy(ctx, ctx->readout_table);
+    }
+    if (rc) {       // a device error: the table may be gone or half written, so no setting is left rather than one that does not match it
+        ctx->readouts.clear();
+        ctx->readout_low_mask = 0;
+        return rc;
+    }
+    ctx->readouts.assign(per_object_or_null, per_object_or_null + count);
+    ctx->readout_low_mask = low_mask;
+    return RPT_OK;
+}
+
+int rpt_render_readouts_async(rpt_ctx *ctx) {
+    if (!ctx) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_readouts(ctx);
+}
+
+int rpt_render_readouts(rpt_ctx *ctx) {
+    if (int rc = rpt_render_readouts_async(ctx)) return rc;
+    return rpt_sync(ctx);
+}
+
+int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels) {
+    if (!ctx || !pixels) return RPT_ERR_ARG;
+    if (ctx->readout_pending) {
+        RPT_HIP(ctx, hipSetDevice(ctx->device));
+        collect_readout_pixels(ctx);
+    }
+    *pixels = ctx->readout_pixels;
     return RPT_OK;
 }
 

@@ -2189,6 +2189,166 @@ __global__ __launch_bounds__(256) void rpt_overlay_tmax_kernel(const rpt_event *
     if ((threadIdx.x & 63) == 0 && mine > 0.0f) atomicMax(out, __float_as_uint(mine));
 }
 
+// ---- Readout pass (rpt_set_readouts / rpt_render_readouts; not in the reference; DESIGN.md "Readout pass") -------------------------------
+// Seven-segment displays on the objects' surfaces that show the hit object's own time, offset + rate * event[0], per pixel.  A sibling
+// of the overlay pass: the same tile, halo and counter, its own kernel; it reads the records and the framebuffer's packed colour and
+// nothing else.  The rules are in include/rpt.h.
+struct alignas(16) ReadoutDisplay {     // one per entry of Object[], derived from rpt_readout on the host (48 B: three 16-byte loads)
+    float rate, offset, scale;          // scale = (float)10^decimals
+    uint32_t digits;                    // digits | decimals << 8; digits == 0: no display
+    float u0, v0, inv_w, inv_h;         // inv_w = 1.0f / (u1 - u0), inv_h = 1.0f / (v1 - v0)
+    uint32_t on_rgba, off_rgba;         // R | G << 8 | B << 16 | A << 24
+    uint32_t pad[2];
+};
+static_assert(sizeof(ReadoutDisplay) == 48, "ReadoutDisplay");
+
+struct ReadoutArgs {
+    const rpt_event *events;            // [height][width] records of the same view
+    rpt_pixel *out16;                   // the framebuffer: only the dword at byte 8 of a pixel is read and written
+    unsigned long long *changed;        // the context's counter of pixels whose RGBA changed: one atomic add per workgroup that changed any
+    const ReadoutDisplay *displays;     // [count]
+    unsigned long long low_mask;        // bit o: object o < 64 has a display (the others: displays[o].digits)
+    int width, height;
+    int count;                          // the Object[]'s
+};
+
+// whether object `o` of a record has a display: the kernel arguments answer for the first 64 objects, the table for the others
+RPT_DEV bool readout_has_display(const ReadoutArgs &a, int o) {
+    if (o < 0 || o >= a.count) return false;
+    if (o < 64) return ((a.low_mask >> o) & 1ull) != 0ull;
+    return (a.displays[o].digits & 255u) != 0u;
+}
+
+// What the rules need of pixel (x, y), put into LDS slot `slot`: its object, and (u, v) where that object has a display.  Outside the
+// frame: RPT_OVERLAY_OUTSIDE as the object.  Returns the record's first 16 bytes; *shown = the pixel is in the frame and has a display.
+RPT_DEV uint4 readout_stage_record(const ReadoutArgs &a, int x, int y, int slot, int *objects, float *us, float *vs, bool *shown) {
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u);
+    *shown = false;
+    if (x >= a.width || y >= a.height) {
+        objects[slot] = RPT_OVERLAY_OUTSIDE;
+        return lo;
+    }
+    const uint4 *record = reinterpret_cast<const uint4 *>(a.events + ((size_t)y * a.width + x));
+    lo = record[0];                                                    // object, dist, event[0], event[1]
+    objects[slot] = (int)lo.x;
+    if (readout_has_display(a, (int)lo.x)) {
+        const uint4 hi = record[1];                                    // event[2], event[3], u, v
+        us[slot] = __uint_as_float(hi.z);
+        vs[slot] = __uint_as_float(hi.w);
+        *shown = true;
+    }
+    return lo;
+}
+
+// the seven-segment mask of a decimal digit, a = bit 0 .. g = bit 6: 0x3f 0x06 0x5b 0x4f 0x66 0x6d 0x7d 0x07 | 0x7f 0x6f
+RPT_DEV uint32_t readout_digit_mask(uint32_t d) {
+    return (uint32_t)((d < 8u ? 0x077d6d664f5b063full >> (8u * d) : 0x6f7full >> (8u * (d - 8u))) & 0x7full);
+}
+
+// the segments and the decimal point (bit 7) whose box holds (lx, t) of a character cell; the bounds are sixteenths, exact in float
+RPT_DEV uint32_t readout_segments_at(float lx, float t) {
+    const bool wide = lx >= 0.1875f && lx < 0.6875f, left = lx >= 0.125f && lx < 0.25f, right = lx >= 0.625f && lx < 0.75f;
+    const bool lower = t >= 0.125f && t < 0.5f, upper = t >= 0.5f && t < 0.875f, foot = t >= 0.0625f && t < 0.1875f;
+    uint32_t m = 0u;
+    if (wide && t >= 0.8125f && t < 0.9375f) m |= 1u;         // a
+    if (right && upper) m |= 2u;                              // b
+    if (right && lower) m |= 4u;                              // c
+    if (wide && foot) m |= 8u;                                // d
+    if (left && lower) m |= 16u;                              // e
+    if (left && upper) m |= 32u;                              // f
+    if (wide && t >= 0.4375f && t < 0.5625f) m |= 64u;        // g
+    if (lx >= 0.8125f && lx < 0.9375f && foot) m |= 128u;     // the decimal point
+    return m;
+}
+
+// 1110: the overlay kernel's shape — a workgroup of 512 lanes owns a 64 x 8 pixel tile, wave w its row w; every lane stages its own
+// record into LDS (object; u and v where the object has a display), the first 64 lanes also the row above the tile, the next 8 the
+// column to its right; one barrier; then a lane whose object has a display forms its footprint from the right and the upper neighbour in
+// LDS, tests its 16 sub-samples and blends into its own pixel's RGBA dword.  The work hangs on the lane's own "has a display": a wave
+// without such a lane (most of them) has every lane off in that branch, so it has read 16 B per pixel and leaves — no sub-sample work, no
+// framebuffer byte read or written — and still reaches both barriers.  LDS: 3 planes of 9 x 65 words and the counter, 7044 B as laid out.
+// Changed pixels are counted as 1100 counts them.
+__global__ __launch_bounds__(512) void rpt_readout_kernel(const ReadoutArgs a) {
+    __shared__ int objects[RPT_OVERLAY_SLOTS];
+    __shared__ float us[RPT_OVERLAY_SLOTS], vs[RPT_OVERLAY_SLOTS];
+    __shared__ unsigned int tile_changed;
+    const int t = (int)threadIdx.x;
+    if (t == 0) tile_changed = 0u;
+    const int lx = t & (RPT_OVERLAY_TILE_W - 1), ly = t >> 6;
+    const int x0 = (int)blockIdx.x * RPT_OVERLAY_TILE_W, y0 = (int)blockIdx.y * RPT_OVERLAY_TILE_H;
+    const int x = x0 + lx, y = y0 + ly;
+    const int slot = ly * RPT_OVERLAY_PITCH + lx;
+    bool shown, halo_shown;
+    const uint4 lo = readout_stage_record(a, x, y, slot, objects, us, vs, &shown);
+    if (t < RPT_OVERLAY_TILE_W) (void)readout_stage_record(a, x0 + t, y0 + RPT_OVERLAY_TILE_H, RPT_OVERLAY_TILE_H * RPT_OVERLAY_PITCH + t, objects, us, vs, &halo_shown);
+    else if (t < RPT_OVERLAY_TILE_W + RPT_OVERLAY_TILE_H)
+        (void)readout_stage_record(a, x0 + RPT_OVERLAY_TILE_W, y0 + t - RPT_OVERLAY_TILE_W, (t - RPT_OVERLAY_TILE_W) * RPT_OVERLAY_PITCH + RPT_OVERLAY_TILE_W, objects, us, vs, &halo_shown);
+    __syncthreads();
+
+    bool changed = false;
+    if (shown) {      // (a wave none of whose lanes is shown has all lanes off here: it skips the body and goes on to the barrier below)
+        const int object = (int)lo.x;
+        const ReadoutDisplay d = a.displays[object];
+        const int digits = (int)(d.digits & 255u), decimals = (int)(d.digits >> 8);
+        // the value, and the nine cells' segment masks packed 7 bits a cell (cell k at bit 7 k)
+        const float sv = (d.rate * __uint_as_float(lo.z) + d.offset) * d.scale;
+        const bool neg = sv < 0.0f;
+        bool over = !(fabsf(sv) < 1e9f);                               // (a NaN overflows too)
+        uint32_t mag = over ? 0u : (uint32_t)(int)floorf(fabsf(sv));   // below 10^9
+        uint32_t limit = 1u;
+        for (int k = 0; k < digits - (neg ? 1 : 0); k++) limit *= 10u;
+        over = over || mag >= limit;
+        unsigned long long cells = 0ull;
+        for (int k = digits - 1; k >= 0; k--) {
+            cells |= (unsigned long long)readout_digit_mask(mag % 10u) << (7 * k);
+            mag /= 10u;
+        }
+        if (neg) cells = (cells & ~0x7full) | 0x40ull;
+        if (over) cells = 0x4081020408102040ull;                       // segment g alone in every cell: 0x40 << 7 k, k = 0..8
+        const int point_cell = (decimals > 0 && !over) ? digits - 1 - decimals : -1;
+        // the footprint: differences to the right and the upper neighbour where it is of the same object, else 0
+        const float u = us[slot], v = vs[slot];
+        float du_x = 0.0f, dv_x = 0.0f, du_y = 0.0f, dv_y = 0.0f;
+        if (objects[slot + 1] == object) {
+            du_x = us[slot + 1] - u;
+            dv_x = vs[slot + 1] - v;
+        }
+        if (objects[slot + RPT_OVERLAY_PITCH] == object) {
+            du_y = us[slot + RPT_OVERLAY_PITCH] - u;
+            dv_y = vs[slot + RPT_OVERLAY_PITCH] - v;
+        }
+        const float fdigits = (float)digits;
+        uint32_t n_in = 0u, n_on = 0u;
+        for (int i = 0; i < 4; i++) {
+            const float ai = -0.375f + 0.25f * (float)i;               // -0.375, -0.125, 0.125, 0.375: exact
+            const float ui = u + ai * du_x, vi = v + ai * dv_x;
+            for (int j = 0; j < 4; j++) {
+                const float aj = -0.375f + 0.25f * (float)j;
+                const float s = ((ui + aj * du_y) - d.u0) * d.inv_w;
+                const float tt = ((vi + aj * dv_y) - d.v0) * d.inv_h;
+                if (s >= 0.0f && s < 1.0f && tt >= 0.0f && tt < 1.0f) {
+                    const float cs = s * fdigits;
+                    int c = (int)floorf(cs);
+                    c = c < digits - 1 ? c : digits - 1;
+                    const uint32_t lit = ((uint32_t)(cells >> (7 * c)) & 0x7fu) | (c == point_cell ? 0x80u : 0u);
+                    n_in++;
+                    if (lit & readout_segments_at(cs - (float)c, tt)) n_on++;
+                }
+            }
+        }
+        uint32_t *rgba = reinterpret_cast<uint32_t *>(a.out16 + ((size_t)y * a.width + x)) + 2;
+        const uint32_t before = *rgba;
+        uint32_t now = overlay_blend(before, d.off_rgba, ((d.off_rgba >> 24) * n_in + 8u) / 16u);
+        now = overlay_blend(now, d.on_rgba, ((d.on_rgba >> 24) * n_on + 8u) / 16u);
+        changed = now != before;
+        if (changed) *rgba = now;
+    }
+    const unsigned long long set = __ballot(changed);
+    if ((t & 63) == 0 && set) atomicAdd(&tile_changed, (unsigned int)__popcll(set));
+    __syncthreads();
+    if (t == 0 && tile_changed) atomicAdd(a.changed, (unsigned long long)tile_changed);
+}
+
 #ifdef RPT_DIAGNOSTICS
 }  // namespace rptd
 #include "rpt_diag_kernels.hip.h"    /* librpt_hip_diag.so only: instrumented kernels, round 1's prepass, the A/B arms of rounds 2 and 3 */

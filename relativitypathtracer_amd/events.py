@@ -1,6 +1,7 @@
 """Host-side helpers for the per-pixel event records of Renderer.render_events (include/rpt_layout.h: rpt_event; DESIGN.md "Event
 pass").  numpy only: nothing here touches a device or a library.  float64 throughout, except `overlay`, which restates the overlay
-pass's float32 and integer rules exactly (include/rpt.h, rpt_set_overlay; DESIGN.md "Overlay pass").
+pass's float32 and integer rules exactly (include/rpt.h, rpt_set_overlay; DESIGN.md "Overlay pass"), and `readout`, which does the
+same for the readout pass (rpt_set_readouts; DESIGN.md "Readout pass").
 
 A record holds, for the closest hit of a pixel's primary ray, the object's index, the camera-frame distance `dist`, the emission event
 (t, x, y, z) in the HIT OBJECT'S rest frame and the surface (u, v); object == -1 marks a miss (every other field 0).
@@ -193,4 +194,139 @@ def overlay(frame_rgba: np.ndarray, events: np.ndarray, interval: int, **layers)
         on[:, :-1] |= obj[:, :-1] != obj[:, 1:]
         on[:-1] |= obj[:-1] != obj[1:]
         _blend(img, on, s["outline_rgba"], s["outline_rgba"][3])
+    return img, int((img != before).any(axis=-1).sum())
+
+
+# ---- the readout pass (include/rpt.h, rpt_set_readouts; DESIGN.md "Readout pass") ------------------------------------------------------
+# segments a..g and the decimal point: (x0, x1, y0, y1) in sixteenths of a character cell; bit k of a cell's mask lights row k
+READOUT_SEGMENTS = ((3, 11, 13, 15), (10, 12, 8, 14), (10, 12, 2, 8), (3, 11, 1, 3), (2, 4, 2, 8), (2, 4, 8, 14), (3, 11, 7, 9), (13, 15, 1, 3))
+READOUT_DIGIT_MASKS = (0x3f, 0x06, 0x5b, 0x4f, 0x66, 0x6d, 0x7d, 0x07, 0x7f, 0x6f)
+READOUT_SUBSAMPLES = (-0.375, -0.125, 0.125, 0.375)
+READOUT_DEFAULT_RECT = (0.1, 0.25, 0.9, 0.75)
+
+
+def readout_settings(rate=1.0, offset=0.0, digits=0, decimals=0, rect=READOUT_DEFAULT_RECT, on_rgba=(255, 0, 0, 255), off_rgba=(0, 0, 0, 160)) -> dict:
+    """One object's display, validated as rpt_set_readouts validates it (ValueError where the library returns RPT_ERR_ARG): the value
+    shown is offset + rate * event[0] with `decimals` places in `digits` character cells (0 = this object has no display), inside
+    rect = (u0, v0, u1, v1) of the hit's (u, v) (u0 > u1 or v0 > v1 mirrors it); lit segments are blended with on_rgba, the rest of the
+    rectangle with off_rgba, both (R, G, B, A) in 0..255 (A = 0 leaves the picture).  The floats are rounded to float32 here."""
+    digits, decimals = int(digits), int(decimals)
+    rect = tuple(rect)
+    if len(rect) != 4:
+        raise ValueError("rect is (u0, v0, u1, v1)")
+    floats = [np.float32(f) for f in (rate, offset) + rect]
+    if not all(np.isfinite(f) for f in floats):
+        raise ValueError("rate, offset and the rectangle must be finite")
+    if not 0 <= digits <= 9:
+        raise ValueError("digits is 0 (no display) or 1..9")
+    if digits and not (0 <= decimals <= 6 and decimals < digits):
+        raise ValueError("decimals is 0..6 and below digits")
+    if digits and (floats[2] == floats[4] or floats[3] == floats[5]):
+        raise ValueError("the rectangle is empty: u0 == u1 or v0 == v1")
+    colours = []
+    for name, c in (("on_rgba", on_rgba), ("off_rgba", off_rgba)):
+        c = tuple(int(b) for b in c)
+        if len(c) != 4 or min(c) < 0 or max(c) > 255:
+            raise ValueError(f"{name} is (R, G, B, A) in 0..255")
+        colours.append(c)
+    return dict(rate=floats[0], offset=floats[1], digits=digits, decimals=decimals, rect=tuple(floats[2:]), on_rgba=colours[0], off_rgba=colours[1])
+
+
+def _readout_coverage(events: np.ndarray, readouts):
+    """(shown, n_in, n_on, value) per pixel: whether the pixel is a hit of an object with a display, how many of its 16 sub-samples lie
+    inside the rectangle and how many on a lit segment, and the scaled value sv the pixel shows (NaN where not shown)."""
+    ev = np.asarray(events)
+    if ev.ndim != 2:
+        raise ValueError("events is the (H, W) array of records")
+    f32 = np.float32
+    table = [readout_settings(**d) if d is not None else None for d in (readouts or [])]
+    obj = ev["object"]
+    if obj.size and int(obj.max()) >= len(table) and table:
+        raise ValueError(f"the records hold object {int(obj.max())}; readouts has {len(table)} entries (one per object)")
+    n = max(len(table), 1)
+    per = {k: np.zeros(n, dtype=f32) for k in ("rate", "offset", "scale", "u0", "v0", "inv_w", "inv_h")}
+    digits_of, decimals_of = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for k, d in enumerate(table):
+        if d is None or d["digits"] == 0:
+            continue
+        u0, v0, u1, v1 = d["rect"]
+        per["rate"][k], per["offset"][k], per["scale"][k] = d["rate"], d["offset"], f32(10 ** d["decimals"])
+        per["u0"][k], per["v0"][k] = u0, v0
+        per["inv_w"][k], per["inv_h"][k] = f32(1.0) / (u1 - u0), f32(1.0) / (v1 - v0)
+        digits_of[k], decimals_of[k] = d["digits"], d["decimals"]
+    o = np.clip(obj, 0, n - 1)
+    digits, decimals = digits_of[o], decimals_of[o]
+    shown = (obj >= 0) & (obj < len(table)) & (digits != 0)
+    u, v, e = ev["uv"][..., 0].astype(f32), ev["uv"][..., 1].astype(f32), ev["event"][..., 0].astype(f32)
+    with np.errstate(all="ignore"):
+        # the value and the nine cells' masks
+        sv = (per["rate"][o] * e + per["offset"][o]) * per["scale"][o]
+        assert sv.dtype == f32
+        neg = sv < 0
+        over = ~(np.abs(sv) < f32(1e9))
+        mag = np.floor(np.where(over, f32(0), np.abs(sv))).astype(np.int64)
+        over |= mag >= 10 ** np.maximum(digits - neg, 0)
+        masks = np.zeros(ev.shape + (9,), dtype=np.int64)
+        digit_masks = np.array(READOUT_DIGIT_MASKS, dtype=np.int64)
+        for k in range(9):
+            m = digit_masks[(mag // 10 ** np.maximum(digits - 1 - k, 0)) % 10]
+            if k == 0:
+                m = np.where(neg, 0x40, m)
+            m = m | np.where((decimals > 0) & (k == digits - 1 - decimals), 0x80, 0)
+            masks[..., k] = np.where(over, 0x40, m)
+        # the footprint: differences to the right and the upper neighbour of the same object, 0 at an edge
+        du_x, dv_x, du_y, dv_y = (np.zeros(ev.shape, dtype=f32) for _ in range(4))
+        same = obj[:, :-1] == obj[:, 1:]
+        du_x[:, :-1] = np.where(same, u[:, 1:] - u[:, :-1], f32(0))
+        dv_x[:, :-1] = np.where(same, v[:, 1:] - v[:, :-1], f32(0))
+        same = obj[:-1] == obj[1:]
+        du_y[:-1] = np.where(same, u[1:] - u[:-1], f32(0))
+        dv_y[:-1] = np.where(same, v[1:] - v[:-1], f32(0))
+        n_in, n_on = np.zeros(ev.shape, dtype=np.int64), np.zeros(ev.shape, dtype=np.int64)
+        fdigits = digits.astype(f32)
+        for ai in READOUT_SUBSAMPLES:
+            for aj in READOUT_SUBSAMPLES:
+                us = (u + f32(ai) * du_x) + f32(aj) * du_y
+                vs = (v + f32(ai) * dv_x) + f32(aj) * dv_y
+                s = (us - per["u0"][o]) * per["inv_w"][o]
+                t = (vs - per["v0"][o]) * per["inv_h"][o]
+                assert s.dtype == f32 and t.dtype == f32
+                inside = shown & (s >= 0) & (s < 1) & (t >= 0) & (t < 1)
+                cs = np.where(inside, s, f32(0)) * fdigits
+                c = np.minimum(np.floor(cs).astype(np.int64), np.maximum(digits - 1, 0))
+                lx = cs - c.astype(f32)
+                mask = np.take_along_axis(masks, c[..., None], axis=-1)[..., 0]
+                lit = np.zeros(ev.shape, dtype=bool)
+                for bit, (x0, x1, y0, y1) in enumerate(READOUT_SEGMENTS):
+                    lit |= ((mask >> bit) & 1).astype(bool) & (lx >= f32(x0 / 16)) & (lx < f32(x1 / 16)) & (t >= f32(y0 / 16)) & (t < f32(y1 / 16))
+                n_in += inside
+                n_on += inside & lit
+    return shown, n_in, n_on, np.where(shown, sv, f32(np.nan)), table, o
+
+
+def readout_coverage(events: np.ndarray, readouts):
+    """What the readout pass sees per pixel of the (H, W) records, before it blends: (shown, n_in, n_on, value) — bool: the pixel hits
+    an object that has a display; the number of its 16 sub-samples inside the display's rectangle and on a lit segment; float32: the
+    scaled value (rate * event[0] + offset) * 10^decimals it shows, NaN where not shown."""
+    return _readout_coverage(events, readouts)[:4]
+
+
+def readout(frame_rgba: np.ndarray, events: np.ndarray, readouts):
+    """The readout pass (Renderer.render_readouts; include/rpt.h, rpt_set_readouts) in numpy, byte for byte: seven-segment displays on
+    the objects' surfaces that show offset + rate * event[0], the hit object's own time when it emitted the light the pixel receives.
+    frame_rgba: the H x W x 4 uint8 colours of the frame; events: the (H, W) records of the same view; readouts: one entry per object,
+    None or the keywords of readout_settings as a dict.  Returns (the H x W x 4 uint8 result, the number of pixels whose RGBA changed).
+    The value is per PIXEL: across a large moving face neighbouring pixels may show different values — the relativity of simultaneity."""
+    shown, n_in, n_on, _, table, o = _readout_coverage(events, readouts)
+    before = np.ascontiguousarray(frame_rgba, dtype=np.uint8).reshape(shown.shape + (4,))
+    img = before.copy()
+    if not table:
+        return img, 0
+    on = np.array([d["on_rgba"] if d else (0, 0, 0, 0) for d in table], dtype=np.uint32)[o]
+    off = np.array([d["off_rgba"] if d else (0, 0, 0, 0) for d in table], dtype=np.uint32)[o]
+    for colour, count in ((off, n_in), (on, n_on)):
+        a = ((colour[..., 3] * count.astype(np.uint32) + np.uint32(8)) // np.uint32(16))[..., None]
+        old = img[..., :3].astype(np.uint32)
+        out = (colour[..., :3] * a + old * (np.uint32(255) - a) + np.uint32(127)) // np.uint32(255)
+        img[..., :3] = np.where(shown[..., None], out, old).astype(np.uint8)
     return img, int((img != before).any(axis=-1).sum())

@@ -206,6 +206,14 @@ class Renderer:
             elif last is None or not np.array_equal(w, last):
                 self.set_object_windows(w)
                 self._scene_windows = w
+            # ... and the scene's `d` commands likewise (Scene.readouts() is cached by the scene too)
+            d, last = scene_or_bytes.readouts(), getattr(self, "_scene_readouts", None)
+            if d is None:
+                if last is not None:
+                    self.set_readouts(None)
+            elif last is None or d != last:
+                self.set_readouts(d)
+                self._scene_readouts = d
         else:
             raw = np.ascontiguousarray(scene_or_bytes).view(np.uint8)
             assert raw.size % 320 == 0
@@ -448,6 +456,44 @@ class Renderer:
         self._check(self._lib.rpt_last_overlay_pixels(self._h, C.byref(n)), "rpt_last_overlay_pixels")
         return int(n.value)
 
+    # -- the readout pass (include/rpt.h, rpt_set_readouts; not in the reference) ------------------
+    def set_readouts(self, readouts):
+        """The objects' displays: a list with one entry per object of the scene, None (no display) or a dict of the keywords of
+        events.readout_settings — rate, offset, digits, decimals, rect=(u0, v0, u1, v1), on_rgba, off_rgba; the display shows
+        offset + rate * the object's own time (event[0] of the event pass) of the light each pixel receives.  None or an empty list
+        clears the setting.  An unknown keyword raises TypeError; what the library refuses raises RenderError.  Per context; copied to the device here, not per frame."""
+        self._scene_readouts = None         # (what set_objects(scene) last passed on is no longer what the context holds)
+        if not readouts:
+            self._check(self._lib.rpt_set_readouts(self._h, None, 0), "rpt_set_readouts")
+            return
+        raw = (_ffi.Readout * len(readouts))()
+        for r, d in zip(raw, readouts):
+            if d is None:
+                continue
+            d = dict(d)
+            unknown = set(d) - {"rate", "offset", "digits", "decimals", "rect", "on_rgba", "off_rgba"}
+            if unknown:                     # (a misspelt key would silently leave the object without a display)
+                raise TypeError(f"unknown readout keyword(s): {sorted(unknown)}")
+            r.rate, r.offset, r.digits, r.decimals = d.get("rate", 1.0), d.get("offset", 0.0), d.get("digits", 0), d.get("decimals", 0)
+            r.u0, r.v0, r.u1, r.v1 = d.get("rect", (0.1, 0.25, 0.9, 0.75))
+            r.on_rgba[:], r.off_rgba[:] = d.get("on_rgba", (255, 0, 0, 255)), d.get("off_rgba", (0, 0, 0, 160))
+        self._check(self._lib.rpt_set_readouts(self._h, raw, len(readouts)), "rpt_set_readouts")
+
+    def render_readouts(self, async_: bool = False):
+        """Draw the displays of set_readouts into the framebuffer, in place, from the records of the last event frame.  The context must
+        have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice blends twice.
+        Independent of render_overlay: either may run first.  async_=True enqueues only (sync waits)."""
+        if async_:
+            self._check(self._lib.rpt_render_readouts_async(self._h), "rpt_render_readouts_async")
+        else:
+            self._check(self._lib.rpt_render_readouts(self._h), "rpt_render_readouts")
+
+    def last_readout_pixels(self) -> int:
+        """Pixels whose RGBA the last finished readout pass changed (0 before the first)."""
+        n = C.c_uint64(0)
+        self._check(self._lib.rpt_last_readout_pixels(self._h, C.byref(n)), "rpt_last_readout_pixels")
+        return int(n.value)
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -580,7 +626,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  projection: Union[None, str, Mapping, np.ndarray] = None, environment: Optional[np.ndarray] = None,
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
-                 fov: float = math.pi, fit: int = 0):
+                 fov: float = math.pi, fit: int = 0, readouts=None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -590,7 +636,9 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     orientation: (yaw, pitch, roll) for Renderer.set_orientation; v_fov: the pinhole's vertical field of view (set_field_of_view).
     adaptive_aa: (samples per axis, threshold) for Renderer.set_adaptive_aa.  overlay: the keywords of Renderer.set_overlay, e.g.
     dict(outlines=True, clock_step=0.5); it implies events=True and runs the three passes — the colour frame, the event frame, the
-    overlay — so the pixels returned carry the lines (rgb, the float colours before packing, does not)."""
+    overlay — so the pixels returned carry the lines (rgb, the float colours before packing, does not).  readouts: the list
+    Renderer.set_readouts takes, or True for the scene's own (`d` commands, Scene.readouts()); it implies events=True too and runs the
+    readout pass last: the colour frame, the event frame, the overlay if asked for, the readouts."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -615,10 +663,14 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        if overlay is not None:
+        if overlay is not None or readouts is not None:
             records = r.render_events()
-            r.set_overlay(**overlay)
-            r.render_overlay()
+            if overlay is not None:
+                r.set_overlay(**overlay)
+                r.render_overlay()
+            if readouts is not None:
+                r.set_readouts(scene.readouts() if readouts is True else readouts)
+                r.render_readouts()
             return r.read_framebuffer(), (r.read_debug_rgb() if debug_rgb else None), records
         frame = r.read_framebuffer(), (r.read_debug_rgb() if debug_rgb else None)
         return frame + (r.render_events(),) if events else frame

@@ -67,6 +67,7 @@ class Scene:
         self._lib.rpt_scene_set_texture_decoder(self._h, _PIL_DECODER, None)
         self.asset_root = asset_root
         self._windows = False               # windows(): not asked yet
+        self._readouts = False              # readouts(): likewise
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -81,6 +82,7 @@ class Scene:
     def inputScene(self, text: str) -> str:
         """Parse a whole scene description (what the reference reads from stdin). Returns diagnostics."""
         self._windows = False
+        self._readouts = False
         self._check(self._lib.rpt_scene_input(self._h, text.encode()), "inputScene")
         return self._lib.rpt_scene_last_error(self._h).decode()
 
@@ -231,6 +233,22 @@ class Scene:
                 out.setflags(write=False)
                 self._windows = out
         return self._windows
+
+    def readouts(self):
+        """The displays of the scene's `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands: a list with one entry per object, None or
+        the dict of events.readout_settings — what Renderer.set_readouts and events.readout take — or None for a scene without any `d`."""
+        if self._readouts is False:         # (only inputScene changes them: asked of the library once per parse)
+            from .events import readout_settings
+            n = C.c_size_t()
+            any_ = C.c_int()
+            self._lib.rpt_scene_get_readouts(self._h, None, 0, C.byref(n), C.byref(any_))
+            self._readouts = None
+            if any_.value:
+                raw = (_ffi.Readout * n.value)()
+                self._lib.rpt_scene_get_readouts(self._h, C.cast(raw, C.c_void_p), n.value, C.byref(n), C.byref(any_))
+                self._readouts = [readout_settings(rate=r.rate, offset=r.offset, digits=r.digits, decimals=r.decimals, rect=(r.u0, r.v0, r.u1, r.v1),
+                                                   on_rgba=tuple(r.on_rgba), off_rgba=tuple(r.off_rgba)) if r.digits else None for r in raw]
+        return self._readouts
 
     def mesh_roots(self):
         p = C.c_void_p()

@@ -77,17 +77,37 @@ class Worldline:
         """(K, 2) float32, the rows Renderer.set_object_windows takes for the legs' objects."""
         return np.array([leg.window for leg in self.legs], dtype=np.float32)
 
-    def to_dsl(self, shape: str = "Os", scale: Sequence[float] = (1.0, 1.0, 1.0), extra: str = "") -> str:
+    def clock_offsets(self, tau0: float = 0.0) -> np.ndarray:
+        """One float64 per leg: offset_j + t is the body's proper time at leg j's rest-frame time t — what a display on leg j's object
+        needs as its `offset` (rate 1) for the legs to show ONE clock.  A leg's rest-frame time is the body's proper time up to a
+        constant, so the proper time is accumulated over the legs' windows; tau0 is its value at the first breakpoint (the end of an
+        open-ended first leg, else the start of the first leg).  At every breakpoint offset_j + window_j[1] == offset_{j+1} + window_{j+1}[0]."""
+        tau = float(tau0)                   # the proper time at the breakpoint where the next leg begins
+        out = []
+        for j, leg in enumerate(self.legs):
+            t0, t1 = leg.window
+            if j == 0 and t0 == -math.inf:
+                out.append(tau - t1)        # (the open-ended first leg ends at the first breakpoint)
+                continue
+            out.append(tau - t0)
+            tau += t1 - t0
+        return np.array(out, dtype=np.float64)
+
+    def to_dsl(self, shape: str = "Os", scale: Sequence[float] = (1.0, 1.0, 1.0), extra: str = "", readout: Optional[str] = None,
+               tau0: float = 0.0) -> str:
         """One `O… p… v… w…` block per leg (repr() of the float64 values: they round to float once, in the scene parser).  shape: the
         object command ("Os", "Oc", "Om0"); scale: the `p` command's three scale factors (no rotation); extra: further commands of every
-        leg, e.g. "c1,0,0 l1"."""
+        leg, e.g. "c1,0,0 l1".  readout: "DIGITS,DECIMALS[,U0,V0,U1,V1]" gives every leg a display of the body's proper time (the
+        DSL's `d` command: `d1,OFFSET_j,…` with clock_offsets(tau0)); without it the text is what it was before displays existed."""
         out = []
-        for leg in self.legs:
+        offsets = self.clock_offsets(tau0) if readout is not None else None
+        for j, leg in enumerate(self.legs):
             p = ",".join(repr(float(c)) for c in leg.position)
             s = ",".join(repr(float(c)) for c in scale)
             v = ",".join(repr(float(c)) for c in leg.velocity)
             w = ",".join("inf" if c == math.inf else ("-inf" if c == -math.inf else repr(float(c))) for c in leg.window)
-            out.append(f"{shape} p{p},0,0,1,0,{s} v{v} w{w}" + (f" {extra}" if extra else ""))
+            d = f" d1,{float(offsets[j])!r},{readout}" if readout is not None else ""
+            out.append(f"{shape} p{p},0,0,1,0,{s} v{v} w{w}{d}" + (f" {extra}" if extra else ""))
         return "\n".join(out) + "\n"
 
 
