@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -27,6 +27,11 @@
 // own clock, of the look-back time and of its rest-frame coordinates (a step of 0 skips that axis), and a tint by light delay (TMAX
 // omitted: the frame's largest).  The host runs the three passes — the colour frame, an event frame of the same view, the overlay — and
 // reports the pixels the overlay changed on stderr.  Without the flag nothing changes.
+//
+// --stars FILE adds a star field before the picture is written (rpt_set_stars, rpt_render_stars; not in the reference): FILE holds raw
+// 32-byte rpt_star records (relativitypathtracer_amd/stars.py `save` writes them) of stars at rest in the scene's frame — the sky's
+// frame is set from the scene's camera.  The host runs the colour frame, an event frame of the same view and the star-field pass, under
+// the overlay's lines, and reports the stars inside the frame and the pixels changed on stderr.  It excludes --projection (a ray map).
 //
 // A scene with `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands gets its displays drawn too (rpt_set_readouts, rpt_render_readouts;
 // not in the reference): seven-segment digits on those objects that show their own time, after the overlay, before the picture is written.
@@ -152,7 +157,7 @@ int main(int argc, char **argv) {
     // the free-look options (degrees), taken out of argv; what is left is positional
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
-    const char *events_path = nullptr, *projection_spec = nullptr;
+    const char *events_path = nullptr, *projection_spec = nullptr, *stars_path = nullptr;
     int aa_n = 1, aa_threshold = 8;
     rpt_overlay_desc overlay;
     std::memset(&overlay, 0, sizeof overlay);
@@ -167,6 +172,11 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--fov")) v_fov = (float)(std::atof(argv[++i]) * deg);
             else if (has_value && !std::strcmp(argv[i], "--events")) events_path = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--projection")) projection_spec = argv[++i];
+            else if (has_value && !std::strcmp(argv[i], "--stars")) stars_path = argv[++i];
+            else if (!std::strcmp(argv[i], "--stars")) {
+                std::fprintf(stderr, "--stars needs a file name (raw 32-byte rpt_star records)\n");
+                return 2;
+            }
             else if (!std::strcmp(argv[i], "--projection")) {
                 std::fprintf(stderr, "--projection needs a value: fisheye[:FOV_DEG[:fit]], equisolid[:FOV_DEG[:fit]], stereographic[:FOV_DEG[:fit]] or cube_strip\n");
                 return 2;
@@ -200,12 +210,24 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
     std::vector<float> raymap;                                   // --projection: the map, filled on the host (no device needed)
     if (projection_spec && !parse_projection(projection_spec, width, height, &raymap)) return 2;
+    std::vector<rpt_star> catalogue;                             // --stars: the raw records
+    if (stars_path) {
+        std::FILE *f = std::fopen(stars_path, "rb");
+        rpt_star s;
+        while (f && std::fread(&s, sizeof s, 1, f) == 1) catalogue.push_back(s);
+        const bool whole = f && std::feof(f) && std::ftell(f) == (long)(catalogue.size() * sizeof(rpt_star));
+        if (f) std::fclose(f);
+        if (!whole || catalogue.empty()) {
+            std::fprintf(stderr, "--stars: %s does not hold a whole number (> 0) of 32-byte rpt_star records\n", stars_path);
+            return 2;
+        }
+    }
     const std::string text((std::istreambuf_iterator<char>(std::cin)), std::istreambuf_iterator<char>());
 
     rpt_scene *scene = rpt_scene_create();                       // inputScene()            main.cpp:31
@@ -307,9 +329,25 @@ int main(int argc, char **argv) {
                      ring.frames_in_flight(), sec / frames * 1e3, (double)width * height * frames / sec / 1e6, presented);
     }
     bool events_rendered = false;
+    if (!catalogue.empty()) {                                    // stars on that frame's sky, at rest in the scene's frame
+        unsigned long long counts[2] = {0, 0};
+        float lorentz[16], inv_lorentz[16];
+        rc = rpt_scene_get_camera_lorentz(scene, lorentz, inv_lorentz);
+        if (!rc) rc = rpt_set_environment_frame(last, inv_lorentz);
+        if (!rc) rc = rpt_render_events(last);
+        events_rendered = !rc;
+        if (!rc) rc = rpt_set_stars(last, catalogue.data(), (int)catalogue.size());
+        if (!rc) rc = rpt_render_stars(last);
+        if (!rc) rc = rpt_last_stars(last, counts);
+        if (rc) {
+            std::fprintf(stderr, "stars: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::fprintf(stderr, "stars: %llu of %zu inside the frame, %llu of %lld pixels changed\n", counts[0], catalogue.size(), counts[1], (long long)width * height);
+    }
     if (overlay.layers) {                                        // lines on that frame, from an event frame of the same view
         unsigned long long changed = 0;
-        rc = rpt_render_events(last);
+        rc = events_rendered ? 0 : rpt_render_events(last);
         events_rendered = !rc;
         if (!rc) rc = rpt_set_overlay(last, &overlay);
         if (!rc) rc = rpt_render_overlay(last);

@@ -43,7 +43,9 @@
  * needed; DESIGN.md, "Ray-map camera"), and opt-in per-object time windows — objects and lights that begin and end, from which
  * piecewise-inertial worldlines are built: rpt_set_object_windows ("Time windows"), and the opt-in readout pass — seven-segment
  * displays on the objects' surfaces that show each object's own proper time: rpt_set_readouts, rpt_render_readouts /
- * rpt_render_readouts_async and rpt_last_readout_pixels ("Readout pass").
+ * rpt_render_readouts_async and rpt_last_readout_pixels ("Readout pass"), and the opt-in star-field pass — a catalogue of point
+ * sources in the sky's rest frame, aberrated, Doppler-shifted and beamed as points: rpt_set_stars, rpt_render_stars /
+ * rpt_render_stars_async and rpt_last_stars ("Star-field pass").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -602,6 +604,46 @@ int rpt_set_readouts(rpt_ctx *ctx, const rpt_readout *per_object_or_null, int co
 int rpt_render_readouts(rpt_ctx *ctx);         /* enqueue and wait */
 int rpt_render_readouts_async(rpt_ctx *ctx);   /* enqueue; rpt_sync waits */
 int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels);
+
+/* The star-field pass (not in the reference; DESIGN.md §19 "Star-field pass" gives every rule operation by operation): a catalogue of
+ * point sources at rest in the sky's frame — the frame of rpt_set_environment_frame, whether or not a sky image is set, so stars and an
+ * image stay registered — aberrated into the camera's frame, Doppler-shifted and beamed as POINT sources, and added to the miss pixels
+ * of a rendered frame.  A third sibling of the overlay and the readout pass with the same discipline: opt-in, per context, not shared by
+ * rpt_share_scene; enqueued on the context's stream after a colour frame and an event frame of the same view; in place into the R, G, B
+ * bytes of the 16-B framebuffer pixels (alpha, bytes 0-7 and 12-15, the debug planes and the record buffer are not written).  The stars
+ * are a display-space layer over the sky, as the overlay's lines are: they light nothing.
+ *
+ *   dir   the direction in which one looks to see the star, in the sky's rest frame (any non-zero length; normalised in double here).
+ *   rgb   the star's linear colour at rest, on the scale of object colours before the tonemap: what one pixel gets when the whole star
+ *         falls on it.
+ *
+ * In short (E' = the sky matrix as a launch re-bases it for the orientation; G = its inverse, formed in double and rounded to float once;
+ * with interval == 0, G inverts E's spatial block only and D = 1): q = G (interval, dir), n = normalize(q.yzw), D = q.x / interval — a
+ * star whose D is not finite or not > 0 is skipped; c = S_f(D, rgb) as rpt_set_doppler defines it, then divided by D^2 when
+ * RPT_DOPPLER_BEAMING is set (a point source also loses solid angle: its flux goes with D, or D^2 without the shift, where a surface's
+ * goes with D^3 or D^4); n is projected by the inverse of the camera's own pixel-to-direction map (pinhole and lens: pixel x AT X = x;
+ * equirect: pixel centre at x + 0.5, column taps wrap when h_fov is the full circle); the four pixels around (X, Y) get c times their
+ * bilinear weight, clamped to 65536 per tap and channel, in 2^-24 fixed point through integer atomic adds — sums that do not depend on
+ * the order of arrival, so a frame is reproducible bit for bit; then every MISS pixel (record's object < 0) with a non-zero sum S gets
+ * byte = min(255, byte + to_u8(min(hable(S) / hable(white_point), 1))) per channel.
+ *
+ * rpt_set_stars copies the catalogue, in its order (the sums do not depend on it), and writes it to the device once, in stream order, as
+ * the sky image; NULL or count 0 switches the pass off.  RPT_ERR_ARG, message "rpt_set_stars: ...", the previous
+ * catalogue kept: a component of dir or rgb that is not finite, a zero-length dir, a negative colour, count < 0 or count > 2^22.
+ * rpt_render_stars[_async] refuses what rpt_render_overlay refuses, with messages that start "rpt_render_stars:", and also, with
+ * RPT_ERR_ARG, RPT_PROJECTION_RAYMAP (a caller's ray map has no inverse) and a sky matrix that cannot be inverted.  The context stays
+ * usable after a refusal.  With no catalogue the call checks nothing, launches nothing and succeeds.  Calling it twice adds the stars twice.
+ * rpt_last_stars: of the last FINISHED pass, out[0] = stars with at least one of their four taps inside the frame (whatever its weight),
+ * out[1] = pixels whose bytes changed; both 0 before the first. */
+typedef struct rpt_star { float dir[3]; float rgb[3]; float _pad[2]; } rpt_star;   /* 32 B */
+int rpt_set_stars(rpt_ctx *ctx, const rpt_star *stars_or_null, int count);
+int rpt_render_stars(rpt_ctx *ctx);         /* enqueue and wait */
+int rpt_render_stars_async(rpt_ctx *ctx);   /* enqueue; rpt_sync waits */
+int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]);
+/* Measurement only (tools/stars_cost.py): timed != 0 brackets the two kernels of every pass with HIP events, and rpt_last_stars_ms waits
+ * for the last pass and returns {splat, resolve} in milliseconds (RPT_ERR_STATE if that pass was not timed). */
+int rpt_set_stars_measurement(rpt_ctx *ctx, int timed);
+int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

@@ -56,6 +56,11 @@ class Readout(C.Structure):
                 ("digits", C.c_uint8), ("decimals", C.c_uint8), ("_pad", C.c_uint8 * 2), ("on_rgba", C.c_uint8 * 4), ("off_rgba", C.c_uint8 * 4)]
 
 
+class Star(C.Structure):
+    """rpt_star of include/rpt.h (32 B): one point source of the star-field pass."""
+    _fields_ = [("dir", C.c_float * 3), ("rgb", C.c_float * 3), ("_pad", C.c_float * 2)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -224,6 +229,12 @@ HIP_SYMBOLS = {
     "rpt_render_readouts": (C.c_int, [C.c_void_p]),
     "rpt_render_readouts_async": (C.c_int, [C.c_void_p]),
     "rpt_last_readout_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_stars": (C.c_int, [C.c_void_p, C.POINTER(Star), C.c_int]),
+    "rpt_render_stars": (C.c_int, [C.c_void_p]),
+    "rpt_render_stars_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_stars": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_stars_measurement": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_last_stars_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -24,6 +24,8 @@
 #include "rpt_bounds_certify.hpp"
 #include "rpt_tile_bitmap.hpp"
 #include "rpt_workers.hpp"
+#include "rpt_stars.hip.h"          /* last: the kernels before it keep their place in the translation unit */
+#include "rpt_stars_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -218,6 +220,18 @@ struct rpt_ctx {
     hipEvent_t readout_counted = nullptr;             // recorded after that copy
     unsigned long long readout_pixels = 0;            // rpt_last_readout_pixels
     bool readout_pending = false;                     // a copy has been enqueued since readout_pixels was read
+    // rpt_set_stars / rpt_render_stars (not in the reference): the star-field pass, per context, never shared; the overlay's discipline
+    int star_count = 0;                               // 0 = no catalogue: the pass is off
+    StagedUpload star_table;                          // rpt_star per star: unit directions, in the caller's order; written once per rpt_set_stars
+    DeviceBuffer star_acc;                            // 24 B per pixel of the largest frame so far: the fixed-point sums, all zero outside a pass
+    DeviceBuffer star_scratch;                        // 16 B: {stars with a tap inside the frame, changed pixels} of the pass in flight
+    unsigned long long *star_host = nullptr;          // pinned, 16 B: the counters of the last pass whose copy has run
+    hipEvent_t star_counted = nullptr;                // recorded after that copy
+    unsigned long long star_counts[2] = {0, 0};       // rpt_last_stars
+    bool star_pending = false;                        // a copy has been enqueued since star_counts was read
+    bool star_timed = false;                          // rpt_set_stars_measurement
+    hipEvent_t star_marks[3] = {nullptr, nullptr, nullptr}; // timed passes: before the splat, between the kernels, after the resolve
+    bool star_marked = false;                         // the last pass recorded them
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -1862,6 +1876,98 @@ int launch_readouts(rpt_ctx *ctx) {
     return RPT_OK;
 }
 
+// One star-field pass on the context's stream (kernels 1120 and 1121): the overlay pass's refusals and two of its own, G, the
+// accumulator, the two launches, then the counters' way home as the overlay's.
+int launch_stars(rpt_ctx *ctx) {
+    if (ctx->star_count == 0) {       // no catalogue: nothing is checked, launched or changed
+        ctx->star_pending = false;
+        ctx->star_counts[0] = ctx->star_counts[1] = 0;
+        ctx->star_marked = false;
+        return RPT_OK;
+    }
+    rpt_pixel *out16 = nullptr;
+    const rpt_event *events = nullptr;
+    if (int rc = frames_of_this_view(ctx, "rpt_render_stars", &out16, &events)) return rc;
+    if (ctx->projection == RPT_PROJECTION_RAYMAP)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a star with");
+    rptd::StarArgs a;
+    std::memset((void *)&a, 0, sizeof a);
+    {   // E' as a colour frame's launch forms it, then G
+        rpt_float4 e[4];
+        std::memcpy(e, ctx->env_frame, sizeof e);
+        if (ctx->oriented) rebase_columns(e, ctx->R, e);
+        float g[16];
+        if (!rpts::sky_to_camera(&e[0].x, ctx->interval, g))
+            return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: the sky matrix (rpt_set_environment_frame) cannot be inverted");
+        std::memcpy(a.G, g, sizeof a.G);
+    }
+    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height, acc_bytes = pixels * 3 * sizeof(unsigned long long);
+    if (acc_bytes > ctx->star_acc.capacity || !ctx->star_acc.ptr) {      // a new accumulator starts all zero; passes leave it so
+        RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (a pass in flight may still use the old one)
+        if (int rc = reserve(ctx, ctx->star_acc, acc_bytes)) return rc;
+        RPT_HIP(ctx, hipMemsetAsync(ctx->star_acc.ptr, 0, ctx->star_acc.capacity, ctx->stream));
+    }
+    if (int rc = reserve(ctx, ctx->star_scratch, 16)) return rc;
+    if (!ctx->star_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->star_host, 16, hipHostMallocDefault));
+    if (!ctx->star_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->star_counted, hipEventDisableTiming));
+    if (ctx->star_timed)
+        for (hipEvent_t &m : ctx->star_marks)
+            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
+
+    a.stars = (const rpt_star *)ctx->star_table.device.ptr;
+    a.acc = (unsigned long long *)ctx->star_acc.ptr;
+    a.counts = (unsigned long long *)ctx->star_scratch.ptr;
+    a.count = ctx->star_count;
+    a.width = ctx->width;
+    a.height = ctx->height;
+    a.interval = ctx->interval;
+    a.doppler = ctx->interval != 0 ? ctx->doppler : 0;
+    if (ctx->projection == RPT_PROJECTION_EQUIRECT) {
+        a.camera = RPT_STARS_EQUIRECT;
+        a.h_fov = ctx->projection_params[0];
+        a.v_fov = ctx->projection_params[1];
+        a.yaw = ctx->projection_params[2];
+        a.wrap = a.h_fov == (float)(2.0 * RPT_PI_D) ? 1 : 0;
+    } else {
+        const float s = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
+        a.plane_x = s * ((float)ctx->width / (float)ctx->height);
+        a.plane_y = s;
+    }
+    rptd::StarResolveArgs b;
+    std::memset((void *)&b, 0, sizeof b);
+    b.acc = a.acc;
+    b.events = events;
+    b.out16 = out16;
+    b.counts = a.counts;
+    b.pixels = pixels;
+    for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
+
+    RPT_HIP(ctx, hipMemsetAsync(ctx->star_scratch.ptr, 0, 16, ctx->stream));
+    if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[0], ctx->stream));
+    void *splat_args[] = {(void *)&a};
+    (void)hipLaunchKernel((const void *)rptd::rpt_stars_splat_kernel, dim3((unsigned)((ctx->star_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[1], ctx->stream));
+    void *resolve_args[] = {(void *)&b};
+    (void)hipLaunchKernel((const void *)rptd::rpt_stars_resolve_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[2], ctx->stream));
+    ctx->star_marked = ctx->star_timed;
+    RPT_HIP(ctx, hipMemcpyAsync(ctx->star_host, ctx->star_scratch.ptr, 16, hipMemcpyDeviceToHost, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(ctx->star_counted, ctx->stream));
+    ctx->last_event = ctx->star_counted;
+    ctx->star_pending = true;
+    return RPT_OK;
+}
+
+void collect_star_counts(rpt_ctx *ctx) {
+    if (ctx->star_pending && ctx->star_counted && hipEventQuery(ctx->star_counted) == hipSuccess) {
+        ctx->star_counts[0] = ctx->star_host[0];
+        ctx->star_counts[1] = ctx->star_host[1];
+        ctx->star_pending = false;
+    }
+}
+
 void collect_readout_pixels(rpt_ctx *ctx) {
     if (ctx->readout_pending && ctx->readout_counted && hipEventQuery(ctx->readout_counted) == hipSuccess) {
         ctx->readout_pixels = *ctx->readout_host;
@@ -1933,16 +2039,19 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch, &ctx->readout_scratch})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch, &ctx->readout_scratch, &ctx->star_acc, &ctx->star_scratch})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table}) release(*u);
     if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
     if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
     if (ctx->overlay_host) (void)hipHostFree(ctx->overlay_host);
     if (ctx->overlay_counted) (void)hipEventDestroy(ctx->overlay_counted);
     if (ctx->readout_host) (void)hipHostFree(ctx->readout_host);
     if (ctx->readout_counted) (void)hipEventDestroy(ctx->readout_counted);
+    if (ctx->star_host) (void)hipHostFree(ctx->star_host);
+    if (ctx->star_counted) (void)hipEventDestroy(ctx->star_counted);
+    for (hipEvent_t m : ctx->star_marks) if (m) (void)hipEventDestroy(m);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -2744,6 +2853,7 @@ int rpt_sync(rpt_ctx *ctx) {
     collect_aa_refined(ctx);
     collect_overlay_pixels(ctx);
     collect_readout_pixels(ctx);
+    collect_star_counts(ctx);
     return RPT_OK;
 }
 
@@ -2946,6 +3056,70 @@ int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels) {
         collect_readout_pixels(ctx);
     }
     *pixels = ctx->readout_pixels;
+    return RPT_OK;
+}
+
+// The catalogue goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused
+// for its arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no catalogue.
+int rpt_set_stars(rpt_ctx *ctx, const rpt_star *stars_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (count < 0 || count > rpts::kMaxStars) return fail(ctx, RPT_ERR_ARG, "rpt_set_stars: " + rpts::catalogue_fault(nullptr, count));
+    if (!stars_or_null || count == 0) {
+        ctx->star_count = 0;
+        return RPT_OK;
+    }
+    const std::string fault = rpts::catalogue_fault(stars_or_null, count);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_stars: " + fault);
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    void *host = nullptr;
+    int rc = staged_host(ctx, ctx->star_table, (size_t)count * sizeof(rpt_star), &host);
+    if (!rc) {
+        rpts::prepare_catalogue(stars_or_null, count, (rpt_star *)host);
+        rc = staged_copy(ctx, ctx->star_table);
+    }
+    if (rc) {
+        ctx->star_count = 0;
+        return rc;
+    }
+    ctx->star_count = count;
+    return RPT_OK;
+}
+
+int rpt_render_stars_async(rpt_ctx *ctx) {
+    if (!ctx) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_stars(ctx);
+}
+
+int rpt_render_stars(rpt_ctx *ctx) {
+    if (int rc = rpt_render_stars_async(ctx)) return rc;
+    return rpt_sync(ctx);
+}
+
+int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]) {
+    if (!ctx || !out) return RPT_ERR_ARG;
+    if (ctx->star_pending) {
+        RPT_HIP(ctx, hipSetDevice(ctx->device));
+        collect_star_counts(ctx);
+    }
+    out[0] = ctx->star_counts[0];
+    out[1] = ctx->star_counts[1];
+    return RPT_OK;
+}
+
+int rpt_set_stars_measurement(rpt_ctx *ctx, int timed) {
+    if (!ctx) return RPT_ERR_ARG;
+    ctx->star_timed = timed != 0;
+    return RPT_OK;
+}
+
+int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]) {
+    if (!ctx || !ms) return RPT_ERR_ARG;
+    if (!ctx->star_marked) return fail(ctx, RPT_ERR_STATE, "rpt_last_stars_ms: the last star-field pass was not timed (rpt_set_stars_measurement)");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    RPT_HIP(ctx, hipEventSynchronize(ctx->star_marks[2]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->star_marks[0], ctx->star_marks[1]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->star_marks[1], ctx->star_marks[2]));
     return RPT_OK;
 }
 

@@ -494,6 +494,45 @@ class Renderer:
         self._check(self._lib.rpt_last_readout_pixels(self._h, C.byref(n)), "rpt_last_readout_pixels")
         return int(n.value)
 
+    # -- the star-field pass (include/rpt.h, rpt_set_stars; not in the reference) -------------------
+    def set_stars(self, catalogue):
+        """The star catalogue: an array of stars.STAR_DTYPE records (or anything of n x 32 bytes in that layout: dir, rgb, two floats of
+        padding), e.g. from stars.random_catalogue / stars.from_arrays / stars.load; None or an empty array switches the pass off.
+        dir is the direction one looks in to see the star, in the sky's rest frame (set_environment_frame); rgb its linear colour at
+        rest.  Copied by the library; per context; what the library refuses raises RenderError."""
+        if catalogue is None or len(catalogue) == 0:
+            self._check(self._lib.rpt_set_stars(self._h, None, 0), "rpt_set_stars")
+            return
+        raw = np.ascontiguousarray(catalogue)
+        if raw.nbytes % 32 or raw.nbytes // 32 != len(raw):
+            raise ValueError("a star catalogue has one 32-byte record (stars.STAR_DTYPE) per star")
+        self._check(self._lib.rpt_set_stars(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Star)), len(raw)), "rpt_set_stars")
+
+    def render_stars(self, async_: bool = False):
+        """Add the stars of set_stars to the miss pixels of the framebuffer, in place.  The context must have rendered (or enqueued) a
+        colour frame and an event frame of the current view first; calling it twice adds them twice.  Independent of render_overlay and
+        render_readouts.  async_=True enqueues only (sync waits)."""
+        if async_:
+            self._check(self._lib.rpt_render_stars_async(self._h), "rpt_render_stars_async")
+        else:
+            self._check(self._lib.rpt_render_stars(self._h), "rpt_render_stars")
+
+    def last_stars(self) -> Tuple[int, int]:
+        """(stars with at least one tap inside the frame, pixels whose bytes changed) of the last finished star-field pass."""
+        n = (C.c_uint64 * 2)(0, 0)
+        self._check(self._lib.rpt_last_stars(self._h, n), "rpt_last_stars")
+        return int(n[0]), int(n[1])
+
+    def set_stars_measurement(self, timed: bool = False):
+        """Measurement only (tools/stars_cost.py): time the two kernels of every pass (last_stars_ms)."""
+        self._check(self._lib.rpt_set_stars_measurement(self._h, int(bool(timed))), "rpt_set_stars_measurement")
+
+    def last_stars_ms(self) -> Tuple[float, float]:
+        """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_stars_measurement)."""
+        ms = (C.c_float * 2)(0.0, 0.0)
+        self._check(self._lib.rpt_last_stars_ms(self._h, ms), "rpt_last_stars_ms")
+        return float(ms[0]), float(ms[1])
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -626,7 +665,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  projection: Union[None, str, Mapping, np.ndarray] = None, environment: Optional[np.ndarray] = None,
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
-                 fov: float = math.pi, fit: int = 0, readouts=None):
+                 fov: float = math.pi, fit: int = 0, readouts=None, stars=None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -638,7 +677,9 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     dict(outlines=True, clock_step=0.5); it implies events=True and runs the three passes — the colour frame, the event frame, the
     overlay — so the pixels returned carry the lines (rgb, the float colours before packing, does not).  readouts: the list
     Renderer.set_readouts takes, or True for the scene's own (`d` commands, Scene.readouts()); it implies events=True too and runs the
-    readout pass last: the colour frame, the event frame, the overlay if asked for, the readouts."""
+    readout pass last: the colour frame, the event frame, the overlay if asked for, the readouts.  stars: a catalogue for
+    Renderer.set_stars, at rest in the scene's frame (the sky's frame is set from the scene's camera, as for environment); it implies
+    events=True as well and runs the star-field pass right after the event frame, under the overlay's lines and the readouts."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -654,6 +695,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
             r.set_projection(**({"mode": projection} if isinstance(projection, str) else dict(projection)))
         if environment is not None:
             r.set_environment(environment)
+        if environment is not None or stars is not None:
             r.set_environment_frame(scene.camera_lorentz()[1])
         r.upload_scene(scene)
         if scene.windows() is not None:       # (the scene's `w` commands)
@@ -663,8 +705,11 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        if overlay is not None or readouts is not None:
+        if overlay is not None or readouts is not None or stars is not None:
             records = r.render_events()
+            if stars is not None:
+                r.set_stars(stars)
+                r.render_stars()
             if overlay is not None:
                 r.set_overlay(**overlay)
                 r.render_overlay()
