@@ -60,6 +60,27 @@ struct StagedUpload {
     hipEvent_t copied = nullptr;                      // recorded after that copy: `host` is rewritten only once it has passed
 };
 
+// The way back: a pass's counters, one or two 64-bit words, left on the device and read later without blocking the caller.
+// tally_ready() on first use, tally_zero() on the stream before the pass, tally_home() behind it (the copy, `copied`, pending);
+// tally_collect() takes the pinned words over once `copied` has passed, tally_off() is a pass switched off: nothing pending, all zero.
+struct Tally {
+    DeviceBuffer device;                              // the words of the pass in flight, then `spare` bytes of the pass's own that are zeroed with them
+    unsigned long long *host = nullptr;               // pinned: the words of the last pass whose copy has run
+    hipEvent_t copied = nullptr;                      // recorded after that copy
+    unsigned long long value[2] = {0, 0};             // what rpt_last_* reports: `host` as last read with `copied` passed
+    size_t words = 1, spare = 0;                      // (as tally_ready was given them)
+    bool pending = false;                             // a copy has been enqueued since `value` was read
+};
+enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_COUNT };     // rpt_ctx::tally
+
+// What the last frame of one kind (colour, event) was enqueued for, as a pass over both asks (frames_of_this_view)
+struct FrameMark {
+    unsigned long long generation = 0;                // rpt_ctx::view_generation then; 0 = no such frame yet
+    int width = 0, height = 0;
+    void *buffer = nullptr;                           // the framebuffer (null: a colour plane) / the records it was rendered into
+    bool rendered() const { return generation != 0; }
+};
+
 // The equirectangular camera's tables (rpt_projection_tables) on the device, and what they were built for (n = 0: nothing yet)
 struct ProjectionTables {
     StagedUpload upload;                              // [n (width + height)] float2: the column table, then the row table
@@ -152,7 +173,6 @@ struct rpt_ctx {
     long host_calls = 0;
 #endif
     float last_ms = 0.0f;
-    bool frame_rendered = false;
     bool has_mesh = true;                             // the current Object[] holds a mesh object (rpt_set_objects); picks the kernel
     // rpt_set_doppler (not in the reference): RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING, 0 = off; per context, never shared
     int doppler = 0;
@@ -186,49 +206,29 @@ struct rpt_ctx {
     hipEvent_t ev_events = nullptr;                   // recorded after every event pass (what last_event names then); created on first use
     int last_events_variant = 0;                      // the event kernel the last pass ran with (rpt_last_events_variant)
     bool last_events_exact_rcp = false;               // ... and whether its walk took 1 / det through rcp_exact (rpt_last_events_exact_rcp)
-    bool events_rendered = false;
-    // the last event frame, as rpt_pick and rpt_read_events address it: its buffer, its size and the rows this context wrote
-    void *events_ptr = nullptr;
-    int events_width = 0, events_height = 0, events_first_tile = 0, events_tile_step = 1, events_run_log2 = 0;
+    FrameMark event_frame;                            // the last event frame, as rpt_pick and rpt_read_events address it
+    int events_first_tile = 0, events_tile_step = 1, events_run_log2 = 0;     // ... and the rows of it this context wrote
     // rpt_set_adaptive_aa (not in the reference): adaptive anti-aliasing, per context, never shared
     int aa_n = 1, aa_threshold = 8;                   // samples per axis (1 = off) and the criterion's threshold
     DeviceBuffer aa_plane;                            // pass A's packed colours, 4 B/pixel: what pass B decides from
-    DeviceBuffer aa_counter;                          // 8 B: the refined pixels of the frame in flight
-    unsigned long long *aa_host = nullptr;            // pinned: the counter of the last frame whose copy has run
-    hipEvent_t aa_counted = nullptr;                  // recorded after that copy
-    unsigned long long aa_refined = 0;                // rpt_last_aa_refined: aa_host as last read with aa_counted passed
-    bool aa_pending = false;                          // a copy has been enqueued since aa_refined was read
     int last_aa_variant = 0;                          // the refine kernel of the last colour frame (rpt_last_aa_variant)
     ProjectionTables aa_pano;                         // panorama: the tables at aa_n times the frame's size, for the refine pass
     // rpt_set_overlay / rpt_render_overlay (not in the reference): the overlay pass, per context, never shared
     rpt_overlay_desc overlay = {};                    // layers == 0: off
     unsigned long long view_generation = 1;           // bumped by every call that changes the view (objects, params, projection, orientation, lens)
-    unsigned long long colour_generation = 0, events_generation = 0;     // the view the last colour frame / event frame was enqueued for (0 = none yet)
-    int colour_width = 0, colour_height = 0;          // the last colour frame's size (the last event frame's: events_width, events_height)
-    void *colour_out = nullptr;                       // ... and the framebuffer it was rendered into (the last event frame's records: events_ptr)
-    DeviceBuffer overlay_scratch;                     // 16 B: the changed pixels of the pass in flight, then the bit pattern of the frame's largest delay
-    unsigned long long *overlay_host = nullptr;       // pinned: the counter of the last pass whose copy has run
-    hipEvent_t overlay_counted = nullptr;             // recorded after that copy
-    unsigned long long overlay_pixels = 0;            // rpt_last_overlay_pixels: overlay_host as last read with overlay_counted passed
-    bool overlay_pending = false;                     // a copy has been enqueued since overlay_pixels was read
-    // rpt_set_readouts / rpt_render_readouts (not in the reference): the readout pass, per context, never shared; the overlay's discipline
+    FrameMark colour_frame;                           // the last colour frame (rendered() is what the read-back calls ask)
+    // what the passes report, by TALLY_*: the refined pixels of an adaptive frame (rpt_last_aa_refined); the overlay's changed pixels and,
+    // as spare bytes, the bit pattern of the frame's largest delay (rpt_last_overlay_pixels); the readouts' changed pixels
+    // (rpt_last_readout_pixels); {stars with a tap inside the frame, changed pixels} (rpt_last_stars)
+    Tally tally[TALLY_COUNT];
+    // rpt_set_readouts / rpt_render_readouts (not in the reference): the readout pass, per context, never shared
     std::vector<rpt_readout> readouts;                // one per entry of Object[]; empty = none set
     unsigned long long readout_low_mask = 0;          // bit o: object o < 64 has a display
     StagedUpload readout_table;                       // rptd::ReadoutDisplay per object, written once per rpt_set_readouts
-    DeviceBuffer readout_scratch;                     // 8 B: the changed pixels of the pass in flight
-    unsigned long long *readout_host = nullptr;       // pinned: the counter of the last pass whose copy has run
-    hipEvent_t readout_counted = nullptr;             // recorded after that copy
-    unsigned long long readout_pixels = 0;            // rpt_last_readout_pixels
-    bool readout_pending = false;                     // a copy has been enqueued since readout_pixels was read
-    // rpt_set_stars / rpt_render_stars (not in the reference): the star-field pass, per context, never shared; the overlay's discipline
+    // rpt_set_stars / rpt_render_stars (not in the reference): the star-field pass, per context, never shared
     int star_count = 0;                               // 0 = no catalogue: the pass is off
     StagedUpload star_table;                          // rpt_star per star: unit directions, in the caller's order; written once per rpt_set_stars
     DeviceBuffer star_acc;                            // 24 B per pixel of the largest frame so far: the fixed-point sums, all zero outside a pass
-    DeviceBuffer star_scratch;                        // 16 B: {stars with a tap inside the frame, changed pixels} of the pass in flight
-    unsigned long long *star_host = nullptr;          // pinned, 16 B: the counters of the last pass whose copy has run
-    hipEvent_t star_counted = nullptr;                // recorded after that copy
-    unsigned long long star_counts[2] = {0, 0};       // rpt_last_stars
-    bool star_pending = false;                        // a copy has been enqueued since star_counts was read
     bool star_timed = false;                          // rpt_set_stars_measurement
     hipEvent_t star_marks[3] = {nullptr, nullptr, nullptr}; // timed passes: before the splat, between the kernels, after the resolve
     bool star_marked = false;                         // the last pass recorded them
@@ -313,6 +313,61 @@ void release(StagedUpload &u) {
     if (u.host) (void)hipHostFree(u.host);
     if (u.copied) (void)hipEventDestroy(u.copied);
     u = StagedUpload();
+}
+
+// First use: `words` 64-bit words on the device with `spare` bytes behind them, as many pinned words, and the event
+int tally_ready(rpt_ctx *ctx, Tally &t, size_t words, size_t spare = 0) {
+    t.words = words;
+    t.spare = spare;
+    if (int rc = reserve(ctx, t.device, words * 8 + spare)) return rc;
+    if (!t.host) RPT_HIP(ctx, hipHostMalloc((void **)&t.host, words * 8, hipHostMallocDefault));
+    if (!t.copied) RPT_HIP(ctx, hipEventCreateWithFlags(&t.copied, hipEventDisableTiming));
+    return RPT_OK;
+}
+
+// ... all zero on the stream before the pass, the spare bytes too
+int tally_zero(rpt_ctx *ctx, Tally &t) {
+    RPT_HIP(ctx, hipMemsetAsync(t.device.ptr, 0, t.words * 8 + t.spare, ctx->stream));
+    return RPT_OK;
+}
+
+// ... and the words' way home behind the pass, in stream order
+int tally_home(rpt_ctx *ctx, Tally &t) {
+    RPT_HIP(ctx, hipMemcpyAsync(t.host, t.device.ptr, t.words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RPT_HIP(ctx, hipEventRecord(t.copied, ctx->stream));
+    t.pending = true;
+    return RPT_OK;
+}
+
+void tally_collect(Tally &t) {
+    if (t.pending && t.copied && hipEventQuery(t.copied) == hipSuccess) {
+        for (size_t k = 0; k < t.words; k++) t.value[k] = t.host[k];
+        t.pending = false;
+    }
+}
+
+void tally_off(Tally &t) {
+    t.pending = false;
+    t.value[0] = t.value[1] = 0;
+}
+
+// A rpt_last_* call: the first `words` words as last collected, after one more look where a copy is still on its way
+int tally_read(rpt_ctx *ctx, int which, unsigned long long *out, int words) {
+    if (!ctx || !out) return RPT_ERR_ARG;
+    Tally &t = ctx->tally[which];
+    if (t.pending) {
+        RPT_HIP(ctx, hipSetDevice(ctx->device));
+        tally_collect(t);
+    }
+    for (int k = 0; k < words; k++) out[k] = t.value[k];
+    return RPT_OK;
+}
+
+void release(Tally &t) {
+    release(t.device);
+    if (t.host) (void)hipHostFree(t.host);
+    if (t.copied) (void)hipEventDestroy(t.copied);
+    t = Tally();
 }
 
 // opencl_kernel.cl:607-616 on the host (same fp32 expression; this file is built without contraction)
@@ -1619,9 +1674,7 @@ int launch(rpt_ctx *ctx, Call call) {
     if (call.colour_frame && ctx->aa_n > 1) {
         // pass A writes its packed colours here as well (the kernels honour `plane` next to `out16`; whole-frame contexts: local rows are the frame's)
         if (int rc = reserve(ctx, ctx->aa_plane, (size_t)tiles * RPT_TILE_ROWS * ctx->width * 4)) return rc;
-        if (int rc = reserve(ctx, ctx->aa_counter, 8)) return rc;
-        if (!ctx->aa_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->aa_host, 8, hipHostMallocDefault));
-        if (!ctx->aa_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->aa_counted, hipEventDisableTiming));
+        if (int rc = tally_ready(ctx, ctx->tally[TALLY_AA], 1)) return rc;
     }
     if (c.nothing) return RPT_OK;
     const bool panorama = ctx->projection == RPT_PROJECTION_EQUIRECT;
@@ -1667,38 +1720,28 @@ int launch(rpt_ctx *ctx, Call call) {
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = c.variant;
     ctx->last_exact_rcp = c.ran_exact(c.launched());
-    if (c.refine) {               // pass B, behind pass A on the same stream; then the counter's way home, in stream order
+    Tally &refined = ctx->tally[TALLY_AA];
+    if (c.refine) {               // pass B, behind pass A on the same stream; then the counter's way home (last_event: the frame's end, render_frame)
         rptd::RefineArgs ra;
         std::memset(&ra, 0, sizeof ra);
         static_cast<rptd::LensArgs &>(ra) = static_cast<const rptd::LensArgs &>(a);
         ra.plane = nullptr;           // (pass B writes the framebuffer and debug_rgb only: the plane is what its neighbours still read)
         ra.aa_plane = (const uint32_t *)ctx->aa_plane.ptr;
-        ra.aa_refined = (unsigned long long *)ctx->aa_counter.ptr;
+        ra.aa_refined = (unsigned long long *)refined.device.ptr;
         ra.aa_cols = panorama ? (const float2 *)ctx->aa_pano.upload.device.ptr : nullptr;
         ra.aa_rows = panorama ? ra.aa_cols + (size_t)ctx->aa_n * ctx->width : nullptr;
         ra.aa_n = ctx->aa_n;
         ra.aa_threshold = ctx->aa_threshold;
-        RPT_HIP(ctx, hipMemsetAsync(ctx->aa_counter.ptr, 0, 8, ctx->stream));
+        if (int rc = tally_zero(ctx, refined)) return rc;
         void *args[] = {(void *)&ra};
         (void)hipLaunchKernel(c.kernel(c.refine), grid1, dim3(64), args, 0, ctx->stream);
         RPT_HIP(ctx, hipGetLastError());
-        RPT_HIP(ctx, hipMemcpyAsync(ctx->aa_host, ctx->aa_counter.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
-        RPT_HIP(ctx, hipEventRecord(ctx->aa_counted, ctx->stream));
-        ctx->aa_pending = true;
+        if (int rc = tally_home(ctx, refined)) return rc;
         ctx->last_aa_variant = c.refine->variant;
     } else if (call.colour_frame) {    // a frame with the setting off refines nothing
-        ctx->aa_pending = false;
-        ctx->aa_refined = 0;
+        tally_off(refined);
     }
     return RPT_OK;
-}
-
-// rpt_last_aa_refined's value: the pinned word, once the copy behind the last adaptive frame has run
-void collect_aa_refined(rpt_ctx *ctx) {
-    if (ctx->aa_pending && ctx->aa_counted && hipEventQuery(ctx->aa_counted) == hipSuccess) {
-        ctx->aa_refined = *ctx->aa_host;
-        ctx->aa_pending = false;
-    }
 }
 
 // One event pass on the context's stream: the record of every pixel of this context's rows, written at y * width + x of the full-frame
@@ -1723,9 +1766,9 @@ int launch_events(rpt_ctx *ctx) {
     ea.plane = nullptr;
     ea.debug_rgb = nullptr;
     ea.events = (rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
-    ctx->events_ptr = ea.events;
-    ctx->events_width = ctx->width;
-    ctx->events_height = ctx->height;
+    ctx->event_frame.buffer = ea.events;
+    ctx->event_frame.width = ctx->width;
+    ctx->event_frame.height = ctx->height;
     ctx->events_first_tile = ctx->first_tile;
     ctx->events_tile_step = ctx->tile_step;
     ctx->events_run_log2 = ctx->run_log2;
@@ -1751,44 +1794,55 @@ int frames_of_this_view(rpt_ctx *ctx, const char *call, rpt_pixel **out16_out, c
     if (!ctx->params_set) return fail(ctx, RPT_ERR_STATE, name + " before rpt_set_params");
     if (ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->colour_plane)
         return fail(ctx, RPT_ERR_ARG, name + ": the pass reads a pixel's upper neighbour, which on a context restricted by rpt_set_rows / rpt_set_tile_pattern (or rendering a colour plane) belongs to another rank");
-    if (ctx->colour_generation == 0 || !ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, name + ": no colour frame rendered yet");
-    if (ctx->events_generation == 0 || !ctx->events_rendered) return fail(ctx, RPT_ERR_STATE, name + ": no event frame rendered yet (rpt_render_events)");
-    if (ctx->colour_width != ctx->width || ctx->colour_height != ctx->height || ctx->events_width != ctx->width || ctx->events_height != ctx->height)
+    const FrameMark &colour = ctx->colour_frame, &event = ctx->event_frame;
+    const auto of_this_size = [ctx](const FrameMark &f) { return f.width == ctx->width && f.height == ctx->height; };
+    if (!colour.rendered()) return fail(ctx, RPT_ERR_STATE, name + ": no colour frame rendered yet");
+    if (!event.rendered()) return fail(ctx, RPT_ERR_STATE, name + ": no event frame rendered yet (rpt_render_events)");
+    if (!of_this_size(colour) || !of_this_size(event))
         return fail(ctx, RPT_ERR_STATE, name + ": the last colour frame and event frame are not both of the current width x height");
-    if (ctx->colour_generation != ctx->view_generation || ctx->events_generation != ctx->view_generation)
+    if (colour.generation != ctx->view_generation || event.generation != ctx->view_generation)
         return fail(ctx, RPT_ERR_STATE, name + ": the view has changed (objects, time windows, params, projection, orientation or lens) since the last colour frame or event frame; render both again");
     rpt_pixel *out16 = (rpt_pixel *)(ctx->external_out ? ctx->external_out : ctx->owned_out.ptr);
     const rpt_event *events = (const rpt_event *)(ctx->external_events ? ctx->external_events : ctx->owned_events.ptr);
     // the buffers the two frames were rendered into are the ones the pass reads and writes: a buffer set since then holds no frame (and
     // a library-owned one may be smaller than this frame)
-    if (!out16 || !events || (void *)out16 != ctx->colour_out || (const void *)events != ctx->events_ptr)
+    if (!out16 || !events || (void *)out16 != colour.buffer || (const void *)events != event.buffer)
         return fail(ctx, RPT_ERR_STATE, name + ": rpt_set_output or rpt_set_events_output has named another buffer since the colour frame and the event frame were rendered");
     *out16_out = out16;
     *events_out = events;
     return RPT_OK;
 }
 
-// One overlay pass on the context's stream (kernel 1100, behind 1101 where the tint's range is the frame's own): the refusals, the
-// counter, the launch, then the counter's way home in stream order, as pass B of an adaptive frame.
-int launch_overlay(rpt_ctx *ctx) {
-    const rpt_overlay_desc &d = ctx->overlay;
-    if (d.layers == 0) {          // off: nothing is checked, launched or changed
-        ctx->overlay_pending = false;
-        ctx->overlay_pixels = 0;
+// The shape of a pass over a rendered frame (the overlay, the readouts, the stars), `call` naming it in the messages and `which` its
+// tally.  Off: nothing is checked, launched or changed, and it reports zero.  On: frames_of_this_view, then `enqueue`, the pass's own
+// part (its refusals, tally_ready, its arguments, tally_zero, its launches), then the tally's way home, whose event is last_event.
+using PassEnqueue = int (*)(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events);
+int frame_pass(rpt_ctx *ctx, const char *call, bool on, int which, PassEnqueue enqueue) {
+    Tally &tally = ctx->tally[which];
+    if (!on) {
+        tally_off(tally);
         return RPT_OK;
     }
     rpt_pixel *out16 = nullptr;
     const rpt_event *events = nullptr;
-    if (int rc = frames_of_this_view(ctx, "rpt_render_overlay", &out16, &events)) return rc;
-    if (int rc = reserve(ctx, ctx->overlay_scratch, 16)) return rc;
-    if (!ctx->overlay_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->overlay_host, 8, hipHostMallocDefault));
-    if (!ctx->overlay_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->overlay_counted, hipEventDisableTiming));
+    if (int rc = frames_of_this_view(ctx, call, &out16, &events)) return rc;
+    if (int rc = enqueue(ctx, tally, out16, events)) return rc;
+    if (int rc = tally_home(ctx, tally)) return rc;
+    ctx->last_event = tally.copied;
+    return RPT_OK;
+}
+
+// One overlay pass on the context's stream (kernel 1100, behind 1101 where the tint's range is the frame's own).  The tally's 8 spare
+// bytes: the bit pattern of the frame's largest delay.
+int enqueue_overlay(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    const rpt_overlay_desc &d = ctx->overlay;
+    if (int rc = tally_ready(ctx, tally, 1, 8)) return rc;
 
     rptd::OverlayArgs a;
     std::memset(&a, 0, sizeof a);
     a.events = events;
     a.out16 = out16;
-    a.changed = (unsigned long long *)ctx->overlay_scratch.ptr;
+    a.changed = (unsigned long long *)tally.device.ptr;
     a.width = ctx->width;
     a.height = ctx->height;
     a.layers = d.layers;
@@ -1809,9 +1863,9 @@ int launch_overlay(rpt_ctx *ctx) {
     a.tint_alpha = d.tint_alpha;
 
     const size_t pixels = (size_t)ctx->width * ctx->height;
-    RPT_HIP(ctx, hipMemsetAsync(ctx->overlay_scratch.ptr, 0, 16, ctx->stream));
+    if (int rc = tally_zero(ctx, tally)) return rc;
     if ((d.layers & RPT_OVERLAY_DELAY_TINT) && d.tint_t_max == 0.0f) {
-        uint32_t *tmax = (uint32_t *)ctx->overlay_scratch.ptr + 2;
+        uint32_t *tmax = (uint32_t *)tally.device.ptr + 2;
         a.tmax_bits = tmax;
         const size_t blocks = (pixels + 255) / 256;
         const float interval = a.interval;
@@ -1823,71 +1877,39 @@ int launch_overlay(rpt_ctx *ctx) {
     void *args[] = {(void *)&a};
     (void)hipLaunchKernel((const void *)rptd::rpt_overlay_kernel, grid, dim3(RPT_OVERLAY_TILE_W * RPT_OVERLAY_TILE_H), args, 0, ctx->stream);
     RPT_HIP(ctx, hipGetLastError());
-    RPT_HIP(ctx, hipMemcpyAsync(ctx->overlay_host, ctx->overlay_scratch.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RPT_HIP(ctx, hipEventRecord(ctx->overlay_counted, ctx->stream));
-    ctx->last_event = ctx->overlay_counted;
-    ctx->overlay_pending = true;
     return RPT_OK;
 }
 
-// rpt_last_overlay_pixels' value: the pinned word, once the copy behind the last overlay pass has run
-void collect_overlay_pixels(rpt_ctx *ctx) {
-    if (ctx->overlay_pending && ctx->overlay_counted && hipEventQuery(ctx->overlay_counted) == hipSuccess) {
-        ctx->overlay_pixels = *ctx->overlay_host;
-        ctx->overlay_pending = false;
-    }
-}
+int launch_overlay(rpt_ctx *ctx) { return frame_pass(ctx, "rpt_render_overlay", ctx->overlay.layers != 0, TALLY_OVERLAY, enqueue_overlay); }
 
-// One readout pass on the context's stream (kernel 1110): the overlay pass's refusals, counter and way home
-int launch_readouts(rpt_ctx *ctx) {
-    if (ctx->readouts.empty()) {      // nothing set: nothing is checked, launched or changed
-        ctx->readout_pending = false;
-        ctx->readout_pixels = 0;
-        return RPT_OK;
-    }
-    rpt_pixel *out16 = nullptr;
-    const rpt_event *events = nullptr;
-    if (int rc = frames_of_this_view(ctx, "rpt_render_readouts", &out16, &events)) return rc;
+// One readout pass on the context's stream (kernel 1110)
+int enqueue_readouts(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
     if (ctx->readouts.size() != (size_t)ctx->object_count)
         return fail(ctx, RPT_ERR_ARG, "rpt_render_readouts: " + std::to_string(ctx->readouts.size()) + " readouts are set, the Object[] holds " + std::to_string(ctx->object_count));
-    if (int rc = reserve(ctx, ctx->readout_scratch, 8)) return rc;
-    if (!ctx->readout_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->readout_host, 8, hipHostMallocDefault));
-    if (!ctx->readout_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->readout_counted, hipEventDisableTiming));
+    if (int rc = tally_ready(ctx, tally, 1)) return rc;
 
     rptd::ReadoutArgs a;
     std::memset(&a, 0, sizeof a);
     a.events = events;
     a.out16 = out16;
-    a.changed = (unsigned long long *)ctx->readout_scratch.ptr;
+    a.changed = (unsigned long long *)tally.device.ptr;
     a.displays = (const rptd::ReadoutDisplay *)ctx->readout_table.device.ptr;
     a.low_mask = ctx->readout_low_mask;
     a.width = ctx->width;
     a.height = ctx->height;
     a.count = ctx->object_count;
-    RPT_HIP(ctx, hipMemsetAsync(ctx->readout_scratch.ptr, 0, 8, ctx->stream));
+    if (int rc = tally_zero(ctx, tally)) return rc;
     const dim3 grid((ctx->width + RPT_OVERLAY_TILE_W - 1) / RPT_OVERLAY_TILE_W, (ctx->height + RPT_OVERLAY_TILE_H - 1) / RPT_OVERLAY_TILE_H);
     void *args[] = {(void *)&a};
     (void)hipLaunchKernel((const void *)rptd::rpt_readout_kernel, grid, dim3(RPT_OVERLAY_TILE_W * RPT_OVERLAY_TILE_H), args, 0, ctx->stream);
     RPT_HIP(ctx, hipGetLastError());
-    RPT_HIP(ctx, hipMemcpyAsync(ctx->readout_host, ctx->readout_scratch.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RPT_HIP(ctx, hipEventRecord(ctx->readout_counted, ctx->stream));
-    ctx->last_event = ctx->readout_counted;
-    ctx->readout_pending = true;
     return RPT_OK;
 }
 
-// One star-field pass on the context's stream (kernels 1120 and 1121): the overlay pass's refusals and two of its own, G, the
-// accumulator, the two launches, then the counters' way home as the overlay's.
-int launch_stars(rpt_ctx *ctx) {
-    if (ctx->star_count == 0) {       // no catalogue: nothing is checked, launched or changed
-        ctx->star_pending = false;
-        ctx->star_counts[0] = ctx->star_counts[1] = 0;
-        ctx->star_marked = false;
-        return RPT_OK;
-    }
-    rpt_pixel *out16 = nullptr;
-    const rpt_event *events = nullptr;
-    if (int rc = frames_of_this_view(ctx, "rpt_render_stars", &out16, &events)) return rc;
+int launch_readouts(rpt_ctx *ctx) { return frame_pass(ctx, "rpt_render_readouts", !ctx->readouts.empty(), TALLY_READOUTS, enqueue_readouts); }
+
+// One star-field pass on the context's stream (kernels 1120 and 1121): two refusals of its own, G, the accumulator, the two launches
+int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
     if (ctx->projection == RPT_PROJECTION_RAYMAP)
         return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a star with");
     rptd::StarArgs a;
@@ -1907,16 +1929,14 @@ int launch_stars(rpt_ctx *ctx) {
         if (int rc = reserve(ctx, ctx->star_acc, acc_bytes)) return rc;
         RPT_HIP(ctx, hipMemsetAsync(ctx->star_acc.ptr, 0, ctx->star_acc.capacity, ctx->stream));
     }
-    if (int rc = reserve(ctx, ctx->star_scratch, 16)) return rc;
-    if (!ctx->star_host) RPT_HIP(ctx, hipHostMalloc((void **)&ctx->star_host, 16, hipHostMallocDefault));
-    if (!ctx->star_counted) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->star_counted, hipEventDisableTiming));
+    if (int rc = tally_ready(ctx, tally, 2)) return rc;
     if (ctx->star_timed)
         for (hipEvent_t &m : ctx->star_marks)
             if (!m) RPT_HIP(ctx, hipEventCreate(&m));
 
     a.stars = (const rpt_star *)ctx->star_table.device.ptr;
     a.acc = (unsigned long long *)ctx->star_acc.ptr;
-    a.counts = (unsigned long long *)ctx->star_scratch.ptr;
+    a.counts = (unsigned long long *)tally.device.ptr;
     a.count = ctx->star_count;
     a.width = ctx->width;
     a.height = ctx->height;
@@ -1942,7 +1962,7 @@ int launch_stars(rpt_ctx *ctx) {
     b.pixels = pixels;
     for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
 
-    RPT_HIP(ctx, hipMemsetAsync(ctx->star_scratch.ptr, 0, 16, ctx->stream));
+    if (int rc = tally_zero(ctx, tally)) return rc;
     if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[0], ctx->stream));
     void *splat_args[] = {(void *)&a};
     (void)hipLaunchKernel((const void *)rptd::rpt_stars_splat_kernel, dim3((unsigned)((ctx->star_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
@@ -1953,26 +1973,35 @@ int launch_stars(rpt_ctx *ctx) {
     RPT_HIP(ctx, hipGetLastError());
     if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[2], ctx->stream));
     ctx->star_marked = ctx->star_timed;
-    RPT_HIP(ctx, hipMemcpyAsync(ctx->star_host, ctx->star_scratch.ptr, 16, hipMemcpyDeviceToHost, ctx->stream));
-    RPT_HIP(ctx, hipEventRecord(ctx->star_counted, ctx->stream));
-    ctx->last_event = ctx->star_counted;
-    ctx->star_pending = true;
     return RPT_OK;
 }
 
-void collect_star_counts(rpt_ctx *ctx) {
-    if (ctx->star_pending && ctx->star_counted && hipEventQuery(ctx->star_counted) == hipSuccess) {
-        ctx->star_counts[0] = ctx->star_host[0];
-        ctx->star_counts[1] = ctx->star_host[1];
-        ctx->star_pending = false;
-    }
+int launch_stars(rpt_ctx *ctx) {
+    if (ctx->star_count == 0) ctx->star_marked = false;      // (no catalogue: no pass, so no marks of one)
+    return frame_pass(ctx, "rpt_render_stars", ctx->star_count != 0, TALLY_STARS, enqueue_stars);
 }
 
-void collect_readout_pixels(rpt_ctx *ctx) {
-    if (ctx->readout_pending && ctx->readout_counted && hipEventQuery(ctx->readout_counted) == hipSuccess) {
-        ctx->readout_pixels = *ctx->readout_host;
-        ctx->readout_pending = false;
-    }
+// The event pass and what it leaves for rpt_pick, rpt_read_events and the passes over the frame
+int launch_event_frame(rpt_ctx *ctx) {
+    if (!ctx->ev_events) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
+    if (int rc = launch_events(ctx)) return rc;
+    RPT_HIP(ctx, hipEventRecord(ctx->ev_events, ctx->stream));
+    ctx->last_event = ctx->ev_events;
+    ctx->event_frame.generation = ctx->view_generation;
+    return RPT_OK;
+}
+
+// rpt_render_events, _overlay, _readouts, _stars and their _async forms: one pass on the context's stream, waited for or not
+int render_pass(rpt_ctx *ctx, int (*launch_pass)(rpt_ctx *), bool wait) {
+    if (!ctx) return RPT_ERR_ARG;
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = launch_pass(ctx)) return rc;
+    return wait ? rpt_sync(ctx) : RPT_OK;
+}
+
+// a colour frame has been enqueued for the present view and size, into the present framebuffer
+void mark_colour_frame(rpt_ctx *ctx) {
+    ctx->colour_frame = FrameMark{ctx->view_generation, ctx->width, ctx->height, ctx->colour_plane ? nullptr : rpt_output_ptr(ctx)};
 }
 
 }  // namespace
@@ -2039,18 +2068,11 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->aa_counter, &ctx->overlay_scratch, &ctx->readout_scratch, &ctx->star_acc, &ctx->star_scratch})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->star_acc})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table}) release(*u);
-    if (ctx->aa_host) (void)hipHostFree(ctx->aa_host);
-    if (ctx->aa_counted) (void)hipEventDestroy(ctx->aa_counted);
-    if (ctx->overlay_host) (void)hipHostFree(ctx->overlay_host);
-    if (ctx->overlay_counted) (void)hipEventDestroy(ctx->overlay_counted);
-    if (ctx->readout_host) (void)hipHostFree(ctx->readout_host);
-    if (ctx->readout_counted) (void)hipEventDestroy(ctx->readout_counted);
-    if (ctx->star_host) (void)hipHostFree(ctx->star_host);
-    if (ctx->star_counted) (void)hipEventDestroy(ctx->star_counted);
+    for (Tally &t : ctx->tally) release(t);
     for (hipEvent_t m : ctx->star_marks) if (m) (void)hipEventDestroy(m);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
@@ -2516,7 +2538,7 @@ int rpt_read_debug_doppler(rpt_ctx *ctx, void *host_dst, size_t bytes) {
     if (!ctx || !host_dst) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     const void *src = ctx->external_doppler ? ctx->external_doppler : (ctx->want_owned_doppler ? ctx->owned_doppler.ptr : nullptr);
-    if (!src || !ctx->frame_rendered || !ctx->doppler_recorded)
+    if (!src || !ctx->colour_frame.rendered() || !ctx->doppler_recorded)
         return fail(ctx, RPT_ERR_STATE, "rpt_read_debug_doppler: the last frame was not rendered with Doppler on and the record hook set");
     if (bytes > (size_t)ctx->width * ctx->height * RPT_DOPPLER_RECORD * sizeof(float)) return fail(ctx, RPT_ERR_ARG, "rpt_read_debug_doppler: too many bytes");
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2770,11 +2792,7 @@ static int render_frame(rpt_ctx *ctx, CallKind kind) {
     ctx->last_event = ee;
     if (timed) ctx->timing_frames++;
     else if (ctx->timing_frames >= 0) return fail(ctx, RPT_ERR_STATE, "timing region is full");
-    ctx->frame_rendered = true;
-    ctx->colour_generation = ctx->view_generation;      // (what rpt_render_overlay asks for)
-    ctx->colour_width = ctx->width;
-    ctx->colour_height = ctx->height;
-    ctx->colour_out = ctx->colour_plane ? nullptr : rpt_output_ptr(ctx);
+    mark_colour_frame(ctx);
     return RPT_OK;
 }
 
@@ -2850,10 +2868,7 @@ int rpt_sync(rpt_ctx *ctx) {
     if (!ctx) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    collect_aa_refined(ctx);
-    collect_overlay_pixels(ctx);
-    collect_readout_pixels(ctx);
-    collect_star_counts(ctx);
+    for (Tally &t : ctx->tally) tally_collect(t);
     return RPT_OK;
 }
 
@@ -2866,15 +2881,7 @@ int rpt_set_adaptive_aa(rpt_ctx *ctx, int samples_per_axis, int threshold) {
     return RPT_OK;
 }
 
-int rpt_last_aa_refined(rpt_ctx *ctx, unsigned long long *pixels) {
-    if (!ctx || !pixels) return RPT_ERR_ARG;
-    if (ctx->aa_pending) {
-        RPT_HIP(ctx, hipSetDevice(ctx->device));
-        collect_aa_refined(ctx);
-    }
-    *pixels = ctx->aa_refined;
-    return RPT_OK;
-}
+int rpt_last_aa_refined(rpt_ctx *ctx, unsigned long long *pixels) { return tally_read(ctx, TALLY_AA, pixels, 1); }
 
 int rpt_last_aa_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_aa_variant : RPT_ERR_ARG; }
 
@@ -2889,44 +2896,29 @@ int rpt_set_events_output(rpt_ctx *ctx, void *device_ptr_or_null) {
     return RPT_OK;
 }
 
-int rpt_render_events_async(rpt_ctx *ctx) {
-    if (!ctx) return RPT_ERR_ARG;
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_events) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
-    if (int rc = launch_events(ctx)) return rc;
-    RPT_HIP(ctx, hipEventRecord(ctx->ev_events, ctx->stream));
-    ctx->last_event = ctx->ev_events;
-    ctx->events_rendered = true;
-    ctx->events_generation = ctx->view_generation;      // (what rpt_render_overlay asks for)
-    return RPT_OK;
-}
-
-int rpt_render_events(rpt_ctx *ctx) {
-    if (!ctx) return RPT_ERR_ARG;
-    if (int rc = rpt_render_events_async(ctx)) return rc;
-    return rpt_sync(ctx);
-}
+int rpt_render_events_async(rpt_ctx *ctx) { return render_pass(ctx, launch_event_frame, false); }
+int rpt_render_events(rpt_ctx *ctx) { return render_pass(ctx, launch_event_frame, true); }
 
 int rpt_read_events(rpt_ctx *ctx, void *host_dst, size_t bytes) {
     if (!ctx || !host_dst) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->events_rendered || !ctx->events_ptr) return fail(ctx, RPT_ERR_STATE, "rpt_read_events: no event frame rendered yet");
-    if (bytes > (size_t)ctx->events_width * ctx->events_height * sizeof(rpt_event)) return fail(ctx, RPT_ERR_ARG, "rpt_read_events: more bytes requested than the event frame holds");
+    if (!ctx->event_frame.rendered() || !ctx->event_frame.buffer) return fail(ctx, RPT_ERR_STATE, "rpt_read_events: no event frame rendered yet");
+    if (bytes > (size_t)ctx->event_frame.width * ctx->event_frame.height * sizeof(rpt_event)) return fail(ctx, RPT_ERR_ARG, "rpt_read_events: more bytes requested than the event frame holds");
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RPT_HIP(ctx, hipMemcpy(host_dst, ctx->events_ptr, bytes, hipMemcpyDeviceToHost));
+    RPT_HIP(ctx, hipMemcpy(host_dst, ctx->event_frame.buffer, bytes, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
 int rpt_pick(rpt_ctx *ctx, int x, int y, rpt_event *out) {
     if (!ctx || !out) return RPT_ERR_ARG;
-    if (!ctx->events_rendered || !ctx->events_ptr) return fail(ctx, RPT_ERR_STATE, "rpt_pick: no event frame rendered yet");
-    if (x < 0 || y < 0 || x >= ctx->events_width || y >= ctx->events_height) return fail(ctx, RPT_ERR_ARG, "rpt_pick: the pixel lies outside the last event frame");
+    if (!ctx->event_frame.rendered() || !ctx->event_frame.buffer) return fail(ctx, RPT_ERR_STATE, "rpt_pick: no event frame rendered yet");
+    if (x < 0 || y < 0 || x >= ctx->event_frame.width || y >= ctx->event_frame.height) return fail(ctx, RPT_ERR_ARG, "rpt_pick: the pixel lies outside the last event frame");
     // the rows of the last event frame that were this context's: tile t is one iff (t - first_tile) mod tile_step < run
     const int tile = y / RPT_TILE_ROWS, rel = tile - ctx->events_first_tile;
     if (rel < 0 || rel % ctx->events_tile_step >= (1 << ctx->events_run_log2)) return fail(ctx, RPT_ERR_ARG, "rpt_pick: the row is not one of this context's (rpt_set_rows)");
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RPT_HIP(ctx, hipMemcpy(out, (const rpt_event *)ctx->events_ptr + ((size_t)y * ctx->events_width + x), sizeof(rpt_event), hipMemcpyDeviceToHost));
+    RPT_HIP(ctx, hipMemcpy(out, (const rpt_event *)ctx->event_frame.buffer + ((size_t)y * ctx->event_frame.width + x), sizeof(rpt_event), hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -2964,26 +2956,10 @@ int rpt_set_overlay(rpt_ctx *ctx, const rpt_overlay_desc *desc_or_null) {
     return RPT_OK;
 }
 
-int rpt_render_overlay_async(rpt_ctx *ctx) {
-    if (!ctx) return RPT_ERR_ARG;
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_overlay(ctx);
-}
+int rpt_render_overlay_async(rpt_ctx *ctx) { return render_pass(ctx, launch_overlay, false); }
+int rpt_render_overlay(rpt_ctx *ctx) { return render_pass(ctx, launch_overlay, true); }
 
-int rpt_render_overlay(rpt_ctx *ctx) {
-    if (int rc = rpt_render_overlay_async(ctx)) return rc;
-    return rpt_sync(ctx);
-}
-
-int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels) {
-    if (!ctx || !pixels) return RPT_ERR_ARG;
-    if (ctx->overlay_pending) {
-        RPT_HIP(ctx, hipSetDevice(ctx->device));
-        collect_overlay_pixels(ctx);
-    }
-    *pixels = ctx->overlay_pixels;
-    return RPT_OK;
-}
+int rpt_last_overlay_pixels(rpt_ctx *ctx, unsigned long long *pixels) { return tally_read(ctx, TALLY_OVERLAY, pixels, 1); }
 
 // The displays go to the device here, once, in stream order (a pass in flight keeps the table it was launched with); a call refused
 // for its arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no setting.
@@ -3038,26 +3014,10 @@ int rpt_set_readouts(rpt_ctx *ctx, const rpt_readout *per_object_or_null, int co
     return RPT_OK;
 }
 
-int rpt_render_readouts_async(rpt_ctx *ctx) {
-    if (!ctx) return RPT_ERR_ARG;
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_readouts(ctx);
-}
+int rpt_render_readouts_async(rpt_ctx *ctx) { return render_pass(ctx, launch_readouts, false); }
+int rpt_render_readouts(rpt_ctx *ctx) { return render_pass(ctx, launch_readouts, true); }
 
-int rpt_render_readouts(rpt_ctx *ctx) {
-    if (int rc = rpt_render_readouts_async(ctx)) return rc;
-    return rpt_sync(ctx);
-}
-
-int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels) {
-    if (!ctx || !pixels) return RPT_ERR_ARG;
-    if (ctx->readout_pending) {
-        RPT_HIP(ctx, hipSetDevice(ctx->device));
-        collect_readout_pixels(ctx);
-    }
-    *pixels = ctx->readout_pixels;
-    return RPT_OK;
-}
+int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels) { return tally_read(ctx, TALLY_READOUTS, pixels, 1); }
 
 // The catalogue goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused
 // for its arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no catalogue.
@@ -3085,27 +3045,10 @@ int rpt_set_stars(rpt_ctx *ctx, const rpt_star *stars_or_null, int count) {
     return RPT_OK;
 }
 
-int rpt_render_stars_async(rpt_ctx *ctx) {
-    if (!ctx) return RPT_ERR_ARG;
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_stars(ctx);
-}
+int rpt_render_stars_async(rpt_ctx *ctx) { return render_pass(ctx, launch_stars, false); }
+int rpt_render_stars(rpt_ctx *ctx) { return render_pass(ctx, launch_stars, true); }
 
-int rpt_render_stars(rpt_ctx *ctx) {
-    if (int rc = rpt_render_stars_async(ctx)) return rc;
-    return rpt_sync(ctx);
-}
-
-int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]) {
-    if (!ctx || !out) return RPT_ERR_ARG;
-    if (ctx->star_pending) {
-        RPT_HIP(ctx, hipSetDevice(ctx->device));
-        collect_star_counts(ctx);
-    }
-    out[0] = ctx->star_counts[0];
-    out[1] = ctx->star_counts[1];
-    return RPT_OK;
-}
+int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_STARS, out, 2); }
 
 int rpt_set_stars_measurement(rpt_ctx *ctx, int timed) {
     if (!ctx) return RPT_ERR_ARG;
@@ -3137,7 +3080,7 @@ int rpt_read_framebuffer(rpt_ctx *ctx, void *host_dst, size_t bytes) {
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     const void *src = ctx->colour_plane ? rpt_colour_plane_ptr(ctx) : rpt_output_ptr(ctx);
     const size_t have = ctx->colour_plane ? (size_t)local_tile_count(ctx) * RPT_TILE_ROWS * ctx->width * 4 : rpt_output_bytes(ctx);
-    if (!src || !ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_read_framebuffer: nothing rendered yet");
+    if (!src || !ctx->colour_frame.rendered()) return fail(ctx, RPT_ERR_STATE, "rpt_read_framebuffer: nothing rendered yet");
     if (bytes > have) return fail(ctx, RPT_ERR_ARG, "rpt_read_framebuffer: more bytes requested than the framebuffer holds");
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     RPT_HIP(ctx, hipMemcpy(host_dst, src, bytes, hipMemcpyDeviceToHost));
@@ -3148,7 +3091,7 @@ int rpt_read_debug_rgb(rpt_ctx *ctx, void *host_dst, size_t bytes) {
     if (!ctx || !host_dst) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     const void *src = ctx->external_rgb ? ctx->external_rgb : (ctx->want_owned_rgb ? ctx->owned_rgb.ptr : nullptr);
-    if (!src || !ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_read_debug_rgb: debug RGB is not enabled or nothing rendered");
+    if (!src || !ctx->colour_frame.rendered()) return fail(ctx, RPT_ERR_STATE, "rpt_read_debug_rgb: debug RGB is not enabled or nothing rendered");
     if (bytes > (size_t)ctx->width * ctx->height * 12) return fail(ctx, RPT_ERR_ARG, "rpt_read_debug_rgb: too many bytes");
     RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     RPT_HIP(ctx, hipMemcpy(host_dst, src, bytes, hipMemcpyDeviceToHost));
@@ -3157,7 +3100,7 @@ int rpt_read_debug_rgb(rpt_ctx *ctx, void *host_dst, size_t bytes) {
 
 int rpt_last_frame_ms(rpt_ctx *ctx, float *ms) {
     if (!ctx || !ms) return RPT_ERR_ARG;
-    if (!ctx->frame_rendered) return fail(ctx, RPT_ERR_STATE, "rpt_last_frame_ms: nothing rendered yet");
+    if (!ctx->colour_frame.rendered()) return fail(ctx, RPT_ERR_STATE, "rpt_last_frame_ms: nothing rendered yet");
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     RPT_HIP(ctx, hipEventSynchronize(ctx->ev_end));
     RPT_HIP(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev_begin, ctx->ev_end));
@@ -3179,11 +3122,7 @@ int rpt_timed_frames(rpt_ctx *ctx, int frames, float *avg_ms) {
     RPT_HIP(ctx, hipEventSynchronize(ctx->ev_end));
     float ms = 0;
     RPT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    ctx->frame_rendered = true;
-    ctx->colour_generation = ctx->view_generation;
-    ctx->colour_width = ctx->width;
-    ctx->colour_height = ctx->height;
-    ctx->colour_out = ctx->colour_plane ? nullptr : rpt_output_ptr(ctx);
+    mark_colour_frame(ctx);
     ctx->last_ms = ms / frames;
     *avg_ms = ctx->last_ms;
     return RPT_OK;

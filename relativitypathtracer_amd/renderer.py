@@ -269,9 +269,7 @@ class Renderer:
 
     def last_aa_refined(self) -> int:
         """Pixels the refine pass of the last finished adaptive frame re-rendered (0 with the setting off)."""
-        n = C.c_uint64(0)
-        self._check(self._lib.rpt_last_aa_refined(self._h, C.byref(n)), "rpt_last_aa_refined")
-        return int(n.value)
+        return self._last_counts("rpt_last_aa_refined")[0]
 
     def last_aa_variant(self) -> int:
         """The refine kernel (include/rpt.h, rpt_set_adaptive_aa) of the last colour frame; 0 if it had no refine pass."""
@@ -382,6 +380,17 @@ class Renderer:
     def sync(self):
         self._check(self._lib.rpt_sync(self._h), "rpt_sync")
 
+    def _run_pass(self, call: str, async_: bool):
+        """One pass over the rendered frame: `call` of include/rpt.h, or with async_ its _async form, which enqueues only."""
+        name = call + "_async" if async_ else call
+        self._check(getattr(self._lib, name)(self._h), name)
+
+    def _last_counts(self, call: str, n: int = 1) -> Tuple[int, ...]:
+        """The n 64-bit counts a rpt_last_* call reports of its pass."""
+        counts = (C.c_uint64 * n)()
+        self._check(getattr(self._lib, call)(self._h, counts), call)
+        return tuple(int(c) for c in counts)
+
     # -- the event pass (include/rpt.h, rpt_render_events; not in the reference) ------------------
     def set_events_output(self, device_ptr: Optional[int]):
         """The record buffer of the event pass: a device pointer to width * height * 32 B, or None for a library-owned one."""
@@ -445,16 +454,11 @@ class Renderer:
         """Blend the layers of set_overlay into the framebuffer, in place, from the records of the last event frame.  The context must
         have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice blends twice.
         async_=True enqueues only (sync waits)."""
-        if async_:
-            self._check(self._lib.rpt_render_overlay_async(self._h), "rpt_render_overlay_async")
-        else:
-            self._check(self._lib.rpt_render_overlay(self._h), "rpt_render_overlay")
+        self._run_pass("rpt_render_overlay", async_)
 
     def last_overlay_pixels(self) -> int:
         """Pixels whose RGBA the last finished overlay pass changed (0 before the first)."""
-        n = C.c_uint64(0)
-        self._check(self._lib.rpt_last_overlay_pixels(self._h, C.byref(n)), "rpt_last_overlay_pixels")
-        return int(n.value)
+        return self._last_counts("rpt_last_overlay_pixels")[0]
 
     # -- the readout pass (include/rpt.h, rpt_set_readouts; not in the reference) ------------------
     def set_readouts(self, readouts):
@@ -483,16 +487,11 @@ class Renderer:
         """Draw the displays of set_readouts into the framebuffer, in place, from the records of the last event frame.  The context must
         have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice blends twice.
         Independent of render_overlay: either may run first.  async_=True enqueues only (sync waits)."""
-        if async_:
-            self._check(self._lib.rpt_render_readouts_async(self._h), "rpt_render_readouts_async")
-        else:
-            self._check(self._lib.rpt_render_readouts(self._h), "rpt_render_readouts")
+        self._run_pass("rpt_render_readouts", async_)
 
     def last_readout_pixels(self) -> int:
         """Pixels whose RGBA the last finished readout pass changed (0 before the first)."""
-        n = C.c_uint64(0)
-        self._check(self._lib.rpt_last_readout_pixels(self._h, C.byref(n)), "rpt_last_readout_pixels")
-        return int(n.value)
+        return self._last_counts("rpt_last_readout_pixels")[0]
 
     # -- the star-field pass (include/rpt.h, rpt_set_stars; not in the reference) -------------------
     def set_stars(self, catalogue):
@@ -512,16 +511,12 @@ class Renderer:
         """Add the stars of set_stars to the miss pixels of the framebuffer, in place.  The context must have rendered (or enqueued) a
         colour frame and an event frame of the current view first; calling it twice adds them twice.  Independent of render_overlay and
         render_readouts.  async_=True enqueues only (sync waits)."""
-        if async_:
-            self._check(self._lib.rpt_render_stars_async(self._h), "rpt_render_stars_async")
-        else:
-            self._check(self._lib.rpt_render_stars(self._h), "rpt_render_stars")
+        self._run_pass("rpt_render_stars", async_)
 
     def last_stars(self) -> Tuple[int, int]:
         """(stars with at least one tap inside the frame, pixels whose bytes changed) of the last finished star-field pass."""
-        n = (C.c_uint64 * 2)(0, 0)
-        self._check(self._lib.rpt_last_stars(self._h, n), "rpt_last_stars")
-        return int(n[0]), int(n[1])
+        inside, changed = self._last_counts("rpt_last_stars", 2)
+        return inside, changed
 
     def set_stars_measurement(self, timed: bool = False):
         """Measurement only (tools/stars_cost.py): time the two kernels of every pass (last_stars_ms)."""
