@@ -380,12 +380,27 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
  * rpt_tile_bitmap_host (host code, no device): the bitmap of mesh object `object_index` of `scene` for a width x height frame under
  * lens_scale (1.0f: the reference's lens) into bits_out[words], bit ty * ceil(width / 8) + tx; boxes_or_null: n_boxes boxes (min.xyz,
  * max.xyz) to use instead of the mesh's own (tests).  1: built, 0: this object gets no bitmap, < 0: -RPT_ERR_*.  stats_out, if not
- * NULL: {boxes, boxes proven, tiles set, tiles, depth of the cut}.
+ * NULL: {boxes, boxes proven, tiles set, tiles, depth of the cut} of the sub-tree stage.  Without the caller's boxes bits_out is the
+ * PRODUCT a context puts on the device: the sub-tree stage ANDed with the triangle stage — one proven region per distinct triangle of
+ * the mesh, for meshes of at most 8 192 triangles — unless RPT_TILE_TRIANGLES=0 is set (a context reads it when it is created; this
+ * call, which has no context, reads it on every call).
+ * rpt_tile_bitmap_stage_host: one stage alone, stage 0 = the sub-tree stage, stage 1 = the triangle stage with at most `max_triangles`
+ * triangles, stage 2 (FOR TESTS ONLY) = their product under that cap (what a context would build if its cap were `max_triangles`; the
+ * sub-tree stage's statistics); the same returns; stats_out, if not NULL: {boxes, boxes proven, tiles set, tiles}.
  * rpt_tile_bitmap_state: out = {bit i = object i has a bitmap on the device for the current frame, bitmaps built so far, host
  * microseconds of the last build, dwords per bitmap}; bits_or_null receives the bitmap of `object_index` (an error if it has none). */
 int rpt_tile_bitmap_host(const rpt_scene_desc *scene, int object_index, int interval, int width, int height, float lens_scale, int max_boxes,
                          const float *boxes_or_null, int n_boxes, uint32_t *bits_out, size_t words, int stats_out[5]);
+int rpt_tile_bitmap_stage_host(const rpt_scene_desc *scene, int object_index, int interval, int width, int height, float lens_scale, int stage,
+                               int max_triangles, uint32_t *bits_out, size_t words, int stats_out[4]);
+/* FOR TESTS ONLY, not part of the supported interface.  The bitmap's rasterisation alone (host code): sets in bits_out[words] the tiles of a width x height frame whose square, grown by
+ * a pixel and a half and scaled by lens_scale, touches the region bounds[8] = {u0, v0, u1, v1, p_lo, p_hi, m_lo, m_hi} (the four
+ * diagonal sides only with `diagonals`).  1: done, 0: an empty region (nothing set), < 0: -RPT_ERR_*. */
+int rpt_tile_rasterise_host(int width, int height, float lens_scale, int diagonals, const float bounds[8], uint32_t *bits_out, size_t words);
 int rpt_tile_bitmap_state(rpt_ctx *ctx, unsigned long long out[4], int object_index, uint32_t *bits_or_null, size_t words);
+/* Tests and diagnostics: contexts that share a scene (rpt_share_scene) share tile bitmap builds through a cache of 64 entries kept with
+ * the scene; out = {bitmaps built for it, requests answered with a copy of an earlier build} since the scene's upload. */
+int rpt_tile_bitmap_shared_state(rpt_ctx *ctx, unsigned long long out[2]);
 /* The derived layouts of a scene as rpt_upload_scene would put them on the device, built on the host alone (no device; tests).
  * which = RPT_LAYOUT_NODES: one 64-B record per octree node in the derived, breadth-first numbering — {min.xyz, link, max.xyz, begin
  *   word, leafCount, nb[6], 0}: link = -1 for a leaf, else first child | leaf mask << 24; begin word = leafBegin | min(leafCount, 255)

@@ -159,6 +159,10 @@ HIP_SYMBOLS = {
     "rpt_certify_screen_bounds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "rpt_tile_bitmap_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_int)]),
+    "rpt_tile_bitmap_stage_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_int)]),
+    "rpt_tile_rasterise_host": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_size_t]),
+    "rpt_tile_bitmap_shared_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_tile_bitmap_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_void_p, C.c_size_t]),
     "rpt_derived_layout_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rpt_probe_tile_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -13,6 +13,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -106,6 +107,26 @@ struct Geometry {
     std::vector<uint8_t> node_holds_its_triangles;   // per node: every triangle of its list lies inside its box (true of a mesh's root
                                                      // unless its list also holds an earlier mesh's triangles, Mesh.cpp:16-19)
     std::map<int, std::vector<float>> mesh_boxes;    // per mesh root (reference node index): the sub-tree boxes of rpt_tile_bitmap.hpp, six floats each
+    std::map<int, std::vector<float>> mesh_tri_boxes;    // ... and its triangle boxes, one per distinct listed triangle (none: over the cap, or the stage is not for this mesh)
+    // Tile bitmaps built against this geometry, for the contexts that share it (rpt_share_scene: four frames in flight ask for the same
+    // bitmap one after the other).  The key is what rpt_tile_bitmap.hpp says a bitmap is a function of, next to the boxes above: the
+    // object's bytes, the interval, the frame's size, the lens scale and the diagonals flag — and which stages the asking context runs.
+    // One mutex; one entry per object slot a context can have a bitmap for (64: contexts ask for their still meshes in the same order, so
+    // fewer entries than still meshes would evict what the next context is about to ask for), the oldest replaced, 16 KB each at 4K; the
+    // build happens UNDER the lock, so a second context asking for the same key waits and then copies.  A new upload is a new Geometry: the
+    // cache goes with its generation.  bitmap_builds / bitmap_copies count the misses and the hits (rpt_tile_bitmap_shared_state).
+    struct BitmapEntry {
+        uint8_t object[sizeof(rpt_object)];
+        int interval, width, height;
+        float lens;
+        bool diagonals, triangles, built;             // built: false = this key gets no bitmap (remembered too)
+        std::vector<uint32_t> bits;
+    };
+    static constexpr size_t BITMAP_CACHE_ENTRIES = 64;
+    std::mutex bitmap_cache_lock;
+    std::vector<BitmapEntry> bitmap_cache;
+    size_t bitmap_cache_next = 0;                     // the slot the next new key replaces once all are taken
+    unsigned long long bitmap_builds = 0, bitmap_copies = 0;
     size_t vertex_count = 0, normal_count = 0, uv_count = 0, triangle_words = 0, octree_count = 0, octree_tri_count = 0;
     ~Geometry() {
         bool any = false;
@@ -240,8 +261,9 @@ struct rpt_ctx {
     int bits_width = 0, bits_height = 0, bits_slots = 0;      // the key: what the bitmaps on the device were built for
     float bits_lens = 0.0f;
     bool bits_diagonals = false;
-    unsigned long long bits_builds = 0;               // bitmaps built so far (rpt_tile_bitmap_state)
-    double bits_last_build_us = 0.0;                  // host time of the last build
+    unsigned long long bits_builds = 0;               // bitmaps that went live in this context so far (rpt_tile_bitmap_state), built here or copied from the scene's cache
+    double bits_last_build_us = 0.0;                  // host time this context spent on the last of them
+    bool tile_triangles = true;                       // RPT_TILE_TRIANGLES=0 at rpt_create: the sub-tree stage alone
 };
 
 namespace {
@@ -599,9 +621,9 @@ int build_derived_geometry(rpt_ctx *ctx, const rpt_scene_desc &s) {
 }
 
 // What the host keeps of a scene's meshes: every node's box, which nodes hold their triangles inside it, how large those triangles
-// are, and the sub-tree boxes of the meshes the scene's objects name.  Host only (rpt_upload_scene; rpt_tile_bitmap_host); `s` is valid
+// are, and the sub-tree and triangle boxes of the meshes the scene's objects name.  Host only (rpt_upload_scene; rpt_tile_bitmap_host); `s` is valid
 // (validate_geometry) and g.compact_ok is set.
-void host_mesh_facts(Geometry &g, const rpt_scene_desc *s, int max_boxes) {
+void host_mesh_facts(Geometry &g, const rpt_scene_desc *s, int max_boxes, int max_triangles) {
     g.host_node_bounds.resize(s->octree_count * 6);
     for (size_t i = 0; i < s->octree_count; i++) {
         float *b = &g.host_node_bounds[6 * i];
@@ -644,7 +666,11 @@ void host_mesh_facts(Geometry &g, const rpt_scene_desc *s, int max_boxes) {
         if (o.type != RPT_MESH || o.meshIndex < 0 || (size_t)o.meshIndex >= s->octree_count || g.mesh_boxes.count(o.meshIndex)) continue;
         if (!g.node_holds_its_triangles[(size_t)o.meshIndex] || !(16.2 * (double)g.node_tri_K[(size_t)o.meshIndex] <= 0.25)) continue;
         std::vector<float> boxes;
-        if (rptb::tiles::subtree_boxes(*s, o.meshIndex, max_boxes, boxes)) g.mesh_boxes[o.meshIndex].swap(boxes);
+        if (!rptb::tiles::subtree_boxes(*s, o.meshIndex, max_boxes, boxes)) continue;
+        g.mesh_boxes[o.meshIndex].swap(boxes);
+        // ... and its triangle boxes (the same rule, the same restriction to lists inside the root's box; over the cap: none)
+        std::vector<float> tri_boxes;
+        if (max_triangles > 0 && rptb::tiles::triangle_boxes(*s, o.meshIndex, max_triangles, tri_boxes)) g.mesh_tri_boxes[o.meshIndex].swap(tri_boxes);
     }
 }
 
@@ -1549,16 +1575,62 @@ bool tile_bits_current(const rpt_ctx *ctx) {
 
 // The tile bitmap of one mesh object for this frame, into `bits`; false: this object gets none (not a mesh with sub-tree boxes, or
 // outside the rule 16.2 K + 3.2u <= 0.25 that DObj::mslope >= 0 stands for, or a box's region could not be proven)
-bool build_tile_bitmap(const rpt_ctx *ctx, const rpt_object &o, uint32_t *bits, rptb::tiles::Stats *stats) {
+// stage: 0 the sub-tree stage alone, 1 the triangle stage alone, -1 the product a context puts on the device — the sub-tree stage ANDed
+// with the triangle stage where that one yields a bitmap (and the context has not switched it off).  stats: those of the stage asked
+// for; of the sub-tree stage for the product.
+bool build_tile_bitmap(const rpt_ctx *ctx, const rpt_object &o, uint32_t *bits, rptb::tiles::Stats *stats, int stage = -1) {
     if (o.type != RPT_MESH) return false;
     const auto it = ctx->geo->mesh_boxes.find(o.meshIndex);
     if (it == ctx->geo->mesh_boxes.end() || it->second.empty() || (size_t)o.meshIndex >= ctx->geo->node_tri_K.size()) return false;
     rptd::DObj d;
     build_dobjs(ctx, &o, 1, &d);
     if (!(d.mslope >= 0.0f)) return false;
-    const double slope = 16.2 * (double)ctx->geo->node_tri_K[(size_t)o.meshIndex] + 3.2 * rptb::cert::U24;
+    const double slope = 16.2 * (double)ctx->geo->node_tri_K[(size_t)o.meshIndex] + 3.2 * rptb::cert::U24, L = (double)ctx->geo->node_tri_L[(size_t)o.meshIndex];
     const rptb::tiles::Frame f{ctx->width, ctx->height, ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f, frame_inside_diagonal_window(ctx)};
-    return rptb::tiles::build(o, ctx->interval, it->second.data(), (int)(it->second.size() / 6), slope, (double)ctx->geo->node_tri_L[(size_t)o.meshIndex], f, bits, stats);
+    const auto tri = ctx->geo->mesh_tri_boxes.find(o.meshIndex);
+    const bool has_tri = tri != ctx->geo->mesh_tri_boxes.end() && !tri->second.empty();
+    if (stage == 1) return has_tri && rptb::tiles::build_pooled(o, ctx->interval, tri->second.data(), (int)(tri->second.size() / 6), slope, L, f, bits, stats);
+    if (!rptb::tiles::build(o, ctx->interval, it->second.data(), (int)(it->second.size() / 6), slope, L, f, bits, stats)) return false;
+    if (stage == 0 || !ctx->tile_triangles || !has_tri) return true;
+    const size_t words = rptb::tiles::bitmap_words(ctx->width, ctx->height);
+    std::vector<uint32_t> fine(words);
+    if (rptb::tiles::build_pooled(o, ctx->interval, tri->second.data(), (int)(tri->second.size() / 6), slope, L, f, fine.data(), nullptr))
+        for (size_t k = 0; k < words; k++) bits[k] &= fine[k];
+    return true;
+}
+
+// RPT_TILE_TRIANGLES=0 (read when a context is created): the sub-tree stage alone, for the A/B and as an escape hatch
+bool tile_triangles_wanted() {
+    const char *e = std::getenv("RPT_TILE_TRIANGLES");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
+// build_tile_bitmap's product through the geometry's cache: the contexts of one scene build a bitmap once
+bool shared_tile_bitmap(const rpt_ctx *ctx, const rpt_object &o, uint32_t *bits) {
+    if (o.type != RPT_MESH) return false;        // (ensure_tile_bits asks for every still object when no bitmap is live: only meshes take a place in the cache)
+    Geometry &g = *ctx->geo;
+    const size_t words = rptb::tiles::bitmap_words(ctx->width, ctx->height);
+    const float lens = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
+    const bool diagonals = frame_inside_diagonal_window(ctx);
+    std::lock_guard<std::mutex> lock(g.bitmap_cache_lock);
+    for (const Geometry::BitmapEntry &e : g.bitmap_cache) {
+        if (e.interval != ctx->interval || e.width != ctx->width || e.height != ctx->height || e.lens != lens || e.diagonals != diagonals ||
+            e.triangles != ctx->tile_triangles || std::memcmp(e.object, &o, sizeof(rpt_object)) != 0)
+            continue;
+        if (e.built) std::memcpy(bits, e.bits.data(), words * 4);
+        g.bitmap_copies++;
+        return e.built;
+    }
+    g.bitmap_builds++;
+    const bool room = g.bitmap_cache.size() < Geometry::BITMAP_CACHE_ENTRIES;
+    if (room) g.bitmap_cache.emplace_back();
+    Geometry::BitmapEntry &e = room ? g.bitmap_cache.back() : g.bitmap_cache[g.bitmap_cache_next++ % Geometry::BITMAP_CACHE_ENTRIES];
+    std::memcpy(e.object, &o, sizeof(rpt_object));
+    e.interval = ctx->interval; e.width = ctx->width; e.height = ctx->height; e.lens = lens; e.diagonals = diagonals; e.triangles = ctx->tile_triangles;
+    e.built = build_tile_bitmap(ctx, o, bits, nullptr);
+    if (e.built) e.bits.assign(bits, bits + words);
+    else e.bits.clear();
+    return e.built;
 }
 
 // Before a colour frame's launch: every still mesh that has no bitmap for this frame yet gets one (or is marked as tried), behind
@@ -1591,7 +1663,7 @@ int ensure_tile_bits(rpt_ctx *ctx) {
     for (int i = 0; i < slots; i++) {
         if (!(todo >> i & 1ull)) continue;
         const auto t0 = std::chrono::steady_clock::now();
-        if (!build_tile_bitmap(ctx, objs[i], (uint32_t *)host + (size_t)i * words, nullptr)) continue;
+        if (!shared_tile_bitmap(ctx, objs[i], (uint32_t *)host + (size_t)i * words)) continue;
         ctx->bits_last_build_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
         ctx->bits_has |= 1ull << i;
         ctx->bits_builds++;
@@ -2023,6 +2095,7 @@ int rpt_create(rpt_ctx **out, int device_ordinal) {
     rpt_ctx *ctx = new (std::nothrow) rpt_ctx();
     if (!ctx) return RPT_ERR_NOMEM;
     ctx->device = device_ordinal;
+    ctx->tile_triangles = tile_triangles_wanted();
     (void)rpth::Workers::instance();       // the helper pool exists from the first context on, not from the first animated frame (rpt_workers.hpp: fork())
     {
         static std::atomic<int> created{0};
@@ -2119,7 +2192,7 @@ int rpt_upload_scene(rpt_ctx *ctx, const rpt_scene_desc *s) {
     ctx->geo->octree_tri_count = s->octree_tri_count;
     if (int rc = build_derived_geometry(ctx, *s)) return rc;
     ctx->geo->exact_rcp_ok = rpt_scene_exact_rcp(s) == 1;
-    host_mesh_facts(*ctx->geo, s, rptb::tiles::MAX_BOXES);
+    host_mesh_facts(*ctx->geo, s, rptb::tiles::MAX_BOXES, rptb::tiles::MAX_TRIANGLES);
     ctx->bits_still = ctx->bits_tried = ctx->bits_has = 0;
     ctx->scene_uploaded = true;
     const int rc = rpt_set_objects(ctx, s->objects, (int)s->object_count);
@@ -2597,7 +2670,9 @@ int rpt_certify_screen_bounds(const void *object, int interval, const float *roo
 // The tile bitmap of mesh object `object_index` of `scene` (its Object[] as it stands) for a frame, on the host alone: what a context
 // would put on the device for the same object, frame and lens.  boxes_or_null: n_boxes sub-tree boxes to use INSTEAD of the mesh's own
 // (tests: a broken box must never clear a tile).  1: built; 0: this object gets no bitmap; < 0: an error.
-// stats_out: boxes, boxes proven, tiles set, tiles, the depth of the cut.
+// stats_out: boxes, boxes proven, tiles set, tiles, the depth of the cut — of the SUB-TREE stage; bits_out is the product with the triangle
+// stage (RPT_TILE_TRIANGLES as a context created now would read it: read on EVERY call here, there is no context to have read it), except
+// with the caller's boxes: those are the whole input then.
 int rpt_tile_bitmap_host(const rpt_scene_desc *s, int object_index, int interval, int width, int height, float lens_scale, int max_boxes,
                          const float *boxes_or_null, int n_boxes, uint32_t *bits_out, size_t words, int stats_out[5]) {
     if (!s || !bits_out || object_index < 0 || (size_t)object_index >= s->object_count || width < 1 || height < 1 || max_boxes < 1) return -RPT_ERR_ARG;
@@ -2609,12 +2684,14 @@ int rpt_tile_bitmap_host(const rpt_scene_desc *s, int object_index, int interval
     tmp.geo = std::make_shared<Geometry>();
     tmp.geo->compact_ok = true;
     tmp.geo->octree_count = s->octree_count;
-    host_mesh_facts(*tmp.geo, s, max_boxes);
+    const bool callers = boxes_or_null && n_boxes > 0;
+    tmp.tile_triangles = tile_triangles_wanted() && !callers;
+    host_mesh_facts(*tmp.geo, s, max_boxes, tmp.tile_triangles ? rptb::tiles::MAX_TRIANGLES : 0);
     int depth = -1;
     if (o.type == RPT_MESH) {
         std::vector<float> own;
         if (tmp.geo->mesh_boxes.count(o.meshIndex)) rptb::tiles::subtree_boxes(*s, o.meshIndex, max_boxes, own, &depth);
-        if (boxes_or_null && n_boxes > 0 && tmp.geo->mesh_boxes.count(o.meshIndex)) tmp.geo->mesh_boxes[o.meshIndex].assign(boxes_or_null, boxes_or_null + 6 * (size_t)n_boxes);
+        if (callers && tmp.geo->mesh_boxes.count(o.meshIndex)) tmp.geo->mesh_boxes[o.meshIndex].assign(boxes_or_null, boxes_or_null + 6 * (size_t)n_boxes);
     }
     tmp.interval = interval;
     tmp.width = width;
@@ -2626,6 +2703,45 @@ int rpt_tile_bitmap_host(const rpt_scene_desc *s, int object_index, int interval
     const bool ok = build_tile_bitmap(&tmp, o, bits_out, &st);
     if (stats_out) { stats_out[0] = st.boxes; stats_out[1] = st.proven; stats_out[2] = st.tiles_set; stats_out[3] = st.tiles; stats_out[4] = depth; }
     return ok ? 1 : 0;
+}
+
+// One stage of the tile bitmap alone, on the host: stage 0 the sub-tree stage (the mesh's own cut, at most 64 boxes), stage 1 the triangle
+// stage with at most `max_triangles` distinct triangles; stage 2 their product under that cap (a mesh over it: the sub-tree stage), with
+// the sub-tree stage's statistics.  rpt_tile_bitmap_host's returns; stats_out: boxes, boxes proven, tiles set, tiles.
+int rpt_tile_bitmap_stage_host(const rpt_scene_desc *s, int object_index, int interval, int width, int height, float lens_scale, int stage, int max_triangles,
+                               uint32_t *bits_out, size_t words, int stats_out[4]) {
+    if (!s || !bits_out || object_index < 0 || (size_t)object_index >= s->object_count || width < 1 || height < 1 || stage < 0 || stage > 2 || max_triangles < 1) return -RPT_ERR_ARG;
+    if (words < rptb::tiles::bitmap_words(width, height)) return -RPT_ERR_ARG;
+    rpt_ctx tmp;
+    if (validate_geometry(&tmp, *s) != RPT_OK) return -RPT_ERR_SCENE;
+    const rpt_object &o = s->objects[object_index];
+    if (o.type == RPT_MESH && (o.meshIndex < 0 || (size_t)o.meshIndex >= s->octree_count)) return -RPT_ERR_SCENE;
+    tmp.geo = std::make_shared<Geometry>();
+    tmp.geo->compact_ok = true;
+    tmp.geo->octree_count = s->octree_count;
+    host_mesh_facts(*tmp.geo, s, rptb::tiles::MAX_BOXES, stage >= 1 ? max_triangles : 0);
+    tmp.interval = interval;
+    tmp.width = width;
+    tmp.height = height;
+    tmp.v_fov = lens_scale == 1.0f ? 0.0f : 1.0f;       // (only "a lens is set" is read from it)
+    tmp.lens_scale = lens_scale;
+    rptb::tiles::Stats st{0, 0, 0, 0};
+    if (!window_holds_frame(&tmp)) return 0;
+    const bool ok = build_tile_bitmap(&tmp, o, bits_out, &st, stage == 2 ? -1 : stage);
+    if (stats_out) { stats_out[0] = st.boxes; stats_out[1] = st.proven; stats_out[2] = st.tiles_set; stats_out[3] = st.tiles; }
+    return ok ? 1 : 0;
+}
+
+// The bitmap's rasterisation alone (tests): the tiles of a width x height frame whose grown square touches the region bounds[8] =
+// {u0, v0, u1, v1, p_lo, p_hi, m_lo, m_hi}, octagon sides only with `diagonals`.  1: done; 0: an empty or NaN region (nothing set).
+int rpt_tile_rasterise_host(int width, int height, float lens_scale, int diagonals, const float bounds[8], uint32_t *bits_out, size_t words) {
+    if (!bounds || !bits_out || width < 1 || height < 1 || !(lens_scale > 0.0f) || words < rptb::tiles::bitmap_words(width, height)) return -RPT_ERR_ARG;
+    for (size_t k = 0; k < words; k++) bits_out[k] = 0u;
+    const rptb::Rect r{bounds[0], bounds[1], bounds[2], bounds[3], bounds[4], bounds[5], bounds[6], bounds[7]};
+    if (!(r.u0 <= r.u1) || !(r.v0 <= r.v1)) return 0;
+    const rptb::tiles::Frame f{width, height, lens_scale, diagonals != 0};
+    rptb::tiles::rasterise(r, diagonals != 0, rptb::tiles::Grid(f), bits_out);
+    return 1;
 }
 
 // The derived layouts of `scene` on the host alone: what build_derived_geometry uploads, array by array (include/rpt.h).
@@ -2664,6 +2780,15 @@ int rpt_tile_bitmap_state(rpt_ctx *ctx, unsigned long long out[4], int object_in
         RPT_HIP(ctx, hipEventSynchronize(ctx->tile_bits.copied));
         std::memcpy(bits_or_null, (const uint32_t *)ctx->tile_bits.host + (size_t)object_index * w, w * 4);
     }
+    return RPT_OK;
+}
+
+// The bitmap cache of the context's scene (tests, diagnostics): out = {keys built, requests answered with a copy} since its upload
+int rpt_tile_bitmap_shared_state(rpt_ctx *ctx, unsigned long long out[2]) {
+    if (!ctx || !out) return RPT_ERR_ARG;
+    std::lock_guard<std::mutex> lock(ctx->geo->bitmap_cache_lock);
+    out[0] = ctx->geo->bitmap_builds;
+    out[1] = ctx->geo->bitmap_copies;
     return RPT_OK;
 }
 
