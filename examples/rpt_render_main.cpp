@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -32,6 +32,13 @@
 // 32-byte rpt_star records (relativitypathtracer_amd/stars.py `save` writes them) of stars at rest in the scene's frame — the sky's
 // frame is set from the scene's camera.  The host runs the colour frame, an event frame of the same view and the star-field pass, under
 // the overlay's lines, and reports the stars inside the frame and the pixels changed on stderr.  It excludes --projection (a ray map).
+//
+// --particles FILE[:inverse_square][:bias=B] adds point sources that ride the scene's objects (rpt_set_particles, rpt_set_particle_options,
+// rpt_render_particles; not in the reference): FILE holds raw 32-byte rpt_particle records (relativitypathtracer_amd/particles.py `save`
+// writes them), each at rest in the rest frame of the object it names; inverse_square divides a particle's colour by its squared
+// rest-frame distance, bias=B (>= 0, in units of distance) lets particles that sit ON a surface show.  The host runs the colour frame, an
+// event frame of the same view and the particle pass — behind the stars, under the overlay's lines — and reports the particles seen and
+// the pixels changed on stderr.  It excludes --projection (a ray map).
 //
 // A scene with `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands gets its displays drawn too (rpt_set_readouts, rpt_render_readouts;
 // not in the reference): seven-segment digits on those objects that show their own time, after the overlay, before the picture is written.
@@ -153,11 +160,47 @@ static bool parse_projection(const char *spec, int width, int height, std::vecto
     return true;
 }
 
+// --particles FILE[:inverse_square][:bias=B]: the file name, the flags and the bias; false (and a message) for what it cannot read
+static bool parse_particles(const char *spec, std::string *path, int *flags, float *bias) {
+    const std::string s(spec);
+    size_t at = s.find(':');
+    *path = s.substr(0, at);
+    *flags = 0;
+    *bias = 0.0f;
+    if (path->empty()) {
+        std::fprintf(stderr, "--particles: '%s' names no file\n", spec);
+        return false;
+    }
+    while (at != std::string::npos) {
+        const size_t next = s.find(':', at + 1);
+        const std::string option = s.substr(at + 1, next == std::string::npos ? std::string::npos : next - at - 1);
+        if (option == "inverse_square") *flags |= RPT_PARTICLES_INVERSE_SQUARE;
+        else if (option.compare(0, 5, "bias=") == 0) {
+            char *end = nullptr;
+            const double b = std::strtod(option.c_str() + 5, &end);
+            if (end == option.c_str() + 5 || *end != '\0' || !std::isfinite(b) || b < 0.0) {
+                std::fprintf(stderr, "--particles: '%s' in '%s' is not a bias (a finite number >= 0)\n", option.c_str() + 5, spec);
+                return false;
+            }
+            *bias = (float)b;
+        } else {
+            std::fprintf(stderr, "--particles: unknown option '%s' (inverse_square, bias=B)\n", option.c_str());
+            return false;
+        }
+        at = next;
+    }
+    std::fprintf(stderr, "particles: file %s, inverse square %d, depth bias %g\n", path->c_str(), *flags & RPT_PARTICLES_INVERSE_SQUARE, (double)*bias);
+    return true;
+}
+
 int main(int argc, char **argv) {
     // the free-look options (degrees), taken out of argv; what is left is positional
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
     const char *events_path = nullptr, *projection_spec = nullptr, *stars_path = nullptr;
+    std::string particles_path;
+    int particle_flags = 0;
+    float particle_bias = 0.0f;
     int aa_n = 1, aa_threshold = 8;
     rpt_overlay_desc overlay;
     std::memset(&overlay, 0, sizeof overlay);
@@ -175,6 +218,12 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--stars")) stars_path = argv[++i];
             else if (!std::strcmp(argv[i], "--stars")) {
                 std::fprintf(stderr, "--stars needs a file name (raw 32-byte rpt_star records)\n");
+                return 2;
+            }
+            else if (has_value && !std::strcmp(argv[i], "--particles")) {
+                if (!parse_particles(argv[++i], &particles_path, &particle_flags, &particle_bias)) return 2;
+            } else if (!std::strcmp(argv[i], "--particles")) {
+                std::fprintf(stderr, "--particles needs a value: FILE[:inverse_square][:bias=B] (raw 32-byte rpt_particle records)\n");
                 return 2;
             }
             else if (!std::strcmp(argv[i], "--projection")) {
@@ -210,7 +259,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -225,6 +274,18 @@ int main(int argc, char **argv) {
         if (f) std::fclose(f);
         if (!whole || catalogue.empty()) {
             std::fprintf(stderr, "--stars: %s does not hold a whole number (> 0) of 32-byte rpt_star records\n", stars_path);
+            return 2;
+        }
+    }
+    std::vector<rpt_particle> particle_set;                      // --particles: the raw records
+    if (!particles_path.empty()) {
+        std::FILE *f = std::fopen(particles_path.c_str(), "rb");
+        rpt_particle p;
+        while (f && std::fread(&p, sizeof p, 1, f) == 1) particle_set.push_back(p);
+        const bool whole = f && std::feof(f) && std::ftell(f) == (long)(particle_set.size() * sizeof(rpt_particle));
+        if (f) std::fclose(f);
+        if (!whole || particle_set.empty()) {
+            std::fprintf(stderr, "--particles: %s does not hold a whole number (> 0) of 32-byte rpt_particle records\n", particles_path.c_str());
             return 2;
         }
     }
@@ -344,6 +405,20 @@ int main(int argc, char **argv) {
             return 1;
         }
         std::fprintf(stderr, "stars: %llu of %zu inside the frame, %llu of %lld pixels changed\n", counts[0], catalogue.size(), counts[1], (long long)width * height);
+    }
+    if (!particle_set.empty()) {                                 // point sources riding the objects, depth-tested against the event frame
+        unsigned long long counts[2] = {0, 0};
+        rc = events_rendered ? 0 : rpt_render_events(last);
+        events_rendered = !rc;
+        if (!rc) rc = rpt_set_particles(last, particle_set.data(), (int)particle_set.size());
+        if (!rc) rc = rpt_set_particle_options(last, particle_flags, particle_bias);
+        if (!rc) rc = rpt_render_particles(last);
+        if (!rc) rc = rpt_last_particles(last, counts);
+        if (rc) {
+            std::fprintf(stderr, "particles: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::fprintf(stderr, "particles: %llu of %zu seen, %llu of %lld pixels changed\n", counts[0], particle_set.size(), counts[1], (long long)width * height);
     }
     if (overlay.layers) {                                        // lines on that frame, from an event frame of the same view
         unsigned long long changed = 0;

@@ -45,7 +45,9 @@
  * displays on the objects' surfaces that show each object's own proper time: rpt_set_readouts, rpt_render_readouts /
  * rpt_render_readouts_async and rpt_last_readout_pixels ("Readout pass"), and the opt-in star-field pass — a catalogue of point
  * sources in the sky's rest frame, aberrated, Doppler-shifted and beamed as points: rpt_set_stars, rpt_render_stars /
- * rpt_render_stars_async and rpt_last_stars ("Star-field pass").
+ * rpt_render_stars_async and rpt_last_stars ("Star-field pass"), and the opt-in particle pass — point sources at a finite
+ * distance, each at rest in an object's frame, seen with light delay and hidden behind what stands in front: rpt_set_particles,
+ * rpt_set_particle_options, rpt_render_particles / rpt_render_particles_async and rpt_last_particles ("Particle pass").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -659,6 +661,52 @@ int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]);
  * for the last pass and returns {splat, resolve} in milliseconds (RPT_ERR_STATE if that pass was not timed). */
 int rpt_set_stars_measurement(rpt_ctx *ctx, int timed);
 int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]);
+
+/* The particle pass (not in the reference; DESIGN.md §20 "Particle pass" gives every rule operation by operation): point sources at a
+ * FINITE distance, each at rest in the rest frame of one entry of Object[] — a lattice of lamps riding a body, runway lights, a dust
+ * cloud, markers on a piecewise worldline — seen with light delay, aberrated, Doppler-shifted and beamed as point sources, and hidden
+ * behind whatever surface stands in front of them.  A fourth sibling of the overlay, the readout and the star-field pass with the same
+ * discipline: opt-in, per context, not shared by rpt_share_scene; enqueued on the context's stream after a colour frame and an event
+ * frame of the same view; in place into the R, G, B bytes of the 16-B framebuffer pixels (alpha, bytes 0-7 and 12-15, the debug planes
+ * and the record buffer are not written).  Particles light nothing, cast no shadow and do not hide one another: they add.
+ *
+ *   pos     the particle's position in the rest frame of Object[object]: the coordinates of rpt_event.event[1..3], so a particle
+ *           placed on a record's event sits on the surface that pixel sees.
+ *   object  the index of that object; the objects are those the frames of this view were rendered with (under rpt_set_orientation
+ *           the re-based ones).
+ *   rgb     the linear colour at rest, on the scale of object colours before the tonemap (as rpt_star.rgb).
+ *
+ * In short (L = Object[object]): w = pos - L.stationaryCam.yzw, r = |w|; the emission event lies on the camera's past light cone,
+ * tau = -r (interval == -1), or on its simultaneity slice, tau = -(I0.yzw . w) / I0.x with I0 = L.InvLorentz[0] (interval == 0);
+ * k = L.InvLorentz (tau, w), dist = |k.yzw| — the distance rpt_event.dist measures —, n = k.yzw / dist; a particle whose r or dist is
+ * not finite or not > 0 is skipped, and so is, while rpt_set_object_windows is set, one whose emission time L.stationaryCam.x + tau lies
+ * outside its object's window; D = dist / r, c = S_f(D, rgb) as rpt_set_doppler defines it, divided by D^2 when RPT_DOPPLER_BEAMING is
+ * set (the star pass's point-source law) and by r^2 with RPT_PARTICLES_INVERSE_SQUARE; n is projected as a star's is (pinhole, lens,
+ * equirect); each of the four pixels around (X, Y) whose record is a miss or has dist - depth_bias < record.dist gets c times its
+ * bilinear weight into the star pass's fixed-point accumulator; then EVERY pixel with a non-zero sum S gets
+ * byte = min(255, byte + to_u8(min(hable(S) / hable(white_point), 1))) per channel.  Integer sums: a frame does not depend on the
+ * set's order.
+ *
+ * rpt_set_particles copies the set, in its order, and writes it to the device once, in stream order; NULL or count 0 switches the pass
+ * off.  RPT_ERR_ARG, message "rpt_set_particles: ...", the previous set kept: a component of pos or rgb that is not finite, a negative
+ * colour, object < 0, count < 0 or count > 2^22.  rpt_set_particle_options: flags = RPT_PARTICLES_INVERSE_SQUARE or 0, depth_bias >= 0
+ * in units of dist (defaults 0, 0.0f); RPT_ERR_ARG for an unknown flag bit and a bias that is negative or not finite.
+ * rpt_render_particles[_async] refuses what rpt_render_overlay refuses, with messages that start "rpt_render_particles:", and also, with
+ * RPT_ERR_ARG, RPT_PROJECTION_RAYMAP, an interval other than -1 or 0 (the cone has no closed form for another) and a set whose largest
+ * object index is not below the context's object count.  The context stays usable after a refusal.  With no set the call checks
+ * nothing, launches nothing and succeeds.  Calling it twice adds the particles twice.
+ * rpt_last_particles: of the last FINISHED pass, out[0] = particles that were not skipped and have at least one tap inside the frame
+ * that passes the depth test, out[1] = pixels whose bytes changed; both 0 before the first. */
+/* rpt_particle: include/rpt_layout.h (32 B) */
+#define RPT_PARTICLES_INVERSE_SQUARE 1   /* divide the colour by the squared rest-frame distance r^2 */
+int rpt_set_particles(rpt_ctx *ctx, const rpt_particle *particles_or_null, int count);
+int rpt_set_particle_options(rpt_ctx *ctx, int flags, float depth_bias);   /* defaults 0, 0.0f */
+int rpt_render_particles(rpt_ctx *ctx);         /* enqueue and wait */
+int rpt_render_particles_async(rpt_ctx *ctx);   /* enqueue; rpt_sync waits */
+int rpt_last_particles(rpt_ctx *ctx, unsigned long long out[2]);
+/* Measurement only (tools/particles_cost.py): as rpt_set_stars_measurement / rpt_last_stars_ms, for the particle pass's two kernels. */
+int rpt_set_particles_measurement(rpt_ctx *ctx, int timed);
+int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

@@ -85,6 +85,14 @@ typedef struct rpt_readout {      /* 36 B, one per entry of Object[] */
     uint8_t on_rgba[4], off_rgba[4];   /* lit segments / the rest of the rectangle; alpha 0 leaves the picture */
 } rpt_readout;
 
+/* One point source of the particle pass (not in the reference; include/rpt.h, rpt_set_particles, states the rules) */
+typedef struct rpt_particle {     /* 32 B: two aligned 16-byte loads */
+    float   pos[3];               /* position in the REST FRAME of Object[object]: the coordinates of rpt_event.event[1..3] */
+    int32_t object;               /* index into the context's Object[]: the frame the particle is at rest in */
+    float   rgb[3];               /* linear colour at rest, on the scale of object colours (as rpt_star.rgb) */
+    float   _pad;
+} rpt_particle;
+
 /*
  * The eight read-only scene arrays the reference uploads once (main.cpp:33-55), in the
  * reference's layouts, as {pointer, element count} pairs.  Zero-length arrays are legal and
@@ -139,5 +147,8 @@ RPT_SA(offsetof(rpt_event, uv) == 24, "uv");
 RPT_SA(sizeof(rpt_readout) == 36, "readout is 36 B");
 RPT_SA(offsetof(rpt_readout, digits) == 24, "digits");
 RPT_SA(offsetof(rpt_readout, on_rgba) == 28, "on_rgba");
+RPT_SA(sizeof(rpt_particle) == 32, "particle is 32 B");
+RPT_SA(offsetof(rpt_particle, object) == 12, "object");
+RPT_SA(offsetof(rpt_particle, rgb) == 16, "rgb");
 
 #endif /* RPT_LAYOUT_H */

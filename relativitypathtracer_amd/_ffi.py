@@ -61,6 +61,11 @@ class Star(C.Structure):
     _fields_ = [("dir", C.c_float * 3), ("rgb", C.c_float * 3), ("_pad", C.c_float * 2)]
 
 
+class Particle(C.Structure):
+    """rpt_particle of include/rpt_layout.h (32 B): one point source of the particle pass, at rest in the frame of Object[object]."""
+    _fields_ = [("pos", C.c_float * 3), ("object", C.c_int32), ("rgb", C.c_float * 3), ("_pad", C.c_float)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -239,6 +244,13 @@ HIP_SYMBOLS = {
     "rpt_last_stars": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_set_stars_measurement": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_last_stars_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_particles": (C.c_int, [C.c_void_p, C.POINTER(Particle), C.c_int]),
+    "rpt_set_particle_options": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "rpt_render_particles": (C.c_int, [C.c_void_p]),
+    "rpt_render_particles_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_particles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_particles_measurement": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_last_particles_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -27,6 +27,8 @@
 #include "rpt_workers.hpp"
 #include "rpt_stars.hip.h"          /* last: the kernels before it keep their place in the translation unit */
 #include "rpt_stars_host.hpp"
+#include "rpt_particles.hip.h"      /* behind the stars: kernels 1130 and 1131 are the translation unit's last */
+#include "rpt_particles_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -72,7 +74,7 @@ struct Tally {
     size_t words = 1, spare = 0;                      // (as tally_ready was given them)
     bool pending = false;                             // a copy has been enqueued since `value` was read
 };
-enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_COUNT };     // rpt_ctx::tally
+enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_COUNT };     // rpt_ctx::tally
 
 // What the last frame of one kind (colour, event) was enqueued for, as a pass over both asks (frames_of_this_view)
 struct FrameMark {
@@ -240,7 +242,8 @@ struct rpt_ctx {
     FrameMark colour_frame;                           // the last colour frame (rendered() is what the read-back calls ask)
     // what the passes report, by TALLY_*: the refined pixels of an adaptive frame (rpt_last_aa_refined); the overlay's changed pixels and,
     // as spare bytes, the bit pattern of the frame's largest delay (rpt_last_overlay_pixels); the readouts' changed pixels
-    // (rpt_last_readout_pixels); {stars with a tap inside the frame, changed pixels} (rpt_last_stars)
+    // (rpt_last_readout_pixels); {stars with a tap inside the frame, changed pixels} (rpt_last_stars); {particles seen, changed pixels}
+    // (rpt_last_particles)
     Tally tally[TALLY_COUNT];
     // rpt_set_readouts / rpt_render_readouts (not in the reference): the readout pass, per context, never shared
     std::vector<rpt_readout> readouts;                // one per entry of Object[]; empty = none set
@@ -253,6 +256,16 @@ struct rpt_ctx {
     bool star_timed = false;                          // rpt_set_stars_measurement
     hipEvent_t star_marks[3] = {nullptr, nullptr, nullptr}; // timed passes: before the splat, between the kernels, after the resolve
     bool star_marked = false;                         // the last pass recorded them
+    // rpt_set_particles / rpt_render_particles (not in the reference): the particle pass, per context, never shared.  Its sums go
+    // through star_acc: the accumulator is all zero outside any pass, and the passes of one context are ordered by its stream
+    int particle_count = 0;                           // 0 = no set: the pass is off
+    int particle_largest_object = -1;                 // the largest Object[] index the set names: held against object_count at every launch
+    StagedUpload particle_table;                      // rpt_particle per particle, in the caller's order; written once per rpt_set_particles
+    int particle_flags = 0;                           // rpt_set_particle_options
+    float particle_depth_bias = 0.0f;
+    bool particle_timed = false;                      // rpt_set_particles_measurement
+    hipEvent_t particle_marks[3] = {nullptr, nullptr, nullptr};
+    bool particle_marked = false;
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -1885,7 +1898,7 @@ int frames_of_this_view(rpt_ctx *ctx, const char *call, rpt_pixel **out16_out, c
     return RPT_OK;
 }
 
-// The shape of a pass over a rendered frame (the overlay, the readouts, the stars), `call` naming it in the messages and `which` its
+// The shape of a pass over a rendered frame (the overlay, the readouts, the stars, the particles), `call` naming it in the messages and `which` its
 // tally.  Off: nothing is checked, launched or changed, and it reports zero.  On: frames_of_this_view, then `enqueue`, the pass's own
 // part (its refusals, tally_ready, its arguments, tally_zero, its launches), then the tally's way home, whose event is last_event.
 using PassEnqueue = int (*)(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events);
@@ -1980,6 +1993,17 @@ int enqueue_readouts(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_eve
 
 int launch_readouts(rpt_ctx *ctx) { return frame_pass(ctx, "rpt_render_readouts", !ctx->readouts.empty(), TALLY_READOUTS, enqueue_readouts); }
 
+// The fixed-point accumulator of the star-field pass and the particle pass, 24 B per pixel of the largest frame so far
+int accumulator_ready(rpt_ctx *ctx, size_t pixels) {
+    const size_t acc_bytes = pixels * 3 * sizeof(unsigned long long);
+    if (acc_bytes > ctx->star_acc.capacity || !ctx->star_acc.ptr) {      // a new accumulator starts all zero; passes leave it so
+        RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (a pass in flight may still use the old one)
+        if (int rc = reserve(ctx, ctx->star_acc, acc_bytes)) return rc;
+        RPT_HIP(ctx, hipMemsetAsync(ctx->star_acc.ptr, 0, ctx->star_acc.capacity, ctx->stream));
+    }
+    return RPT_OK;
+}
+
 // One star-field pass on the context's stream (kernels 1120 and 1121): two refusals of its own, G, the accumulator, the two launches
 int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
     if (ctx->projection == RPT_PROJECTION_RAYMAP)
@@ -1995,12 +2019,8 @@ int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event 
             return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: the sky matrix (rpt_set_environment_frame) cannot be inverted");
         std::memcpy(a.G, g, sizeof a.G);
     }
-    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height, acc_bytes = pixels * 3 * sizeof(unsigned long long);
-    if (acc_bytes > ctx->star_acc.capacity || !ctx->star_acc.ptr) {      // a new accumulator starts all zero; passes leave it so
-        RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (a pass in flight may still use the old one)
-        if (int rc = reserve(ctx, ctx->star_acc, acc_bytes)) return rc;
-        RPT_HIP(ctx, hipMemsetAsync(ctx->star_acc.ptr, 0, ctx->star_acc.capacity, ctx->stream));
-    }
+    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
+    if (int rc = accumulator_ready(ctx, pixels)) return rc;
     if (int rc = tally_ready(ctx, tally, 2)) return rc;
     if (ctx->star_timed)
         for (hipEvent_t &m : ctx->star_marks)
@@ -2053,6 +2073,77 @@ int launch_stars(rpt_ctx *ctx) {
     return frame_pass(ctx, "rpt_render_stars", ctx->star_count != 0, TALLY_STARS, enqueue_stars);
 }
 
+// One particle pass on the context's stream (kernels 1130 and 1131): three refusals of its own — the last is what keeps every index
+// the splat follows inside Object[] —, the accumulator it shares with the stars, the two launches
+int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    if (ctx->projection == RPT_PROJECTION_RAYMAP)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a particle with");
+    if (ctx->interval != -1 && ctx->interval != 0)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: interval is " + std::to_string(ctx->interval) + "; the light cone has a closed form for -1 and 0 only");
+    if (ctx->particle_largest_object >= ctx->object_count)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: the set names object " + std::to_string(ctx->particle_largest_object) + ", the Object[] holds " + std::to_string(ctx->object_count));
+    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
+    if (int rc = accumulator_ready(ctx, pixels)) return rc;
+    if (int rc = tally_ready(ctx, tally, 2)) return rc;
+    if (ctx->particle_timed)
+        for (hipEvent_t &m : ctx->particle_marks)
+            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
+
+    rptd::ParticleArgs a;
+    std::memset((void *)&a, 0, sizeof a);
+    a.particles = (const rpt_particle *)ctx->particle_table.device.ptr;
+    a.objects = (const rpt_object *)ctx->objects.ptr;
+    if (!ctx->windows.empty())          // (their count is the Object[]'s: the frames of this view were launched with them)
+        a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
+    a.events = events;
+    a.acc = (unsigned long long *)ctx->star_acc.ptr;
+    a.counts = (unsigned long long *)tally.device.ptr;
+    a.count = ctx->particle_count;
+    a.object_count = ctx->object_count;
+    a.width = ctx->width;
+    a.height = ctx->height;
+    a.interval = ctx->interval;
+    a.doppler = ctx->interval != 0 ? ctx->doppler : 0;
+    a.inverse_square = ctx->particle_flags & RPT_PARTICLES_INVERSE_SQUARE;
+    a.depth_bias = ctx->particle_depth_bias;
+    if (ctx->projection == RPT_PROJECTION_EQUIRECT) {
+        a.camera = RPT_STARS_EQUIRECT;
+        a.h_fov = ctx->projection_params[0];
+        a.v_fov = ctx->projection_params[1];
+        a.yaw = ctx->projection_params[2];
+        a.wrap = a.h_fov == (float)(2.0 * RPT_PI_D) ? 1 : 0;
+    } else {
+        const float s = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
+        a.plane_x = s * ((float)ctx->width / (float)ctx->height);
+        a.plane_y = s;
+    }
+    rptd::ParticleResolveArgs b;
+    std::memset((void *)&b, 0, sizeof b);
+    b.acc = a.acc;
+    b.out16 = out16;
+    b.counts = a.counts;
+    b.pixels = pixels;
+    for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
+
+    if (int rc = tally_zero(ctx, tally)) return rc;
+    if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[0], ctx->stream));
+    void *splat_args[] = {(void *)&a};
+    (void)hipLaunchKernel((const void *)rptd::rpt_particles_splat_kernel, dim3((unsigned)((ctx->particle_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[1], ctx->stream));
+    void *resolve_args[] = {(void *)&b};
+    (void)hipLaunchKernel((const void *)rptd::rpt_particles_resolve_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[2], ctx->stream));
+    ctx->particle_marked = ctx->particle_timed;
+    return RPT_OK;
+}
+
+int launch_particles(rpt_ctx *ctx) {
+    if (ctx->particle_count == 0) ctx->particle_marked = false;
+    return frame_pass(ctx, "rpt_render_particles", ctx->particle_count != 0, TALLY_PARTICLES, enqueue_particles);
+}
+
 // The event pass and what it leaves for rpt_pick, rpt_read_events and the passes over the frame
 int launch_event_frame(rpt_ctx *ctx) {
     if (!ctx->ev_events) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
@@ -2063,7 +2154,7 @@ int launch_event_frame(rpt_ctx *ctx) {
     return RPT_OK;
 }
 
-// rpt_render_events, _overlay, _readouts, _stars and their _async forms: one pass on the context's stream, waited for or not
+// rpt_render_events, _overlay, _readouts, _stars, _particles and their _async forms: one pass on the context's stream, waited for or not
 int render_pass(rpt_ctx *ctx, int (*launch_pass)(rpt_ctx *), bool wait) {
     if (!ctx) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2144,9 +2235,10 @@ void rpt_destroy(rpt_ctx *ctx) {
     for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->star_acc})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table, &ctx->particle_table}) release(*u);
     for (Tally &t : ctx->tally) release(t);
     for (hipEvent_t m : ctx->star_marks) if (m) (void)hipEventDestroy(m);
+    for (hipEvent_t m : ctx->particle_marks) if (m) (void)hipEventDestroy(m);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -3188,6 +3280,65 @@ int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]) {
     RPT_HIP(ctx, hipEventSynchronize(ctx->star_marks[2]));
     RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->star_marks[0], ctx->star_marks[1]));
     RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->star_marks[1], ctx->star_marks[2]));
+    return RPT_OK;
+}
+
+// The set goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused for its
+// arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no set.
+int rpt_set_particles(rpt_ctx *ctx, const rpt_particle *particles_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (count < 0 || count > rptp::kMaxParticles) return fail(ctx, RPT_ERR_ARG, "rpt_set_particles: " + rptp::set_fault(nullptr, count));
+    if (!particles_or_null || count == 0) {
+        ctx->particle_count = 0;
+        ctx->particle_largest_object = -1;
+        return RPT_OK;
+    }
+    const std::string fault = rptp::set_fault(particles_or_null, count);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_particles: " + fault);
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    void *host = nullptr;
+    int rc = staged_host(ctx, ctx->particle_table, (size_t)count * sizeof(rpt_particle), &host);
+    if (!rc) {
+        rptp::prepare_set(particles_or_null, count, (rpt_particle *)host);
+        rc = staged_copy(ctx, ctx->particle_table);
+    }
+    if (rc) {
+        ctx->particle_count = 0;
+        ctx->particle_largest_object = -1;
+        return rc;
+    }
+    ctx->particle_count = count;
+    ctx->particle_largest_object = rptp::largest_object(particles_or_null, count);
+    return RPT_OK;
+}
+
+int rpt_set_particle_options(rpt_ctx *ctx, int flags, float depth_bias) {
+    if (!ctx) return RPT_ERR_ARG;
+    const std::string fault = rptp::options_fault(flags, depth_bias);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_particle_options: " + fault);
+    ctx->particle_flags = flags;
+    ctx->particle_depth_bias = depth_bias;
+    return RPT_OK;
+}
+
+int rpt_render_particles_async(rpt_ctx *ctx) { return render_pass(ctx, launch_particles, false); }
+int rpt_render_particles(rpt_ctx *ctx) { return render_pass(ctx, launch_particles, true); }
+
+int rpt_last_particles(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_PARTICLES, out, 2); }
+
+int rpt_set_particles_measurement(rpt_ctx *ctx, int timed) {
+    if (!ctx) return RPT_ERR_ARG;
+    ctx->particle_timed = timed != 0;
+    return RPT_OK;
+}
+
+int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]) {
+    if (!ctx || !ms) return RPT_ERR_ARG;
+    if (!ctx->particle_marked) return fail(ctx, RPT_ERR_STATE, "rpt_last_particles_ms: the last particle pass was not timed (rpt_set_particles_measurement)");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    RPT_HIP(ctx, hipEventSynchronize(ctx->particle_marks[2]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->particle_marks[0], ctx->particle_marks[1]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->particle_marks[1], ctx->particle_marks[2]));
     return RPT_OK;
 }
 

@@ -528,6 +528,49 @@ class Renderer:
         self._check(self._lib.rpt_last_stars_ms(self._h, ms), "rpt_last_stars_ms")
         return float(ms[0]), float(ms[1])
 
+    # -- the particle pass (include/rpt.h, rpt_set_particles; not in the reference) -----------------
+    def set_particles(self, particles):
+        """The particle set: an array of particles.PARTICLE_DTYPE records (or anything of n x 32 bytes in that layout: pos, object,
+        rgb, one float of padding), e.g. from particles.lattice / particles.at_events / particles.load; None or an empty array switches
+        the pass off.  pos is the position in the rest frame of the scene's object number `object` (the coordinates of an event
+        record's event[1..3]); rgb the linear colour at rest.  Copied by the library; per context; what the library refuses raises
+        RenderError."""
+        if particles is None or len(particles) == 0:
+            self._check(self._lib.rpt_set_particles(self._h, None, 0), "rpt_set_particles")
+            return
+        raw = np.ascontiguousarray(particles)
+        if raw.nbytes % 32 or raw.nbytes // 32 != len(raw):
+            raise ValueError("a particle set has one 32-byte record (particles.PARTICLE_DTYPE) per particle")
+        self._check(self._lib.rpt_set_particles(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Particle)), len(raw)), "rpt_set_particles")
+
+    def set_particle_options(self, inverse_square: bool = False, depth_bias: float = 0.0):
+        """inverse_square: divide a particle's colour by its squared rest-frame distance (rgb is then an intensity, not what a pixel
+        gets).  depth_bias >= 0, in units of the records' dist: a tap is drawn where dist - depth_bias < the record's dist, so a
+        particle ON a surface (particles.at_events) shows with a small bias and is hidden, by rounding, without one."""
+        self._check(self._lib.rpt_set_particle_options(self._h, 1 if inverse_square else 0, float(depth_bias)), "rpt_set_particle_options")
+
+    def render_particles(self, async_: bool = False):
+        """Add the particles of set_particles to the framebuffer, in place, each tap depth-tested against the last event frame.  The
+        context must have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice adds them
+        twice.  Independent of the other passes.  async_=True enqueues only (sync waits)."""
+        self._run_pass("rpt_render_particles", async_)
+
+    def last_particles(self) -> Tuple[int, int]:
+        """(particles with at least one tap inside the frame that passed the depth test, pixels whose bytes changed) of the last
+        finished particle pass."""
+        seen, changed = self._last_counts("rpt_last_particles", 2)
+        return seen, changed
+
+    def set_particles_measurement(self, timed: bool = False):
+        """Measurement only (tools/particles_cost.py): time the two kernels of every pass (last_particles_ms)."""
+        self._check(self._lib.rpt_set_particles_measurement(self._h, int(bool(timed))), "rpt_set_particles_measurement")
+
+    def last_particles_ms(self) -> Tuple[float, float]:
+        """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_particles_measurement)."""
+        ms = (C.c_float * 2)(0.0, 0.0)
+        self._check(self._lib.rpt_last_particles_ms(self._h, ms), "rpt_last_particles_ms")
+        return float(ms[0]), float(ms[1])
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -660,7 +703,8 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  projection: Union[None, str, Mapping, np.ndarray] = None, environment: Optional[np.ndarray] = None,
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
-                 fov: float = math.pi, fit: int = 0, readouts=None, stars=None):
+                 fov: float = math.pi, fit: int = 0, readouts=None, stars=None, particles=None,
+                 particle_options: Optional[Mapping] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -674,7 +718,10 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     Renderer.set_readouts takes, or True for the scene's own (`d` commands, Scene.readouts()); it implies events=True too and runs the
     readout pass last: the colour frame, the event frame, the overlay if asked for, the readouts.  stars: a catalogue for
     Renderer.set_stars, at rest in the scene's frame (the sky's frame is set from the scene's camera, as for environment); it implies
-    events=True as well and runs the star-field pass right after the event frame, under the overlay's lines and the readouts."""
+    events=True as well and runs the star-field pass right after the event frame, under the overlay's lines and the readouts.
+    particles: a set for Renderer.set_particles (particles.lattice, particles.at_events, ...), particle_options the keywords of
+    Renderer.set_particle_options; it implies events=True too — the pass depth-tests against the event frame — and runs behind the
+    stars, under the overlay's lines and the readouts."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -700,11 +747,15 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        if overlay is not None or readouts is not None or stars is not None:
+        if overlay is not None or readouts is not None or stars is not None or particles is not None:
             records = r.render_events()
             if stars is not None:
                 r.set_stars(stars)
                 r.render_stars()
+            if particles is not None:
+                r.set_particles(particles)
+                r.set_particle_options(**dict(particle_options or {}))
+                r.render_particles()
             if overlay is not None:
                 r.set_overlay(**overlay)
                 r.render_overlay()
