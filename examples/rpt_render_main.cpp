@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -39,6 +39,12 @@
 // rest-frame distance, bias=B (>= 0, in units of distance) lets particles that sit ON a surface show.  The host runs the colour frame, an
 // event frame of the same view and the particle pass — behind the stars, under the overlay's lines — and reports the particles seen and
 // the pixels changed on stderr.  It excludes --projection (a ray map).
+//
+// --doppler shift|beaming|both turns the Doppler shift and the searchlight beaming on for every pass (rpt_set_doppler; not in the
+// reference).  --star-temperatures FILE and --particle-temperatures FILE make the stars of --stars and the particles of --particles
+// thermal sources (rpt_set_star_temperatures, rpt_set_particle_temperatures; not in the reference): FILE holds raw float32 kelvin, one per
+// record of the other file in its order, 0 for a source that is none; under --doppler shift or both such a source is shifted as a
+// blackbody and is never moved out of the visible band.
 //
 // A scene with `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands gets its displays drawn too (rpt_set_readouts, rpt_render_readouts;
 // not in the reference): seven-segment digits on those objects that show their own time, after the overlay, before the picture is written.
@@ -198,6 +204,8 @@ int main(int argc, char **argv) {
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
     const char *events_path = nullptr, *projection_spec = nullptr, *stars_path = nullptr;
+    const char *star_kelvin_path = nullptr, *particle_kelvin_path = nullptr;
+    int doppler = 0;
     std::string particles_path;
     int particle_flags = 0;
     float particle_bias = 0.0f;
@@ -216,6 +224,24 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--events")) events_path = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--projection")) projection_spec = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--stars")) stars_path = argv[++i];
+            else if (has_value && !std::strcmp(argv[i], "--star-temperatures")) star_kelvin_path = argv[++i];
+            else if (has_value && !std::strcmp(argv[i], "--particle-temperatures")) particle_kelvin_path = argv[++i];
+            else if (!std::strcmp(argv[i], "--star-temperatures") || !std::strcmp(argv[i], "--particle-temperatures")) {
+                std::fprintf(stderr, "%s needs a file name (raw float32 kelvin, one per record)\n", argv[i]);
+                return 2;
+            }
+            else if (has_value && !std::strcmp(argv[i], "--doppler")) {
+                const char *v = argv[++i];
+                doppler = !std::strcmp(v, "shift") ? RPT_DOPPLER_SHIFT : !std::strcmp(v, "beaming") ? RPT_DOPPLER_BEAMING
+                        : !std::strcmp(v, "both") ? (RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING) : -1;
+                if (doppler < 0) {
+                    std::fprintf(stderr, "--doppler takes shift, beaming or both\n");
+                    return 2;
+                }
+            } else if (!std::strcmp(argv[i], "--doppler")) {
+                std::fprintf(stderr, "--doppler needs a value: shift, beaming or both\n");
+                return 2;
+            }
             else if (!std::strcmp(argv[i], "--stars")) {
                 std::fprintf(stderr, "--stars needs a file name (raw 32-byte rpt_star records)\n");
                 return 2;
@@ -259,7 +285,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -286,6 +312,27 @@ int main(int argc, char **argv) {
         if (f) std::fclose(f);
         if (!whole || particle_set.empty()) {
             std::fprintf(stderr, "--particles: %s does not hold a whole number (> 0) of 32-byte rpt_particle records\n", particles_path.c_str());
+            return 2;
+        }
+    }
+    std::vector<float> star_kelvin, particle_kelvin;             // --star-temperatures, --particle-temperatures: raw float32, one per record
+    for (int k = 0; k < 2; k++) {
+        const char *path = k == 0 ? star_kelvin_path : particle_kelvin_path;
+        const char *flag = k == 0 ? "--star-temperatures" : "--particle-temperatures";
+        std::vector<float> &kelvin = k == 0 ? star_kelvin : particle_kelvin;
+        const size_t records = k == 0 ? catalogue.size() : particle_set.size();
+        if (!path) continue;
+        if (records == 0) {
+            std::fprintf(stderr, "%s needs %s\n", flag, k == 0 ? "--stars" : "--particles");
+            return 2;
+        }
+        std::FILE *f = std::fopen(path, "rb");
+        float t;
+        while (f && std::fread(&t, sizeof t, 1, f) == 1) kelvin.push_back(t);
+        const bool whole = f && std::feof(f) && std::ftell(f) == (long)(kelvin.size() * sizeof(float));
+        if (f) std::fclose(f);
+        if (!whole || kelvin.size() != records) {
+            std::fprintf(stderr, "%s: %s does not hold %zu float32 temperatures, one per record\n", flag, path, records);
             return 2;
         }
     }
@@ -318,6 +365,7 @@ int main(int argc, char **argv) {
     if (turned) rc = rpt_set_orientation(ctx, ypr);              // the context's view: before any Object[] is handed over
     if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ctx, v_fov);
     if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ctx, aa_n, aa_threshold);
+    if (!rc && doppler) rc = rpt_set_doppler(ctx, doppler);
     if (!rc && !raymap.empty()) rc = rpt_set_raymap(ctx, raymap.data(), width, height);
     if (!rc && !raymap.empty()) rc = rpt_set_projection(ctx, RPT_PROJECTION_RAYMAP, nullptr);
     {   // the scene's `wT0,T1` commands (not in the reference): objects and lights that begin and end; a scene without any sets nothing
@@ -352,6 +400,7 @@ int main(int argc, char **argv) {
             if (turned) rc = rpt_set_orientation(ring.slot(k), ypr);
             if (!rc && v_fov != 0) rc = rpt_set_field_of_view(ring.slot(k), v_fov);
             if (!rc && aa_n != 1) rc = rpt_set_adaptive_aa(ring.slot(k), aa_n, aa_threshold);
+            if (!rc && doppler) rc = rpt_set_doppler(ring.slot(k), doppler);
             if (!rc && !raymap.empty()) rc = rpt_set_raymap(ring.slot(k), raymap.data(), width, height);      // (the map is per context: every slot its copy)
             if (!rc && !raymap.empty()) rc = rpt_set_projection(ring.slot(k), RPT_PROJECTION_RAYMAP, nullptr);
         }
@@ -398,6 +447,7 @@ int main(int argc, char **argv) {
         if (!rc) rc = rpt_render_events(last);
         events_rendered = !rc;
         if (!rc) rc = rpt_set_stars(last, catalogue.data(), (int)catalogue.size());
+        if (!rc && !star_kelvin.empty()) rc = rpt_set_star_temperatures(last, star_kelvin.data(), (int)star_kelvin.size());
         if (!rc) rc = rpt_render_stars(last);
         if (!rc) rc = rpt_last_stars(last, counts);
         if (rc) {
@@ -412,6 +462,7 @@ int main(int argc, char **argv) {
         events_rendered = !rc;
         if (!rc) rc = rpt_set_particles(last, particle_set.data(), (int)particle_set.size());
         if (!rc) rc = rpt_set_particle_options(last, particle_flags, particle_bias);
+        if (!rc && !particle_kelvin.empty()) rc = rpt_set_particle_temperatures(last, particle_kelvin.data(), (int)particle_kelvin.size());
         if (!rc) rc = rpt_render_particles(last);
         if (!rc) rc = rpt_last_particles(last, counts);
         if (rc) {

@@ -708,6 +708,26 @@ int rpt_last_particles(rpt_ctx *ctx, unsigned long long out[2]);
 int rpt_set_particles_measurement(rpt_ctx *ctx, int timed);
 int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]);
 
+/* Thermal point sources (not in the reference; DESIGN.md §21 "Thermal point sources" gives the operator operation by operation): an
+ * opt-in temperature per star and per particle.  S_f draws a piecewise-linear spectrum through a colour's three samples and cuts it to
+ * zero beyond its outer knots, so with RPT_DOPPLER_SHIFT every source seen at D > 1.8 or D < 0.66 is black; a blackbody shifted by D is
+ * a blackbody at D T and never leaves the band.  Where a source has a temperature and the shift is on, its colour rule is T_f in place
+ * of S_f: with x_k = (h c / k) / (lambda_k T) at the three primaries (700.0, 546.1, 435.8 nm),
+ *     o_k = c_k expm1(x_k) / (D^3 expm1(x_k / D))     RPT_DOPPLER_SHIFT
+ *     o_k = c_k expm1(x_k) / expm1(x_k / D)           RPT_DOPPLER_SHIFT | RPT_DOPPLER_BEAMING: for c = A * Planck(T), A * Planck(D T)
+ * D == 1 returns c bit for bit; RPT_DOPPLER_BEAMING alone is c D^4 as before; the point-source division by D^2 and the particles' 1 / r^2
+ * follow unchanged; with interval == 0 or Doppler off the colour is untouched, as before.
+ *
+ * kelvin[i] belongs to entry i of the catalogue (the set): 0 = not thermal, the source keeps S_f; otherwise finite with
+ * 500 <= T <= 1e8.  The array is per context, converted once (x_G = (h c / k) / (546.1 nm T), in double, rounded to float) and written
+ * to the device once, in stream order; NULL or count 0 switches the thermal law off.  RPT_ERR_ARG, a message that starts with the
+ * call's name and names the entry, the previous array kept: an entry that is not finite or outside the range, count < 0, count > 2^22.
+ * Replacing the catalogue (the set) keeps the temperatures; rpt_render_stars / rpt_render_particles refuse with RPT_ERR_ARG, the context
+ * still usable, while an array is set whose count differs from the catalogue's (the set's).  With no array set every launch is what it
+ * was (kernels 1120 / 1130); with one, the splat is kernel 1122 / 1132: one more 4-byte load per source. */
+int rpt_set_star_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count);
+int rpt_set_particle_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count);
+
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);
 void *rpt_colour_plane_ptr(rpt_ctx *ctx);    /* device pointer of the compact plane (rpt_set_rows) */
@@ -787,7 +807,8 @@ void rpt_free_host(void *p);
  * textured-sphere (u,v) (3 -> 2), 5 the walk's pure steps: exit face of a leaf and child selection, general and fast (6 -> 12),
  * 6 the Doppler kernels' colour operator S_f (5 -> 3: {D, r, g, b, flags as a float} -> the operated r, g, b),
  * 7 the sky lookup alone on the context's current environment (3 -> 5: a direction {d.x, d.y, d.z} of the sky's rest frame, normalised
- * by the probe, -> {u, v, r, g, b}; RPT_ERR_STATE without an environment). */
+ * by the probe, -> {u, v, r, g, b}; RPT_ERR_STATE without an environment),
+ * 8 the thermal point sources' colour operator T_f (6 -> 3: {D, r, g, b, flags as a float, x_G} -> the operated r, g, b). */
 int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int n);
 /* Test hook, one object's functions at ray level (the oracle's counterpart: rpt_oracle_object_rays): which = 0 n 4-D rays
  * {origin4, dir4} of object `object_index`'s rest frame through its intersector in the general form of opencl_kernel.cl:312-359 /

@@ -251,6 +251,8 @@ HIP_SYMBOLS = {
     "rpt_last_particles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_set_particles_measurement": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_last_particles_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_star_temperatures": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "rpt_set_particle_temperatures": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "rpt_version": (C.c_char_p, []),
 }
 

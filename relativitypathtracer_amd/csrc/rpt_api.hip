@@ -29,6 +29,8 @@
 #include "rpt_stars_host.hpp"
 #include "rpt_particles.hip.h"      /* behind the stars: kernels 1130 and 1131 are the translation unit's last */
 #include "rpt_particles_host.hpp"
+#include "rpt_thermal.hip.h"        /* behind the particles: the thermal probe and kernels 1122 and 1132 are the translation unit's last */
+#include "rpt_thermal_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -266,6 +268,12 @@ struct rpt_ctx {
     bool particle_timed = false;                      // rpt_set_particles_measurement
     hipEvent_t particle_marks[3] = {nullptr, nullptr, nullptr};
     bool particle_marked = false;
+    // rpt_set_star_temperatures / rpt_set_particle_temperatures (not in the reference): x_G per source, parallel to the
+    // catalogue and to the set; 0 entries = none set, and the passes launch kernels 1120 / 1130 as before
+    int star_thermal_count = 0;
+    StagedUpload star_thermal_table;                  // one float per star, written once per rpt_set_star_temperatures
+    int particle_thermal_count = 0;
+    StagedUpload particle_thermal_table;
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -2008,6 +2016,8 @@ int accumulator_ready(rpt_ctx *ctx, size_t pixels) {
 int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
     if (ctx->projection == RPT_PROJECTION_RAYMAP)
         return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a star with");
+    if (ctx->star_thermal_count != 0 && ctx->star_thermal_count != ctx->star_count)     // (what keeps kernel 1122's xg[i] inside its array)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: " + std::to_string(ctx->star_thermal_count) + " temperatures are set (rpt_set_star_temperatures), the catalogue holds " + std::to_string(ctx->star_count));
     rptd::StarArgs a;
     std::memset((void *)&a, 0, sizeof a);
     {   // E' as a colour frame's launch forms it, then G
@@ -2056,8 +2066,10 @@ int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event 
 
     if (int rc = tally_zero(ctx, tally)) return rc;
     if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[0], ctx->stream));
-    void *splat_args[] = {(void *)&a};
-    (void)hipLaunchKernel((const void *)rptd::rpt_stars_splat_kernel, dim3((unsigned)((ctx->star_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    const float *xg = (const float *)ctx->star_thermal_table.device.ptr;
+    void *splat_args[] = {(void *)&a, (void *)&xg};     // (1120 takes the first only)
+    (void)hipLaunchKernel(ctx->star_thermal_count != 0 ? (const void *)rptd::rpt_stars_thermal_splat_kernel : (const void *)rptd::rpt_stars_splat_kernel,
+                          dim3((unsigned)((ctx->star_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
     RPT_HIP(ctx, hipGetLastError());
     if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[1], ctx->stream));
     void *resolve_args[] = {(void *)&b};
@@ -2082,6 +2094,8 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
         return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: interval is " + std::to_string(ctx->interval) + "; the light cone has a closed form for -1 and 0 only");
     if (ctx->particle_largest_object >= ctx->object_count)
         return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: the set names object " + std::to_string(ctx->particle_largest_object) + ", the Object[] holds " + std::to_string(ctx->object_count));
+    if (ctx->particle_thermal_count != 0 && ctx->particle_thermal_count != ctx->particle_count)     // (what keeps kernel 1132's xg[i] inside its array)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: " + std::to_string(ctx->particle_thermal_count) + " temperatures are set (rpt_set_particle_temperatures), the set holds " + std::to_string(ctx->particle_count));
     const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
     if (int rc = accumulator_ready(ctx, pixels)) return rc;
     if (int rc = tally_ready(ctx, tally, 2)) return rc;
@@ -2127,8 +2141,10 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
 
     if (int rc = tally_zero(ctx, tally)) return rc;
     if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[0], ctx->stream));
-    void *splat_args[] = {(void *)&a};
-    (void)hipLaunchKernel((const void *)rptd::rpt_particles_splat_kernel, dim3((unsigned)((ctx->particle_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    const float *xg = (const float *)ctx->particle_thermal_table.device.ptr;
+    void *splat_args[] = {(void *)&a, (void *)&xg};     // (1130 takes the first only)
+    (void)hipLaunchKernel(ctx->particle_thermal_count != 0 ? (const void *)rptd::rpt_particles_thermal_splat_kernel : (const void *)rptd::rpt_particles_splat_kernel,
+                          dim3((unsigned)((ctx->particle_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
     RPT_HIP(ctx, hipGetLastError());
     if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[1], ctx->stream));
     void *resolve_args[] = {(void *)&b};
@@ -2235,7 +2251,7 @@ void rpt_destroy(rpt_ctx *ctx) {
     for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->star_acc})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table, &ctx->particle_table}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table, &ctx->particle_table, &ctx->star_thermal_table, &ctx->particle_thermal_table}) release(*u);
     for (Tally &t : ctx->tally) release(t);
     for (hipEvent_t m : ctx->star_marks) if (m) (void)hipEventDestroy(m);
     for (hipEvent_t m : ctx->particle_marks) if (m) (void)hipEventDestroy(m);
@@ -3342,6 +3358,43 @@ int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]) {
     return RPT_OK;
 }
 
+// rpt_set_star_temperatures and rpt_set_particle_temperatures: the array goes to the device here, once, as x_G per source, in stream
+// order (a pass in flight keeps the one it was launched with); a call refused for its arguments has changed nothing, one that fails on
+// the device (RPT_ERR_DEVICE) leaves no array.  Whether its count matches the catalogue's is asked at the launch, not here.
+static int set_temperatures(rpt_ctx *ctx, const char *call, StagedUpload &table, int &table_count, const float *kelvin_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (count < 0 || count > rptt::kMaxTemperatures) return fail(ctx, RPT_ERR_ARG, std::string(call) + ": " + rptt::temperatures_fault(nullptr, count));
+    if (!kelvin_or_null || count == 0) {
+        table_count = 0;
+        return RPT_OK;
+    }
+    const std::string fault = rptt::temperatures_fault(kelvin_or_null, count);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, std::string(call) + ": " + fault);
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    void *host = nullptr;
+    int rc = staged_host(ctx, table, (size_t)count * sizeof(float), &host);
+    if (!rc) {
+        rptt::prepare_temperatures(kelvin_or_null, count, (float *)host);
+        rc = staged_copy(ctx, table);
+    }
+    if (rc) {
+        table_count = 0;
+        return rc;
+    }
+    table_count = count;
+    return RPT_OK;
+}
+
+int rpt_set_star_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    return set_temperatures(ctx, "rpt_set_star_temperatures", ctx->star_thermal_table, ctx->star_thermal_count, kelvin_or_null, count);
+}
+
+int rpt_set_particle_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    return set_temperatures(ctx, "rpt_set_particle_temperatures", ctx->particle_thermal_table, ctx->particle_thermal_count, kelvin_or_null, count);
+}
+
 void *rpt_output_ptr(rpt_ctx *ctx) {
     if (!ctx) return nullptr;
     return ctx->external_out ? ctx->external_out : ctx->owned_out.ptr;
@@ -3489,8 +3542,8 @@ int rpt_read_wave_times(rpt_ctx *ctx, unsigned long long *out, size_t max_words,
 }
 
 int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int n) {
-    static const int in_w[8] = {15, 12, 4, 3, 3, 6, 5, 3}, out_w[8] = {4, 5, 3, 3, 2, 12, 3, 5};
-    if (!ctx || which < 0 || which > 7 || !host_in || !host_out || n <= 0) return RPT_ERR_ARG;
+    static const int in_w[9] = {15, 12, 4, 3, 3, 6, 5, 3, 6}, out_w[9] = {4, 5, 3, 3, 2, 12, 3, 5, 3};
+    if (!ctx || which < 0 || which > 8 || !host_in || !host_out || n <= 0) return RPT_ERR_ARG;
     if (which == 7 && !ctx->env_on) return fail(ctx, RPT_ERR_STATE, "rpt_probe 7: the context has no environment (rpt_set_environment)");
     RPT_HIP(ctx, hipSetDevice(ctx->device));
     float *d_in = nullptr, *d_out = nullptr;
@@ -3503,6 +3556,7 @@ int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int 
     if (hipMemcpy(d_in, host_in, sizeof(float) * in_w[which] * n, hipMemcpyHostToDevice) != hipSuccess) rc = RPT_ERR_DEVICE;
     if (!rc) {
         if (which == 6) hipLaunchKernelGGL(rptd::rpt_probe_doppler_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_in, d_out, n);
+        else if (which == 8) hipLaunchKernelGGL(rptd::rpt_probe_thermal_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_in, d_out, n);
         else if (which == 7) hipLaunchKernelGGL(rptd::rpt_probe_environment_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->env.device.ptr, ctx->env_width, ctx->env_height, d_in, d_out, n);
         else hipLaunchKernelGGL(rptd::rpt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, which, d_in, d_out, n);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||

@@ -40,8 +40,10 @@ struct ParticleResolveArgs {
     float hable_wp[3];
 };
 
-// Rules 1-4 for one particle of object L: false = the particle is skipped
-RPT_DEV bool particle_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam, const DObj *window, f3 pos, f3 rgb, float &X, float &Y, float &dist, f3 &c) {
+// Rules 1-4 for one particle of object L: false = the particle is skipped.  THERMAL: the colour rule is T_f with the
+// particle's xg (kernel 1132); without it xg is not looked at and the rule is S_f (kernel 1130).
+template <bool THERMAL>
+RPT_DEV bool particle_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam, const DObj *window, f3 pos, f3 rgb, float xg, float &X, float &Y, float &dist, f3 &c) {
     const f3 w = pos - yzw(cam);
     const float r = __builtin_sqrtf(dot(w, w));
     if (!(r > 0.0f) || !(r <= 3.402823466e38f)) return false;
@@ -60,7 +62,8 @@ RPT_DEV bool particle_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam
     if (a.doppler != 0) {
         const float D = dist / r;
         if (!(D > 0.0f) || !(D <= 3.402823466e38f)) return false;
-        c = doppler_colour(a.doppler, D, rgb);
+        if constexpr (THERMAL) c = thermal_colour(a.doppler, D, rgb, xg);
+        else c = doppler_colour(a.doppler, D, rgb);
         if (a.doppler & 2) c = c / (D * D);              // a point source also loses solid angle by D^2
     }
     if (a.inverse_square) c = c / (r * r);
@@ -88,6 +91,7 @@ RPT_DEV bool particle_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam
 // adds that return nothing.  Every tap is tested against the frame after the wrap and BEFORE its record is read, so no particle,
 // whatever its numbers, addresses a record or a word outside the frame.  The records are not written and the sums are integers: the
 // frame does not depend on the order of arrival.  Particles seen: a ballot per wave, LDS, one global atomic per workgroup, as 1120.
+// Kernel 1132 (rpt_thermal.hip.h) restates this body around particle_place<true>, as 1122 restates 1120's.
 __global__ __launch_bounds__(256) void rpt_particles_splat_kernel(const ParticleArgs a) {
     __shared__ unsigned int block_seen;
     const int t = (int)threadIdx.x;
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(256) void rpt_particles_splat_kernel(const Particle
             const f4 cam = ld4(L->stationaryCam);
             float X, Y, dist;
             f3 c;
-            if (particle_place(a, inv, cam, a.dobjs ? a.dobjs + object : nullptr, mk3(lo.x, lo.y, lo.z), mk3(hi.x, hi.y, hi.z), X, Y, dist, c)) {
+            if (particle_place<false>(a, inv, cam, a.dobjs ? a.dobjs + object : nullptr, mk3(lo.x, lo.y, lo.z), mk3(hi.x, hi.y, hi.z), 0.0f, X, Y, dist, c)) {
                 const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
                 const int x0 = (int)xf, y0 = (int)yf;    // |X|, |Y| < 1e9: in range
                 const float fx = X - xf, fy = Y - yf;

@@ -40,14 +40,22 @@ struct StarResolveArgs {
     float hable_wp[3];
 };
 
+// T_f of rpt_thermal.hip.h, which rpt_api.hip includes last: S_f where xg == 0, Planck's law elsewhere
+RPT_DEV f3 thermal_colour(int flags, float D, f3 c, float xg);
+
 // Rules 1-4 for one star: false = the star is skipped (D not finite or not > 0, behind the pinhole, no finite position).
-RPT_DEV bool star_place(const StarArgs &a, f3 s, f3 rgb, float &X, float &Y, f3 &c) {
+// THERMAL: the colour rule is T_f with the star's xg (kernel 1122); without it xg is not looked at and the rule is S_f (kernel 1120).
+template <bool THERMAL>
+RPT_DEV bool star_place(const StarArgs &a, f3 s, f3 rgb, float xg, float &X, float &Y, f3 &c) {
     const f4 q = transformPoint4D(a.G, mk4((float)a.interval, s.x, s.y, s.z));
     c = rgb;
     if (a.interval != 0) {
         const float D = q.x / (float)a.interval;
         if (!(D > 0.0f) || !(D <= 3.402823466e38f)) return false;
-        if (a.doppler != 0) c = doppler_colour(a.doppler, D, rgb);
+        if (a.doppler != 0) {
+            if constexpr (THERMAL) c = thermal_colour(a.doppler, D, rgb, xg);
+            else c = doppler_colour(a.doppler, D, rgb);
+        }
         if (a.doppler & 2) c = c / (D * D);              // a point source also loses solid angle by D^2
     }
     const f3 n = normalize(yzw(q));
@@ -80,6 +88,8 @@ RPT_DEV void star_add(unsigned long long *word, float p) {
 // three words 24 consecutive bytes and a row's two pixels 48.  Every tap is tested against the frame after the wrap, so no star, whatever
 // its numbers, addresses a word outside the width * height * 3 of `acc`.  Integer sums do not depend on the order of arrival.
 // Stars with a tap inside the frame: a ballot per wave, the four waves' counts added in LDS, one global atomic per workgroup.
+// Kernel 1122 (rpt_thermal.hip.h) restates this body around star_place<true>: wrapping the body itself in a function template changed
+// this kernel's machine code, templating star_place alone does not (profiles/r22_thermal_kernel_code_diff.txt).
 __global__ __launch_bounds__(256) void rpt_stars_splat_kernel(const StarArgs a) {
     __shared__ unsigned int block_inside;
     const int t = (int)threadIdx.x;
@@ -92,7 +102,7 @@ __global__ __launch_bounds__(256) void rpt_stars_splat_kernel(const StarArgs a) 
         const float4 lo = record[0], hi = record[1];     // dir.xyz, rgb.r | rgb.g, rgb.b, padding
         float X, Y;
         f3 c;
-        if (star_place(a, mk3(lo.x, lo.y, lo.z), mk3(lo.w, hi.x, hi.y), X, Y, c)) {
+        if (star_place<false>(a, mk3(lo.x, lo.y, lo.z), mk3(lo.w, hi.x, hi.y), 0.0f, X, Y, c)) {
             const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
             const int x0 = (int)xf, y0 = (int)yf;        // |X|, |Y| < 1e9: in range
             const float fx = X - xf, fy = Y - yf;

@@ -13,7 +13,7 @@ from typing import Mapping, Optional
 import numpy as np
 
 from .events import EVENT_DTYPE, _objects_array
-from .stars import point_source_colour
+from .stars import point_source_colour, thermal_colour
 
 PARTICLE_DTYPE = np.dtype([("pos", "<f4", (3,)), ("object", "<i4"), ("rgb", "<f4", (3,)), ("_pad", "<f4")])
 assert PARTICLE_DTYPE.itemsize == 32
@@ -70,13 +70,14 @@ def window_accepts(t0, t1, t):
 
 
 def project(particles, objects, camera: Mapping, W: int, H: int, interval: int = -1, flags: int = 0, options: Optional[Mapping] = None,
-            windows=None) -> dict:
+            windows=None, temperatures=None) -> dict:
     """Rules 1-4 of the particle pass in float64.  particles: PARTICLE_DTYPE records; objects: the Object[] the frames were rendered with
     (a Scene, its objects(), or n x 320 raw bytes — under an orientation the re-based ones of renderer.orient_objects; the camera's
     own `orientation` key is NOT applied here); camera: a mapping with mode="pinhole" (default), optionally v_fov (the lens) — or
     mode="equirect", optionally h_fov, v_fov, yaw; interval: -1 (light delay) or 0; flags: those of Renderer.set_doppler (1 shift,
     2 beaming); options: dict(inverse_square=..., depth_bias=...) as Renderer.set_particle_options takes; windows: (n, 2) {t0, t1} per
-    object, or None.  Returns a dict of arrays, one entry per particle: visible, X and Y (pixel x at X = x for the pinhole, pixel centre
+    object, or None; temperatures: kelvin per particle as Renderer.set_particle_temperatures takes them (0: not thermal), or None: rule
+    3's S_f becomes stars.thermal_colour.  Returns a dict of arrays, one entry per particle: visible, X and Y (pixel x at X = x for the pinhole, pixel centre
     at x + 0.5 for the panorama; NaN where not visible), dist (the camera-frame distance, what rpt_event.dist measures), r (the
     rest-frame distance), D (dist / r; 1 with interval 0), te (the emission time in the object's rest frame), k (N, 4) the emission
     event's displacement from the camera event in the camera frame, n (N, 3) and rgb (N, 3) the colour after rule 3."""
@@ -108,6 +109,10 @@ def project(particles, objects, camera: Mapping, W: int, H: int, interval: int =
             D = dist / r
             visible &= (D > 0.0) & np.isfinite(D)
             rgb = point_source_colour(flags, D, rgb0)
+            if temperatures is not None:
+                rgb = thermal_colour(flags, D, rgb0, temperatures)
+                if flags & 2:
+                    rgb = rgb / (D ** 2)[:, None]
         else:
             D = dist / r if interval != 0 else np.ones(len(p))
             rgb = rgb0.copy()

@@ -494,11 +494,16 @@ class Renderer:
         return self._last_counts("rpt_last_readout_pixels")[0]
 
     # -- the star-field pass (include/rpt.h, rpt_set_stars; not in the reference) -------------------
-    def set_stars(self, catalogue):
+    def set_stars(self, catalogue, temperatures=None):
         """The star catalogue: an array of stars.STAR_DTYPE records (or anything of n x 32 bytes in that layout: dir, rgb, two floats of
         padding), e.g. from stars.random_catalogue / stars.from_arrays / stars.load; None or an empty array switches the pass off.
         dir is the direction one looks in to see the star, in the sky's rest frame (set_environment_frame); rgb its linear colour at
-        rest.  Copied by the library; per context; what the library refuses raises RenderError."""
+        rest.  Copied by the library; per context; what the library refuses raises RenderError.  temperatures: if given, passed to
+        set_star_temperatures after the catalogue (None leaves the temperatures of the context as they are)."""
+        if temperatures is not None:
+            self.set_stars(catalogue)
+            self.set_star_temperatures(temperatures)
+            return
         if catalogue is None or len(catalogue) == 0:
             self._check(self._lib.rpt_set_stars(self._h, None, 0), "rpt_set_stars")
             return
@@ -506,6 +511,21 @@ class Renderer:
         if raw.nbytes % 32 or raw.nbytes // 32 != len(raw):
             raise ValueError("a star catalogue has one 32-byte record (stars.STAR_DTYPE) per star")
         self._check(self._lib.rpt_set_stars(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Star)), len(raw)), "rpt_set_stars")
+
+    def _set_temperatures(self, call: str, kelvin):
+        if kelvin is None or len(kelvin) == 0:
+            self._check(getattr(self._lib, call)(self._h, None, 0), call)
+            return
+        raw = np.ascontiguousarray(kelvin, dtype=np.float32).reshape(-1)
+        self._check(getattr(self._lib, call)(self._h, raw.ctypes.data_as(C.POINTER(C.c_float)), len(raw)), call)
+
+    def set_star_temperatures(self, kelvin):
+        """Thermal stars (include/rpt.h, rpt_set_star_temperatures): one temperature in kelvin per star of the catalogue,
+        in its order — 0 for a star that keeps the piecewise-linear spectrum, otherwise 500 .. 1e8.  With the Doppler shift on, a star
+        with a temperature is shifted as a blackbody (at D it is one of D T) and is never moved out of the band.  None or an empty
+        array switches the thermal law off.  Kept when the catalogue is replaced; render_stars refuses a count that differs from the
+        catalogue's."""
+        self._set_temperatures("rpt_set_star_temperatures", kelvin)
 
     def render_stars(self, async_: bool = False):
         """Add the stars of set_stars to the miss pixels of the framebuffer, in place.  The context must have rendered (or enqueued) a
@@ -529,12 +549,17 @@ class Renderer:
         return float(ms[0]), float(ms[1])
 
     # -- the particle pass (include/rpt.h, rpt_set_particles; not in the reference) -----------------
-    def set_particles(self, particles):
+    def set_particles(self, particles, temperatures=None):
         """The particle set: an array of particles.PARTICLE_DTYPE records (or anything of n x 32 bytes in that layout: pos, object,
         rgb, one float of padding), e.g. from particles.lattice / particles.at_events / particles.load; None or an empty array switches
         the pass off.  pos is the position in the rest frame of the scene's object number `object` (the coordinates of an event
         record's event[1..3]); rgb the linear colour at rest.  Copied by the library; per context; what the library refuses raises
-        RenderError."""
+        RenderError.  temperatures: if given, passed to set_particle_temperatures after the set (None leaves the temperatures of the
+        context as they are)."""
+        if temperatures is not None:
+            self.set_particles(particles)
+            self.set_particle_temperatures(temperatures)
+            return
         if particles is None or len(particles) == 0:
             self._check(self._lib.rpt_set_particles(self._h, None, 0), "rpt_set_particles")
             return
@@ -542,6 +567,10 @@ class Renderer:
         if raw.nbytes % 32 or raw.nbytes // 32 != len(raw):
             raise ValueError("a particle set has one 32-byte record (particles.PARTICLE_DTYPE) per particle")
         self._check(self._lib.rpt_set_particles(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Particle)), len(raw)), "rpt_set_particles")
+
+    def set_particle_temperatures(self, kelvin):
+        """Thermal particles (rpt_set_particle_temperatures): as set_star_temperatures, one temperature per particle of the set."""
+        self._set_temperatures("rpt_set_particle_temperatures", kelvin)
 
     def set_particle_options(self, inverse_square: bool = False, depth_bias: float = 0.0):
         """inverse_square: divide a particle's colour by its squared rest-frame distance (rgb is then an intensity, not what a pixel
@@ -661,7 +690,8 @@ class Renderer:
             self._lib.rpt_free_host(tris)
 
     def probe(self, which: int, inputs: np.ndarray, out_width: int) -> np.ndarray:
-        """rpt_probe (include/rpt.h); which = 6: the Doppler colour operator, (n, 5) {D, r, g, b, flags} -> (n, 3)."""
+        """rpt_probe (include/rpt.h); which = 6: the Doppler colour operator, (n, 5) {D, r, g, b, flags} -> (n, 3); which = 8: the thermal
+        point sources' operator, (n, 6) {D, r, g, b, flags, x_G} -> (n, 3)."""
         inputs = np.ascontiguousarray(inputs, dtype=np.float32)
         n = inputs.shape[0]
         out = np.empty((n, out_width), dtype=np.float32)
@@ -704,7 +734,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
                  fov: float = math.pi, fit: int = 0, readouts=None, stars=None, particles=None,
-                 particle_options: Optional[Mapping] = None):
+                 particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -721,7 +751,8 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     events=True as well and runs the star-field pass right after the event frame, under the overlay's lines and the readouts.
     particles: a set for Renderer.set_particles (particles.lattice, particles.at_events, ...), particle_options the keywords of
     Renderer.set_particle_options; it implies events=True too — the pass depth-tests against the event frame — and runs behind the
-    stars, under the overlay's lines and the readouts."""
+    stars, under the overlay's lines and the readouts.  star_temperatures, particle_temperatures: kelvin per star and per particle
+    (Renderer.set_star_temperatures, set_particle_temperatures): those sources are Doppler-shifted as blackbodies."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -750,10 +781,10 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if overlay is not None or readouts is not None or stars is not None or particles is not None:
             records = r.render_events()
             if stars is not None:
-                r.set_stars(stars)
+                r.set_stars(stars, star_temperatures)
                 r.render_stars()
             if particles is not None:
-                r.set_particles(particles)
+                r.set_particles(particles, particle_temperatures)
                 r.set_particle_options(**dict(particle_options or {}))
                 r.render_particles()
             if overlay is not None:

@@ -44,10 +44,11 @@ def _catalogue(directions, rgb) -> np.ndarray:
 
 
 def random_catalogue(n: int, seed: int = 0, alpha: float = 1.5, faintest: float = 0.02, brightest: float = 50.0,
-                     temperatures: Sequence[float] = (3000.0, 12000.0)) -> np.ndarray:
+                     temperatures: Sequence[float] = (3000.0, 12000.0), return_temperatures: bool = False):
     """n stars uniform on the sphere.  Brightness: a power law, N(> S) ~ S^-alpha from `faintest` up, cut at `brightest` (alpha = 1.5
     is what a uniform population in flat space gives).  Colour: a blackbody of a temperature drawn log-uniformly from `temperatures`,
-    through blackbody_rgb, times the brightness."""
+    through blackbody_rgb, times the brightness.  return_temperatures=True returns (catalogue, temperatures): the float32 kelvin per
+    star that Renderer.set_star_temperatures takes (the colours are built from those rounded values)."""
     rng = np.random.default_rng(seed)
     z = rng.uniform(-1.0, 1.0, n)
     lon = rng.uniform(-math.pi, math.pi, n)
@@ -55,18 +56,26 @@ def random_catalogue(n: int, seed: int = 0, alpha: float = 1.5, faintest: float 
     d = np.stack([r * np.sin(lon), z, r * np.cos(lon)], -1)
     flux = np.minimum(faintest * (1.0 - rng.uniform(0.0, 1.0, n)) ** (-1.0 / alpha), brightest)
     T = np.exp(rng.uniform(math.log(temperatures[0]), math.log(temperatures[1]), n))
+    if return_temperatures:
+        T32 = T.astype(np.float32)
+        return _catalogue(d, blackbody_rgb(T32) * flux[:, None]), T32
     return _catalogue(d, blackbody_rgb(T) * flux[:, None])
 
 
-def from_arrays(ra, dec, magnitude, temperature, magnitude_zero: float = 1.0) -> np.ndarray:
+def from_arrays(ra, dec, magnitude, temperature, magnitude_zero: float = 1.0, return_temperatures: bool = False):
     """A catalogue from columns of a real one: right ascension and declination in radians (dir = (cos dec sin ra, sin dec, cos dec
     cos ra): declination is the latitude above the x-z plane, ra = 0 lies ahead), apparent magnitude (a star of magnitude 0 gets the
-    brightness magnitude_zero, five magnitudes are a factor of 100) and temperature in kelvin (blackbody_rgb)."""
+    brightness magnitude_zero, five magnitudes are a factor of 100) and temperature in kelvin (blackbody_rgb).
+    return_temperatures=True returns (catalogue, temperatures): the float32 kelvin per star that Renderer.set_star_temperatures takes
+    (the colours are built from those rounded values)."""
     ra, dec, mag, T = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (ra, dec, magnitude, temperature))
     if not (ra.shape == dec.shape == mag.shape == T.shape):
         raise ValueError("ra, dec, magnitude and temperature have one entry per star")
     d = np.stack([np.cos(dec) * np.sin(ra), np.sin(dec), np.cos(dec) * np.cos(ra)], -1)
     flux = magnitude_zero * 10.0 ** (-0.4 * mag)
+    if return_temperatures:
+        T32 = T.astype(np.float32)
+        return _catalogue(d, blackbody_rgb(T32) * flux[:, None]), T32
     return _catalogue(d, blackbody_rgb(T) * flux[:, None])
 
 
@@ -113,6 +122,38 @@ def point_source_colour(flags: int, D, rgb) -> np.ndarray:
     return o
 
 
+def x_green(temperature) -> np.ndarray:
+    """x_G = (h c / k) / (546.1 nm T) in float64, 0 where T is 0 (not a thermal source): what the library uploads, before its rounding
+    to float."""
+    T = np.asarray(temperature, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.where(T == 0.0, 0.0, _HC_OVER_K_NM / (WAVELENGTHS_NM[1] * np.where(T == 0.0, 1.0, T)))
+
+
+def thermal_colour(flags: int, D, rgb, T) -> np.ndarray:
+    """T_f(flags, D, rgb, T) in float64, the colour rule of a source with a temperature: with the shift (bit 0), channel k
+    is rgb_k expm1(x_k) / expm1(x_k / D), x_k = (h c / k) / (lambda_k T) — for rgb = A blackbody_rgb(T), A times the Planck samples of
+    D T on the same scale —, over D^3 unless beaming (bit 1) is set as well.  Without the shift, and for every source whose T is 0, it
+    is S_f (point_source_colour before its / D^2).  D (n,), rgb (n, 3), T (n,) or a scalar."""
+    D = np.asarray(D, dtype=np.float64).reshape(-1)
+    c = np.asarray(rgb, dtype=np.float64).reshape(-1, 3)
+    T = np.broadcast_to(np.asarray(T, dtype=np.float64), D.shape)
+    with np.errstate(all="ignore"):
+        plain = point_source_colour(flags, D, c)
+        if flags & 2:
+            plain = plain * (D ** 2)[:, None]           # (S_f itself: point_source_colour has divided by D^2)
+        if not flags & 1:
+            return plain
+        nu = np.array([NU_R, 1.0, NU_B])
+        x = x_green(np.where(T == 0.0, 1.0, T))[:, None] * nu[None, :]
+        y = x / D[:, None]
+        q = np.exp(x - y) * (-np.expm1(-x)) / (-np.expm1(-y))
+        if not flags & 2:
+            q = q / (D ** 3)[:, None]
+        o = np.where((D == 1.0)[:, None], c, c * q)
+    return np.where((T == 0.0)[:, None], plain, o)
+
+
 def sky_to_camera(E, interval: int, orientation: Optional[Sequence[float]] = None) -> np.ndarray:
     """Rule 1 in float64: G = (E diag(1, R))^-1, R the orientation's rotation; with interval == 0 the inverse of the spatial block only,
     under a first row and column of the identity."""
@@ -129,12 +170,13 @@ def sky_to_camera(E, interval: int, orientation: Optional[Sequence[float]] = Non
     return g
 
 
-def project(catalogue, E, interval: int, camera: Mapping, doppler: int = 0) -> dict:
+def project(catalogue, E, interval: int, camera: Mapping, doppler: int = 0, temperatures=None) -> dict:
     """Rules 1-4 of the star-field pass in float64.  catalogue: STAR_DTYPE records; E: the sky matrix (Renderer.set_environment_frame);
     interval: the scene's (0 = light delay off); camera: a mapping with width and height and
         mode="pinhole" (default), optionally v_fov (the lens; absent or 0: the reference's) — or
         mode="equirect", optionally h_fov, v_fov, yaw (defaults: the full sphere) —
-    and optionally orientation=(yaw, pitch, roll); doppler: the flags of Renderer.set_doppler (1 shift, 2 beaming).
+    and optionally orientation=(yaw, pitch, roll); doppler: the flags of Renderer.set_doppler (1 shift, 2 beaming); temperatures: kelvin
+    per star as Renderer.set_star_temperatures takes them (0: not thermal), or None: rule 3's S_f becomes thermal_colour.
     Returns a dict of arrays, one entry per star: n (N, 3) the unit camera direction, D the Doppler factor (1 with interval 0),
     rgb (N, 3) the colour after rule 3, X and Y the continuous pixel position (pixel x at X = x for the pinhole, pixel centre at x + 0.5
     for the panorama; NaN where the star is not visible), visible (D finite and > 0, and n.z > 0 for the pinhole)."""
@@ -151,6 +193,10 @@ def project(catalogue, E, interval: int, camera: Mapping, doppler: int = 0) -> d
             D = q[:, 0] / float(interval)
             visible = np.isfinite(D) & (D > 0.0)
             rgb = point_source_colour(doppler, D, cat["rgb"]) if doppler else np.asarray(cat["rgb"], dtype=np.float64)
+            if doppler and temperatures is not None:
+                rgb = thermal_colour(doppler, D, cat["rgb"], temperatures)
+                if doppler & 2:
+                    rgb = rgb / (D ** 2)[:, None]
         else:
             D = np.ones(len(s))
             visible = np.ones(len(s), dtype=bool)

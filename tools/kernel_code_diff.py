@@ -54,6 +54,9 @@ def kernels(code, tmp):
         ins = re.sub(r"\s*//.*$", "", line).strip()
         if ins:
             ks[cur].append(re.sub(r"\s+", " ", ins))
+    for body in ks.values():        # the padding behind a code object's last function is not that function's code
+        while body and body[-1] in ("s_nop 0", "s_code_end"):
+            body.pop()
     notes = subprocess.run([READELF, "--notes", path], capture_output=True, text=True).stdout
     sizes = {}
     for m in re.finditer(r"\.kernarg_segment_size:\s+(\d+).*?\.name:\s+(\S+)", notes, re.S):
