@@ -1,11 +1,13 @@
 """Float64 model of what a pixel goes through besides the octree walk: spheres, cubes, the choice of the nearest object, the boost
-into each rest frame, the flash, the time windows and the light-delay shading — TEST INFRASTRUCTURE.
+into each rest frame, the flash, the time windows, the texture fetch, a mesh hit's normal and (u, v), and the light-delay shading — TEST
+INFRASTRUCTURE.
 
 A helper, no tests in it.  Plain numpy, float64 throughout, written from the geometry and from special relativity, as
 tests/mesh_truth.py is for meshes.  It shares nothing with oracle/, tests/native/*.c or csrc/ but DATA: the Object records' M, InvM,
 Lorentz, InvLorentz, stationaryCam, type, colour, light flag and flash fields (float32 values taken as float64), the per-pixel float32
-directions, the windows, `ambient`, `white_point` and `interval`.  It imports none of those restatements and calls none of their entry
-points.  tests/test_primitive_ground_truth.py holds the CPU restatements against it, tests/test_gpu_primitive_ground_truth.py the device.
+directions, the windows, `ambient`, `white_point` and `interval`, the texture pool's bytes with each object's textureIndex, textureWidth
+and textureHeight, and mesh_truth.arrays' vertices, normals, uvs and triangle words.  It imports none of those restatements and calls
+none of their entry points.  tests/test_primitive_ground_truth.py holds the CPU restatements against it, tests/test_gpu_primitive_ground_truth.py the device.
 
 Rules
 -----
@@ -20,7 +22,15 @@ back, and stationaryCam_i is the camera event in object i's rest frame.
  * Record.  event = stationaryCam + s dir4 in the hit object's rest frame.  Sphere: (u, v) = (0.5 + atan2(z, x) / 2 pi, asin(y) / pi + 0.5)
    of the object-space point.  Cube: (a + 1) / 2 of the two in-face coordinates, in the face order x: (y, z), y: (x, z), z: (x, y).
    The normal is normalize(InvM^T g): g the object-space point for the sphere (OUTWARD also when seen from inside), -sign(d_a) e_a for
-   the cube face on axis a (AGAINST the ray, also from inside).
+   the cube face on axis a (AGAINST the ray, also from inside).  A mesh hit takes both from mesh_truth.hit_attributes: the vertex normals
+   interpolated by the barycentrics, through InvM^T, normalised (as the mesh gives them: not turned against the ray), and the corners' uv
+   entries interpolated likewise.  A mesh without `vt` lines reads the one padded entry the arrays hold at every corner: data, not a rule.
+ * Texture.  Texel (x, y) of a W x H image is its RGB bytes / 255 at byte textureIndex + 3 (W y + x) of the pool.  With U = W u,
+   V = H (1 - v) (row 0 is v = 1; no half-texel offset, no wrap), x0 = min(floor U, W - 1), y0 = min(floor V, H - 1), a = U - x0, b = V - y0,
+   x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1):   sample = (1 - b) [(1 - a) T(x0, y0) + a T(x1, y0)] + b [(1 - a) T(xl, y1) + a T(x1, y1)],
+   xl = x0 — but see "Exception, the reference's" below for the last column.  c, the colour the shading starts from, is the sample, or
+   the object's `color` without a texture, doubled by the flash.  (u, v) outside [0, 1]^2 is outside the rule (the reference reads
+   whatever lies there in the pool): ill-conditioned by name, not modelled.
  * Flash.  The colour doubles where event[0] - period floor(event[0] / period) < duration (period > 0).
  * Windows.  A hit exists iff t0 <= event[0] < t1 on the object's own clock — an object whose candidate hit is outside its window is
    not there for this ray at all (its far wall does not show either).  The same holds for an occluder's crossing event and for a
@@ -34,7 +44,8 @@ back, and stationaryCam_i is the camera event in object i's rest frame.
    tested in its own rest frame with the shape rules above (parameter tau in (0, 1) of the segment), crossing event inside its window.
    Weight k = cos(theta) / (1 + 0.1 r + 0.01 r^2), r the spatial length of D in the hit object's frame.
    colour = c (ambient + [hit object is a light]) + sum_l c k c_l;  interval == 0: colour = c (1 + [is a light]);  a miss: (0.15, 0.15, 0.25).
-   Then Hable's curve over the white point's, clamped at 1.
+   Then Hable's curve over the white point's, clamped at 1.  For a mesh hit the normal of the 0.001 offset, of the facing test and of cos(theta)
+   is the interpolated one, and the hit mesh is an occluder of its own segment through brute_force like any other mesh.
 
 Bounds — derived, not tuned  (u = 2^-24)
 ----------------------------------------
@@ -50,9 +61,25 @@ slack: with s+ and s- those two,
 with tol_p = |d| tol_s the object-space move of the hit point and J the Jacobian of (u, v): 1 / 2 for the cube, 1 / (pi rho) for the
 sphere (v's; u's is half that), rho the distance of the point from the sphere's axis through its poles in object space, plus 8u for the
 4 ulp OpenCL leaves asin and atan2.  u of the sphere is compared modulo 1 (the seam at atan2 = pi).  A mesh hit takes mesh_truth's dt
-(its docstring) for tol_s, the direction budget joining dQ; its (u, v) and colour are not compared.
+(its docstring) for tol_s, the direction budget joining dQ, and tol_normal and tol_uv from mesh_truth.hit_tolerances with the same
+budget as extra_dq and the 4-D ray's direction length as world_dirlen; its (u, v) is compared where mesh_truth.well_conditioned passes the hit.
 The colour's chain (two more boosts with cancellation, the weight, the tonemap) is not derived here: tests/test_primitive_ground_truth.py
-measures it on the CPU oracle and asserts 8 x that value, as tests/test_events_model.py does for the null-cone residual.
+measures it on the CPU oracle and asserts 8 x that value, as tests/test_events_model.py does for the null-cone residual.  Two terms come on
+top of that constant per pixel (`rgb_extra`, absolute, 0 for an untextured sphere or cube), both derived:
+ * texture: the sample is continuous and piecewise bilinear in (U, V), so while W tol_u < 1 and H tol_v < 1
+       |dc|  <=  W tol_u Gx + H tol_v Gy + 8u,
+   Gx / Gy the largest differences between horizontally / vertically adjacent texels of the 3 x 3 neighbourhood of (x0, y0), per channel
+   (in the last column Gy + Gx stands for Gy: the exception below).  Otherwise the pixel has no finite texture term: ill-conditioned.
+ * normal, mesh hits: tol_normal moves cos(theta) of a lamp by at most tol_normal, its term by the factor 1 -+ tol_normal / cos(theta);
+   a lamp with |cos(theta)| <= tol_normal may face either way: ill-conditioned ("light near the horizon of the surface").
+   Both are carried through the tonemap by evaluating the shading at c -+ dc and k (1 -+ rho): Hable's curve is increasing for x >= 0, so
+   the two ends bound the colour — an interval, not an estimate.  tol_normal charges every barycentric error to the most unequal vertex
+   normals (mesh_truth), so the interval is wide on a mesh (median 3 % of a channel on the pear): wrong normals or uv corners are
+   still caught (the tests that bite), a slip of a few per mille in a mesh hit's weight is not.
+END_MARGIN and SHADOW_SLACK, set for spheres and cubes, sufficed for a mesh hit's own segment too: the 0.001 offset is 50 x the slack, a
+start within END_MARGIN of the hit mesh's own triangles is flagged like any crossing at the segment's end, and every committed mesh case keeps the caps
+(the concave bunny 94 %).  The offset taken along the FACE normal instead of the interpolated one moves no well-conditioned pixel of any
+committed case beyond its bound, so no test claims to catch it.
 
 Conditioning
 ------------
@@ -66,12 +93,22 @@ passed).  `well_col` (colours) in addition: the flash phase is more than FLASH_M
 light |cos theta| >= MIN_COS_LIGHT, the emission time is clear of the window's ends, no occluder's verdict differs between grown and
 shrunk (grown there by SHADOW_SLACK more: the segment starts from a float hit point), no occluder crosses within END_MARGIN of the segment's
 ends or through a cube's edge, and the segment's line stays more than mesh_truth.MARGIN (barycentric) from every edge line of a
-mesh occluder's triangles that could decide it.  A channel at the tonemap's clamp is a figure only: min(x, 1) is continuous.
+mesh occluder's triangles that could decide it; a textured sphere's u is more than tol_u from the seam (the fetch does not wrap: columns
+0 and W - 1 meet there discontinuously), (u, v) lies in the unit square, the texture term has a finite bound, the sample is clear of the
+last texel column's discontinuities (below), and a mesh hit passes mesh_truth.well_conditioned (edge margin, |cos|, second hit, t floor).  A channel at the tonemap's clamp is a figure only: min(x, 1) is continuous.
 `candidates` says which objects (or a miss) a float program may name on a pixel that is not well-conditioned: the winners of the three
 models, every object within 2 MIN_GAP of the front, and — where an object's verdict itself may go either way (a window's end, an origin
 at a surface, a ray through a cube's edge) — everything the ray meets, or nothing.
 Exception, the reference's: a ray exactly through a cube's edge is left to neither face (both in-face tests are strict), so a float
 program following the reference misses the cube there; the model hits it, marks the pixel, and allows the miss.
+Exception, the reference's: the texture fetch steps x -> x + 1 (clamped), y -> y + 1 (clamped), x -> x - 1 (clamped at 0) between its four
+taps, so in the LAST column (x0 = W - 1, W >= 2) the lower-left tap is column xl = W - 2, not W - 1: there the sample jumps where U
+crosses W - 1 and where V crosses a row boundary 1 .. H - 1, and down the column it changes by a horizontal difference as well as a
+vertical one.  Oracle and device follow the reference; the model takes xl = max(x1 - 1, 0) as the rule, widens the bound there and marks
+pixels within the (u, v) bound of those lines ("last texel column's boundary").
+
+What the model does not reach: (u, v) outside the unit square; a texture so fine, or a shape so unequal, that the derived (u, v) bound
+spans a texel (the needles of scene_fuzz's ellipsoids under an 800 x 400 texture); a mesh hit's weight to better than tol_normal / cos(theta).
 """
 from __future__ import annotations
 
@@ -232,11 +269,18 @@ def _window_dist(windows, i, t, scale):
 
 # ---- the frame -----------------------------------------------------------------------------------------------------------------------
 
-def context(objs, windows=None, mesh_arrays=None):
+def context(objs, windows=None, mesh_arrays=None, textures=None):
     """What the model reads of a scene: `objs` the Object records (scene.OBJECT_DTYPE; a corrupted copy is as good), `windows` (n, 2) or
-    None, `mesh_arrays` mesh_truth.arrays(scene) when the scene has mesh objects."""
+    None, `mesh_arrays` mesh_truth.arrays(scene) when the scene has mesh objects, `textures` the pool's bytes when an object is textured
+    (default: the arrays' own)."""
     objs = np.asarray(objs).reshape(-1)
     cache = {}
+    if textures is None and mesh_arrays is not None:
+        textures = mesh_arrays.get("textures")
+    arrays = None
+    if mesh_arrays is not None:
+        arrays = dict(mesh_arrays)
+        arrays["objects"] = objs
 
     def mesh(i):
         if i not in cache:
@@ -245,7 +289,8 @@ def context(objs, windows=None, mesh_arrays=None):
             cache[i] = mesh_truth.mesh_triangles(a, i)
         return cache[i]
     w = None if windows is None else np.asarray(windows, dtype=np.float64)
-    return {"objs": objs, "types": object_types(objs), "windows": w, "mesh": mesh, "budget": [_dir_budget(o) for o in objs],
+    return {"objs": objs, "types": object_types(objs), "windows": w, "mesh": mesh, "budget": [_dir_budget(o) for o in objs], "arrays": arrays,
+            "textures": None if textures is None else np.asarray(textures, dtype=np.uint8).reshape(-1),
             "L": objs["Lorentz"].astype(np.float64), "IL": objs["InvLorentz"].astype(np.float64), "sc": objs["stationaryCam"].astype(np.float64)}
 
 
@@ -265,6 +310,7 @@ def _first_hit(ctx, ray4, grow):
         s, f, nr, eg = _shape(ctx, i, o4, d4, grow)
         if not grow and int(ctx["types"][i]) == MESH:
             mesh_tol[i] = _mesh_tol(ctx)
+            ctx.setdefault("mesh_hits", {})[i] = ctx["last_bf"]
         with np.errstate(invalid="ignore"):
             te = o4[:, 0] + np.where(np.isfinite(s), s, 0.0) * d4[:, 0]
         scale = np.abs(o4[:, 0]) + np.where(np.isfinite(s), s, 0.0) * np.abs(ctx["L"][i][0]).sum()
@@ -320,15 +366,50 @@ def tonemap(colour, white_point):
     return np.minimum(hable(colour) / hable(np.asarray(white_point, dtype=np.float64)), 1.0)
 
 
-def frame(objs, dirs, interval, ambient=0.0, white_point=(1.0, 1.0, 1.0), windows=None, mesh_arrays=None, colour=True):
+# ---- the texture fetch ---------------------------------------------------------------------------------------------------------------
+
+def texel_coords(u, v, W, H):
+    """Texel coordinates of (u, v) in a W x H image: (W u, H (1 - v)) — row 0 is v = 1, and there is no half-texel offset."""
+    return W * u, H * (1.0 - v)
+
+
+def texels(pool, index, W, x, y):
+    """RGB / 255 of the texels (x, y) (integer arrays) of the W-wide image whose first byte is byte `index` of the pool: (n, 3).  (An
+    address outside the pool is clamped into it, which only keeps numpy quiet: it happens on no pixel inside the rules.)"""
+    addr = np.asarray(index + 3 * (W * y + x), dtype=np.int64)
+    return pool[np.clip(addr[..., None] + np.arange(3), 0, len(pool) - 1)].astype(np.float64) / 255.0
+
+
+def sample_texture(pool, index, W, H, uv):
+    """The bilinear sample at uv (n, 2) and what its bound needs: (colour (n, 3), Gx (n, 3), Gy (n, 3), x0, y0, U, V) — Gx / Gy the
+    largest differences between horizontally / vertically adjacent texels of the 3 x 3 neighbourhood of (x0, y0), per channel."""
+    Uc, Vc = texel_coords(uv[:, 0], uv[:, 1], W, H)
+    x0 = np.clip(np.floor(Uc), 0, W - 1).astype(np.int64)
+    y0 = np.clip(np.floor(Vc), 0, H - 1).astype(np.int64)
+    a, b = (Uc - x0)[:, None], (Vc - y0)[:, None]
+    x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
+    xl = np.maximum(x1 - 1, 0)                                    # "Exception, the reference's": x0, but W - 2 in the last column
+    t = lambda x, y: texels(pool, index, W, x, y)                 # noqa: E731
+    colour = (1.0 - b) * ((1.0 - a) * t(x0, y0) + a * t(x1, y0)) + b * ((1.0 - a) * t(xl, y1) + a * t(x1, y1))
+    xs = np.clip(x0[:, None] + np.arange(-1, 2), 0, W - 1)
+    ys = np.clip(y0[:, None] + np.arange(-1, 2), 0, H - 1)
+    block = texels(pool, index, W, xs[:, None, :], ys[:, :, None])                 # (n, 3 rows, 3 columns, 3 channels)
+    Gx = np.abs(np.diff(block, axis=2)).max(axis=(1, 2))
+    Gy = np.abs(np.diff(block, axis=1)).max(axis=(1, 2))
+    return colour, Gx, Gy, x0, y0, Uc, Vc
+
+
+def frame(objs, dirs, interval, ambient=0.0, white_point=(1.0, 1.0, 1.0), windows=None, mesh_arrays=None, colour=True, textures=None):
     """The model's frame for per-pixel directions `dirs` (N, 3; float32 values, not necessarily unit).  Returns a dict of (N, ...) arrays:
       object (-1: miss), dist, event (4), uv (2), normal (3), face;  tol_dist, tol_event (4), tol_uv (2);
       well_rec, well_col, candidates (n_obj + 1, N) bool — which objects (last row: a miss) a float program may name where ~well_rec;
-      rgb (3) after the tonemap (nan for mesh / textured hits), lit (n_obj, N) bool per light, shadowed (n_obj, N) per light,
+      tol_normal (mesh hits; 0 elsewhere), mesh_well (mesh_truth's own filter; True off meshes), face_side (-1 / +1: which cube face of the axis);
+      rgb (3) after the tonemap, rgb_extra (3): the derived texture and normal terms through the tonemap, absolute, on top of the
+      measured constant; texel (x0, y0) and clamped_tap (x0 = W - 1 or y0 = H - 1) of textured hits; lit (n_obj, N) bool per light, shadowed (n_obj, N) per light,
       shadow_by (n_obj, N): pixels some light of which occluder i blocks, self_shadow, flashing, windowed_out (a nearer candidate fell
       outside its window), inside (the hit is a far wall seen from inside), `figures`, the conditioning figures by name, and `why`, the
       verdicts drawn from them by name (True: the pixel is ill-conditioned for that reason)."""
-    ctx = context(objs, windows, mesh_arrays)
+    ctx = context(objs, windows, mesh_arrays, textures)
     objs = ctx["objs"]
     n_obj = len(objs)
     dirs = np.asarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -380,6 +461,9 @@ def frame(objs, dirs, interval, ambient=0.0, white_point=(1.0, 1.0, 1.0), window
     figures = {"gap": gap, "same_grown_shrunk": same, "origin_near": near.min(axis=0), "window_dist": wdist.min(axis=0),
                "cube_edge": np.where(hit, edge_fig[win, cols], np.inf)}
     cosv = np.full(N, np.nan)
+    out["tol_normal"] = np.zeros(N)
+    out["face_side"] = np.zeros(N, dtype=np.int64)
+    mesh_well = np.ones(N, dtype=bool)
     inside = np.zeros(N, dtype=bool)
     flashing = np.zeros(N, dtype=bool)
     flash_dist = np.full(N, np.inf)
@@ -411,11 +495,30 @@ def frame(objs, dirs, interval, ambient=0.0, white_point=(1.0, 1.0, 1.0), window
             flash_dist[idx] = np.minimum(np.minimum(np.abs(phase - duration), phase), period - phase) / period / scale
         if kind == MESH:
             cosv[idx] = 1.0
+            _, bf, tris, o3, d3 = ctx["mesh_hits"][i]
+            ids = ctx["mesh"](i)[0]
+            sub = {k: v[idx] for k, v in bf.items()}
+            dlen = np.linalg.norm(d3[idx], axis=1)
+            rays = np.hstack([o3[idx], d3[idx]])
+            extra = ctx["budget"][i] / dlen * (np.linalg.norm(o3[idx], axis=1) + si * dlen)
+            wlen = np.linalg.norm(d4[:, 1:], axis=1)
+            _, nrm, uv = mesh_truth.hit_attributes(ctx["arrays"], i, rays, ids, sub, world_dirlen=wlen)
+            _, tol_n, tol_t = mesh_truth.hit_tolerances(ctx["arrays"], i, rays, ids, tris, sub, extra_dq=extra, world_dirlen=wlen)
+            out["normal"][idx], out["uv"][idx] = nrm, uv
+            out["tol_normal"][idx] = np.where(np.isfinite(tol_n), tol_n, np.inf)
+            out["tol_uv"][idx] = np.where(np.isfinite(tol_t), tol_t, np.inf)[:, None]
+            lo, hi = mesh_truth.root_box(ctx["arrays"], i)
+            sub["t_edge"] = sub["t_edge"] * dlen                   # (brute_force's t is the ray's parameter; the floor is a length)
+            mesh_well[idx] = mesh_truth.well_conditioned(sub, 1e-3 * float(np.linalg.norm(hi - lo)))
             continue
         event, uv, nrm, cos, J, olen, dlen = _attributes(ctx, i, o4, d4, si, out["face"][idx])
         out["uv"][idx], out["normal"][idx], cosv[idx] = uv, nrm, cos
         o3 = _object_ray(objs[i], o4, d4)[0]
         inside[idx] = (np.linalg.norm(o3, axis=1) < 1.0) if kind == SPHERE else (np.abs(o3) < 1.0).all(axis=1)
+        if kind == CUBE:                                           # which of the two faces on that axis: the sign of the hit point's coordinate
+            ax = np.maximum(out["face"][idx], 0)
+            d3 = _object_ray(objs[i], o4, d4)[1]
+            out["face_side"][idx] = np.sign((o3 + si[:, None] * d3)[np.arange(len(idx)), ax]).astype(np.int64)
         spread = np.zeros_like(uv)
         ok = np.isfinite(s_pm[+1][idx]) & np.isfinite(s_pm[-1][idx])
         if ok.any():
@@ -442,6 +545,8 @@ def frame(objs, dirs, interval, ambient=0.0, white_point=(1.0, 1.0, 1.0), window
                       "origin at a surface": (near <= ORIGIN_MARGIN).any(axis=0), "ray through a cube's edge": on_edge, "event time at a window's end": (wdist <= TIME_MARGIN).any(axis=0),
                       "no finite bound": no_bound}
     out["candidates"] = cand
+    out["mesh_well"] = mesh_well
+    out["why"]["mesh hit that mesh_truth calls ill-conditioned"] = ~mesh_well
     out["inside"] = inside & hit
     out["flashing"] = flashing
     out["windowed_out"] = np.zeros(N, dtype=bool)
@@ -461,8 +566,12 @@ def _shade(ctx, out, ray4, interval, ambient, white_point):
     well = out["well_rec"] & (out["figures"]["flash_dist"] > FLASH_MARGIN)
     why = out["why"]
     why["flash phase at its boundary"] = ~(out["figures"]["flash_dist"] > FLASH_MARGIN)
-    for key in ("light near the horizon of the surface", "emission time at a window's end", "occluder verdict turns on the slack", "occluder crossing at the segment's end"):
+    for key in ("light near the horizon of the surface", "emission time at a window's end", "occluder verdict turns on the slack", "occluder crossing at the segment's end",
+                "sphere u at the seam", "uv outside the unit square", "texture term without a finite bound", "last texel column's boundary"):
         why[key] = np.zeros(N, dtype=bool)
+    lin_lo, lin_hi = rgb_lin.copy(), rgb_lin.copy()
+    out["texel"] = np.full((N, 2), -1, dtype=np.int64)
+    out["clamped_tap"] = np.zeros(N, dtype=bool)
     lit = np.zeros((n_obj, N), dtype=bool)
     shadowed = np.zeros((n_obj, N), dtype=bool)
     shadow_by = np.zeros((n_obj, N), dtype=bool)
@@ -474,19 +583,42 @@ def _shade(ctx, out, ray4, interval, ambient, white_point):
         idx = np.flatnonzero(obj_idx == h)
         if not idx.size:
             continue
-        if int(ctx["types"][h]) == MESH or int(objs[h]["textureIndex"]) != -1:
-            rgb_lin[idx] = np.nan
-            continue
-        c = objs[h]["color"].astype(np.float64)[:3][None, :] * np.where(out["flashing"][idx], 2.0, 1.0)[:, None]
+        c = np.tile(objs[h]["color"].astype(np.float64)[:3], (len(idx), 1))
+        dc = np.zeros_like(c)
+        ok_px = np.ones(len(idx), dtype=bool)
+        if int(objs[h]["textureIndex"]) != -1:
+            Wt, Ht = int(objs[h]["textureWidth"]), int(objs[h]["textureHeight"])
+            uv, tol = out["uv"][idx], out["tol_uv"][idx]
+            c, Gx, Gy, x0, y0, Uc, Vc = sample_texture(ctx["textures"], int(objs[h]["textureIndex"]), Wt, Ht, uv)
+            with np.errstate(invalid="ignore"):
+                finite = (Wt * tol[:, 0] < 1.0) & (Ht * tol[:, 1] < 1.0)
+                # in the last column the lower row blends columns W - 2 and W - 1 while the upper row is column W - 1 alone ("Exception,
+                # the reference's"): down a column the sample changes by a vertical AND a horizontal difference
+                in_last = (Wt >= 2) & (x0 == Wt - 1)
+                dc = np.where(finite[:, None], Wt * tol[:, :1] * Gx + Ht * tol[:, 1:] * (Gy + np.where(in_last[:, None], Gx, 0.0)), 0.0) + ROUNDINGS * U
+                outside = ~((uv >= 0.0) & (uv <= 1.0)).all(axis=1)
+                seam = (int(ctx["types"][h]) == SPHERE) & (np.minimum(uv[:, 0], 1.0 - uv[:, 0]) <= tol[:, 0])
+                row = np.rint(Vc)
+                last = (Wt >= 2) & ((np.abs(Uc - (Wt - 1)) <= Wt * tol[:, 0]) | (in_last & (np.abs(Vc - row) <= Ht * tol[:, 1]) & (row >= 1) & (row <= Ht - 1)))
+            why["uv outside the unit square"][idx], why["texture term without a finite bound"][idx] = outside, ~finite
+            why["sphere u at the seam"][idx], why["last texel column's boundary"][idx] = seam, last
+            ok_px &= finite & ~outside & ~seam & ~last
+            out["texel"][idx] = np.stack([x0, y0], axis=1)
+            out["clamped_tap"][idx] = (x0 == Wt - 1) | (y0 == Ht - 1)
+        flash = np.where(out["flashing"][idx], 2.0, 1.0)[:, None]
+        c, dc = c * flash, dc * flash
+        c_lo, c_hi = np.maximum(c - dc, 0.0), c + dc
         is_light = 1.0 if objs[h]["light"] else 0.0
         if interval == 0:
-            rgb_lin[idx] = c * (1.0 + is_light)
+            rgb_lin[idx], lin_lo[idx], lin_hi[idx] = c * (1.0 + is_light), c_lo * (1.0 + is_light), c_hi * (1.0 + is_light)
+            well[idx] &= ok_px
             continue
         col = c * (float(ambient) + is_light)
+        col_lo, col_hi = c_lo * (float(ambient) + is_light), c_hi * (float(ambient) + is_light)
         nrm = out["normal"][idx]
+        tol_n = out["tol_normal"][idx]
         P = out["event"][idx] + np.hstack([np.zeros((len(idx), 1)), 0.001 * nrm])
         X = P @ ctx["IL"][h].T                                    # the start of the segment, camera frame
-        ok_px = np.ones(len(idx), dtype=bool)
         for l in lights:
             if l == h:
                 continue
@@ -508,8 +640,9 @@ def _shade(ctx, out, ray4, interval, ambient, white_point):
                                     f"relative residual {float(res.max()):.3e} > {bound:.3e}")
             null_res = max(null_res, float(res.max()) if res.size else 0.0)
             cos = np.einsum("ij,ij->i", nrm, D_h[:, 1:]) / np.maximum(r, 1e-300)
-            ok_px &= (wd > TIME_MARGIN) & (np.abs(cos) >= MIN_COS_LIGHT)
-            why["light near the horizon of the surface"][idx] |= ~(np.abs(cos) >= MIN_COS_LIGHT)
+            facing_sure = (np.abs(cos) >= MIN_COS_LIGHT) & (np.abs(cos) > tol_n)      # (tol_normal: 0 but for mesh hits)
+            ok_px &= (wd > TIME_MARGIN) & facing_sure
+            why["light near the horizon of the surface"][idx] |= ~facing_sure
             why["emission time at a window's end"][idx] |= ~(wd > TIME_MARGIN)
             light_cos[idx] = np.minimum(light_cos[idx], np.abs(cos))
             todo = np.flatnonzero(on & (cos > 0.0))
@@ -550,18 +683,26 @@ def _shade(ctx, out, ray4, interval, ambient, white_point):
                     self_shadow[idx[todo]] |= verdicts[0]
             ok_px[todo] &= ~unsure
             k = weight(cos[todo], r[todo], rL[todo])
-            add = c[todo] * k[:, None] * objs[l]["color"].astype(np.float64)[:3][None, :]
-            col[todo] += np.where(blocked[:, None], 0.0, add)
+            kc = np.where(blocked, 0.0, k)[:, None] * objs[l]["color"].astype(np.float64)[:3][None, :]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                rho = np.where(tol_n[todo] > 0.0, tol_n[todo] / cos[todo], 0.0)[:, None]      # cos theta moves by tol_normal at the most
+            col[todo] += c[todo] * kc
+            col_lo[todo] += c_lo[todo] * kc * np.maximum(1.0 - rho, 0.0)
+            col_hi[todo] += c_hi[todo] * kc * (1.0 + rho)
             lit[l, idx[todo]] = ~blocked
             shadowed[l, idx[todo]] = blocked
-        rgb_lin[idx] = col
+        rgb_lin[idx], lin_lo[idx], lin_hi[idx] = col, col_lo, col_hi
         well[idx] &= ok_px
     rgb = tonemap(rgb_lin, white_point)
+    # the texture's and the normal's terms through the tonemap: Hable's curve is increasing for x >= 0, so [lo, hi] maps to an interval
+    with np.errstate(invalid="ignore"):
+        extra = np.maximum(tonemap(lin_hi, white_point) - rgb, rgb - tonemap(lin_lo, white_point))
+    out["rgb_extra"] = np.where(np.isnan(extra), np.inf, np.maximum(extra, 0.0))
     with np.errstate(invalid="ignore"):
         raw = hable(rgb_lin) / hable(np.asarray(white_point, dtype=np.float64))
         at_clamp = (np.abs(raw - 1.0) < CLAMP_MARGIN).any(axis=1)
     out["rgb"] = rgb
-    out["well_col"] = well & np.isfinite(rgb).all(axis=1) & (obj_idx >= 0)
+    out["well_col"] = well & np.isfinite(rgb).all(axis=1) & (obj_idx >= 0) & out["mesh_well"] & np.isfinite(out["rgb_extra"]).all(axis=1)
     out["lit"], out["shadowed"], out["shadow_by"], out["self_shadow"] = lit, shadowed, shadow_by, self_shadow
     out["figures"]["light_cos"] = light_cos
     out["figures"]["at_clamp"] = at_clamp
@@ -606,8 +747,7 @@ def compare_records(model, rec, objs):
     types = object_types(np.asarray(objs).reshape(-1))
     is_sphere = np.zeros(N, dtype=bool)
     is_sphere[want >= 0] = types[want[want >= 0]] == SPHERE
-    not_mesh = np.ones(N, dtype=bool)
-    not_mesh[want >= 0] = types[want[want >= 0]] != MESH
+    uv_held = model["mesh_well"]                 # a mesh hit's (u, v) is held to its bound where mesh_truth's own filter passes it
     e_d = np.abs(rec["dist"].astype(np.float64) - model["dist"])
     e_e = np.abs(rec["event"].astype(np.float64) - model["event"])
     e_uv = np.abs(rec["uv"].astype(np.float64) - model["uv"])
@@ -615,7 +755,8 @@ def compare_records(model, rec, objs):
     with np.errstate(invalid="ignore", divide="ignore"):
         r_d = np.where(both, e_d / model["tol_dist"], 0.0)
         r_e = np.where(both[:, None], e_e / model["tol_event"], 0.0)
-        r_uv = np.where((both & not_mesh)[:, None], e_uv / model["tol_uv"], 0.0)
+        # (an exact (u, v) under a bound of 0 — every corner of a vt-less mesh carries the one padded entry — is within it)
+        r_uv = np.where((both & uv_held)[:, None] & (e_uv > 0.0), e_uv / model["tol_uv"], 0.0)
         rel = np.where(both, e_d / np.maximum(model["dist"], 1e-300), 0.0)
     r_d, r_e, r_uv = (np.where(np.isnan(x), np.inf, x) for x in (r_d, r_e, r_uv))
     attr_bad = both & ((r_d > 1.0) | (r_e > 1.0).any(axis=1) | (r_uv > 1.0).any(axis=1))
@@ -633,7 +774,9 @@ def compare_colours(model, rgb, floor=1e-3):
     rgb = np.asarray(rgb, dtype=np.float64).reshape(-1, 3)
     well = model["well_col"]
     with np.errstate(invalid="ignore"):
-        err = np.abs(rgb - model["rgb"]) / np.maximum(model["rgb"], floor)
+        # the per-pixel derived allowance (texture and normal terms, absolute, through the tonemap; 0 where neither applies) comes off
+        # first: what is left is held to the one constant
+        err = np.maximum(np.abs(rgb - model["rgb"]) - np.where(well[:, None], model["rgb_extra"], 0.0), 0.0) / np.maximum(model["rgb"], floor)
     e = np.where(well[:, None], err, 0.0).max(axis=1)
     coloured = (model["object"] >= 0) & np.isfinite(model["rgb"]).all(axis=1)
     miss = (model["object"] < 0) & model["well_rec"]

@@ -2,8 +2,10 @@
  — directly, not through the oracle: the same assertions, constants and caps as
 tests/test_primitive_ground_truth.py, imported from it and not re-measured.  Every kernel form reads the model's verdict: the pinhole in
 every variant tests/test_gpu_parity.py runs (culled and un-culled), a lens below and above 90 degrees, an orientation, the panorama, a
-fisheye ray map, the blocking and the in-flight form, the windowed kernels (colour and events).  Doppler, the sky, MSAA and adaptive
-anti-aliasing stay off.  The model's frames are computed once per case and shared with nothing re-derived here."""
+fisheye ray map, the blocking and the in-flight form, the windowed kernels (colour and events).  Textured and mesh hits carry a colour
+too: the `textured` cases, a textured scene with a textured mesh through every camera form, and the texture fetch at each of its three
+places in the kernels' source.  Doppler, the sky, MSAA and adaptive anti-aliasing stay off.  The model's frames are computed once per
+case and shared with nothing re-derived here."""
 import math
 
 import numpy as np
@@ -141,12 +143,7 @@ def _five(camera="rest", interval=-1):
 CAMERA_FORMS = ("lens60", "lens100", "turned", "panorama", "fisheye")
 
 
-@pytest.mark.parametrize("windowed", [False, True])
-@pytest.mark.parametrize("camera", ["rest", "oblique"])
-@pytest.mark.parametrize("form", CAMERA_FORMS)
-def test_device_agrees_with_the_model_through_every_camera(renderer, wlib, form, camera, windowed):
-    W, H = 128, 72
-    scene = _five(camera)
+def _through_a_camera(renderer, wlib, scene, W, H, label, form, camera, windowed, flip=False):
     objs, mask, view = scene.objects(), None, {}
     if form in ("lens60", "lens100"):
         v = LENS60 if form == "lens60" else LENS100
@@ -161,11 +158,66 @@ def test_device_agrees_with_the_model_through_every_camera(renderer, wlib, form,
         view, dirs, mask = dict(ray_map=m), rc.oracle_dirs(m), rc.has_ray(m)
     windows = None
     if windowed:
-        windows = wo.choose_windows(wlib, scene, W, H, dirs=dirs, objects=None if form != "turned" else objs)
+        windows = wo.choose_windows(wlib, scene, W, H, dirs=dirs, objects=None if form != "turned" else objs, flip=flip)
         assert np.isfinite(windows).any()
     model = truth.model_frame(scene, objs, dirs, windows)
     assert int((model["object"][mask if mask is not None else slice(None)] >= 0).sum()) >= pc.MIN_HIT_PIXELS
     _setup(renderer, scene, W, H, windows=windows, **view)
-    kernels = _check_forms(renderer, f"five {camera} {form}{' windowed' if windowed else ''}", model, objs, (0, 3), mask=mask)
+    kernels = _check_forms(renderer, f"{label} {camera} {form}{' windowed' if windowed else ''}", model, objs, (0, 3), mask=mask)
     assert all((k >= 2000) == windowed for k in kernels), kernels
     _reset(renderer)
+
+
+@pytest.mark.parametrize("windowed", [False, True])
+@pytest.mark.parametrize("camera", ["rest", "oblique"])
+@pytest.mark.parametrize("form", CAMERA_FORMS)
+def test_device_agrees_with_the_model_through_every_camera(renderer, wlib, form, camera, windowed):
+    _through_a_camera(renderer, wlib, _five(camera), 128, 72, "five", form, camera, windowed)
+
+
+@pytest.mark.parametrize("windowed", [False, True])
+@pytest.mark.parametrize("camera", ["rest", "oblique"])
+@pytest.mark.parametrize("form", CAMERA_FORMS)
+def test_device_agrees_with_the_model_on_a_textured_scene_through_every_camera(renderer, wlib, form, camera, windowed):
+    """primitive_cases.TEX_FORMS — the five-object scene with its floor textured by the 3 x 5 and its cube by the noise, and the pear added,
+    textured by the 5 x 3 — at 64 x 36 (the pear is brute-forced).  The panorama's windows are chosen in the other alternation: at rest the
+    first leaves 83 % of its 750 hit pixels well-conditioned for colours at this size, the other 92 % (chosen on the CPU oracle)."""
+    _through_a_camera(renderer, wlib, pc.textured_forms_scene(camera), 64, 36, "textured", form, camera, windowed, flip=(form == "panorama"))
+
+
+# ---- 3. the texture fetch at each of its places in the source ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def diag_renderer():
+    r = Renderer(0, diag=True)
+    yield r
+    r.close()
+
+
+def test_every_texture_fetch_in_the_source_is_reached(renderer, diag_renderer, wlib):
+    """`sample_texture` is called at three places: in `trace` (rpt_kernels.hip.h), which every product kernel shades through — reached by
+    kernels 1, 3, 41 and 43 here, as by the cases and camera forms above; in `shade_uniform` (rpt_persistent.hip.h), the shading of the
+    persistent-workgroup kernels — reached by kernel 60; and in `render_strip_queued` (rpt_persistent.hip.h), the ray-queue kernel —
+    reached by kernel 61.  60 and 61 are measurement arms of the diagnostic library (tests/test_gpu_diag_arms.py), plain pinhole only:
+    each renders the textured scene at rest, and its float RGB is held to the model like any other form (the records are the product's)."""
+    W, H = 64, 36
+    scene = pc.textured_forms_scene("rest")
+    objs = scene.objects()
+    model = truth.model_frame(scene, objs, eo.pinhole_dirs(W, H))
+    _setup(renderer, scene, W, H)
+    product = _check_forms(renderer, "textured rest pinhole", model, objs, (1, 3, 41, 43))
+    rec = renderer.render_events().copy()
+    _reset(renderer)
+    assert product and not product & {60, 61}, product
+    r, reached = diag_renderer, set()
+    for variant in (60, 61):
+        r.set_variant(variant)
+        r.upload_scene(scene)
+        r.set_scene_params(scene, W, H)
+        r.set_rows(0, 1, False)
+        r.set_output(None)
+        r.set_debug_rgb(True)
+        r.render()
+        assert r.last_variant() == variant
+        reached.add(r.last_variant())
+        truth.check_frame(f"textured rest pinhole kernel {variant}", model, objs, rec.reshape(-1), r.read_debug_rgb().copy().reshape(-1, 3))
+    assert reached == {60, 61}, reached
