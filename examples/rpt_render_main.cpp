@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -39,6 +39,14 @@
 // rest-frame distance, bias=B (>= 0, in units of distance) lets particles that sit ON a surface show.  The host runs the colour frame, an
 // event frame of the same view and the particle pass — behind the stars, under the overlay's lines — and reports the particles seen and
 // the pixels changed on stderr.  It excludes --projection (a ray map).
+//
+// --segments FILE[:inverse_square][:bias=B][:pieces=N] adds straight rods that ride the scene's objects (rpt_set_segments,
+// rpt_set_segment_options, rpt_render_segments; not in the reference): FILE holds raw 48-byte rpt_segment records
+// (relativitypathtracer_amd/segments.py `save` writes them), each rod at rest in the rest frame of the object it names, its colour per unit
+// rest-frame length; inverse_square and bias=B as for --particles; pieces=N (1, 2, 4, ..., 64; default 16) is the number of parts a rod is
+// cut into — its N + 1 nodes are placed exactly, light delay and all, and joined by chords.  The host runs the colour frame, an event
+// frame of the same view and the segment pass — behind the particles, under the overlay's lines — and reports the pieces drawn and the
+// pixels changed on stderr.  It excludes --projection (a ray map).
 //
 // --doppler shift|beaming|both turns the Doppler shift and the searchlight beaming on for every pass (rpt_set_doppler; not in the
 // reference).  --star-temperatures FILE and --particle-temperatures FILE make the stars of --stars and the particles of --particles
@@ -199,6 +207,50 @@ static bool parse_particles(const char *spec, std::string *path, int *flags, flo
     return true;
 }
 
+// --segments FILE[:inverse_square][:bias=B][:pieces=N]: the file name, the flags, the bias and the pieces; false (and a message) for
+// what it cannot read
+static bool parse_segments(const char *spec, std::string *path, int *flags, float *bias, int *pieces) {
+    const std::string s(spec);
+    size_t at = s.find(':');
+    *path = s.substr(0, at);
+    *flags = 0;
+    *bias = 0.0f;
+    *pieces = 16;
+    if (path->empty()) {
+        std::fprintf(stderr, "--segments: '%s' names no file\n", spec);
+        return false;
+    }
+    while (at != std::string::npos) {
+        const size_t next = s.find(':', at + 1);
+        const std::string option = s.substr(at + 1, next == std::string::npos ? std::string::npos : next - at - 1);
+        if (option == "inverse_square") {
+            *flags |= RPT_SEGMENTS_INVERSE_SQUARE;
+        } else if (option.compare(0, 5, "bias=") == 0) {
+            char *end = nullptr;
+            const double b = std::strtod(option.c_str() + 5, &end);
+            if (end == option.c_str() + 5 || *end != '\0' || !std::isfinite(b) || b < 0.0) {
+                std::fprintf(stderr, "--segments: '%s' in '%s' is not a bias (a finite number >= 0)\n", option.c_str() + 5, spec);
+                return false;
+            }
+            *bias = (float)b;
+        } else if (option.compare(0, 7, "pieces=") == 0) {
+            char *end = nullptr;
+            const long n = std::strtol(option.c_str() + 7, &end, 10);
+            if (end == option.c_str() + 7 || *end != '\0' || n < 1 || n > 64 || (n & (n - 1)) != 0) {
+                std::fprintf(stderr, "--segments: '%s' in '%s' is not a number of pieces (1, 2, 4, 8, 16, 32 or 64)\n", option.c_str() + 7, spec);
+                return false;
+            }
+            *pieces = (int)n;
+        } else {
+            std::fprintf(stderr, "--segments: unknown option '%s' (inverse_square, bias=B, pieces=N)\n", option.c_str());
+            return false;
+        }
+        at = next;
+    }
+    std::fprintf(stderr, "segments: file %s, inverse square %d, depth bias %g, pieces %d\n", path->c_str(), *flags & RPT_SEGMENTS_INVERSE_SQUARE, (double)*bias, *pieces);
+    return true;
+}
+
 int main(int argc, char **argv) {
     // the free-look options (degrees), taken out of argv; what is left is positional
     float ypr[3] = {0, 0, 0}, v_fov = 0;
@@ -209,6 +261,9 @@ int main(int argc, char **argv) {
     std::string particles_path;
     int particle_flags = 0;
     float particle_bias = 0.0f;
+    std::string segments_path;
+    int segment_flags = 0, segment_pieces = 16;
+    float segment_bias = 0.0f;
     int aa_n = 1, aa_threshold = 8;
     rpt_overlay_desc overlay;
     std::memset(&overlay, 0, sizeof overlay);
@@ -244,6 +299,12 @@ int main(int argc, char **argv) {
             }
             else if (!std::strcmp(argv[i], "--stars")) {
                 std::fprintf(stderr, "--stars needs a file name (raw 32-byte rpt_star records)\n");
+                return 2;
+            }
+            else if (has_value && !std::strcmp(argv[i], "--segments")) {
+                if (!parse_segments(argv[++i], &segments_path, &segment_flags, &segment_bias, &segment_pieces)) return 2;
+            } else if (!std::strcmp(argv[i], "--segments")) {
+                std::fprintf(stderr, "--segments needs a value: FILE[:inverse_square][:bias=B][:pieces=N] (raw 48-byte rpt_segment records)\n");
                 return 2;
             }
             else if (has_value && !std::strcmp(argv[i], "--particles")) {
@@ -285,7 +346,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -312,6 +373,18 @@ int main(int argc, char **argv) {
         if (f) std::fclose(f);
         if (!whole || particle_set.empty()) {
             std::fprintf(stderr, "--particles: %s does not hold a whole number (> 0) of 32-byte rpt_particle records\n", particles_path.c_str());
+            return 2;
+        }
+    }
+    std::vector<rpt_segment> segment_set;                        // --segments: the raw records
+    if (!segments_path.empty()) {
+        std::FILE *f = std::fopen(segments_path.c_str(), "rb");
+        rpt_segment s;
+        while (f && std::fread(&s, sizeof s, 1, f) == 1) segment_set.push_back(s);
+        const bool whole = f && std::feof(f) && std::ftell(f) == (long)(segment_set.size() * sizeof(rpt_segment));
+        if (f) std::fclose(f);
+        if (!whole || segment_set.empty()) {
+            std::fprintf(stderr, "--segments: %s does not hold a whole number (> 0) of 48-byte rpt_segment records\n", segments_path.c_str());
             return 2;
         }
     }
@@ -470,6 +543,20 @@ int main(int argc, char **argv) {
             return 1;
         }
         std::fprintf(stderr, "particles: %llu of %zu seen, %llu of %lld pixels changed\n", counts[0], particle_set.size(), counts[1], (long long)width * height);
+    }
+    if (!segment_set.empty()) {                                  // rods riding the objects, depth-tested against the event frame
+        unsigned long long counts[2] = {0, 0};
+        rc = events_rendered ? 0 : rpt_render_events(last);
+        events_rendered = !rc;
+        if (!rc) rc = rpt_set_segment_options(last, segment_flags, segment_bias, segment_pieces);
+        if (!rc) rc = rpt_set_segments(last, segment_set.data(), (int)segment_set.size());
+        if (!rc) rc = rpt_render_segments(last);
+        if (!rc) rc = rpt_last_segments(last, counts);
+        if (rc) {
+            std::fprintf(stderr, "segments: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::fprintf(stderr, "segments: %llu of %zu pieces drawn, %llu of %lld pixels changed\n", counts[0], segment_set.size() * (size_t)segment_pieces, counts[1], (long long)width * height);
     }
     if (overlay.layers) {                                        // lines on that frame, from an event frame of the same view
         unsigned long long changed = 0;

@@ -47,7 +47,10 @@
  * sources in the sky's rest frame, aberrated, Doppler-shifted and beamed as points: rpt_set_stars, rpt_render_stars /
  * rpt_render_stars_async and rpt_last_stars ("Star-field pass"), and the opt-in particle pass — point sources at a finite
  * distance, each at rest in an object's frame, seen with light delay and hidden behind what stands in front: rpt_set_particles,
- * rpt_set_particle_options, rpt_render_particles / rpt_render_particles_async and rpt_last_particles ("Particle pass").
+ * rpt_set_particle_options, rpt_render_particles / rpt_render_particles_async and rpt_last_particles ("Particle pass"),
+ * and the opt-in segment pass — straight rods at rest in an object's frame, drawn as a continuum of such point sources, so that a
+ * rod bends on the screen as light delay bends it: rpt_set_segments, rpt_set_segment_options, rpt_render_segments /
+ * rpt_render_segments_async and rpt_last_segments ("Segment pass").
  *
  * There is no CPU or OpenCL fallback: without a gfx950 device rpt_create fails.
  */
@@ -727,6 +730,49 @@ int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]);
  * was (kernels 1120 / 1130); with one, the splat is kernel 1122 / 1132: one more 4-byte load per source. */
 int rpt_set_star_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count);
 int rpt_set_particle_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count);
+
+/* The segment pass (not in the reference; DESIGN.md §22 "Segment pass" gives every rule operation by operation): straight rods, each at
+ * rest in the rest frame of one entry of Object[] — a lattice of rods, a wire-frame box, a ruler's edge, the track of a piecewise
+ * worldline — drawn as a CONTINUUM OF PARTICLES: rgb is a linear colour per unit rest-frame length, and the element dl of a rod is a
+ * particle (above) of colour rgb dl.  Every point of a rod is seen at its own emission time, so a rod is not straight on the screen: it
+ * is cut into `pieces` equal parts, the pieces + 1 nodes are placed by the particle pass's rules 1-4, and between two placed nodes the
+ * image is the chord, sampled about once per pixel.  A fifth sibling of the overlay, readout, star and particle passes with the same
+ * discipline: opt-in, per context, not shared by rpt_share_scene; after a colour frame and an event frame of the same view; in place
+ * into the R, G, B bytes.  Rods light nothing, cast no shadow and hide nothing: they add.
+ *
+ * In short, P = pieces, d = b - a, len = |d| / P (a segment whose len is not > 0 or not finite is skipped); node j = a + d (j / P),
+ * node P = b; a node is placed as a particle at that position of colour rgb (Doppler, beaming with the point-source / D^2, the optional
+ * / r^2, the window test, the projection with its n.z > 0 and 1e9 tests).  A piece needs both its nodes placed; on the panorama its
+ * second node is brought within half a period Px = W (2 pi / h_fov) of the first; L = max(|X1 - X0|, |Y1 - Y0|) must be <=
+ * RPT_SEGMENT_MAX_STEPS; m = max(1, ceil(L)) samples at u = (s + 0.5) / m interpolate X, Y, dist and the colour linearly, each of
+ * colour c len / m, and are splatted as particles are: four bilinear taps, the seam wrap (once, either way), the frame test, the depth
+ * test dist - depth_bias < record.dist or a miss, the star pass's accumulator; then the particle pass's resolve (kernel 1131).
+ *
+ * rpt_set_segments copies the set and writes it to the device once, in stream order; NULL or count 0 switches the pass off.
+ * RPT_ERR_ARG, message "rpt_set_segments: ...", the previous set kept: a component of a, b or rgb that is not finite, a negative colour,
+ * object < 0, count < 0, count * pieces > 2^21 with the pieces in force (a piece adds to one accumulator word at most 4 times, each add
+ * at most 2^40: 2^21 * 4 * 2^40 < 2^64).  rpt_set_segment_options: flags = RPT_SEGMENTS_INVERSE_SQUARE or 0, depth_bias >= 0 in units
+ * of dist, pieces one of 1, 2, 4, 8, 16, 32, 64 (defaults 0, 0.0f, 16); RPT_ERR_ARG for anything else and for count * pieces > 2^21
+ * with the set held.  rpt_render_segments[_async] refuses what rpt_render_particles refuses (the ray-map camera, an interval other than
+ * -1 or 0, a set whose largest object index is not below the object count), with messages that start "rpt_render_segments:"; the
+ * context stays usable.  With no set the call launches nothing and reports zeros.  Calling it twice adds the segments twice.
+ * rpt_last_segments: of the last FINISHED pass, out[0] = pieces with at least one tap of at least one sample inside the frame that
+ * passes the depth test, out[1] = pixels whose bytes changed.
+ *
+ * Limits: clipping at the pinhole's plane and at a window's edge has the granularity of a piece; between nodes the image is a chord of
+ * the true curve; a panorama piece that passes over a pole or spans half the circle is drawn badly; particle temperatures do not apply;
+ * the ray-map camera is refused; the number of pieces is fixed per set, not adaptive. */
+/* rpt_segment: include/rpt_layout.h (48 B) */
+#define RPT_SEGMENTS_INVERSE_SQUARE 1   /* divide the colour by the squared rest-frame distance r^2 */
+#define RPT_SEGMENT_MAX_STEPS 1024      /* a piece longer than this on the screen, in pixels along its longer axis, is dropped */
+int rpt_set_segments(rpt_ctx *ctx, const rpt_segment *segments_or_null, int count);
+int rpt_set_segment_options(rpt_ctx *ctx, int flags, float depth_bias, int pieces);   /* defaults 0, 0.0f, 16 */
+int rpt_render_segments(rpt_ctx *ctx);          /* enqueue and wait */
+int rpt_render_segments_async(rpt_ctx *ctx);    /* enqueue; rpt_sync waits */
+int rpt_last_segments(rpt_ctx *ctx, unsigned long long out[2]);   /* pieces drawn, pixels changed */
+/* Measurement only (tools/segments_cost.py): as rpt_set_particles_measurement / rpt_last_particles_ms, for the segment pass's two kernels. */
+int rpt_set_segments_measurement(rpt_ctx *ctx, int timed);
+int rpt_last_segments_ms(rpt_ctx *ctx, float ms[2]);
 
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);

@@ -93,6 +93,16 @@ typedef struct rpt_particle {     /* 32 B: two aligned 16-byte loads */
     float   _pad;
 } rpt_particle;
 
+/* One rod of the segment pass (not in the reference; include/rpt.h, rpt_set_segments, states the rules) */
+typedef struct rpt_segment {      /* 48 B: three aligned 16-byte loads */
+    float   a[3];                 /* one end, in the REST FRAME of Object[object]: the coordinates of rpt_event.event[1..3] */
+    int32_t object;               /* index into the context's Object[]: the frame the rod is at rest in */
+    float   b[3];                 /* the other end, same frame */
+    float   _pad0;
+    float   rgb[3];               /* linear colour at rest PER UNIT REST-FRAME LENGTH, on the scale of object colours */
+    float   _pad1;
+} rpt_segment;
+
 /*
  * The eight read-only scene arrays the reference uploads once (main.cpp:33-55), in the
  * reference's layouts, as {pointer, element count} pairs.  Zero-length arrays are legal and
@@ -150,5 +160,11 @@ RPT_SA(offsetof(rpt_readout, on_rgba) == 28, "on_rgba");
 RPT_SA(sizeof(rpt_particle) == 32, "particle is 32 B");
 RPT_SA(offsetof(rpt_particle, object) == 12, "object");
 RPT_SA(offsetof(rpt_particle, rgb) == 16, "rgb");
+RPT_SA(sizeof(rpt_segment) == 48, "segment is 48 B");
+RPT_SA(offsetof(rpt_segment, object) == 12, "object");
+RPT_SA(offsetof(rpt_segment, b) == 16, "b");
+RPT_SA(offsetof(rpt_segment, _pad0) == 28, "_pad0");
+RPT_SA(offsetof(rpt_segment, rgb) == 32, "rgb");
+RPT_SA(offsetof(rpt_segment, _pad1) == 44, "_pad1");
 
 #endif /* RPT_LAYOUT_H */

@@ -66,6 +66,11 @@ class Particle(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("object", C.c_int32), ("rgb", C.c_float * 3), ("_pad", C.c_float)]
 
 
+class Segment(C.Structure):
+    """rpt_segment of include/rpt_layout.h (48 B): one rod of the segment pass, at rest in the frame of Object[object]."""
+    _fields_ = [("a", C.c_float * 3), ("object", C.c_int32), ("b", C.c_float * 3), ("_pad0", C.c_float), ("rgb", C.c_float * 3), ("_pad1", C.c_float)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -253,6 +258,13 @@ HIP_SYMBOLS = {
     "rpt_last_particles_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_set_star_temperatures": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "rpt_set_particle_temperatures": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "rpt_set_segments": (C.c_int, [C.c_void_p, C.POINTER(Segment), C.c_int]),
+    "rpt_set_segment_options": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int]),
+    "rpt_render_segments": (C.c_int, [C.c_void_p]),
+    "rpt_render_segments_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_segments": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_segments_measurement": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_last_segments_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -29,8 +29,10 @@
 #include "rpt_stars_host.hpp"
 #include "rpt_particles.hip.h"      /* behind the stars: kernels 1130 and 1131 are the translation unit's last */
 #include "rpt_particles_host.hpp"
-#include "rpt_thermal.hip.h"        /* behind the particles: the thermal probe and kernels 1122 and 1132 are the translation unit's last */
+#include "rpt_thermal.hip.h"        /* behind the particles: the thermal probe and kernels 1122 and 1132 */
 #include "rpt_thermal_host.hpp"
+#include "rpt_segments.hip.h"       /* behind the thermal kernels: kernel 1140 is the translation unit's last */
+#include "rpt_segments_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -76,7 +78,7 @@ struct Tally {
     size_t words = 1, spare = 0;                      // (as tally_ready was given them)
     bool pending = false;                             // a copy has been enqueued since `value` was read
 };
-enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_COUNT };     // rpt_ctx::tally
+enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_SEGMENTS, TALLY_COUNT };     // rpt_ctx::tally
 
 // What the last frame of one kind (colour, event) was enqueued for, as a pass over both asks (frames_of_this_view)
 struct FrameMark {
@@ -245,7 +247,7 @@ struct rpt_ctx {
     // what the passes report, by TALLY_*: the refined pixels of an adaptive frame (rpt_last_aa_refined); the overlay's changed pixels and,
     // as spare bytes, the bit pattern of the frame's largest delay (rpt_last_overlay_pixels); the readouts' changed pixels
     // (rpt_last_readout_pixels); {stars with a tap inside the frame, changed pixels} (rpt_last_stars); {particles seen, changed pixels}
-    // (rpt_last_particles)
+    // (rpt_last_particles); {pieces drawn, changed pixels} (rpt_last_segments)
     Tally tally[TALLY_COUNT];
     // rpt_set_readouts / rpt_render_readouts (not in the reference): the readout pass, per context, never shared
     std::vector<rpt_readout> readouts;                // one per entry of Object[]; empty = none set
@@ -274,6 +276,17 @@ struct rpt_ctx {
     StagedUpload star_thermal_table;                  // one float per star, written once per rpt_set_star_temperatures
     int particle_thermal_count = 0;
     StagedUpload particle_thermal_table;
+    // rpt_set_segments / rpt_render_segments (not in the reference): the segment pass, per context, never shared; its sums
+    // go through star_acc too
+    int segment_count = 0;                            // 0 = no set: the pass is off
+    int segment_largest_object = -1;                  // held against object_count at every launch
+    StagedUpload segment_table;                       // rpt_segment per rod, in the caller's order; written once per rpt_set_segments
+    int segment_flags = 0;                            // rpt_set_segment_options
+    float segment_depth_bias = 0.0f;
+    int segment_pieces = rptg::kDefaultPieces;
+    bool segment_timed = false;                       // rpt_set_segments_measurement
+    hipEvent_t segment_marks[3] = {nullptr, nullptr, nullptr};
+    bool segment_marked = false;
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -2085,6 +2098,40 @@ int launch_stars(rpt_ctx *ctx) {
     return frame_pass(ctx, "rpt_render_stars", ctx->star_count != 0, TALLY_STARS, enqueue_stars);
 }
 
+// What the particle pass and the segment pass hand their kernels alike: the objects and their windows, the records, the accumulator, the
+// tally, the view as rule 4 projects it, and the resolve's arguments (kernel 1131).  The set, its count and its options are the caller's.
+void point_pass_args(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events, rptd::ParticleArgs &a, rptd::ParticleResolveArgs &b) {
+    std::memset((void *)&a, 0, sizeof a);
+    a.objects = (const rpt_object *)ctx->objects.ptr;
+    if (!ctx->windows.empty())          // (their count is the Object[]'s: the frames of this view were launched with them)
+        a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
+    a.events = events;
+    a.acc = (unsigned long long *)ctx->star_acc.ptr;
+    a.counts = (unsigned long long *)tally.device.ptr;
+    a.object_count = ctx->object_count;
+    a.width = ctx->width;
+    a.height = ctx->height;
+    a.interval = ctx->interval;
+    a.doppler = ctx->interval != 0 ? ctx->doppler : 0;
+    if (ctx->projection == RPT_PROJECTION_EQUIRECT) {
+        a.camera = RPT_STARS_EQUIRECT;
+        a.h_fov = ctx->projection_params[0];
+        a.v_fov = ctx->projection_params[1];
+        a.yaw = ctx->projection_params[2];
+        a.wrap = a.h_fov == (float)(2.0 * RPT_PI_D) ? 1 : 0;
+    } else {
+        const float s = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
+        a.plane_x = s * ((float)ctx->width / (float)ctx->height);
+        a.plane_y = s;
+    }
+    std::memset((void *)&b, 0, sizeof b);
+    b.acc = a.acc;
+    b.out16 = out16;
+    b.counts = a.counts;
+    b.pixels = (size_t)ctx->width * (size_t)ctx->height;
+    for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
+}
+
 // One particle pass on the context's stream (kernels 1130 and 1131): three refusals of its own — the last is what keeps every index
 // the splat follows inside Object[] —, the accumulator it shares with the stars, the two launches
 int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
@@ -2104,40 +2151,12 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
             if (!m) RPT_HIP(ctx, hipEventCreate(&m));
 
     rptd::ParticleArgs a;
-    std::memset((void *)&a, 0, sizeof a);
+    rptd::ParticleResolveArgs b;
+    point_pass_args(ctx, tally, out16, events, a, b);
     a.particles = (const rpt_particle *)ctx->particle_table.device.ptr;
-    a.objects = (const rpt_object *)ctx->objects.ptr;
-    if (!ctx->windows.empty())          // (their count is the Object[]'s: the frames of this view were launched with them)
-        a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
-    a.events = events;
-    a.acc = (unsigned long long *)ctx->star_acc.ptr;
-    a.counts = (unsigned long long *)tally.device.ptr;
     a.count = ctx->particle_count;
-    a.object_count = ctx->object_count;
-    a.width = ctx->width;
-    a.height = ctx->height;
-    a.interval = ctx->interval;
-    a.doppler = ctx->interval != 0 ? ctx->doppler : 0;
     a.inverse_square = ctx->particle_flags & RPT_PARTICLES_INVERSE_SQUARE;
     a.depth_bias = ctx->particle_depth_bias;
-    if (ctx->projection == RPT_PROJECTION_EQUIRECT) {
-        a.camera = RPT_STARS_EQUIRECT;
-        a.h_fov = ctx->projection_params[0];
-        a.v_fov = ctx->projection_params[1];
-        a.yaw = ctx->projection_params[2];
-        a.wrap = a.h_fov == (float)(2.0 * RPT_PI_D) ? 1 : 0;
-    } else {
-        const float s = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
-        a.plane_x = s * ((float)ctx->width / (float)ctx->height);
-        a.plane_y = s;
-    }
-    rptd::ParticleResolveArgs b;
-    std::memset((void *)&b, 0, sizeof b);
-    b.acc = a.acc;
-    b.out16 = out16;
-    b.counts = a.counts;
-    b.pixels = pixels;
-    for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
 
     if (int rc = tally_zero(ctx, tally)) return rc;
     if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[0], ctx->stream));
@@ -2160,6 +2179,58 @@ int launch_particles(rpt_ctx *ctx) {
     return frame_pass(ctx, "rpt_render_particles", ctx->particle_count != 0, TALLY_PARTICLES, enqueue_particles);
 }
 
+// One segment pass on the context's stream (kernels 1140 and 1131): the particle pass's refusals — the last is what keeps every index
+// the splat follows inside Object[] —, the accumulator it shares with the stars and the particles, the two launches.  One lane per piece.
+int enqueue_segments(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    if (ctx->projection == RPT_PROJECTION_RAYMAP)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_segments: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a node with");
+    if (ctx->interval != -1 && ctx->interval != 0)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_segments: interval is " + std::to_string(ctx->interval) + "; the light cone has a closed form for -1 and 0 only");
+    if (ctx->segment_largest_object >= ctx->object_count)
+        return fail(ctx, RPT_ERR_ARG, "rpt_render_segments: the set names object " + std::to_string(ctx->segment_largest_object) + ", the Object[] holds " + std::to_string(ctx->object_count));
+    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
+    if (int rc = accumulator_ready(ctx, pixels)) return rc;
+    if (int rc = tally_ready(ctx, tally, 2)) return rc;
+    if (ctx->segment_timed)
+        for (hipEvent_t &m : ctx->segment_marks)
+            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
+
+    rptd::SegmentArgs a;
+    std::memset((void *)&a, 0, sizeof a);
+    rptd::ParticleResolveArgs b;
+    point_pass_args(ctx, tally, out16, events, a.p, b);
+    a.p.count = ctx->segment_count;
+    a.p.inverse_square = ctx->segment_flags & RPT_SEGMENTS_INVERSE_SQUARE;
+    a.p.depth_bias = ctx->segment_depth_bias;
+    a.segments = (const rpt_segment *)ctx->segment_table.device.ptr;
+    a.pieces = ctx->segment_pieces;
+    while ((1 << a.shift) < a.pieces) a.shift++;
+    if (a.p.camera == RPT_STARS_EQUIRECT) a.period = (float)ctx->width * ((float)(2.0 * RPT_PI_D) / a.p.h_fov);
+
+    const void *splat = (const void *)rptd::rpt_segments_splat_kernel;
+#ifdef RPT_DIAGNOSTICS
+    if (ctx->variant == 1141) splat = (const void *)rptd::rpt_segments_splat_loop_kernel;      // the measurement arm: a loop per lane
+#endif
+    const unsigned lanes = (unsigned)ctx->segment_count * (unsigned)ctx->segment_pieces;      // <= 2^21 (rptg::kMaxPieces)
+    if (int rc = tally_zero(ctx, tally)) return rc;
+    if (ctx->segment_timed) RPT_HIP(ctx, hipEventRecord(ctx->segment_marks[0], ctx->stream));
+    void *splat_args[] = {(void *)&a};
+    (void)hipLaunchKernel(splat, dim3((lanes + 255u) / 256u), dim3(256), splat_args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    if (ctx->segment_timed) RPT_HIP(ctx, hipEventRecord(ctx->segment_marks[1], ctx->stream));
+    void *resolve_args[] = {(void *)&b};
+    (void)hipLaunchKernel((const void *)rptd::rpt_particles_resolve_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
+    RPT_HIP(ctx, hipGetLastError());
+    if (ctx->segment_timed) RPT_HIP(ctx, hipEventRecord(ctx->segment_marks[2], ctx->stream));
+    ctx->segment_marked = ctx->segment_timed;
+    return RPT_OK;
+}
+
+int launch_segments(rpt_ctx *ctx) {
+    if (ctx->segment_count == 0) ctx->segment_marked = false;
+    return frame_pass(ctx, "rpt_render_segments", ctx->segment_count != 0, TALLY_SEGMENTS, enqueue_segments);
+}
+
 // The event pass and what it leaves for rpt_pick, rpt_read_events and the passes over the frame
 int launch_event_frame(rpt_ctx *ctx) {
     if (!ctx->ev_events) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
@@ -2170,7 +2241,7 @@ int launch_event_frame(rpt_ctx *ctx) {
     return RPT_OK;
 }
 
-// rpt_render_events, _overlay, _readouts, _stars, _particles and their _async forms: one pass on the context's stream, waited for or not
+// rpt_render_events, _overlay, _readouts, _stars, _particles, _segments and their _async forms: one pass on the context's stream, waited for or not
 int render_pass(rpt_ctx *ctx, int (*launch_pass)(rpt_ctx *), bool wait) {
     if (!ctx) return RPT_ERR_ARG;
     RPT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2251,10 +2322,11 @@ void rpt_destroy(rpt_ctx *ctx) {
     for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->star_acc})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table, &ctx->particle_table, &ctx->star_thermal_table, &ctx->particle_thermal_table}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table, &ctx->particle_table, &ctx->star_thermal_table, &ctx->particle_thermal_table, &ctx->segment_table}) release(*u);
     for (Tally &t : ctx->tally) release(t);
     for (hipEvent_t m : ctx->star_marks) if (m) (void)hipEventDestroy(m);
     for (hipEvent_t m : ctx->particle_marks) if (m) (void)hipEventDestroy(m);
+    for (hipEvent_t m : ctx->segment_marks) if (m) (void)hipEventDestroy(m);
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -3393,6 +3465,67 @@ int rpt_set_star_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int cou
 int rpt_set_particle_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) {
     if (!ctx) return RPT_ERR_ARG;
     return set_temperatures(ctx, "rpt_set_particle_temperatures", ctx->particle_thermal_table, ctx->particle_thermal_count, kelvin_or_null, count);
+}
+
+// The set goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused for its
+// arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no set.
+int rpt_set_segments(rpt_ctx *ctx, const rpt_segment *segments_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (count < 0 || !rptg::load_fault(count, ctx->segment_pieces).empty())
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_segments: " + rptg::set_fault(nullptr, count, ctx->segment_pieces));
+    if (!segments_or_null || count == 0) {
+        ctx->segment_count = 0;
+        ctx->segment_largest_object = -1;
+        return RPT_OK;
+    }
+    const std::string fault = rptg::set_fault(segments_or_null, count, ctx->segment_pieces);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_segments: " + fault);
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    void *host = nullptr;
+    int rc = staged_host(ctx, ctx->segment_table, (size_t)count * sizeof(rpt_segment), &host);
+    if (!rc) {
+        rptg::prepare_set(segments_or_null, count, (rpt_segment *)host);
+        rc = staged_copy(ctx, ctx->segment_table);
+    }
+    if (rc) {
+        ctx->segment_count = 0;
+        ctx->segment_largest_object = -1;
+        return rc;
+    }
+    ctx->segment_count = count;
+    ctx->segment_largest_object = rptg::largest_object(segments_or_null, count);
+    return RPT_OK;
+}
+
+int rpt_set_segment_options(rpt_ctx *ctx, int flags, float depth_bias, int pieces) {
+    if (!ctx) return RPT_ERR_ARG;
+    const std::string fault = rptg::options_fault(flags, depth_bias, pieces, ctx->segment_count);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_segment_options: " + fault);
+    ctx->segment_flags = flags;
+    ctx->segment_depth_bias = depth_bias;
+    ctx->segment_pieces = pieces;
+    return RPT_OK;
+}
+
+int rpt_render_segments_async(rpt_ctx *ctx) { return render_pass(ctx, launch_segments, false); }
+int rpt_render_segments(rpt_ctx *ctx) { return render_pass(ctx, launch_segments, true); }
+
+int rpt_last_segments(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_SEGMENTS, out, 2); }
+
+int rpt_set_segments_measurement(rpt_ctx *ctx, int timed) {
+    if (!ctx) return RPT_ERR_ARG;
+    ctx->segment_timed = timed != 0;
+    return RPT_OK;
+}
+
+int rpt_last_segments_ms(rpt_ctx *ctx, float ms[2]) {
+    if (!ctx || !ms) return RPT_ERR_ARG;
+    if (!ctx->segment_marked) return fail(ctx, RPT_ERR_STATE, "rpt_last_segments_ms: the last segment pass was not timed (rpt_set_segments_measurement)");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    RPT_HIP(ctx, hipEventSynchronize(ctx->segment_marks[2]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->segment_marks[0], ctx->segment_marks[1]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->segment_marks[1], ctx->segment_marks[2]));
+    return RPT_OK;
 }
 
 void *rpt_output_ptr(rpt_ctx *ctx) {

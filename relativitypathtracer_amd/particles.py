@@ -83,17 +83,23 @@ def project(particles, objects, camera: Mapping, W: int, H: int, interval: int =
     event's displacement from the camera event in the camera frame, n (N, 3) and rgb (N, 3) the colour after rule 3."""
     if interval not in (-1, 0):
         raise ValueError("project: the light cone has a closed form for interval -1 and 0 only")
-    options = dict(options or {})
     p = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE).reshape(-1)
+    return project_columns(p["pos"].astype(np.float64), p["object"].astype(np.int64), p["rgb"].astype(np.float64), objects, camera, W, H,
+                           interval, flags, options, windows, temperatures)
+
+
+def project_columns(pos, idx, rgb0, objects, camera: Mapping, W: int, H: int, interval: int = -1, flags: int = 0,
+                    options: Optional[Mapping] = None, windows=None, temperatures=None) -> dict:
+    """project() on float64 columns — pos (N, 3), idx (N,) object indices, rgb0 (N, 3) — for positions that are no float32 numbers
+    (segments.project's nodes)."""
+    options = dict(options or {})
     objs = _objects_array(objects)
-    idx = p["object"].astype(np.int64)
-    if len(p) and (idx.min() < 0 or idx.max() >= len(objs)):
+    if len(idx) and (idx.min() < 0 or idx.max() >= len(objs)):
         raise ValueError(f"project: a particle names object {int(idx.max())}, the Object[] holds {len(objs)}")
     inv = objs["InvLorentz"].astype(np.float64).reshape(-1, 4, 4)[idx]
     cam = objs["stationaryCam"].astype(np.float64).reshape(-1, 4)[idx]
-    rgb0 = p["rgb"].astype(np.float64)
     with np.errstate(all="ignore"):
-        w = p["pos"].astype(np.float64) - cam[:, 1:]
+        w = pos - cam[:, 1:]
         r = np.sqrt((w * w).sum(axis=1))
         visible = (r > 0.0) & np.isfinite(r)
         tau = -r if interval == -1 else -(inv[:, 0, 1:] * w).sum(axis=1) / inv[:, 0, 0]
@@ -114,7 +120,7 @@ def project(particles, objects, camera: Mapping, W: int, H: int, interval: int =
                 if flags & 2:
                     rgb = rgb / (D ** 2)[:, None]
         else:
-            D = dist / r if interval != 0 else np.ones(len(p))
+            D = dist / r if interval != 0 else np.ones(len(idx))
             rgb = rgb0.copy()
         if options.get("inverse_square"):
             rgb = rgb / (r * r)[:, None]

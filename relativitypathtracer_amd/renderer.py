@@ -600,6 +600,47 @@ class Renderer:
         self._check(self._lib.rpt_last_particles_ms(self._h, ms), "rpt_last_particles_ms")
         return float(ms[0]), float(ms[1])
 
+    # -- the segment pass (include/rpt.h, rpt_set_segments; not in the reference) -------------------
+    def set_segments(self, segments):
+        """The rods: an array of segments.SEGMENT_DTYPE records (or anything of n x 48 bytes in that layout: a, object, b, padding, rgb,
+        padding), e.g. from segments.box_edges / segments.rod_lattice / segments.polyline / segments.load; None or an empty array
+        switches the pass off.  a and b are the ends in the rest frame of the scene's object number `object`; rgb is the linear colour
+        at rest PER UNIT REST-FRAME LENGTH.  Copied by the library; per context; what the library refuses raises RenderError."""
+        if segments is None or len(segments) == 0:
+            self._check(self._lib.rpt_set_segments(self._h, None, 0), "rpt_set_segments")
+            return
+        raw = np.ascontiguousarray(segments)
+        if raw.nbytes % 48 or raw.nbytes // 48 != len(raw):
+            raise ValueError("a segment set has one 48-byte record (segments.SEGMENT_DTYPE) per rod")
+        self._check(self._lib.rpt_set_segments(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Segment)), len(raw)), "rpt_set_segments")
+
+    def set_segment_options(self, inverse_square: bool = False, depth_bias: float = 0.0, pieces: int = 16):
+        """inverse_square, depth_bias: as set_particle_options, for every element of a rod.  pieces: 1, 2, 4, ..., 64 — the parts a rod is
+        cut into; its pieces + 1 nodes are placed exactly, between them the image is a chord.  count x pieces may not exceed 2^21."""
+        self._check(self._lib.rpt_set_segment_options(self._h, 1 if inverse_square else 0, float(depth_bias), int(pieces)), "rpt_set_segment_options")
+
+    def render_segments(self, async_: bool = False):
+        """Add the rods of set_segments to the framebuffer, in place, each tap depth-tested against the last event frame.  The context
+        must have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice adds them twice.
+        Independent of the other passes.  async_=True enqueues only (sync waits)."""
+        self._run_pass("rpt_render_segments", async_)
+
+    def last_segments(self) -> Tuple[int, int]:
+        """(pieces with at least one tap inside the frame that passed the depth test, pixels whose bytes changed) of the last finished
+        segment pass."""
+        drawn, changed = self._last_counts("rpt_last_segments", 2)
+        return drawn, changed
+
+    def set_segments_measurement(self, timed: bool = False):
+        """Measurement only (tools/segments_cost.py): time the two kernels of every pass (last_segments_ms)."""
+        self._check(self._lib.rpt_set_segments_measurement(self._h, int(bool(timed))), "rpt_set_segments_measurement")
+
+    def last_segments_ms(self) -> Tuple[float, float]:
+        """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_segments_measurement)."""
+        ms = (C.c_float * 2)(0.0, 0.0)
+        self._check(self._lib.rpt_last_segments_ms(self._h, ms), "rpt_last_segments_ms")
+        return float(ms[0]), float(ms[1])
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -734,7 +775,8 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  orientation: Optional[Sequence[float]] = None, v_fov: Optional[float] = None, events: bool = False,
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
                  fov: float = math.pi, fit: int = 0, readouts=None, stars=None, particles=None,
-                 particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None):
+                 particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None,
+                 segments=None, segment_options: Optional[Mapping] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -752,7 +794,9 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     particles: a set for Renderer.set_particles (particles.lattice, particles.at_events, ...), particle_options the keywords of
     Renderer.set_particle_options; it implies events=True too — the pass depth-tests against the event frame — and runs behind the
     stars, under the overlay's lines and the readouts.  star_temperatures, particle_temperatures: kelvin per star and per particle
-    (Renderer.set_star_temperatures, set_particle_temperatures): those sources are Doppler-shifted as blackbodies."""
+    (Renderer.set_star_temperatures, set_particle_temperatures): those sources are Doppler-shifted as blackbodies.  segments: rods for
+    Renderer.set_segments (segments.box_edges, segments.rod_lattice, ...), segment_options the keywords of
+    Renderer.set_segment_options; it implies events=True as the particles do, and the pass runs right behind them."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -778,7 +822,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        if overlay is not None or readouts is not None or stars is not None or particles is not None:
+        if overlay is not None or readouts is not None or stars is not None or particles is not None or segments is not None:
             records = r.render_events()
             if stars is not None:
                 r.set_stars(stars, star_temperatures)
@@ -787,6 +831,10 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                 r.set_particles(particles, particle_temperatures)
                 r.set_particle_options(**dict(particle_options or {}))
                 r.render_particles()
+            if segments is not None:
+                r.set_segment_options(**dict(segment_options or {}))
+                r.set_segments(segments)
+                r.render_segments()
             if overlay is not None:
                 r.set_overlay(**overlay)
                 r.render_overlay()
