@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -39,6 +39,10 @@
 // rest-frame distance, bias=B (>= 0, in units of distance) lets particles that sit ON a surface show.  The host runs the colour frame, an
 // event frame of the same view and the particle pass — behind the stars, under the overlay's lines — and reports the particles seen and
 // the pixels changed on stderr.  It excludes --projection (a ray map).
+//
+// --particle-lighting lit[,shadows][,ambient] makes the particles of --particles dust (rpt_set_particle_lighting; not in the reference): their
+// rgb is an albedo and they show what they scatter from the scene's lights, with light delay on the way from the lamp too; shadows adds
+// the renderer's shadow ray per particle and light, ambient the scene's ambient term.  The host reports the pairs lit and shadowed.
 //
 // --segments FILE[:inverse_square][:bias=B][:pieces=N] adds straight rods that ride the scene's objects (rpt_set_segments,
 // rpt_set_segment_options, rpt_render_segments; not in the reference): FILE holds raw 48-byte rpt_segment records
@@ -174,6 +178,29 @@ static bool parse_projection(const char *spec, int width, int height, std::vecto
     return true;
 }
 
+// --particle-lighting lit[,shadows][,ambient]: the flags of rpt_set_particle_lighting; false (and a message) for what it cannot read.
+// (What the library refuses — shadows or ambient without lit — is left to the library, whose message the host prints.)
+static bool parse_particle_lighting(const char *spec, int *flags) {
+    *flags = 0;
+    const std::string s(spec);
+    size_t at = 0;
+    while (at <= s.size()) {
+        const size_t next = s.find(',', at);
+        const std::string word = s.substr(at, next == std::string::npos ? std::string::npos : next - at);
+        if (word == "lit") *flags |= RPT_PARTICLES_LIT;
+        else if (word == "shadows") *flags |= RPT_PARTICLES_SHADOWED;
+        else if (word == "ambient") *flags |= RPT_PARTICLES_AMBIENT;
+        else {
+            std::fprintf(stderr, "--particle-lighting: unknown word '%s' in '%s' (lit, shadows, ambient)\n", word.c_str(), spec);
+            return false;
+        }
+        if (next == std::string::npos) break;
+        at = next + 1;
+    }
+    std::fprintf(stderr, "particle lighting: lit %d, shadows %d, ambient %d\n", !!(*flags & RPT_PARTICLES_LIT), !!(*flags & RPT_PARTICLES_SHADOWED), !!(*flags & RPT_PARTICLES_AMBIENT));
+    return true;
+}
+
 // --particles FILE[:inverse_square][:bias=B]: the file name, the flags and the bias; false (and a message) for what it cannot read
 static bool parse_particles(const char *spec, std::string *path, int *flags, float *bias) {
     const std::string s(spec);
@@ -261,6 +288,7 @@ int main(int argc, char **argv) {
     std::string particles_path;
     int particle_flags = 0;
     float particle_bias = 0.0f;
+    int particle_lighting = 0;                                   // --particle-lighting
     std::string segments_path;
     int segment_flags = 0, segment_pieces = 16;
     float segment_bias = 0.0f;
@@ -307,6 +335,12 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "--segments needs a value: FILE[:inverse_square][:bias=B][:pieces=N] (raw 48-byte rpt_segment records)\n");
                 return 2;
             }
+            else if (has_value && !std::strcmp(argv[i], "--particle-lighting")) {
+                if (!parse_particle_lighting(argv[++i], &particle_lighting)) return 2;
+            } else if (!std::strcmp(argv[i], "--particle-lighting")) {
+                std::fprintf(stderr, "--particle-lighting needs a value: lit[,shadows][,ambient]\n");
+                return 2;
+            }
             else if (has_value && !std::strcmp(argv[i], "--particles")) {
                 if (!parse_particles(argv[++i], &particles_path, &particle_flags, &particle_bias)) return 2;
             } else if (!std::strcmp(argv[i], "--particles")) {
@@ -346,7 +380,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -387,6 +421,10 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "--segments: %s does not hold a whole number (> 0) of 48-byte rpt_segment records\n", segments_path.c_str());
             return 2;
         }
+    }
+    if (particle_lighting && particle_set.empty()) {
+        std::fprintf(stderr, "--particle-lighting needs --particles\n");
+        return 2;
     }
     std::vector<float> star_kelvin, particle_kelvin;             // --star-temperatures, --particle-temperatures: raw float32, one per record
     for (int k = 0; k < 2; k++) {
@@ -536,13 +574,17 @@ int main(int argc, char **argv) {
         if (!rc) rc = rpt_set_particles(last, particle_set.data(), (int)particle_set.size());
         if (!rc) rc = rpt_set_particle_options(last, particle_flags, particle_bias);
         if (!rc && !particle_kelvin.empty()) rc = rpt_set_particle_temperatures(last, particle_kelvin.data(), (int)particle_kelvin.size());
+        if (!rc) rc = rpt_set_particle_lighting(last, particle_lighting);
         if (!rc) rc = rpt_render_particles(last);
         if (!rc) rc = rpt_last_particles(last, counts);
+        unsigned long long pairs[2] = {0, 0};
+        if (!rc) rc = rpt_last_particle_lighting(last, pairs);
         if (rc) {
             std::fprintf(stderr, "particles: %s\n", rpt_last_error(last));
             return 1;
         }
         std::fprintf(stderr, "particles: %llu of %zu seen, %llu of %lld pixels changed\n", counts[0], particle_set.size(), counts[1], (long long)width * height);
+        if (particle_lighting) std::fprintf(stderr, "particle lighting: %llu (particle, light) pairs lit, %llu shadowed\n", pairs[0], pairs[1]);
     }
     if (!segment_set.empty()) {                                  // rods riding the objects, depth-tested against the event frame
         unsigned long long counts[2] = {0, 0};

@@ -774,6 +774,42 @@ int rpt_last_segments(rpt_ctx *ctx, unsigned long long out[2]);   /* pieces draw
 int rpt_set_segments_measurement(rpt_ctx *ctx, int timed);
 int rpt_last_segments_ms(rpt_ctx *ctx, float ms[2]);
 
+/* Lit particles (not in the reference; DESIGN.md §23 "Lit particles" gives every rule operation by operation): dust.  With
+ * RPT_PARTICLES_LIT a particle's rgb is an ALBEDO, and its colour at rest is what it scatters from the scene's lights — the light loop
+ * the renderer runs for a surface, with the normal taken out (a grain scatters alike in every direction).  Light delay applies on the
+ * light -> grain leg as on the grain -> camera leg: with rpt_set_object_windows a lamp switched on shows its front expanding through the
+ * dust (a light echo), a moving lamp's beam is aberrated, shifted and beamed, and with RPT_PARTICLES_SHADOWED a body's shadow stands in
+ * the dust, tilted by light delay.
+ *
+ * In short, per particle that has a tap inside the frame passing the depth test (L = Object[object], tau of the particle pass): its
+ * event E = (L.stationaryCam.x + tau, pos), hitPos = L.InvLorentz E; sum = rgb * ambient (RPT_PARTICLES_AMBIENT; rpt_set_params) or 0;
+ * for every Object[i] with light != 0, in index order, i == object included: P = Lorentz_i hitPos, d3 = (M_i[0].w, M_i[1].w, M_i[2].w)
+ * - P.yzw, len = |d3| (the light is skipped unless 0 < len <= FLT_MAX), dLF = (interval * len, d3); with windows set the light is
+ * skipped unless P.x + dLF.x lies in its window; lightDir = InvLorentz_i dLF, dObj = L.Lorentz lightDir, l3 = dObj.yzw; with
+ * RPT_PARTICLES_SHADOWED the pair is skipped, and counted, if the renderer's own shadow ray from hitPos along lightDir.yzw meets any
+ * object but i below |lightDir.yzw| (meshes through the octree walk; occluders held against their windows); k = 1 / (1 + 0.1 |l3| +
+ * 0.01 l3.l3); col = color_i, through S_f(dObj.x / dLF.x, .) while rpt_set_doppler is set; sum += (rgb * k) * col.  The particle pass
+ * then goes on with sum where it had rgb (the camera factor D = dist / r, / D^2, / r^2, the taps, the resolve).  With interval == 0
+ * nothing of this runs and the pass is the plain one, byte for byte: the renderer lights nothing without light propagation.
+ *
+ * rpt_set_particle_lighting: flags = 0 (default: the particle pass as it was, its kernels 1130 / 1132) or RPT_PARTICLES_LIT, optionally
+ * with RPT_PARTICLES_SHADOWED and RPT_PARTICLES_AMBIENT.  RPT_ERR_ARG, message "rpt_set_particle_lighting: ...", the previous value
+ * kept: an unknown bit, SHADOWED or AMBIENT without LIT.  Per context, not shared by rpt_share_scene.  While LIT is set
+ * rpt_render_particles[_async] also refuses, the context still usable: with RPT_ERR_ARG particle temperatures (a scattered spectrum is
+ * not the grain's blackbody) and, with SHADOWED and RPT_ERR_STATE, a scene whose octrees have no derived layout (what rpt_probe_object
+ * refuses, with the same code).
+ * rpt_last_particle_lighting: of the last FINISHED particle pass, out[0] = (particle, light) pairs that lit, out[1] = pairs a shadow ray
+ * found occluded, both over the particles rpt_last_particles counts as seen; zeros for a plain pass and before the first.
+ *
+ * Limits: single scattering, isotropic, no extinction — grains do not shade one another or the surfaces, and the frame's surfaces do
+ * not see the dust; the shadow ray starts AT the grain (there is no normal to step along), so a grain placed on a surface
+ * (particles.at_events) is shadowed by that surface or not by rounding; rods (the segment pass) stay self-luminous. */
+#define RPT_PARTICLES_LIT       1   /* rgb is an albedo: the grain shows what it scatters from the scene's lights */
+#define RPT_PARTICLES_SHADOWED  2   /* needs LIT: a shadow ray per (grain, light), the reference's sample_light */
+#define RPT_PARTICLES_AMBIENT   4   /* needs LIT: add rgb * ambient (rpt_set_params), as trace does for a surface */
+int rpt_set_particle_lighting(rpt_ctx *ctx, int flags);                       /* default 0: today's pass, today's kernels */
+int rpt_last_particle_lighting(rpt_ctx *ctx, unsigned long long out[2]);     /* (grain, light) pairs that lit; pairs shadowed */
+
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);
 void *rpt_colour_plane_ptr(rpt_ctx *ctx);    /* device pointer of the compact plane (rpt_set_rows) */

@@ -265,6 +265,8 @@ HIP_SYMBOLS = {
     "rpt_last_segments": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_set_segments_measurement": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_last_segments_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_particle_lighting": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_last_particle_lighting": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_version": (C.c_char_p, []),
 }
 

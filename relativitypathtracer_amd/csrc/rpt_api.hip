@@ -33,6 +33,8 @@
 #include "rpt_thermal_host.hpp"
 #include "rpt_segments.hip.h"       /* behind the thermal kernels: kernel 1140 is the translation unit's last */
 #include "rpt_segments_host.hpp"
+#include "rpt_dust.hip.h"           /* behind the segments: kernels 1134, 1135 and 1136 are the translation unit's last */
+#include "rpt_dust_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -74,7 +76,7 @@ struct Tally {
     DeviceBuffer device;                              // the words of the pass in flight, then `spare` bytes of the pass's own that are zeroed with them
     unsigned long long *host = nullptr;               // pinned: the words of the last pass whose copy has run
     hipEvent_t copied = nullptr;                      // recorded after that copy
-    unsigned long long value[2] = {0, 0};             // what rpt_last_* reports: `host` as last read with `copied` passed
+    unsigned long long value[4] = {0, 0, 0, 0};       // what rpt_last_* reports: `host` as last read with `copied` passed (the particle pass has four words)
     size_t words = 1, spare = 0;                      // (as tally_ready was given them)
     bool pending = false;                             // a copy has been enqueued since `value` was read
 };
@@ -267,6 +269,7 @@ struct rpt_ctx {
     StagedUpload particle_table;                      // rpt_particle per particle, in the caller's order; written once per rpt_set_particles
     int particle_flags = 0;                           // rpt_set_particle_options
     float particle_depth_bias = 0.0f;
+    int particle_lighting = 0;                        // rpt_set_particle_lighting: RPT_PARTICLES_LIT | _SHADOWED | _AMBIENT
     bool particle_timed = false;                      // rpt_set_particles_measurement
     hipEvent_t particle_marks[3] = {nullptr, nullptr, nullptr};
     bool particle_marked = false;
@@ -404,7 +407,7 @@ void tally_collect(Tally &t) {
 
 void tally_off(Tally &t) {
     t.pending = false;
-    t.value[0] = t.value[1] = 0;
+    for (unsigned long long &v : t.value) v = 0;
 }
 
 // A rpt_last_* call: the first `words` words as last collected, after one more look where a copy is still on its way
@@ -2098,6 +2101,31 @@ int launch_stars(rpt_ctx *ctx) {
     return frame_pass(ctx, "rpt_render_stars", ctx->star_count != 0, TALLY_STARS, enqueue_stars);
 }
 
+// the arguments the ray-level probes and the lit particles' shadow ray need: the resident scene and the current Object[] / DObj[] (no
+// frame, no outputs)
+void probe_kernel_args(rpt_ctx *ctx, rptd::KernelArgs &a) {
+    std::memset(&a, 0, sizeof a);
+    a.dnodes = (const rptd::DNode *)ctx->geo->dnodes.ptr;
+    a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
+    a.links = (const int *)ctx->geo->dlinks.ptr;
+    a.first_tris = (const rptd::DTri *)ctx->geo->dfirst.ptr;
+    a.exits = (const rptd::DExit *)ctx->geo->dexits.ptr;
+    a.hits = (const rptd::DHit *)ctx->geo->dhits.ptr;
+    a.top_count = ctx->geo->top_count;
+    a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
+    a.objects = (const rpt_object *)ctx->objects.ptr;
+    a.vertices = (const rpt_float3 *)ctx->geo->vertices.ptr;
+    a.normals = (const rpt_float3 *)ctx->geo->normals.ptr;
+    a.uvs = (const rpt_float2 *)ctx->geo->uvs.ptr;
+    a.triangles = (const uint32_t *)ctx->geo->triangles.ptr;
+    a.octrees = (const rpt_octree *)ctx->geo->octrees.ptr;
+    a.octreeTris = (const int32_t *)ctx->geo->octreeTris.ptr;
+    a.textures = (const uint8_t *)ctx->geo->textures.ptr;
+    a.texture_bytes = (long long)ctx->geo->textures.bytes;
+    a.object_count = ctx->object_count;
+    a.interval = ctx->interval;
+}
+
 // What the particle pass and the segment pass hand their kernels alike: the objects and their windows, the records, the accumulator, the
 // tally, the view as rule 4 projects it, and the resolve's arguments (kernel 1131).  The set, its count and its options are the caller's.
 void point_pass_args(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events, rptd::ParticleArgs &a, rptd::ParticleResolveArgs &b) {
@@ -2133,7 +2161,9 @@ void point_pass_args(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_eve
 }
 
 // One particle pass on the context's stream (kernels 1130 and 1131): three refusals of its own — the last is what keeps every index
-// the splat follows inside Object[] —, the accumulator it shares with the stars, the two launches
+// the splat follows inside Object[] —, the accumulator it shares with the stars, the two launches.  With rpt_set_particle_lighting the
+// splat is one of the lit kernels (1134, 1135, 1136; rptl::splat_kernel chooses) after two more refusals (rptl::launch_fault), and two
+// more words of the tally come home: the (particle, light) pairs that lit and the pairs shadowed
 int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
     if (ctx->projection == RPT_PROJECTION_RAYMAP)
         return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a particle with");
@@ -2145,7 +2175,9 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
         return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: " + std::to_string(ctx->particle_thermal_count) + " temperatures are set (rpt_set_particle_temperatures), the set holds " + std::to_string(ctx->particle_count));
     const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
     if (int rc = accumulator_ready(ctx, pixels)) return rc;
-    if (int rc = tally_ready(ctx, tally, 2)) return rc;
+    const rptl::LaunchFault dust_fault = rptl::launch_fault(ctx->particle_lighting, ctx->particle_thermal_count, ctx->geo->compact_ok);
+    if (dust_fault.code != RPT_OK) return fail(ctx, dust_fault.code, "rpt_render_particles: " + dust_fault.message);
+    if (int rc = tally_ready(ctx, tally, 4)) return rc;       // seen, changed pixels; (particle, light) pairs lit, pairs shadowed (zero for a plain pass)
     if (ctx->particle_timed)
         for (hipEvent_t &m : ctx->particle_marks)
             if (!m) RPT_HIP(ctx, hipEventCreate(&m));
@@ -2160,10 +2192,26 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
 
     if (int rc = tally_zero(ctx, tally)) return rc;
     if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[0], ctx->stream));
-    const float *xg = (const float *)ctx->particle_thermal_table.device.ptr;
-    void *splat_args[] = {(void *)&a, (void *)&xg};     // (1130 takes the first only)
-    (void)hipLaunchKernel(ctx->particle_thermal_count != 0 ? (const void *)rptd::rpt_particles_thermal_splat_kernel : (const void *)rptd::rpt_particles_splat_kernel,
-                          dim3((unsigned)((ctx->particle_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    const int splat = rptl::splat_kernel(ctx->particle_lighting, ctx->interval, ctx->particle_thermal_count, !ctx->windows.empty());
+    const dim3 splat_grid((unsigned)((ctx->particle_count + 255) / 256));
+    if (splat == 1130 || splat == 1132) {
+        const float *xg = (const float *)ctx->particle_thermal_table.device.ptr;
+        void *splat_args[] = {(void *)&a, (void *)&xg};     // (1130 takes the first only)
+        (void)hipLaunchKernel(splat == 1132 ? (const void *)rptd::rpt_particles_thermal_splat_kernel : (const void *)rptd::rpt_particles_splat_kernel,
+                              splat_grid, dim3(256), splat_args, 0, ctx->stream);
+    } else {                                                // lit particles: 1134, or 1135 / 1136 with the scene for the shadow ray
+        rptd::DustArgs d;
+        std::memset((void *)&d, 0, sizeof d);
+        d.p = a;
+        d.ambient = ctx->ambient;
+        d.add_ambient = ctx->particle_lighting & RPT_PARTICLES_AMBIENT;
+        rptd::KernelArgs k;
+        probe_kernel_args(ctx, k);
+        void *splat_args[] = {(void *)&d, (void *)&k};      // (1134 takes the first only)
+        (void)hipLaunchKernel(splat == 1134 ? (const void *)rptd::rpt_dust_splat_kernel
+                              : splat == 1135 ? (const void *)rptd::rpt_dust_shadowed_splat_kernel : (const void *)rptd::rpt_dust_shadowed_windowed_splat_kernel,
+                              splat_grid, dim3(256), splat_args, 0, ctx->stream);
+    }
     RPT_HIP(ctx, hipGetLastError());
     if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[1], ctx->stream));
     void *resolve_args[] = {(void *)&b};
@@ -3409,6 +3457,23 @@ int rpt_set_particle_options(rpt_ctx *ctx, int flags, float depth_bias) {
     return RPT_OK;
 }
 
+int rpt_set_particle_lighting(rpt_ctx *ctx, int flags) {
+    if (!ctx) return RPT_ERR_ARG;
+    const std::string fault = rptl::lighting_fault(flags);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_particle_lighting: " + fault);
+    ctx->particle_lighting = flags;
+    return RPT_OK;
+}
+
+int rpt_last_particle_lighting(rpt_ctx *ctx, unsigned long long out[2]) {
+    unsigned long long all[4] = {0, 0, 0, 0};
+    if (!out) return RPT_ERR_ARG;
+    if (int rc = tally_read(ctx, TALLY_PARTICLES, all, 4)) return rc;
+    out[0] = all[2];
+    out[1] = all[3];
+    return RPT_OK;
+}
+
 int rpt_render_particles_async(rpt_ctx *ctx) { return render_pass(ctx, launch_particles, false); }
 int rpt_render_particles(rpt_ctx *ctx) { return render_pass(ctx, launch_particles, true); }
 
@@ -3699,30 +3764,6 @@ int rpt_probe(rpt_ctx *ctx, int which, const void *host_in, void *host_out, int 
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return rc;
-}
-
-// the arguments the ray-level probes need: the resident scene and the current Object[] / DObj[] (no frame, no outputs)
-static void probe_kernel_args(rpt_ctx *ctx, rptd::KernelArgs &a) {
-    std::memset(&a, 0, sizeof a);
-    a.dnodes = (const rptd::DNode *)ctx->geo->dnodes.ptr;
-    a.dtris = (const rptd::DTri *)ctx->geo->dtris.ptr;
-    a.links = (const int *)ctx->geo->dlinks.ptr;
-    a.first_tris = (const rptd::DTri *)ctx->geo->dfirst.ptr;
-    a.exits = (const rptd::DExit *)ctx->geo->dexits.ptr;
-    a.hits = (const rptd::DHit *)ctx->geo->dhits.ptr;
-    a.top_count = ctx->geo->top_count;
-    a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
-    a.objects = (const rpt_object *)ctx->objects.ptr;
-    a.vertices = (const rpt_float3 *)ctx->geo->vertices.ptr;
-    a.normals = (const rpt_float3 *)ctx->geo->normals.ptr;
-    a.uvs = (const rpt_float2 *)ctx->geo->uvs.ptr;
-    a.triangles = (const uint32_t *)ctx->geo->triangles.ptr;
-    a.octrees = (const rpt_octree *)ctx->geo->octrees.ptr;
-    a.octreeTris = (const int32_t *)ctx->geo->octreeTris.ptr;
-    a.textures = (const uint8_t *)ctx->geo->textures.ptr;
-    a.texture_bytes = (long long)ctx->geo->textures.bytes;
-    a.object_count = ctx->object_count;
-    a.interval = ctx->interval;
 }
 
 int rpt_probe_walk(rpt_ctx *ctx, int object_index, const float *host_rays, float *host_out, int n) {

@@ -144,3 +144,97 @@ def project_columns(pos, idx, rgb0, objects, camera: Mapping, W: int, H: int, in
     X = np.where(visible, X, np.nan)
     Y = np.where(visible, Y, np.nan)
     return {"visible": visible, "X": X, "Y": Y, "dist": dist, "r": r, "D": D, "te": te, "k": k, "n": n, "rgb": rgb}
+
+
+# ---- lit particles (rpt_set_particle_lighting) -------------------------------------------------------------------------
+LIT, SHADOWED, AMBIENT = 1, 2, 4      # RPT_PARTICLES_LIT, RPT_PARTICLES_SHADOWED, RPT_PARTICLES_AMBIENT
+
+
+def dust(object: int, lo, hi, count: int, rgb, seed: int = 0) -> np.ndarray:
+    """count grains uniform at random in the box from the corner lo to the corner hi, at rest in the frame of `object`, of albedo rgb:
+    a dust cloud for the lit pass.  Random rather than particles.lattice on purpose: a regular lattice puts whole planes of grains on
+    the edge of a shadow or of a light front, where they flicker together."""
+    if int(count) < 0:
+        raise ValueError("dust: count is negative")
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    u = np.random.default_rng(seed).random((int(count), 3))
+    return from_arrays(lo + (hi - lo) * u, object, rgb)
+
+
+def _doppler_operator(flags: int, D, rgb) -> np.ndarray:
+    """S_f(D, rgb) of the Doppler model in float64, without the point source's / D^2: what a light's colour goes through."""
+    D = np.asarray(D, dtype=np.float64)
+    o = point_source_colour(flags, D, rgb)
+    return o * (D ** 2)[:, None] if flags & 2 else o
+
+
+def illuminate(particles, objects, interval: int = -1, doppler: int = 0, ambient: float = 0.0, flags: int = LIT, windows=None) -> dict:
+    """Rules D0-D7 of the lit particles in float64, WITHOUT shadows (flags' SHADOWED bit is ignored: no geometry is looked at) and
+    without the depth test: what every grain scatters, as if it were seen.  particles, objects, windows: as project takes them;
+    interval -1 or 0; doppler: the flags of Renderer.set_doppler; ambient: the scene's; flags: LIT, optionally | AMBIENT (0: the plain
+    pass, c_rest = rgb).  Returns a dict: lights (the indices of the objects that are lights, in order), and per grain and light,
+    shaped (N, len(lights)): te (the light's emission time in ITS rest frame, P.x + dLF.x), len (the light-frame distance), k (the
+    falloff), di (the light's Doppler factor, dObj.x / dLF.x), lit (the pair contributes: len > 0 and finite, and the window holds te),
+    contribution (N, len(lights), 3), light_dir (N, len(lights), 4) the grain -> lamp displacement in the camera frame (the lamp's
+    emission event is hit_pos + light_dir); per grain: hit_pos (N, 4) the grain's event in the camera frame, c_rest (N, 3) the colour at
+    rest (rule D7's input), and rgb (N, 3) the colour after rule 3 (the camera factor D = dist / r through S_f, / D^2 with beaming;
+    the optional / r^2 is project's option and is not applied here), D (N,).  With interval 0 (rule D0) or flags 0: lit is all False,
+    c_rest = the grains' rgb."""
+    if interval not in (-1, 0):
+        raise ValueError("illuminate: the light cone has a closed form for interval -1 and 0 only")
+    p = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE).reshape(-1)
+    objs = _objects_array(objects)
+    idx = p["object"].astype(np.int64)
+    if len(idx) and (idx.min() < 0 or idx.max() >= len(objs)):
+        raise ValueError(f"illuminate: a particle names object {int(idx.max())}, the Object[] holds {len(objs)}")
+    pos, rgb0 = p["pos"].astype(np.float64), p["rgb"].astype(np.float64)
+    lor = objs["Lorentz"].astype(np.float64).reshape(-1, 4, 4)
+    inv = objs["InvLorentz"].astype(np.float64).reshape(-1, 4, 4)
+    cam = objs["stationaryCam"].astype(np.float64).reshape(-1, 4)[idx]
+    M = objs["M"].astype(np.float64).reshape(-1, 4, 4)
+    lights = np.nonzero(objs["light"] != 0)[0]
+    N, nl = len(p), len(lights)
+    with np.errstate(all="ignore"):
+        w = pos - cam[:, 1:]
+        r = np.sqrt((w * w).sum(axis=1))
+        tau = -r if interval == -1 else -(inv[idx][:, 0, 1:] * w).sum(axis=1) / inv[idx][:, 0, 0]
+        kcam = np.einsum("nij,nj->ni", inv[idx], np.concatenate([tau[:, None], w], axis=1))
+        dist = np.sqrt((kcam[:, 1:] ** 2).sum(axis=1))
+        E = np.concatenate([(cam[:, 0] + tau)[:, None], pos], axis=1)
+        hit_pos = np.einsum("nij,nj->ni", inv[idx], E)
+        out = {"lights": lights, "hit_pos": hit_pos, "te": np.full((N, nl), np.nan), "len": np.full((N, nl), np.nan),
+               "k": np.zeros((N, nl)), "di": np.ones((N, nl)), "lit": np.zeros((N, nl), dtype=bool), "contribution": np.zeros((N, nl, 3)), "light_dir": np.zeros((N, nl, 4))}
+        if not (flags & LIT) or interval == 0:
+            c_rest = rgb0.copy()
+        else:
+            c_rest = rgb0 * float(ambient) if flags & AMBIENT else np.zeros_like(rgb0)
+            for j, i in enumerate(lights):
+                P = hit_pos @ lor[i].T
+                d3 = M[i][:3, 3][None, :] - P[:, 1:]
+                ln = np.sqrt((d3 * d3).sum(axis=1))
+                dLF = np.concatenate([(interval * ln)[:, None], d3], axis=1)
+                te = P[:, 0] + dLF[:, 0]
+                ok = (ln > 0.0) & np.isfinite(ln)
+                if windows is not None:
+                    win = np.asarray(windows, dtype=np.float64).reshape(-1, 2)[i]
+                    ok &= window_accepts(win[0], win[1], te)
+                light_dir = dLF @ inv[i].T
+                d_obj = np.einsum("nij,nj->ni", lor[idx], light_dir)
+                l3 = d_obj[:, 1:]
+                k = 1.0 / (1.0 + 0.1 * np.sqrt((l3 * l3).sum(axis=1)) + 0.01 * (l3 * l3).sum(axis=1))
+                di = d_obj[:, 0] / dLF[:, 0]
+                col = np.broadcast_to(objs["color"][i].astype(np.float64).reshape(-1)[:3], (N, 3))
+                if doppler:
+                    col = _doppler_operator(doppler, np.where(ok, di, 1.0), col)
+                contribution = np.where(ok[:, None], (rgb0 * k[:, None]) * col, 0.0)
+                c_rest = c_rest + contribution
+                out["te"][:, j], out["len"][:, j], out["k"][:, j], out["di"][:, j] = te, ln, k, di
+                out["lit"][:, j], out["contribution"][:, j], out["light_dir"][:, j] = ok, contribution, light_dir
+        if doppler and interval != 0:
+            D = dist / r
+            rgb = point_source_colour(doppler, D, c_rest)
+        else:
+            D = dist / r if interval != 0 else np.ones(N)
+            rgb = c_rest.copy()
+    out.update({"c_rest": c_rest, "rgb": rgb, "D": D, "r": r, "dist": dist})
+    return out

@@ -578,6 +578,22 @@ class Renderer:
         particle ON a surface (particles.at_events) shows with a small bias and is hidden, by rounding, without one."""
         self._check(self._lib.rpt_set_particle_options(self._h, 1 if inverse_square else 0, float(depth_bias)), "rpt_set_particle_options")
 
+    def set_particle_lighting(self, lit: bool = False, shadows: bool = False, ambient: bool = False):
+        """Lit particles (include/rpt.h, rpt_set_particle_lighting): dust.  lit: a particle's rgb is an albedo, and its
+        colour at rest is what it scatters from the scene's lights — with light delay on the light -> grain leg too, the light's
+        Doppler factor and its time window (set_object_windows: a lamp switched on shows its front expanding through the dust).
+        shadows: a shadow ray per (grain, light), the one the renderer shoots for a surface.  ambient: add rgb * ambient, as a surface
+        gets it.  shadows and ambient need lit; the default, all off, is the self-luminous pass.  With light propagation off
+        (interval 0) the scene lights nothing and a lit pass equals the plain one."""
+        flags = (1 if lit else 0) | (2 if shadows else 0) | (4 if ambient else 0)      # RPT_PARTICLES_LIT, _SHADOWED, _AMBIENT
+        self._check(self._lib.rpt_set_particle_lighting(self._h, flags), "rpt_set_particle_lighting")
+
+    def last_particle_lighting(self) -> Tuple[int, int]:
+        """((particle, light) pairs that lit, pairs a shadow ray found occluded) of the last finished particle pass, over the particles
+        last_particles counts as seen; (0, 0) for a pass that was not lit."""
+        lit, shadowed = self._last_counts("rpt_last_particle_lighting", 2)
+        return lit, shadowed
+
     def render_particles(self, async_: bool = False):
         """Add the particles of set_particles to the framebuffer, in place, each tap depth-tested against the last event frame.  The
         context must have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice adds them
@@ -776,7 +792,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
                  fov: float = math.pi, fit: int = 0, readouts=None, stars=None, particles=None,
                  particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None,
-                 segments=None, segment_options: Optional[Mapping] = None):
+                 segments=None, segment_options: Optional[Mapping] = None, particle_lighting: Optional[Mapping] = None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -796,7 +812,9 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     stars, under the overlay's lines and the readouts.  star_temperatures, particle_temperatures: kelvin per star and per particle
     (Renderer.set_star_temperatures, set_particle_temperatures): those sources are Doppler-shifted as blackbodies.  segments: rods for
     Renderer.set_segments (segments.box_edges, segments.rod_lattice, ...), segment_options the keywords of
-    Renderer.set_segment_options; it implies events=True as the particles do, and the pass runs right behind them."""
+    Renderer.set_segment_options; it implies events=True as the particles do, and the pass runs right behind them.  particle_lighting:
+    the keywords of Renderer.set_particle_lighting, e.g. dict(lit=True, shadows=True): the particles are dust that scatters the
+    scene's lights."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -830,6 +848,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
             if particles is not None:
                 r.set_particles(particles, particle_temperatures)
                 r.set_particle_options(**dict(particle_options or {}))
+                r.set_particle_lighting(**dict(particle_lighting or {}))
                 r.render_particles()
             if segments is not None:
                 r.set_segment_options(**dict(segment_options or {}))
