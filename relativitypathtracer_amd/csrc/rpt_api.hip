@@ -82,6 +82,22 @@ struct Tally {
 };
 enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_SEGMENTS, TALLY_COUNT };     // rpt_ctx::tally
 
+// A splat pass (the stars, the particles, the segments): its records on the device, the temperatures beside them, and the marks of a
+// timed pass.  What differs between the passes — their options — stays with the context.
+struct SplatPass {
+    int count = 0;                                    // 0 = no catalogue, no set: the pass is off
+    int largest_object = -1;                          // the largest Object[] index the set names, held against object_count at every launch; -1 for the stars, who name none
+    StagedUpload table;                               // rpt_star / rpt_particle / rpt_segment per record, in the caller's order; written once per rpt_set_*
+    // rpt_set_star_temperatures / rpt_set_particle_temperatures: x_G per source, parallel to the records; 0 entries =
+    // none set, and the pass launches kernel 1120 / 1130 as before.  The segments have none
+    int thermal_count = 0;
+    StagedUpload thermal_table;                       // one float per source, written once per rpt_set_*_temperatures
+    bool timed = false;                               // rpt_set_*_measurement
+    hipEvent_t marks[3] = {nullptr, nullptr, nullptr};    // timed passes: before the splat, between the kernels, after the resolve
+    bool marked = false;                              // the last pass recorded them
+};
+enum { SPLAT_STARS, SPLAT_PARTICLES, SPLAT_SEGMENTS, SPLAT_COUNT };     // rpt_ctx::splat
+
 // What the last frame of one kind (colour, event) was enqueued for, as a pass over both asks (frames_of_this_view)
 struct FrameMark {
     unsigned long long generation = 0;                // rpt_ctx::view_generation then; 0 = no such frame yet
@@ -255,41 +271,17 @@ struct rpt_ctx {
     std::vector<rpt_readout> readouts;                // one per entry of Object[]; empty = none set
     unsigned long long readout_low_mask = 0;          // bit o: object o < 64 has a display
     StagedUpload readout_table;                       // rptd::ReadoutDisplay per object, written once per rpt_set_readouts
-    // rpt_set_stars / rpt_render_stars (not in the reference): the star-field pass, per context, never shared
-    int star_count = 0;                               // 0 = no catalogue: the pass is off
-    StagedUpload star_table;                          // rpt_star per star: unit directions, in the caller's order; written once per rpt_set_stars
-    DeviceBuffer star_acc;                            // 24 B per pixel of the largest frame so far: the fixed-point sums, all zero outside a pass
-    bool star_timed = false;                          // rpt_set_stars_measurement
-    hipEvent_t star_marks[3] = {nullptr, nullptr, nullptr}; // timed passes: before the splat, between the kernels, after the resolve
-    bool star_marked = false;                         // the last pass recorded them
-    // rpt_set_particles / rpt_render_particles (not in the reference): the particle pass, per context, never shared.  Its sums go
-    // through star_acc: the accumulator is all zero outside any pass, and the passes of one context are ordered by its stream
-    int particle_count = 0;                           // 0 = no set: the pass is off
-    int particle_largest_object = -1;                 // the largest Object[] index the set names: held against object_count at every launch
-    StagedUpload particle_table;                      // rpt_particle per particle, in the caller's order; written once per rpt_set_particles
+    // rpt_set_stars, rpt_set_particles, rpt_set_segments and their rpt_render_* (not in the reference): the splat
+    // passes, by SPLAT_*, per context, never shared.  All three sum through splat_acc: it is all zero outside any pass, and the passes of
+    // one context are ordered by its stream
+    SplatPass splat[SPLAT_COUNT];
+    DeviceBuffer splat_acc;                           // 24 B per pixel of the largest frame so far: the fixed-point sums, all zero outside a pass
     int particle_flags = 0;                           // rpt_set_particle_options
     float particle_depth_bias = 0.0f;
     int particle_lighting = 0;                        // rpt_set_particle_lighting: RPT_PARTICLES_LIT | _SHADOWED | _AMBIENT
-    bool particle_timed = false;                      // rpt_set_particles_measurement
-    hipEvent_t particle_marks[3] = {nullptr, nullptr, nullptr};
-    bool particle_marked = false;
-    // rpt_set_star_temperatures / rpt_set_particle_temperatures (not in the reference): x_G per source, parallel to the
-    // catalogue and to the set; 0 entries = none set, and the passes launch kernels 1120 / 1130 as before
-    int star_thermal_count = 0;
-    StagedUpload star_thermal_table;                  // one float per star, written once per rpt_set_star_temperatures
-    int particle_thermal_count = 0;
-    StagedUpload particle_thermal_table;
-    // rpt_set_segments / rpt_render_segments (not in the reference): the segment pass, per context, never shared; its sums
-    // go through star_acc too
-    int segment_count = 0;                            // 0 = no set: the pass is off
-    int segment_largest_object = -1;                  // held against object_count at every launch
-    StagedUpload segment_table;                       // rpt_segment per rod, in the caller's order; written once per rpt_set_segments
     int segment_flags = 0;                            // rpt_set_segment_options
     float segment_depth_bias = 0.0f;
     int segment_pieces = rptg::kDefaultPieces;
-    bool segment_timed = false;                       // rpt_set_segments_measurement
-    hipEvent_t segment_marks[3] = {nullptr, nullptr, nullptr};
-    bool segment_marked = false;
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -1894,7 +1886,7 @@ int launch_events(rpt_ctx *ctx) {
 
 uint32_t packed_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
 
-// What a pass over a rendered frame and its records (the overlay, the readouts) asks for before it launches, `call` naming it in the
+// What a pass over a rendered frame and its records (the overlay, the readouts, the splat passes) asks for before it launches, `call` naming it in the
 // messages: a context that renders whole frames, and a colour frame and an event frame of the current size and view in the buffers
 // now set.  *out16 and *events: those buffers.
 int frames_of_this_view(rpt_ctx *ctx, const char *call, rpt_pixel **out16_out, const rpt_event **events_out) {
@@ -1922,9 +1914,10 @@ int frames_of_this_view(rpt_ctx *ctx, const char *call, rpt_pixel **out16_out, c
     return RPT_OK;
 }
 
-// The shape of a pass over a rendered frame (the overlay, the readouts, the stars, the particles), `call` naming it in the messages and `which` its
-// tally.  Off: nothing is checked, launched or changed, and it reports zero.  On: frames_of_this_view, then `enqueue`, the pass's own
-// part (its refusals, tally_ready, its arguments, tally_zero, its launches), then the tally's way home, whose event is last_event.
+// The shape of a pass over a rendered frame (the overlay, the readouts and the three splat passes: the stars, the particles, the
+// segments), `call` naming it in the messages and `which` its tally.  Off: nothing is checked, launched or changed, and it reports zero.
+// On: frames_of_this_view, then `enqueue`, the pass's own part (its refusals, tally_ready, its arguments, tally_zero, its launches; a
+// splat pass has enqueue_splat do all but the first and the arguments), then the tally's way home, whose event is last_event.
 using PassEnqueue = int (*)(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events);
 int frame_pass(rpt_ctx *ctx, const char *call, bool on, int which, PassEnqueue enqueue) {
     Tally &tally = ctx->tally[which];
@@ -2017,45 +2010,42 @@ int enqueue_readouts(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_eve
 
 int launch_readouts(rpt_ctx *ctx) { return frame_pass(ctx, "rpt_render_readouts", !ctx->readouts.empty(), TALLY_READOUTS, enqueue_readouts); }
 
-// The fixed-point accumulator of the star-field pass and the particle pass, 24 B per pixel of the largest frame so far
+// The fixed-point accumulator of the splat passes, 24 B per pixel of the largest frame so far
 int accumulator_ready(rpt_ctx *ctx, size_t pixels) {
     const size_t acc_bytes = pixels * 3 * sizeof(unsigned long long);
-    if (acc_bytes > ctx->star_acc.capacity || !ctx->star_acc.ptr) {      // a new accumulator starts all zero; passes leave it so
+    if (acc_bytes > ctx->splat_acc.capacity || !ctx->splat_acc.ptr) {    // a new accumulator starts all zero; passes leave it so
         RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (a pass in flight may still use the old one)
-        if (int rc = reserve(ctx, ctx->star_acc, acc_bytes)) return rc;
-        RPT_HIP(ctx, hipMemsetAsync(ctx->star_acc.ptr, 0, ctx->star_acc.capacity, ctx->stream));
+        if (int rc = reserve(ctx, ctx->splat_acc, acc_bytes)) return rc;
+        RPT_HIP(ctx, hipMemsetAsync(ctx->splat_acc.ptr, 0, ctx->splat_acc.capacity, ctx->stream));
     }
     return RPT_OK;
 }
 
-// One star-field pass on the context's stream (kernels 1120 and 1121): two refusals of its own, G, the accumulator, the two launches
-int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+// The refusals the splat passes share, `call` naming the pass and `noun` what it projects: a caller's ray map (all three); and for a
+// pass whose records ride objects an interval the light cone has no closed form for, and a set that names an object beyond Object[] —
+// what keeps every index the splat follows inside it.  Like all of a pass's refusals they come before anything touches the device.
+int splat_refusals(rpt_ctx *ctx, const SplatPass &p, const char *call, const char *noun, bool rides_objects) {
+    const std::string name(call);
     if (ctx->projection == RPT_PROJECTION_RAYMAP)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a star with");
-    if (ctx->star_thermal_count != 0 && ctx->star_thermal_count != ctx->star_count)     // (what keeps kernel 1122's xg[i] inside its array)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: " + std::to_string(ctx->star_thermal_count) + " temperatures are set (rpt_set_star_temperatures), the catalogue holds " + std::to_string(ctx->star_count));
-    rptd::StarArgs a;
-    std::memset((void *)&a, 0, sizeof a);
-    {   // E' as a colour frame's launch forms it, then G
-        rpt_float4 e[4];
-        std::memcpy(e, ctx->env_frame, sizeof e);
-        if (ctx->oriented) rebase_columns(e, ctx->R, e);
-        float g[16];
-        if (!rpts::sky_to_camera(&e[0].x, ctx->interval, g))
-            return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: the sky matrix (rpt_set_environment_frame) cannot be inverted");
-        std::memcpy(a.G, g, sizeof a.G);
-    }
-    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
-    if (int rc = accumulator_ready(ctx, pixels)) return rc;
-    if (int rc = tally_ready(ctx, tally, 2)) return rc;
-    if (ctx->star_timed)
-        for (hipEvent_t &m : ctx->star_marks)
-            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
+        return fail(ctx, RPT_ERR_ARG, name + ": RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a " + noun + " with");
+    if (!rides_objects) return RPT_OK;
+    if (ctx->interval != -1 && ctx->interval != 0)
+        return fail(ctx, RPT_ERR_ARG, name + ": interval is " + std::to_string(ctx->interval) + "; the light cone has a closed form for -1 and 0 only");
+    if (p.largest_object >= ctx->object_count)
+        return fail(ctx, RPT_ERR_ARG, name + ": the set names object " + std::to_string(p.largest_object) + ", the Object[] holds " + std::to_string(ctx->object_count));
+    return RPT_OK;
+}
 
-    a.stars = (const rpt_star *)ctx->star_table.device.ptr;
-    a.acc = (unsigned long long *)ctx->star_acc.ptr;
-    a.counts = (unsigned long long *)tally.device.ptr;
-    a.count = ctx->star_count;
+// ... and the one of the passes with temperatures, `setter` having set them and `records` naming what they run parallel to: a count that
+// is not the records' (what keeps xg[i] of kernels 1122 and 1132 inside its array)
+int thermal_refusal(rpt_ctx *ctx, const SplatPass &p, const char *call, const char *setter, const char *records) {
+    if (p.thermal_count == 0 || p.thermal_count == p.count) return RPT_OK;
+    return fail(ctx, RPT_ERR_ARG, std::string(call) + ": " + std::to_string(p.thermal_count) + " temperatures are set (" + setter + "), the " + records + " holds " + std::to_string(p.count));
+}
+
+// The view as §19 rule 4 projects it, for StarArgs and ParticleArgs alike
+template <typename Args>
+void splat_view(const rpt_ctx *ctx, Args &a) {
     a.width = ctx->width;
     a.height = ctx->height;
     a.interval = ctx->interval;
@@ -2071,35 +2061,80 @@ int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event 
         a.plane_x = s * ((float)ctx->width / (float)ctx->height);
         a.plane_y = s;
     }
-    rptd::StarResolveArgs b;
-    std::memset((void *)&b, 0, sizeof b);
-    b.acc = a.acc;
-    b.events = events;
+}
+
+// What follows a splat pass's refusals, once for the three: the accumulator, the tally's `words`, the marks of a timed pass, the tally
+// zeroed, `splat` — the pass's own launch, handed the accumulator and the tally's words for its arguments — and the resolve, kernel
+// `resolve` with `b`: the caller has set what is its kernel's alone (1121's records), the rest is filled here.
+template <typename ResolveArgs, typename Splat>
+int enqueue_splat(rpt_ctx *ctx, int which, Tally &tally, size_t words, rpt_pixel *out16, const void *resolve, ResolveArgs &b, Splat splat) {
+    SplatPass &p = ctx->splat[which];
+    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
+    if (int rc = accumulator_ready(ctx, pixels)) return rc;
+    if (int rc = tally_ready(ctx, tally, words)) return rc;
+    if (p.timed)
+        for (hipEvent_t &m : p.marks)
+            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
+
+    b.acc = (unsigned long long *)ctx->splat_acc.ptr;
     b.out16 = out16;
-    b.counts = a.counts;
+    b.counts = (unsigned long long *)tally.device.ptr;
     b.pixels = pixels;
     for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
 
     if (int rc = tally_zero(ctx, tally)) return rc;
-    if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[0], ctx->stream));
-    const float *xg = (const float *)ctx->star_thermal_table.device.ptr;
-    void *splat_args[] = {(void *)&a, (void *)&xg};     // (1120 takes the first only)
-    (void)hipLaunchKernel(ctx->star_thermal_count != 0 ? (const void *)rptd::rpt_stars_thermal_splat_kernel : (const void *)rptd::rpt_stars_splat_kernel,
-                          dim3((unsigned)((ctx->star_count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    if (p.timed) RPT_HIP(ctx, hipEventRecord(p.marks[0], ctx->stream));
+    splat(b.acc, b.counts);
     RPT_HIP(ctx, hipGetLastError());
-    if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[1], ctx->stream));
+    if (p.timed) RPT_HIP(ctx, hipEventRecord(p.marks[1], ctx->stream));
     void *resolve_args[] = {(void *)&b};
-    (void)hipLaunchKernel((const void *)rptd::rpt_stars_resolve_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
+    (void)hipLaunchKernel(resolve, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
     RPT_HIP(ctx, hipGetLastError());
-    if (ctx->star_timed) RPT_HIP(ctx, hipEventRecord(ctx->star_marks[2], ctx->stream));
-    ctx->star_marked = ctx->star_timed;
+    if (p.timed) RPT_HIP(ctx, hipEventRecord(p.marks[2], ctx->stream));
+    p.marked = p.timed;
     return RPT_OK;
 }
 
-int launch_stars(rpt_ctx *ctx) {
-    if (ctx->star_count == 0) ctx->star_marked = false;      // (no catalogue: no pass, so no marks of one)
-    return frame_pass(ctx, "rpt_render_stars", ctx->star_count != 0, TALLY_STARS, enqueue_stars);
+// rpt_render_stars, _particles, _segments: a pass that is off has no marks of one either; then frame_pass
+int launch_splat(rpt_ctx *ctx, int which, const char *call, int tally, PassEnqueue enqueue) {
+    SplatPass &p = ctx->splat[which];
+    if (p.count == 0) p.marked = false;
+    return frame_pass(ctx, call, p.count != 0, tally, enqueue);
 }
+
+// One star-field pass on the context's stream (kernels 1120 or 1122, and 1121): its refusals, G, the launch
+int enqueue_stars(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    const SplatPass &p = ctx->splat[SPLAT_STARS];
+    if (int rc = splat_refusals(ctx, p, "rpt_render_stars", "star", false)) return rc;
+    if (int rc = thermal_refusal(ctx, p, "rpt_render_stars", "rpt_set_star_temperatures", "catalogue")) return rc;
+    rptd::StarArgs a;
+    std::memset((void *)&a, 0, sizeof a);
+    {   // E' as a colour frame's launch forms it, then G
+        rpt_float4 e[4];
+        std::memcpy(e, ctx->env_frame, sizeof e);
+        if (ctx->oriented) rebase_columns(e, ctx->R, e);
+        float g[16];
+        if (!rpts::sky_to_camera(&e[0].x, ctx->interval, g))
+            return fail(ctx, RPT_ERR_ARG, "rpt_render_stars: the sky matrix (rpt_set_environment_frame) cannot be inverted");
+        std::memcpy(a.G, g, sizeof a.G);
+    }
+    a.stars = (const rpt_star *)p.table.device.ptr;
+    a.count = p.count;
+    splat_view(ctx, a);
+    rptd::StarResolveArgs b;
+    std::memset((void *)&b, 0, sizeof b);
+    b.events = events;
+    return enqueue_splat(ctx, SPLAT_STARS, tally, 2, out16, (const void *)rptd::rpt_stars_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
+        a.acc = acc;
+        a.counts = counts;
+        const float *xg = (const float *)p.thermal_table.device.ptr;
+        void *splat_args[] = {(void *)&a, (void *)&xg};     // (1120 takes the first only)
+        (void)hipLaunchKernel(p.thermal_count != 0 ? (const void *)rptd::rpt_stars_thermal_splat_kernel : (const void *)rptd::rpt_stars_splat_kernel,
+                              dim3((unsigned)((p.count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    });
+}
+
+int launch_stars(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_STARS, "rpt_render_stars", TALLY_STARS, enqueue_stars); }
 
 // the arguments the ray-level probes and the lit particles' shadow ray need: the resident scene and the current Object[] / DObj[] (no
 // frame, no outputs)
@@ -2126,158 +2161,97 @@ void probe_kernel_args(rpt_ctx *ctx, rptd::KernelArgs &a) {
     a.interval = ctx->interval;
 }
 
-// What the particle pass and the segment pass hand their kernels alike: the objects and their windows, the records, the accumulator, the
-// tally, the view as rule 4 projects it, and the resolve's arguments (kernel 1131).  The set, its count and its options are the caller's.
-void point_pass_args(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events, rptd::ParticleArgs &a, rptd::ParticleResolveArgs &b) {
+// What the particle pass and the segment pass hand their splat kernels alike: the objects and their windows, the records of the view,
+// and the view.  The set, its count and its options are the caller's; the accumulator and the tally's words come with the launch.
+void object_pass_args(rpt_ctx *ctx, const rpt_event *events, rptd::ParticleArgs &a) {
     std::memset((void *)&a, 0, sizeof a);
     a.objects = (const rpt_object *)ctx->objects.ptr;
     if (!ctx->windows.empty())          // (their count is the Object[]'s: the frames of this view were launched with them)
         a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
     a.events = events;
-    a.acc = (unsigned long long *)ctx->star_acc.ptr;
-    a.counts = (unsigned long long *)tally.device.ptr;
     a.object_count = ctx->object_count;
-    a.width = ctx->width;
-    a.height = ctx->height;
-    a.interval = ctx->interval;
-    a.doppler = ctx->interval != 0 ? ctx->doppler : 0;
-    if (ctx->projection == RPT_PROJECTION_EQUIRECT) {
-        a.camera = RPT_STARS_EQUIRECT;
-        a.h_fov = ctx->projection_params[0];
-        a.v_fov = ctx->projection_params[1];
-        a.yaw = ctx->projection_params[2];
-        a.wrap = a.h_fov == (float)(2.0 * RPT_PI_D) ? 1 : 0;
-    } else {
-        const float s = ctx->v_fov != 0.0f ? ctx->lens_scale : 1.0f;
-        a.plane_x = s * ((float)ctx->width / (float)ctx->height);
-        a.plane_y = s;
-    }
-    std::memset((void *)&b, 0, sizeof b);
-    b.acc = a.acc;
-    b.out16 = out16;
-    b.counts = a.counts;
-    b.pixels = (size_t)ctx->width * (size_t)ctx->height;
-    for (int c = 0; c < 3; c++) b.hable_wp[c] = hable_host(ctx->white_point[c]);
+    splat_view(ctx, a);
 }
 
-// One particle pass on the context's stream (kernels 1130 and 1131): three refusals of its own — the last is what keeps every index
-// the splat follows inside Object[] —, the accumulator it shares with the stars, the two launches.  With rpt_set_particle_lighting the
-// splat is one of the lit kernels (1134, 1135, 1136; rptl::splat_kernel chooses) after two more refusals (rptl::launch_fault), and two
-// more words of the tally come home: the (particle, light) pairs that lit and the pairs shadowed
+// One particle pass on the context's stream (kernels 1130 or 1132, and 1131): its refusals, the launch.  With rpt_set_particle_lighting
+// the splat is one of the lit kernels (1134, 1135, 1136; rptl::splat_kernel chooses) after two more refusals (rptl::launch_fault), and
+// two more words of the tally come home: the (particle, light) pairs that lit and the pairs shadowed
 int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
-    if (ctx->projection == RPT_PROJECTION_RAYMAP)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a particle with");
-    if (ctx->interval != -1 && ctx->interval != 0)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: interval is " + std::to_string(ctx->interval) + "; the light cone has a closed form for -1 and 0 only");
-    if (ctx->particle_largest_object >= ctx->object_count)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: the set names object " + std::to_string(ctx->particle_largest_object) + ", the Object[] holds " + std::to_string(ctx->object_count));
-    if (ctx->particle_thermal_count != 0 && ctx->particle_thermal_count != ctx->particle_count)     // (what keeps kernel 1132's xg[i] inside its array)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_particles: " + std::to_string(ctx->particle_thermal_count) + " temperatures are set (rpt_set_particle_temperatures), the set holds " + std::to_string(ctx->particle_count));
-    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
-    if (int rc = accumulator_ready(ctx, pixels)) return rc;
-    const rptl::LaunchFault dust_fault = rptl::launch_fault(ctx->particle_lighting, ctx->particle_thermal_count, ctx->geo->compact_ok);
+    const SplatPass &p = ctx->splat[SPLAT_PARTICLES];
+    if (int rc = splat_refusals(ctx, p, "rpt_render_particles", "particle", true)) return rc;
+    if (int rc = thermal_refusal(ctx, p, "rpt_render_particles", "rpt_set_particle_temperatures", "set")) return rc;
+    const rptl::LaunchFault dust_fault = rptl::launch_fault(ctx->particle_lighting, p.thermal_count, ctx->geo->compact_ok);
     if (dust_fault.code != RPT_OK) return fail(ctx, dust_fault.code, "rpt_render_particles: " + dust_fault.message);
-    if (int rc = tally_ready(ctx, tally, 4)) return rc;       // seen, changed pixels; (particle, light) pairs lit, pairs shadowed (zero for a plain pass)
-    if (ctx->particle_timed)
-        for (hipEvent_t &m : ctx->particle_marks)
-            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
 
     rptd::ParticleArgs a;
-    rptd::ParticleResolveArgs b;
-    point_pass_args(ctx, tally, out16, events, a, b);
-    a.particles = (const rpt_particle *)ctx->particle_table.device.ptr;
-    a.count = ctx->particle_count;
+    object_pass_args(ctx, events, a);
+    a.particles = (const rpt_particle *)p.table.device.ptr;
+    a.count = p.count;
     a.inverse_square = ctx->particle_flags & RPT_PARTICLES_INVERSE_SQUARE;
     a.depth_bias = ctx->particle_depth_bias;
-
-    if (int rc = tally_zero(ctx, tally)) return rc;
-    if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[0], ctx->stream));
-    const int splat = rptl::splat_kernel(ctx->particle_lighting, ctx->interval, ctx->particle_thermal_count, !ctx->windows.empty());
-    const dim3 splat_grid((unsigned)((ctx->particle_count + 255) / 256));
-    if (splat == 1130 || splat == 1132) {
-        const float *xg = (const float *)ctx->particle_thermal_table.device.ptr;
-        void *splat_args[] = {(void *)&a, (void *)&xg};     // (1130 takes the first only)
-        (void)hipLaunchKernel(splat == 1132 ? (const void *)rptd::rpt_particles_thermal_splat_kernel : (const void *)rptd::rpt_particles_splat_kernel,
-                              splat_grid, dim3(256), splat_args, 0, ctx->stream);
-    } else {                                                // lit particles: 1134, or 1135 / 1136 with the scene for the shadow ray
-        rptd::DustArgs d;
-        std::memset((void *)&d, 0, sizeof d);
-        d.p = a;
-        d.ambient = ctx->ambient;
-        d.add_ambient = ctx->particle_lighting & RPT_PARTICLES_AMBIENT;
-        rptd::KernelArgs k;
-        probe_kernel_args(ctx, k);
-        void *splat_args[] = {(void *)&d, (void *)&k};      // (1134 takes the first only)
-        (void)hipLaunchKernel(splat == 1134 ? (const void *)rptd::rpt_dust_splat_kernel
-                              : splat == 1135 ? (const void *)rptd::rpt_dust_shadowed_splat_kernel : (const void *)rptd::rpt_dust_shadowed_windowed_splat_kernel,
-                              splat_grid, dim3(256), splat_args, 0, ctx->stream);
-    }
-    RPT_HIP(ctx, hipGetLastError());
-    if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[1], ctx->stream));
-    void *resolve_args[] = {(void *)&b};
-    (void)hipLaunchKernel((const void *)rptd::rpt_particles_resolve_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
-    RPT_HIP(ctx, hipGetLastError());
-    if (ctx->particle_timed) RPT_HIP(ctx, hipEventRecord(ctx->particle_marks[2], ctx->stream));
-    ctx->particle_marked = ctx->particle_timed;
-    return RPT_OK;
+    rptd::ParticleResolveArgs b;
+    std::memset((void *)&b, 0, sizeof b);
+    // the tally's four words: seen, changed pixels; (particle, light) pairs lit, pairs shadowed (zero for a plain pass)
+    return enqueue_splat(ctx, SPLAT_PARTICLES, tally, 4, out16, (const void *)rptd::rpt_particles_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
+        a.acc = acc;
+        a.counts = counts;
+        const int splat = rptl::splat_kernel(ctx->particle_lighting, ctx->interval, p.thermal_count, !ctx->windows.empty());
+        const dim3 splat_grid((unsigned)((p.count + 255) / 256));
+        if (splat == 1130 || splat == 1132) {
+            const float *xg = (const float *)p.thermal_table.device.ptr;
+            void *splat_args[] = {(void *)&a, (void *)&xg};     // (1130 takes the first only)
+            (void)hipLaunchKernel(splat == 1132 ? (const void *)rptd::rpt_particles_thermal_splat_kernel : (const void *)rptd::rpt_particles_splat_kernel,
+                                  splat_grid, dim3(256), splat_args, 0, ctx->stream);
+        } else {                                                // lit particles: 1134, or 1135 / 1136 with the scene for the shadow ray
+            rptd::DustArgs d;
+            std::memset((void *)&d, 0, sizeof d);
+            d.p = a;
+            d.ambient = ctx->ambient;
+            d.add_ambient = ctx->particle_lighting & RPT_PARTICLES_AMBIENT;
+            rptd::KernelArgs k;
+            probe_kernel_args(ctx, k);
+            void *splat_args[] = {(void *)&d, (void *)&k};      // (1134 takes the first only)
+            (void)hipLaunchKernel(splat == 1134 ? (const void *)rptd::rpt_dust_splat_kernel
+                                  : splat == 1135 ? (const void *)rptd::rpt_dust_shadowed_splat_kernel : (const void *)rptd::rpt_dust_shadowed_windowed_splat_kernel,
+                                  splat_grid, dim3(256), splat_args, 0, ctx->stream);
+        }
+    });
 }
 
-int launch_particles(rpt_ctx *ctx) {
-    if (ctx->particle_count == 0) ctx->particle_marked = false;
-    return frame_pass(ctx, "rpt_render_particles", ctx->particle_count != 0, TALLY_PARTICLES, enqueue_particles);
-}
+int launch_particles(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_PARTICLES, "rpt_render_particles", TALLY_PARTICLES, enqueue_particles); }
 
-// One segment pass on the context's stream (kernels 1140 and 1131): the particle pass's refusals — the last is what keeps every index
-// the splat follows inside Object[] —, the accumulator it shares with the stars and the particles, the two launches.  One lane per piece.
+// One segment pass on the context's stream (kernels 1140 and 1131): the refusals of a pass that rides objects, the launch.  One lane
+// per piece.
 int enqueue_segments(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
-    if (ctx->projection == RPT_PROJECTION_RAYMAP)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_segments: RPT_PROJECTION_RAYMAP is set, and a caller's ray map has no inverse to project a node with");
-    if (ctx->interval != -1 && ctx->interval != 0)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_segments: interval is " + std::to_string(ctx->interval) + "; the light cone has a closed form for -1 and 0 only");
-    if (ctx->segment_largest_object >= ctx->object_count)
-        return fail(ctx, RPT_ERR_ARG, "rpt_render_segments: the set names object " + std::to_string(ctx->segment_largest_object) + ", the Object[] holds " + std::to_string(ctx->object_count));
-    const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
-    if (int rc = accumulator_ready(ctx, pixels)) return rc;
-    if (int rc = tally_ready(ctx, tally, 2)) return rc;
-    if (ctx->segment_timed)
-        for (hipEvent_t &m : ctx->segment_marks)
-            if (!m) RPT_HIP(ctx, hipEventCreate(&m));
+    const SplatPass &p = ctx->splat[SPLAT_SEGMENTS];
+    if (int rc = splat_refusals(ctx, p, "rpt_render_segments", "node", true)) return rc;
 
     rptd::SegmentArgs a;
     std::memset((void *)&a, 0, sizeof a);
-    rptd::ParticleResolveArgs b;
-    point_pass_args(ctx, tally, out16, events, a.p, b);
-    a.p.count = ctx->segment_count;
+    object_pass_args(ctx, events, a.p);
+    a.p.count = p.count;
     a.p.inverse_square = ctx->segment_flags & RPT_SEGMENTS_INVERSE_SQUARE;
     a.p.depth_bias = ctx->segment_depth_bias;
-    a.segments = (const rpt_segment *)ctx->segment_table.device.ptr;
+    a.segments = (const rpt_segment *)p.table.device.ptr;
     a.pieces = ctx->segment_pieces;
     while ((1 << a.shift) < a.pieces) a.shift++;
     if (a.p.camera == RPT_STARS_EQUIRECT) a.period = (float)ctx->width * ((float)(2.0 * RPT_PI_D) / a.p.h_fov);
-
-    const void *splat = (const void *)rptd::rpt_segments_splat_kernel;
+    rptd::ParticleResolveArgs b;
+    std::memset((void *)&b, 0, sizeof b);
+    return enqueue_splat(ctx, SPLAT_SEGMENTS, tally, 2, out16, (const void *)rptd::rpt_particles_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
+        a.p.acc = acc;
+        a.p.counts = counts;
+        const void *splat = (const void *)rptd::rpt_segments_splat_kernel;
 #ifdef RPT_DIAGNOSTICS
-    if (ctx->variant == 1141) splat = (const void *)rptd::rpt_segments_splat_loop_kernel;      // the measurement arm: a loop per lane
+        if (ctx->variant == 1141) splat = (const void *)rptd::rpt_segments_splat_loop_kernel;      // the measurement arm: a loop per lane
 #endif
-    const unsigned lanes = (unsigned)ctx->segment_count * (unsigned)ctx->segment_pieces;      // <= 2^21 (rptg::kMaxPieces)
-    if (int rc = tally_zero(ctx, tally)) return rc;
-    if (ctx->segment_timed) RPT_HIP(ctx, hipEventRecord(ctx->segment_marks[0], ctx->stream));
-    void *splat_args[] = {(void *)&a};
-    (void)hipLaunchKernel(splat, dim3((lanes + 255u) / 256u), dim3(256), splat_args, 0, ctx->stream);
-    RPT_HIP(ctx, hipGetLastError());
-    if (ctx->segment_timed) RPT_HIP(ctx, hipEventRecord(ctx->segment_marks[1], ctx->stream));
-    void *resolve_args[] = {(void *)&b};
-    (void)hipLaunchKernel((const void *)rptd::rpt_particles_resolve_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
-    RPT_HIP(ctx, hipGetLastError());
-    if (ctx->segment_timed) RPT_HIP(ctx, hipEventRecord(ctx->segment_marks[2], ctx->stream));
-    ctx->segment_marked = ctx->segment_timed;
-    return RPT_OK;
+        const unsigned lanes = (unsigned)p.count * (unsigned)ctx->segment_pieces;      // <= 2^21 (rptg::kMaxPieces)
+        void *splat_args[] = {(void *)&a};
+        (void)hipLaunchKernel(splat, dim3((lanes + 255u) / 256u), dim3(256), splat_args, 0, ctx->stream);
+    });
 }
 
-int launch_segments(rpt_ctx *ctx) {
-    if (ctx->segment_count == 0) ctx->segment_marked = false;
-    return frame_pass(ctx, "rpt_render_segments", ctx->segment_count != 0, TALLY_SEGMENTS, enqueue_segments);
-}
+int launch_segments(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_SEGMENTS, "rpt_render_segments", TALLY_SEGMENTS, enqueue_segments); }
 
 // The event pass and what it leaves for rpt_pick, rpt_read_events and the passes over the frame
 int launch_event_frame(rpt_ctx *ctx) {
@@ -2300,6 +2274,54 @@ int render_pass(rpt_ctx *ctx, int (*launch_pass)(rpt_ctx *), bool wait) {
 // a colour frame has been enqueued for the present view and size, into the present framebuffer
 void mark_colour_frame(rpt_ctx *ctx) {
     ctx->colour_frame = FrameMark{ctx->view_generation, ctx->width, ctx->height, ctx->colour_plane ? nullptr : rpt_output_ptr(ctx)};
+}
+
+// rpt_set_stars, rpt_set_particles, rpt_set_segments and the two rpt_set_*_temperatures, `call` naming the one: `count` records go to
+// the device here, once, as `prepare` writes them, in stream order (a pass in flight keeps what it was launched with).  Null or zero
+// switches off; a call refused for its arguments (`fault`: "" or what is wrong with them) has changed nothing, one that fails on the
+// device (RPT_ERR_DEVICE) leaves nothing set — the table may be gone or half written.  `largest`, for records that name objects: what
+// every launch holds against object_count.
+template <typename Record, typename Fault>
+int set_records(rpt_ctx *ctx, const char *call, StagedUpload &table, int &table_count, int &largest_object, const Record *records_or_null, int count,
+                int max_count, Fault fault, void (*prepare)(const Record *, int, Record *), int (*largest)(const Record *, int) = nullptr) {
+    const std::string name(call);
+    if (count < 0 || count > max_count) return fail(ctx, RPT_ERR_ARG, name + ": " + fault((const Record *)nullptr, count));
+    const bool off = !records_or_null || count == 0;
+    if (!off) {
+        const std::string what = fault(records_or_null, count);
+        if (!what.empty()) return fail(ctx, RPT_ERR_ARG, name + ": " + what);
+    }
+    if (!off) RPT_HIP(ctx, hipSetDevice(ctx->device));
+    table_count = 0;                    // (off, or until the copy below is on its way)
+    largest_object = -1;
+    if (off) return RPT_OK;
+    void *host = nullptr;
+    if (int rc = staged_host(ctx, table, (size_t)count * sizeof(Record), &host)) return rc;
+    prepare(records_or_null, count, (Record *)host);
+    if (int rc = staged_copy(ctx, table)) return rc;
+    table_count = count;
+    if (largest) largest_object = largest(records_or_null, count);
+    return RPT_OK;
+}
+
+// rpt_set_stars_measurement, _particles_, _segments_
+int set_splat_measurement(rpt_ctx *ctx, int which, int timed) {
+    if (!ctx) return RPT_ERR_ARG;
+    ctx->splat[which].timed = timed != 0;
+    return RPT_OK;
+}
+
+// rpt_last_stars_ms, _particles_, _segments_: `name` as those calls spell the pass, `pass` as their message does
+int last_splat_ms(rpt_ctx *ctx, int which, float ms[2], const char *name, const char *pass) {
+    if (!ctx || !ms) return RPT_ERR_ARG;
+    const SplatPass &p = ctx->splat[which];
+    if (!p.marked)
+        return fail(ctx, RPT_ERR_STATE, std::string("rpt_last_") + name + "_ms: the last " + pass + " pass was not timed (rpt_set_" + name + "_measurement)");
+    RPT_HIP(ctx, hipSetDevice(ctx->device));
+    RPT_HIP(ctx, hipEventSynchronize(p.marks[2]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], p.marks[0], p.marks[1]));
+    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], p.marks[1], p.marks[2]));
+    return RPT_OK;
 }
 
 }  // namespace
@@ -2367,14 +2389,16 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->star_acc})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->splat_acc})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
-    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table, &ctx->star_table, &ctx->particle_table, &ctx->star_thermal_table, &ctx->particle_thermal_table, &ctx->segment_table}) release(*u);
+    for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table}) release(*u);
     for (Tally &t : ctx->tally) release(t);
-    for (hipEvent_t m : ctx->star_marks) if (m) (void)hipEventDestroy(m);
-    for (hipEvent_t m : ctx->particle_marks) if (m) (void)hipEventDestroy(m);
-    for (hipEvent_t m : ctx->segment_marks) if (m) (void)hipEventDestroy(m);
+    for (SplatPass &p : ctx->splat) {
+        release(p.table);
+        release(p.thermal_table);
+        for (hipEvent_t m : p.marks) if (m) (void)hipEventDestroy(m);
+    }
     for (hipEvent_t e : ctx->staging_done) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -3372,30 +3396,11 @@ int rpt_render_readouts(rpt_ctx *ctx) { return render_pass(ctx, launch_readouts,
 
 int rpt_last_readout_pixels(rpt_ctx *ctx, unsigned long long *pixels) { return tally_read(ctx, TALLY_READOUTS, pixels, 1); }
 
-// The catalogue goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused
-// for its arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no catalogue.
+// The star-field pass.  The catalogue goes to the device once, here (set_records)
 int rpt_set_stars(rpt_ctx *ctx, const rpt_star *stars_or_null, int count) {
     if (!ctx) return RPT_ERR_ARG;
-    if (count < 0 || count > rpts::kMaxStars) return fail(ctx, RPT_ERR_ARG, "rpt_set_stars: " + rpts::catalogue_fault(nullptr, count));
-    if (!stars_or_null || count == 0) {
-        ctx->star_count = 0;
-        return RPT_OK;
-    }
-    const std::string fault = rpts::catalogue_fault(stars_or_null, count);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_stars: " + fault);
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    void *host = nullptr;
-    int rc = staged_host(ctx, ctx->star_table, (size_t)count * sizeof(rpt_star), &host);
-    if (!rc) {
-        rpts::prepare_catalogue(stars_or_null, count, (rpt_star *)host);
-        rc = staged_copy(ctx, ctx->star_table);
-    }
-    if (rc) {
-        ctx->star_count = 0;
-        return rc;
-    }
-    ctx->star_count = count;
-    return RPT_OK;
+    SplatPass &p = ctx->splat[SPLAT_STARS];
+    return set_records(ctx, "rpt_set_stars", p.table, p.count, p.largest_object, stars_or_null, count, rpts::kMaxStars, rpts::catalogue_fault, rpts::prepare_catalogue);
 }
 
 int rpt_render_stars_async(rpt_ctx *ctx) { return render_pass(ctx, launch_stars, false); }
@@ -3403,49 +3408,15 @@ int rpt_render_stars(rpt_ctx *ctx) { return render_pass(ctx, launch_stars, true)
 
 int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_STARS, out, 2); }
 
-int rpt_set_stars_measurement(rpt_ctx *ctx, int timed) {
-    if (!ctx) return RPT_ERR_ARG;
-    ctx->star_timed = timed != 0;
-    return RPT_OK;
-}
+int rpt_set_stars_measurement(rpt_ctx *ctx, int timed) { return set_splat_measurement(ctx, SPLAT_STARS, timed); }
+int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]) { return last_splat_ms(ctx, SPLAT_STARS, ms, "stars", "star-field"); }
 
-int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]) {
-    if (!ctx || !ms) return RPT_ERR_ARG;
-    if (!ctx->star_marked) return fail(ctx, RPT_ERR_STATE, "rpt_last_stars_ms: the last star-field pass was not timed (rpt_set_stars_measurement)");
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    RPT_HIP(ctx, hipEventSynchronize(ctx->star_marks[2]));
-    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->star_marks[0], ctx->star_marks[1]));
-    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->star_marks[1], ctx->star_marks[2]));
-    return RPT_OK;
-}
-
-// The set goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused for its
-// arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no set.
+// The particle pass.  The set goes to the device once, here (set_records)
 int rpt_set_particles(rpt_ctx *ctx, const rpt_particle *particles_or_null, int count) {
     if (!ctx) return RPT_ERR_ARG;
-    if (count < 0 || count > rptp::kMaxParticles) return fail(ctx, RPT_ERR_ARG, "rpt_set_particles: " + rptp::set_fault(nullptr, count));
-    if (!particles_or_null || count == 0) {
-        ctx->particle_count = 0;
-        ctx->particle_largest_object = -1;
-        return RPT_OK;
-    }
-    const std::string fault = rptp::set_fault(particles_or_null, count);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_particles: " + fault);
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    void *host = nullptr;
-    int rc = staged_host(ctx, ctx->particle_table, (size_t)count * sizeof(rpt_particle), &host);
-    if (!rc) {
-        rptp::prepare_set(particles_or_null, count, (rpt_particle *)host);
-        rc = staged_copy(ctx, ctx->particle_table);
-    }
-    if (rc) {
-        ctx->particle_count = 0;
-        ctx->particle_largest_object = -1;
-        return rc;
-    }
-    ctx->particle_count = count;
-    ctx->particle_largest_object = rptp::largest_object(particles_or_null, count);
-    return RPT_OK;
+    SplatPass &p = ctx->splat[SPLAT_PARTICLES];
+    return set_records(ctx, "rpt_set_particles", p.table, p.count, p.largest_object, particles_or_null, count, rptp::kMaxParticles, rptp::set_fault, rptp::prepare_set,
+                       rptp::largest_object);
 }
 
 int rpt_set_particle_options(rpt_ctx *ctx, int flags, float depth_bias) {
@@ -3479,92 +3450,34 @@ int rpt_render_particles(rpt_ctx *ctx) { return render_pass(ctx, launch_particle
 
 int rpt_last_particles(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_PARTICLES, out, 2); }
 
-int rpt_set_particles_measurement(rpt_ctx *ctx, int timed) {
+int rpt_set_particles_measurement(rpt_ctx *ctx, int timed) { return set_splat_measurement(ctx, SPLAT_PARTICLES, timed); }
+int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]) { return last_splat_ms(ctx, SPLAT_PARTICLES, ms, "particles", "particle"); }
+
+// rpt_set_star_temperatures and rpt_set_particle_temperatures: the array goes to the device as x_G per source (set_records).  Whether
+// its count matches the catalogue's or the set's is asked at the launch, not here.
+static int set_temperatures(rpt_ctx *ctx, const char *call, int which, const float *kelvin_or_null, int count) {
     if (!ctx) return RPT_ERR_ARG;
-    ctx->particle_timed = timed != 0;
-    return RPT_OK;
+    SplatPass &p = ctx->splat[which];
+    int none = -1;
+    return set_records(ctx, call, p.thermal_table, p.thermal_count, none, kelvin_or_null, count, rptt::kMaxTemperatures, rptt::temperatures_fault, rptt::prepare_temperatures);
 }
 
-int rpt_last_particles_ms(rpt_ctx *ctx, float ms[2]) {
-    if (!ctx || !ms) return RPT_ERR_ARG;
-    if (!ctx->particle_marked) return fail(ctx, RPT_ERR_STATE, "rpt_last_particles_ms: the last particle pass was not timed (rpt_set_particles_measurement)");
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    RPT_HIP(ctx, hipEventSynchronize(ctx->particle_marks[2]));
-    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->particle_marks[0], ctx->particle_marks[1]));
-    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->particle_marks[1], ctx->particle_marks[2]));
-    return RPT_OK;
-}
+int rpt_set_star_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) { return set_temperatures(ctx, "rpt_set_star_temperatures", SPLAT_STARS, kelvin_or_null, count); }
+int rpt_set_particle_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) { return set_temperatures(ctx, "rpt_set_particle_temperatures", SPLAT_PARTICLES, kelvin_or_null, count); }
 
-// rpt_set_star_temperatures and rpt_set_particle_temperatures: the array goes to the device here, once, as x_G per source, in stream
-// order (a pass in flight keeps the one it was launched with); a call refused for its arguments has changed nothing, one that fails on
-// the device (RPT_ERR_DEVICE) leaves no array.  Whether its count matches the catalogue's is asked at the launch, not here.
-static int set_temperatures(rpt_ctx *ctx, const char *call, StagedUpload &table, int &table_count, const float *kelvin_or_null, int count) {
-    if (!ctx) return RPT_ERR_ARG;
-    if (count < 0 || count > rptt::kMaxTemperatures) return fail(ctx, RPT_ERR_ARG, std::string(call) + ": " + rptt::temperatures_fault(nullptr, count));
-    if (!kelvin_or_null || count == 0) {
-        table_count = 0;
-        return RPT_OK;
-    }
-    const std::string fault = rptt::temperatures_fault(kelvin_or_null, count);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, std::string(call) + ": " + fault);
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    void *host = nullptr;
-    int rc = staged_host(ctx, table, (size_t)count * sizeof(float), &host);
-    if (!rc) {
-        rptt::prepare_temperatures(kelvin_or_null, count, (float *)host);
-        rc = staged_copy(ctx, table);
-    }
-    if (rc) {
-        table_count = 0;
-        return rc;
-    }
-    table_count = count;
-    return RPT_OK;
-}
-
-int rpt_set_star_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) {
-    if (!ctx) return RPT_ERR_ARG;
-    return set_temperatures(ctx, "rpt_set_star_temperatures", ctx->star_thermal_table, ctx->star_thermal_count, kelvin_or_null, count);
-}
-
-int rpt_set_particle_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) {
-    if (!ctx) return RPT_ERR_ARG;
-    return set_temperatures(ctx, "rpt_set_particle_temperatures", ctx->particle_thermal_table, ctx->particle_thermal_count, kelvin_or_null, count);
-}
-
-// The set goes to the device here, once, in stream order (a pass in flight keeps the one it was launched with); a call refused for its
-// arguments has changed nothing, one that fails on the device (RPT_ERR_DEVICE) leaves no set.
+// The segment pass.  The set goes to the device once, here (set_records); the count is held against the pieces first (rptg::load_fault)
 int rpt_set_segments(rpt_ctx *ctx, const rpt_segment *segments_or_null, int count) {
     if (!ctx) return RPT_ERR_ARG;
-    if (count < 0 || !rptg::load_fault(count, ctx->segment_pieces).empty())
-        return fail(ctx, RPT_ERR_ARG, "rpt_set_segments: " + rptg::set_fault(nullptr, count, ctx->segment_pieces));
-    if (!segments_or_null || count == 0) {
-        ctx->segment_count = 0;
-        ctx->segment_largest_object = -1;
-        return RPT_OK;
-    }
-    const std::string fault = rptg::set_fault(segments_or_null, count, ctx->segment_pieces);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_segments: " + fault);
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    void *host = nullptr;
-    int rc = staged_host(ctx, ctx->segment_table, (size_t)count * sizeof(rpt_segment), &host);
-    if (!rc) {
-        rptg::prepare_set(segments_or_null, count, (rpt_segment *)host);
-        rc = staged_copy(ctx, ctx->segment_table);
-    }
-    if (rc) {
-        ctx->segment_count = 0;
-        ctx->segment_largest_object = -1;
-        return rc;
-    }
-    ctx->segment_count = count;
-    ctx->segment_largest_object = rptg::largest_object(segments_or_null, count);
-    return RPT_OK;
+    SplatPass &p = ctx->splat[SPLAT_SEGMENTS];
+    const int pieces = ctx->segment_pieces;
+    const auto fault = [pieces](const rpt_segment *segments, int n) { return rptg::set_fault(segments, n, pieces); };
+    if (count < 0 || !rptg::load_fault(count, pieces).empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_segments: " + fault(nullptr, count));
+    return set_records(ctx, "rpt_set_segments", p.table, p.count, p.largest_object, segments_or_null, count, (int)rptg::kMaxPieces, fault, rptg::prepare_set, rptg::largest_object);
 }
 
 int rpt_set_segment_options(rpt_ctx *ctx, int flags, float depth_bias, int pieces) {
     if (!ctx) return RPT_ERR_ARG;
-    const std::string fault = rptg::options_fault(flags, depth_bias, pieces, ctx->segment_count);
+    const std::string fault = rptg::options_fault(flags, depth_bias, pieces, ctx->splat[SPLAT_SEGMENTS].count);
     if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_segment_options: " + fault);
     ctx->segment_flags = flags;
     ctx->segment_depth_bias = depth_bias;
@@ -3577,21 +3490,8 @@ int rpt_render_segments(rpt_ctx *ctx) { return render_pass(ctx, launch_segments,
 
 int rpt_last_segments(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_SEGMENTS, out, 2); }
 
-int rpt_set_segments_measurement(rpt_ctx *ctx, int timed) {
-    if (!ctx) return RPT_ERR_ARG;
-    ctx->segment_timed = timed != 0;
-    return RPT_OK;
-}
-
-int rpt_last_segments_ms(rpt_ctx *ctx, float ms[2]) {
-    if (!ctx || !ms) return RPT_ERR_ARG;
-    if (!ctx->segment_marked) return fail(ctx, RPT_ERR_STATE, "rpt_last_segments_ms: the last segment pass was not timed (rpt_set_segments_measurement)");
-    RPT_HIP(ctx, hipSetDevice(ctx->device));
-    RPT_HIP(ctx, hipEventSynchronize(ctx->segment_marks[2]));
-    RPT_HIP(ctx, hipEventElapsedTime(&ms[0], ctx->segment_marks[0], ctx->segment_marks[1]));
-    RPT_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->segment_marks[1], ctx->segment_marks[2]));
-    return RPT_OK;
-}
+int rpt_set_segments_measurement(rpt_ctx *ctx, int timed) { return set_splat_measurement(ctx, SPLAT_SEGMENTS, timed); }
+int rpt_last_segments_ms(rpt_ctx *ctx, float ms[2]) { return last_splat_ms(ctx, SPLAT_SEGMENTS, ms, "segments", "segment"); }
 
 void *rpt_output_ptr(rpt_ctx *ctx) {
     if (!ctx) return nullptr;

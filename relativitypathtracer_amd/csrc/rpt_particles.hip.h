@@ -3,8 +3,8 @@
 // its simultaneity slice), taken into the camera's frame by that object's InvLorentz, Doppler-shifted and beamed as point sources,
 // depth-tested tap by tap against the event records and splatted bilinearly into the star pass's per-pixel integer accumulator (kernel
 // 1130, a scatter), which kernel 1131 adds to the pixels of a rendered frame, hit or miss.  A sibling of the star-field pass: included by
-// rpt_api.hip behind rpt_stars.hip.h, whose star_add, clamp and fixed point it uses as they are; the projection (§19 rule 4) is restated
-// here rather than shared, so that kernel 1120's code stays what it was.  tests/native/particles_oracle.c restates every rule in C.
+// rpt_api.hip behind rpt_stars.hip.h, whose star_add, clamp, fixed point and projection (§19 rule 4, project_to_frame) it uses as
+// they are.  tests/native/particles_oracle.c restates every rule in C.
 #pragma once
 
 #include "rpt_stars.hip.h"
@@ -67,20 +67,7 @@ RPT_DEV bool particle_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam
         if (a.doppler & 2) c = c / (D * D);              // a point source also loses solid angle by D^2
     }
     if (a.inverse_square) c = c / (r * r);
-    if (a.camera == RPT_STARS_EQUIRECT) {                // §19 rule 4, as star_place has it
-        const float pi = (float)RPT_PI_D, two_pi = (float)(2.0 * RPT_PI_D);
-        float lambda = rpt_atan2f(n.x, n.z) - a.yaw;
-        lambda = lambda - two_pi * __builtin_floorf((lambda + pi) / two_pi);
-        const float ny = n.y < -1.0f ? -1.0f : (n.y > 1.0f ? 1.0f : n.y);
-        const float phi = rpt_asinf(ny);
-        X = (float)a.width * (lambda / a.h_fov + 0.5f) - 0.5f;
-        Y = (float)a.height * (phi / a.v_fov + 0.5f) - 0.5f;
-    } else {
-        if (!(n.z > 0.0f)) return false;
-        X = (float)a.width * (0.5f + ((0.5f * n.x) / n.z) / a.plane_x);
-        Y = (float)a.height * (0.5f + ((0.5f * n.y) / n.z) / a.plane_y);
-    }
-    return fabsf(X) < 1e9f && fabsf(Y) < 1e9f;           // (a NaN fails both)
+    return project_to_frame(a, n, X, Y);                 // §19 rule 4, as star_place has it
 }
 
 // 1130: one lane per particle.  Two 16-byte loads of its record, then the five rpt_float4 of its object — InvLorentz and stationaryCam,

@@ -43,6 +43,26 @@ struct StarResolveArgs {
 // T_f of rpt_thermal.hip.h, which rpt_api.hip includes last: S_f where xg == 0, Planck's law elsewhere
 RPT_DEV f3 thermal_colour(int flags, float D, f3 c, float xg);
 
+// Rule 4 for a unit direction n in the camera's frame, for StarArgs and ParticleArgs alike (the view's fields have the same names in
+// both): the equirect or the pinhole projection to (X, Y).  false = behind the pinhole, or no finite position.
+template <typename Args>
+RPT_DEV bool project_to_frame(const Args &a, f3 n, float &X, float &Y) {
+    if (a.camera == RPT_STARS_EQUIRECT) {
+        const float pi = (float)RPT_PI_D, two_pi = (float)(2.0 * RPT_PI_D);
+        float lambda = rpt_atan2f(n.x, n.z) - a.yaw;
+        lambda = lambda - two_pi * __builtin_floorf((lambda + pi) / two_pi);
+        const float ny = n.y < -1.0f ? -1.0f : (n.y > 1.0f ? 1.0f : n.y);
+        const float phi = rpt_asinf(ny);
+        X = (float)a.width * (lambda / a.h_fov + 0.5f) - 0.5f;
+        Y = (float)a.height * (phi / a.v_fov + 0.5f) - 0.5f;
+    } else {
+        if (!(n.z > 0.0f)) return false;
+        X = (float)a.width * (0.5f + ((0.5f * n.x) / n.z) / a.plane_x);
+        Y = (float)a.height * (0.5f + ((0.5f * n.y) / n.z) / a.plane_y);
+    }
+    return fabsf(X) < 1e9f && fabsf(Y) < 1e9f;           // (a NaN fails both)
+}
+
 // Rules 1-4 for one star: false = the star is skipped (D not finite or not > 0, behind the pinhole, no finite position).
 // THERMAL: the colour rule is T_f with the star's xg (kernel 1122); without it xg is not looked at and the rule is S_f (kernel 1120).
 template <bool THERMAL>
@@ -58,21 +78,7 @@ RPT_DEV bool star_place(const StarArgs &a, f3 s, f3 rgb, float xg, float &X, flo
         }
         if (a.doppler & 2) c = c / (D * D);              // a point source also loses solid angle by D^2
     }
-    const f3 n = normalize(yzw(q));
-    if (a.camera == RPT_STARS_EQUIRECT) {
-        const float pi = (float)RPT_PI_D, two_pi = (float)(2.0 * RPT_PI_D);
-        float lambda = rpt_atan2f(n.x, n.z) - a.yaw;
-        lambda = lambda - two_pi * __builtin_floorf((lambda + pi) / two_pi);
-        const float ny = n.y < -1.0f ? -1.0f : (n.y > 1.0f ? 1.0f : n.y);
-        const float phi = rpt_asinf(ny);
-        X = (float)a.width * (lambda / a.h_fov + 0.5f) - 0.5f;
-        Y = (float)a.height * (phi / a.v_fov + 0.5f) - 0.5f;
-    } else {
-        if (!(n.z > 0.0f)) return false;
-        X = (float)a.width * (0.5f + ((0.5f * n.x) / n.z) / a.plane_x);
-        Y = (float)a.height * (0.5f + ((0.5f * n.y) / n.z) / a.plane_y);
-    }
-    return fabsf(X) < 1e9f && fabsf(Y) < 1e9f;           // (a NaN fails both)
+    return project_to_frame(a, normalize(yzw(q)), X, Y);
 }
 
 // one channel of one tap into the accumulator: nothing for p <= 0 or NaN, the clamp, the fixed point, a fire-and-forget integer add

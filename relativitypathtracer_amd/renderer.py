@@ -391,6 +391,28 @@ class Renderer:
         self._check(getattr(self._lib, call)(self._h, counts), call)
         return tuple(int(c) for c in counts)
 
+    def _set_records(self, call: str, records, record, what: str):
+        """The records of a splat pass for its rpt_set_* call: an array with one `record` (a ctypes structure of _ffi) per entry; None
+        or an empty one switches the pass off.  Another size raises ValueError(what)."""
+        if records is None or len(records) == 0:
+            self._check(getattr(self._lib, call)(self._h, None, 0), call)
+            return
+        raw = np.ascontiguousarray(records)
+        size = C.sizeof(record)
+        if raw.nbytes % size or raw.nbytes // size != len(raw):
+            raise ValueError(what)
+        self._check(getattr(self._lib, call)(self._h, C.cast(raw.ctypes.data, C.POINTER(record)), len(raw)), call)
+
+    def _set_measurement(self, call: str, timed: bool):
+        """A rpt_set_*_measurement call: time the two kernels of every pass, or no longer."""
+        self._check(getattr(self._lib, call)(self._h, int(bool(timed))), call)
+
+    def _last_ms(self, call: str) -> Tuple[float, float]:
+        """The (splat, resolve) device milliseconds a rpt_last_*_ms call reports of its last pass."""
+        ms = (C.c_float * 2)(0.0, 0.0)
+        self._check(getattr(self._lib, call)(self._h, ms), call)
+        return float(ms[0]), float(ms[1])
+
     # -- the event pass (include/rpt.h, rpt_render_events; not in the reference) ------------------
     def set_events_output(self, device_ptr: Optional[int]):
         """The record buffer of the event pass: a device pointer to width * height * 32 B, or None for a library-owned one."""
@@ -504,13 +526,7 @@ class Renderer:
             self.set_stars(catalogue)
             self.set_star_temperatures(temperatures)
             return
-        if catalogue is None or len(catalogue) == 0:
-            self._check(self._lib.rpt_set_stars(self._h, None, 0), "rpt_set_stars")
-            return
-        raw = np.ascontiguousarray(catalogue)
-        if raw.nbytes % 32 or raw.nbytes // 32 != len(raw):
-            raise ValueError("a star catalogue has one 32-byte record (stars.STAR_DTYPE) per star")
-        self._check(self._lib.rpt_set_stars(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Star)), len(raw)), "rpt_set_stars")
+        self._set_records("rpt_set_stars", catalogue, _ffi.Star, "a star catalogue has one 32-byte record (stars.STAR_DTYPE) per star")
 
     def _set_temperatures(self, call: str, kelvin):
         if kelvin is None or len(kelvin) == 0:
@@ -540,13 +556,11 @@ class Renderer:
 
     def set_stars_measurement(self, timed: bool = False):
         """Measurement only (tools/stars_cost.py): time the two kernels of every pass (last_stars_ms)."""
-        self._check(self._lib.rpt_set_stars_measurement(self._h, int(bool(timed))), "rpt_set_stars_measurement")
+        self._set_measurement("rpt_set_stars_measurement", timed)
 
     def last_stars_ms(self) -> Tuple[float, float]:
         """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_stars_measurement)."""
-        ms = (C.c_float * 2)(0.0, 0.0)
-        self._check(self._lib.rpt_last_stars_ms(self._h, ms), "rpt_last_stars_ms")
-        return float(ms[0]), float(ms[1])
+        return self._last_ms("rpt_last_stars_ms")
 
     # -- the particle pass (include/rpt.h, rpt_set_particles; not in the reference) -----------------
     def set_particles(self, particles, temperatures=None):
@@ -560,13 +574,7 @@ class Renderer:
             self.set_particles(particles)
             self.set_particle_temperatures(temperatures)
             return
-        if particles is None or len(particles) == 0:
-            self._check(self._lib.rpt_set_particles(self._h, None, 0), "rpt_set_particles")
-            return
-        raw = np.ascontiguousarray(particles)
-        if raw.nbytes % 32 or raw.nbytes // 32 != len(raw):
-            raise ValueError("a particle set has one 32-byte record (particles.PARTICLE_DTYPE) per particle")
-        self._check(self._lib.rpt_set_particles(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Particle)), len(raw)), "rpt_set_particles")
+        self._set_records("rpt_set_particles", particles, _ffi.Particle, "a particle set has one 32-byte record (particles.PARTICLE_DTYPE) per particle")
 
     def set_particle_temperatures(self, kelvin):
         """Thermal particles (rpt_set_particle_temperatures): as set_star_temperatures, one temperature per particle of the set."""
@@ -608,13 +616,11 @@ class Renderer:
 
     def set_particles_measurement(self, timed: bool = False):
         """Measurement only (tools/particles_cost.py): time the two kernels of every pass (last_particles_ms)."""
-        self._check(self._lib.rpt_set_particles_measurement(self._h, int(bool(timed))), "rpt_set_particles_measurement")
+        self._set_measurement("rpt_set_particles_measurement", timed)
 
     def last_particles_ms(self) -> Tuple[float, float]:
         """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_particles_measurement)."""
-        ms = (C.c_float * 2)(0.0, 0.0)
-        self._check(self._lib.rpt_last_particles_ms(self._h, ms), "rpt_last_particles_ms")
-        return float(ms[0]), float(ms[1])
+        return self._last_ms("rpt_last_particles_ms")
 
     # -- the segment pass (include/rpt.h, rpt_set_segments; not in the reference) -------------------
     def set_segments(self, segments):
@@ -622,13 +628,7 @@ class Renderer:
         padding), e.g. from segments.box_edges / segments.rod_lattice / segments.polyline / segments.load; None or an empty array
         switches the pass off.  a and b are the ends in the rest frame of the scene's object number `object`; rgb is the linear colour
         at rest PER UNIT REST-FRAME LENGTH.  Copied by the library; per context; what the library refuses raises RenderError."""
-        if segments is None or len(segments) == 0:
-            self._check(self._lib.rpt_set_segments(self._h, None, 0), "rpt_set_segments")
-            return
-        raw = np.ascontiguousarray(segments)
-        if raw.nbytes % 48 or raw.nbytes // 48 != len(raw):
-            raise ValueError("a segment set has one 48-byte record (segments.SEGMENT_DTYPE) per rod")
-        self._check(self._lib.rpt_set_segments(self._h, C.cast(raw.ctypes.data, C.POINTER(_ffi.Segment)), len(raw)), "rpt_set_segments")
+        self._set_records("rpt_set_segments", segments, _ffi.Segment, "a segment set has one 48-byte record (segments.SEGMENT_DTYPE) per rod")
 
     def set_segment_options(self, inverse_square: bool = False, depth_bias: float = 0.0, pieces: int = 16):
         """inverse_square, depth_bias: as set_particle_options, for every element of a rod.  pieces: 1, 2, 4, ..., 64 — the parts a rod is
@@ -649,13 +649,11 @@ class Renderer:
 
     def set_segments_measurement(self, timed: bool = False):
         """Measurement only (tools/segments_cost.py): time the two kernels of every pass (last_segments_ms)."""
-        self._check(self._lib.rpt_set_segments_measurement(self._h, int(bool(timed))), "rpt_set_segments_measurement")
+        self._set_measurement("rpt_set_segments_measurement", timed)
 
     def last_segments_ms(self) -> Tuple[float, float]:
         """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_segments_measurement)."""
-        ms = (C.c_float * 2)(0.0, 0.0)
-        self._check(self._lib.rpt_last_segments_ms(self._h, ms), "rpt_last_segments_ms")
-        return float(ms[0]), float(ms[1])
+        return self._last_ms("rpt_last_segments_ms")
 
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
