@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -40,6 +40,11 @@
 // event frame of the same view and the particle pass — behind the stars, under the overlay's lines — and reports the particles seen and
 // the pixels changed on stderr.  It excludes --projection (a ray map).
 //
+// --ballistics FILE[:inverse_square][:bias=B] adds point sources with a velocity of their own (rpt_set_ballistics, rpt_set_ballistic_options,
+// rpt_render_ballistics; not in the reference): FILE holds raw 48-byte rpt_ballistic records (relativitypathtracer_amd/ballistics.py `save`
+// writes them), each a straight worldline in the rest frame of the object it names; the options as for --particles.  The pass runs behind
+// the segments, under the overlay's lines, and the host reports the records seen and the pixels changed.  --ballistic-temperatures FILE:
+// raw float32 kelvin, one per record (rpt_set_ballistic_temperatures).
 // --particle-lighting lit[,shadows][,ambient] makes the particles of --particles dust (rpt_set_particle_lighting; not in the reference): their
 // rgb is an albedo and they show what they scatter from the scene's lights, with light delay on the way from the lamp too; shadows adds
 // the renderer's shadow ray per particle and light, ambient the scene's ambient term.  The host reports the pairs lit and shadowed.
@@ -201,15 +206,16 @@ static bool parse_particle_lighting(const char *spec, int *flags) {
     return true;
 }
 
-// --particles FILE[:inverse_square][:bias=B]: the file name, the flags and the bias; false (and a message) for what it cannot read
-static bool parse_particles(const char *spec, std::string *path, int *flags, float *bias) {
+// --particles / --ballistics FILE[:inverse_square][:bias=B] (`noun` = particles / ballistics): the file name, the flags and the bias;
+// false (and a message) for what it cannot read
+static bool parse_particles(const char *noun, const char *spec, std::string *path, int *flags, float *bias) {
     const std::string s(spec);
     size_t at = s.find(':');
     *path = s.substr(0, at);
     *flags = 0;
     *bias = 0.0f;
     if (path->empty()) {
-        std::fprintf(stderr, "--particles: '%s' names no file\n", spec);
+        std::fprintf(stderr, "--%s: '%s' names no file\n", noun, spec);
         return false;
     }
     while (at != std::string::npos) {
@@ -220,17 +226,17 @@ static bool parse_particles(const char *spec, std::string *path, int *flags, flo
             char *end = nullptr;
             const double b = std::strtod(option.c_str() + 5, &end);
             if (end == option.c_str() + 5 || *end != '\0' || !std::isfinite(b) || b < 0.0) {
-                std::fprintf(stderr, "--particles: '%s' in '%s' is not a bias (a finite number >= 0)\n", option.c_str() + 5, spec);
+                std::fprintf(stderr, "--%s: '%s' in '%s' is not a bias (a finite number >= 0)\n", noun, option.c_str() + 5, spec);
                 return false;
             }
             *bias = (float)b;
         } else {
-            std::fprintf(stderr, "--particles: unknown option '%s' (inverse_square, bias=B)\n", option.c_str());
+            std::fprintf(stderr, "--%s: unknown option '%s' (inverse_square, bias=B)\n", noun, option.c_str());
             return false;
         }
         at = next;
     }
-    std::fprintf(stderr, "particles: file %s, inverse square %d, depth bias %g\n", path->c_str(), *flags & RPT_PARTICLES_INVERSE_SQUARE, (double)*bias);
+    std::fprintf(stderr, "%s: file %s, inverse square %d, depth bias %g\n", noun, path->c_str(), *flags & RPT_PARTICLES_INVERSE_SQUARE, (double)*bias);
     return true;
 }
 
@@ -283,12 +289,15 @@ int main(int argc, char **argv) {
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
     const char *events_path = nullptr, *projection_spec = nullptr, *stars_path = nullptr;
-    const char *star_kelvin_path = nullptr, *particle_kelvin_path = nullptr;
+    const char *star_kelvin_path = nullptr, *particle_kelvin_path = nullptr, *ballistic_kelvin_path = nullptr;
     int doppler = 0;
     std::string particles_path;
     int particle_flags = 0;
     float particle_bias = 0.0f;
     int particle_lighting = 0;                                   // --particle-lighting
+    std::string ballistics_path;                                 // --ballistics
+    int ballistic_flags = 0;
+    float ballistic_bias = 0.0f;
     std::string segments_path;
     int segment_flags = 0, segment_pieces = 16;
     float segment_bias = 0.0f;
@@ -309,7 +318,8 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--stars")) stars_path = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--star-temperatures")) star_kelvin_path = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--particle-temperatures")) particle_kelvin_path = argv[++i];
-            else if (!std::strcmp(argv[i], "--star-temperatures") || !std::strcmp(argv[i], "--particle-temperatures")) {
+            else if (has_value && !std::strcmp(argv[i], "--ballistic-temperatures")) ballistic_kelvin_path = argv[++i];
+            else if (!std::strcmp(argv[i], "--star-temperatures") || !std::strcmp(argv[i], "--particle-temperatures") || !std::strcmp(argv[i], "--ballistic-temperatures")) {
                 std::fprintf(stderr, "%s needs a file name (raw float32 kelvin, one per record)\n", argv[i]);
                 return 2;
             }
@@ -341,8 +351,14 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "--particle-lighting needs a value: lit[,shadows][,ambient]\n");
                 return 2;
             }
+            else if (has_value && !std::strcmp(argv[i], "--ballistics")) {
+                if (!parse_particles("ballistics", argv[++i], &ballistics_path, &ballistic_flags, &ballistic_bias)) return 2;
+            } else if (!std::strcmp(argv[i], "--ballistics")) {
+                std::fprintf(stderr, "--ballistics needs a value: FILE[:inverse_square][:bias=B] (raw 48-byte rpt_ballistic records)\n");
+                return 2;
+            }
             else if (has_value && !std::strcmp(argv[i], "--particles")) {
-                if (!parse_particles(argv[++i], &particles_path, &particle_flags, &particle_bias)) return 2;
+                if (!parse_particles("particles", argv[++i], &particles_path, &particle_flags, &particle_bias)) return 2;
             } else if (!std::strcmp(argv[i], "--particles")) {
                 std::fprintf(stderr, "--particles needs a value: FILE[:inverse_square][:bias=B] (raw 32-byte rpt_particle records)\n");
                 return 2;
@@ -380,7 +396,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -422,19 +438,31 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    std::vector<rpt_ballistic> ballistic_set;                    // --ballistics: the raw records
+    if (!ballistics_path.empty()) {
+        std::FILE *f = std::fopen(ballistics_path.c_str(), "rb");
+        rpt_ballistic b;
+        while (f && std::fread(&b, sizeof b, 1, f) == 1) ballistic_set.push_back(b);
+        const bool whole = f && std::feof(f) && std::ftell(f) == (long)(ballistic_set.size() * sizeof(rpt_ballistic));
+        if (f) std::fclose(f);
+        if (!whole || ballistic_set.empty()) {
+            std::fprintf(stderr, "--ballistics: %s does not hold a whole number (> 0) of 48-byte rpt_ballistic records\n", ballistics_path.c_str());
+            return 2;
+        }
+    }
     if (particle_lighting && particle_set.empty()) {
         std::fprintf(stderr, "--particle-lighting needs --particles\n");
         return 2;
     }
-    std::vector<float> star_kelvin, particle_kelvin;             // --star-temperatures, --particle-temperatures: raw float32, one per record
-    for (int k = 0; k < 2; k++) {
-        const char *path = k == 0 ? star_kelvin_path : particle_kelvin_path;
-        const char *flag = k == 0 ? "--star-temperatures" : "--particle-temperatures";
-        std::vector<float> &kelvin = k == 0 ? star_kelvin : particle_kelvin;
-        const size_t records = k == 0 ? catalogue.size() : particle_set.size();
+    std::vector<float> star_kelvin, particle_kelvin, ballistic_kelvin;      // --star-, --particle-, --ballistic-temperatures: raw float32, one per record
+    for (int k = 0; k < 3; k++) {
+        const char *path = k == 0 ? star_kelvin_path : k == 1 ? particle_kelvin_path : ballistic_kelvin_path;
+        const char *flag = k == 0 ? "--star-temperatures" : k == 1 ? "--particle-temperatures" : "--ballistic-temperatures";
+        std::vector<float> &kelvin = k == 0 ? star_kelvin : k == 1 ? particle_kelvin : ballistic_kelvin;
+        const size_t records = k == 0 ? catalogue.size() : k == 1 ? particle_set.size() : ballistic_set.size();
         if (!path) continue;
         if (records == 0) {
-            std::fprintf(stderr, "%s needs %s\n", flag, k == 0 ? "--stars" : "--particles");
+            std::fprintf(stderr, "%s needs %s\n", flag, k == 0 ? "--stars" : k == 1 ? "--particles" : "--ballistics");
             return 2;
         }
         std::FILE *f = std::fopen(path, "rb");
@@ -599,6 +627,21 @@ int main(int argc, char **argv) {
             return 1;
         }
         std::fprintf(stderr, "segments: %llu of %zu pieces drawn, %llu of %lld pixels changed\n", counts[0], segment_set.size() * (size_t)segment_pieces, counts[1], (long long)width * height);
+    }
+    if (!ballistic_set.empty()) {                                // point sources with their own velocity, depth-tested against the event frame
+        unsigned long long counts[2] = {0, 0};
+        rc = events_rendered ? 0 : rpt_render_events(last);
+        events_rendered = !rc;
+        if (!rc) rc = rpt_set_ballistics(last, ballistic_set.data(), (int)ballistic_set.size());
+        if (!rc) rc = rpt_set_ballistic_options(last, ballistic_flags, ballistic_bias);
+        if (!rc && !ballistic_kelvin.empty()) rc = rpt_set_ballistic_temperatures(last, ballistic_kelvin.data(), (int)ballistic_kelvin.size());
+        if (!rc) rc = rpt_render_ballistics(last);
+        if (!rc) rc = rpt_last_ballistics(last, counts);
+        if (rc) {
+            std::fprintf(stderr, "ballistics: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::fprintf(stderr, "ballistics: %llu of %zu seen, %llu of %lld pixels changed\n", counts[0], ballistic_set.size(), counts[1], (long long)width * height);
     }
     if (overlay.layers) {                                        // lines on that frame, from an event frame of the same view
         unsigned long long changed = 0;

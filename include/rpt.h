@@ -810,6 +810,56 @@ int rpt_last_segments_ms(rpt_ctx *ctx, float ms[2]);
 int rpt_set_particle_lighting(rpt_ctx *ctx, int flags);                       /* default 0: today's pass, today's kernels */
 int rpt_last_particle_lighting(rpt_ctx *ctx, unsigned long long out[2]);     /* (grain, light) pairs that lit; pairs shadowed */
 
+/* The ballistic pass (not in the reference; DESIGN.md §24 "Ballistic particles" gives every rule operation by operation): point sources
+ * with a velocity of their own — a jet, an exploding shell, debris, a gas — without one Object per velocity.  A record is a straight
+ * worldline written in the rest frame of one entry of Object[], and the window of that frame's time in which the source shines; the
+ * pass finds the event of the worldline on the camera's past light cone in closed form, and from there on is the particle pass: the same
+ * projection, depth test, point-source Doppler law, accumulator and resolve.  A sixth sibling of the overlay, readout, star, particle and
+ * segment passes with the same discipline: opt-in, per context, not shared by rpt_share_scene; after a colour frame and an event frame
+ * of the same view; in place into the R, G, B bytes.  Ballistic particles light nothing, cast no shadow and hide nothing: they add.
+ *
+ *   pos     where the particle is at time 0 of the rest-frame clock of Object[object] (the clock of rpt_event.event[0]), in that frame's
+ *           coordinates (rpt_event.event[1..3]).
+ *   object  the frame the worldline is WRITTEN in.  The particle does not ride the body, and the object's own time window
+ *           (rpt_set_object_windows) is NOT applied to it.
+ *   rgb     the linear colour at rest in the PARTICLE's own frame, on the scale of object colours.
+ *   u       the proper velocity gamma * beta in that object's rest frame: every finite u is a subluminal velocity, and 1 - beta^2 is
+ *           never formed.
+ *   t0, t1  the particle shines while t0 <= t < t1 on that object's clock; -infinity / +infinity = always.
+ *
+ * In short (L = Object[object], cam = L.stationaryCam, I = L.InvLorentz): g = sqrt(1 + u.u), beta = u / g; w0 = (pos + beta cam.x) -
+ * cam.yzw, a = u.w0, r' = sqrt(w0.w0 + a a) — the camera's distance in the particle's own rest frame, gamma (r + beta.w) — and a record
+ * whose r' is not finite or not > 0 is skipped; tau = g (a - r') where a <= 0 and -g (w0.w0) / (a + r') elsewhere (interval == -1: the
+ * same root of the light-cone equation, each form without cancellation on its side), or -(I0.yzw.w0) / (I0.x + I0.yzw.beta) (interval ==
+ * 0); w = w0 + beta tau, t = cam.x + tau, skipped unless !(t < t0) && !(t >= t1); k = I (tau, w), dist = |k.yzw|, n = k.yzw / dist,
+ * skipped as a particle is; then the particle pass's colour rule with r' for r (D = dist / r', S_f or T_f, / D^2 with beaming, / r'^2
+ * with RPT_PARTICLES_INVERSE_SQUARE), its projection, taps, depth test, accumulator and resolve.  With u = 0 and the window open the
+ * pass is the particle pass, operation for operation.
+ *
+ * rpt_set_ballistics copies the set and writes it to the device once, in stream order; NULL or count 0 switches the pass off.
+ * RPT_ERR_ARG, message "rpt_set_ballistics: ...", the previous set kept: a component of pos, rgb or u that is not finite, |u_k| > 1000,
+ * a negative colour, object < 0, a t0 or t1 that is NaN, t0 >= t1, count < 0 or count > 2^22.  rpt_set_ballistic_options: as
+ * rpt_set_particle_options, kept apart from the particle pass's (flags = RPT_PARTICLES_INVERSE_SQUARE or 0; depth_bias >= 0).
+ * rpt_set_ballistic_temperatures: as rpt_set_particle_temperatures, one temperature per record (the splat is then kernel 1152 for 1150).
+ * rpt_render_ballistics[_async] refuses what rpt_render_particles refuses (the ray-map camera, an interval other than -1 or 0, a set
+ * whose largest object index is not below the object count, a temperature count that is not the set's), with messages that start
+ * "rpt_render_ballistics:"; the context stays usable.  With no set the call launches nothing and reports zeros.  Calling it twice adds
+ * the particles twice.  rpt_last_ballistics: of the last FINISHED pass, out[0] = records that were not skipped and have at least one
+ * tap inside the frame that passes the depth test, out[1] = pixels whose bytes changed.
+ *
+ * Limits: straight worldlines only; the sources are not lit by the scene's lights (rpt_set_particle_lighting does not apply); the
+ * ray-map camera is refused. */
+/* rpt_ballistic: include/rpt_layout.h (48 B) */
+int rpt_set_ballistics(rpt_ctx *ctx, const rpt_ballistic *records_or_null, int count);
+int rpt_set_ballistic_options(rpt_ctx *ctx, int flags, float depth_bias);   /* defaults 0, 0.0f */
+int rpt_set_ballistic_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count);
+int rpt_render_ballistics(rpt_ctx *ctx);        /* enqueue and wait */
+int rpt_render_ballistics_async(rpt_ctx *ctx);  /* enqueue; rpt_sync waits */
+int rpt_last_ballistics(rpt_ctx *ctx, unsigned long long out[2]);   /* records seen, pixels changed */
+/* Measurement only (tools/ballistics_cost.py): as rpt_set_particles_measurement / rpt_last_particles_ms, for the ballistic pass's two kernels. */
+int rpt_set_ballistics_measurement(rpt_ctx *ctx, int timed);
+int rpt_last_ballistics_ms(rpt_ctx *ctx, float ms[2]);
+
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);
 void *rpt_colour_plane_ptr(rpt_ctx *ctx);    /* device pointer of the compact plane (rpt_set_rows) */

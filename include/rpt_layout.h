@@ -103,6 +103,16 @@ typedef struct rpt_segment {      /* 48 B: three aligned 16-byte loads */
     float   _pad1;
 } rpt_segment;
 
+/* One point source of the ballistic pass (not in the reference; include/rpt.h, rpt_set_ballistics, states the rules) */
+typedef struct rpt_ballistic {    /* 48 B: three aligned 16-byte loads */
+    float   pos[3];               /* position at time 0 of Object[object]'s rest-frame clock (the clock of rpt_event.event[0]) */
+    int32_t object;               /* index into the context's Object[]: the frame the worldline is WRITTEN in; the particle does not ride it */
+    float   rgb[3];               /* linear colour at rest in the PARTICLE's own frame, on the scale of object colours */
+    float   t0;                   /* the emission window [t0, t1) on that object's clock; -inf / +inf = always */
+    float   u[3];                 /* proper velocity gamma * beta in that object's rest frame: every finite u is subluminal */
+    float   t1;
+} rpt_ballistic;
+
 /*
  * The eight read-only scene arrays the reference uploads once (main.cpp:33-55), in the
  * reference's layouts, as {pointer, element count} pairs.  Zero-length arrays are legal and
@@ -166,5 +176,11 @@ RPT_SA(offsetof(rpt_segment, b) == 16, "b");
 RPT_SA(offsetof(rpt_segment, _pad0) == 28, "_pad0");
 RPT_SA(offsetof(rpt_segment, rgb) == 32, "rgb");
 RPT_SA(offsetof(rpt_segment, _pad1) == 44, "_pad1");
+RPT_SA(sizeof(rpt_ballistic) == 48, "ballistic is 48 B");
+RPT_SA(offsetof(rpt_ballistic, object) == 12, "object");
+RPT_SA(offsetof(rpt_ballistic, rgb) == 16, "rgb");
+RPT_SA(offsetof(rpt_ballistic, t0) == 28, "t0");
+RPT_SA(offsetof(rpt_ballistic, u) == 32, "u");
+RPT_SA(offsetof(rpt_ballistic, t1) == 44, "t1");
 
 #endif /* RPT_LAYOUT_H */

@@ -71,6 +71,11 @@ class Segment(C.Structure):
     _fields_ = [("a", C.c_float * 3), ("object", C.c_int32), ("b", C.c_float * 3), ("_pad0", C.c_float), ("rgb", C.c_float * 3), ("_pad1", C.c_float)]
 
 
+class Ballistic(C.Structure):
+    """rpt_ballistic of include/rpt_layout.h (48 B): one point source of the ballistic pass, a straight worldline in the frame of Object[object]."""
+    _fields_ = [("pos", C.c_float * 3), ("object", C.c_int32), ("rgb", C.c_float * 3), ("t0", C.c_float), ("u", C.c_float * 3), ("t1", C.c_float)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -267,6 +272,14 @@ HIP_SYMBOLS = {
     "rpt_last_segments_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_set_particle_lighting": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_last_particle_lighting": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_ballistics": (C.c_int, [C.c_void_p, C.POINTER(Ballistic), C.c_int]),
+    "rpt_set_ballistic_options": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "rpt_set_ballistic_temperatures": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "rpt_render_ballistics": (C.c_int, [C.c_void_p]),
+    "rpt_render_ballistics_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_ballistics": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_ballistics_measurement": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_last_ballistics_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -655,6 +655,49 @@ class Renderer:
         """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_segments_measurement)."""
         return self._last_ms("rpt_last_segments_ms")
 
+    # -- the ballistic pass (include/rpt.h, rpt_set_ballistics; not in the reference) ----------------
+    def set_ballistics(self, ballistics, temperatures=None):
+        """Point sources with a velocity of their own: an array of ballistics.BALLISTIC_DTYPE records (or anything of n x 48 bytes in
+        that layout: pos, object, rgb, t0, u, t1), e.g. from ballistics.from_arrays / ballistics.jet / ballistics.shell /
+        ballistics.load; None or an empty array switches the pass off.  pos is where the particle is at time 0 of the rest-frame clock
+        of the scene's object number `object`, u its proper velocity gamma * beta in that frame, [t0, t1) the window of that clock in
+        which it shines, rgb the linear colour at rest in the particle's own frame.  Copied by the library; per context; what the
+        library refuses raises RenderError.  temperatures: if given, passed to set_ballistic_temperatures after the set."""
+        if temperatures is not None:
+            self.set_ballistics(ballistics)
+            self.set_ballistic_temperatures(temperatures)
+            return
+        self._set_records("rpt_set_ballistics", ballistics, _ffi.Ballistic, "a ballistic set has one 48-byte record (ballistics.BALLISTIC_DTYPE) per particle")
+
+    def set_ballistic_temperatures(self, kelvin):
+        """Thermal ballistic particles (rpt_set_ballistic_temperatures): as set_star_temperatures, one temperature per record of the set."""
+        self._set_temperatures("rpt_set_ballistic_temperatures", kelvin)
+
+    def set_ballistic_options(self, inverse_square: bool = False, depth_bias: float = 0.0):
+        """As set_particle_options, for the ballistic pass alone; inverse_square divides by the squared distance of the camera in the
+        PARTICLE's rest frame."""
+        self._check(self._lib.rpt_set_ballistic_options(self._h, 1 if inverse_square else 0, float(depth_bias)), "rpt_set_ballistic_options")
+
+    def render_ballistics(self, async_: bool = False):
+        """Add the particles of set_ballistics to the framebuffer, in place, each tap depth-tested against the last event frame.  The
+        context must have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice adds them
+        twice.  Independent of the other passes.  async_=True enqueues only (sync waits)."""
+        self._run_pass("rpt_render_ballistics", async_)
+
+    def last_ballistics(self) -> Tuple[int, int]:
+        """(records with at least one tap inside the frame that passed the depth test, pixels whose bytes changed) of the last finished
+        ballistic pass."""
+        seen, changed = self._last_counts("rpt_last_ballistics", 2)
+        return seen, changed
+
+    def set_ballistics_measurement(self, timed: bool = False):
+        """Measurement only (tools/ballistics_cost.py): time the two kernels of every pass (last_ballistics_ms)."""
+        self._set_measurement("rpt_set_ballistics_measurement", timed)
+
+    def last_ballistics_ms(self) -> Tuple[float, float]:
+        """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_ballistics_measurement)."""
+        return self._last_ms("rpt_last_ballistics_ms")
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -790,7 +833,8 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  adaptive_aa: Optional[Tuple[int, int]] = None, overlay: Optional[Mapping] = None,
                  fov: float = math.pi, fit: int = 0, readouts=None, stars=None, particles=None,
                  particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None,
-                 segments=None, segment_options: Optional[Mapping] = None, particle_lighting: Optional[Mapping] = None):
+                 segments=None, segment_options: Optional[Mapping] = None, particle_lighting: Optional[Mapping] = None,
+                 ballistics=None, ballistic_options: Optional[Mapping] = None, ballistic_temperatures=None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -812,7 +856,9 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     Renderer.set_segments (segments.box_edges, segments.rod_lattice, ...), segment_options the keywords of
     Renderer.set_segment_options; it implies events=True as the particles do, and the pass runs right behind them.  particle_lighting:
     the keywords of Renderer.set_particle_lighting, e.g. dict(lit=True, shadows=True): the particles are dust that scatters the
-    scene's lights."""
+    scene's lights.  ballistics: a set for Renderer.set_ballistics (ballistics.jet, ballistics.shell, ...), ballistic_options the
+    keywords of Renderer.set_ballistic_options, ballistic_temperatures kelvin per record; it implies events=True as the particles do,
+    and the pass runs right behind the segments."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -838,7 +884,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        if overlay is not None or readouts is not None or stars is not None or particles is not None or segments is not None:
+        if overlay is not None or readouts is not None or stars is not None or particles is not None or segments is not None or ballistics is not None:
             records = r.render_events()
             if stars is not None:
                 r.set_stars(stars, star_temperatures)
@@ -852,6 +898,10 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                 r.set_segment_options(**dict(segment_options or {}))
                 r.set_segments(segments)
                 r.render_segments()
+            if ballistics is not None:
+                r.set_ballistics(ballistics, ballistic_temperatures)
+                r.set_ballistic_options(**dict(ballistic_options or {}))
+                r.render_ballistics()
             if overlay is not None:
                 r.set_overlay(**overlay)
                 r.render_overlay()
