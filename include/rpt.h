@@ -338,6 +338,19 @@ int rpt_set_msaa(rpt_ctx *ctx, int samples_per_axis);
 int rpt_last_variant(const rpt_ctx *ctx);
 /* 1 if this context's last launch tested triangles with the exact reciprocal (41 / 43 on a scene inside its domain), else 0. */
 int rpt_last_exact_rcp(const rpt_ctx *ctx);
+/* 1 if this context's last launch was a sky split, else 0.  A split frame is two kernels on the context's stream: a fill that writes
+ * {x, y, background, 0} to every pixel outside a box of 8x8 tiles, then the frame's own kernel (what rpt_last_variant reports, as ever)
+ * over the box alone; the framebuffer's bytes are those of the single launch.  rect (may be NULL) receives the box in tiles, {x0, y0,
+ * x1, y1} with x1 and y1 exclusive — outside it no tile's object mask (rpt_probe_tile_masks) holds an object — or four zeros.  Split are
+ * frames in flight (rpt_render_async, rpt_timed_frames; never the blocking rpt_render) of more than 6 000 000 pixels:
+ * plain pinhole frames of kernels 41 / 44 / 48 (not the band-first 43 / 49) with 1..64 objects whose box covers at most half of the frame's tiles, on a
+ * context that renders whole frames into the 16-byte framebuffer; a lens, the panorama, a ray map, the sky image, Doppler, MSAA, time
+ * windows, adaptive anti-aliasing, debug_rgb, a colour plane or rpt_set_rows / rpt_set_tile_pattern keep the single launch.  In the
+ * environment, read when a context is created: RPT_SKY_SPLIT_SHARE=<percent> sets the largest box that is still split (0: never split,
+ * the escape hatch), RPT_SKY_SPLIT_MIN_PIXELS=<n> the floor (frames of more than n pixels split; tests and the A/B).
+ * rpt_verify_frame renders into colour planes and therefore checks the frame's kernel as ONE launch, never the box or the fill (those
+ * are held against the un-culled kernel by tests/test_gpu_sky_split.py); after it this call reports 0, as of the launch it checked. */
+int rpt_last_sky_split(const rpt_ctx *ctx, int rect[4]);
 /* Host code, no device: 1 if every triangle the octrees' lists name has |e1| |e2| <= 2^60 (e1 = B - A, e2 = C - A in float, finite
  * vertices), the domain on which kernels 41 / 43 use the exact reciprocal; 0 if not; -RPT_ERR_ARG / -RPT_ERR_SCENE for a bad desc. */
 int rpt_scene_exact_rcp(const rpt_scene_desc *s);

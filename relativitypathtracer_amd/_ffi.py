@@ -184,6 +184,7 @@ HIP_SYMBOLS = {
     "rpt_verify_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_last_variant": (C.c_int, [C.c_void_p]),
     "rpt_last_exact_rcp": (C.c_int, [C.c_void_p]),
+    "rpt_last_sky_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rpt_scene_exact_rcp": (C.c_int, [C.c_void_p]),
     "rpt_probe_reciprocal": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_uint64), C.c_void_p, C.c_int]),
     "rpt_set_msaa": (C.c_int, [C.c_void_p, C.c_int]),

@@ -24,6 +24,7 @@
 #include "rpt_screen_bounds.hpp"
 #include "rpt_bounds_certify.hpp"
 #include "rpt_tile_bitmap.hpp"
+#include "rpt_sky_split.hpp"
 #include "rpt_workers.hpp"
 #include "rpt_stars.hip.h"          /* last: the kernels before it keep their place in the translation unit */
 #include "rpt_stars_host.hpp"
@@ -209,6 +210,8 @@ struct rpt_ctx {
     bool colour_plane = false;
     int variant = 0;
     int last_variant = 0;                             // the kernel the last launch was made with (rpt_last_variant)
+    bool last_sky_split = false;                      // ... as a sky split (launch(); rpt_last_sky_split), with this box of 8x8 tiles: x0, y0, x1, y1
+    int last_sky_box[4] = {0, 0, 0, 0};
     // rpt_set_object_windows (not in the reference): {t0, t1} per object, per context, never shared; empty = none (today's kernels)
     std::vector<float> windows;
     bool last_exact_rcp = false;                      // ... and whether its walk took 1 / det through rcp_exact (rpt_last_exact_rcp)
@@ -297,6 +300,8 @@ struct rpt_ctx {
     unsigned long long bits_builds = 0;               // bitmaps that went live in this context so far (rpt_tile_bitmap_state), built here or copied from the scene's cache
     double bits_last_build_us = 0.0;                  // host time this context spent on the last of them
     bool tile_triangles = true;                       // RPT_TILE_TRIANGLES=0 at rpt_create: the sub-tree stage alone
+    int sky_split_share = 50;                         // the sky split's largest box, in percent of the frame's tiles (RPT_SKY_SPLIT_SHARE at rpt_create; 0: never split)
+    long long sky_split_min_pixels = 6000000;      // ... and frames of more pixels than this are split (RPT_SKY_SPLIT_MIN_PIXELS at rpt_create)
 };
 
 namespace {
@@ -1065,6 +1070,7 @@ int launch_persistent(rpt_ctx *ctx, rptd::KernelArgs &a, int tiles, int v) {
 #ifdef RPT_DIAGNOSTICS
 // librpt_hip_diag.so only: the measurement arms (rpt_diag_kernels.hip.h)
 #define RPT_LAUNCH_X(N) case N: hipLaunchKernelGGL(rptd::rpt_render_kernel_x##N, grid, dim3(256), 0, ctx->stream, a); break;
+void launch_sky_fill(rpt_ctx *ctx, const rptd::KernelArgs &a, int tiles, const int box[4]);      // (arm 786; defined with the sky split, below)
 int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, int v) {
     if (v == 143 || v == 2573 || (v >= 256 && v < 1000 && (v & 8))) set_band_first(ctx, a, tiles);     // (DiagPolicy::band_first)
     switch (v) {
@@ -1105,6 +1111,12 @@ int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, i
         hipLaunchKernelGGL(rptd::rpt_render_kernel_v1_diag, grid, dim3(256), 0, ctx->stream, a);
         break;
     case 8: hipLaunchKernelGGL(rptd::rpt_render_kernel_primary_only, grid, dim3(256), 0, ctx->stream, a); break;
+    case 786: {  // MEASUREMENT (the image of an empty Object[] only): the sky fill of a split frame alone, over the whole frame
+        if (!a.out16) return fail(ctx, RPT_ERR_ARG, "variant 786 writes the 16-byte framebuffer only");
+        const int no_box[4] = {0, 0, 0, 0};
+        launch_sky_fill(ctx, a, tiles, no_box);
+        break;
+    }
     case 11:
         if (int rc = reserve(ctx, ctx->wave_times, (size_t)grid.x * grid.y * 4 * 10 * sizeof(unsigned long long))) return rc;
         RPT_HIP(ctx, hipMemsetAsync(ctx->wave_times.ptr, 0, ctx->wave_times.bytes, ctx->stream));
@@ -1769,11 +1781,73 @@ void fill_frame_args(const rpt_ctx *ctx, rptd::LensArgs &a) {
     }
 }
 
+// ---- the sky split (rpt_sky_split.hpp; rpt_kernels.hip.h: rpt_sky_fill_kernel) --------------------------------------
+// A plain pinhole colour frame whose objects' regions lie in a box of tiles that is a small share of the frame is launched as two
+// kernels: rpt_sky_fill_kernel writes every pixel outside the box, the frame's own kernel runs over the box alone.  The sky's waves then
+// hold a dozen registers for their microsecond, not the 96 of a walk kernel, and fit next to the walkers of the frames in flight.
+// The rule — everything else gets the single launch:
+//   * a frame in flight (rpt_render_async, rpt_timed_frames) of more than RPT_SKY_SPLIT_MIN_PIXELS pixels: the throughput case, where
+//     the fill runs beside the walkers of the other frames.  On one stream the frame's own kernel starts when the fill has ended, so
+//     a frame its caller waits for gets longer by the fill, and so does a frame too small to keep the chip full of walks: the blocking
+//     rpt_render lost 5 % at 4K; in flight, bunny.txt lost 5 % at 1080p and 3 % at 2560x1440, was level at 3200x1800 (5.8 Mpx) and
+//     gained 7 % at 3840x2160 (8.3 Mpx) (§6.2d).  RPT_SKY_SPLIT_MIN_PIXELS=<n> in the environment, read when a context is created, sets
+//     another floor (frames of MORE than n pixels split): the tests' way to the small frames on which a box's placement can go wrong,
+//     and the A/B's;
+//   * kernels 41 / 44 / 48 as the frame's only pass: no lens, panorama or ray map, no sky image, no Doppler, no MSAA, no time windows,
+//     no refine pass, no debug_rgb (a miss pixel's triple would have to be written as well).  Not the band-first kernels 43 / 49: they
+//     serve the blocking call and the small frames, which the first point excludes, so their code is left as it was
+//     (rpt_kernels.hip.h: tile_origin_policy);
+//   * a context that renders whole frames into the 16-byte framebuffer (no colour plane, no rpt_set_rows / rpt_set_tile_pattern);
+//   * 1 .. 64 objects, the rectangles of this frame at hand (those rpt_set_objects put on the device);
+//   * a box of at most RPT_SKY_SPLIT_SHARE percent of the frame's tiles: split whatever the box covers, cubes.txt at 4K lost 1 % and
+//     arch.txt at 1080p 6 % (§6.2d).  RPT_SKY_SPLIT_SHARE=<0..100> in the environment, read when a context is created, sets another
+//     share: 0 is the escape hatch (never split), the others are for the A/B.
+#define RPT_SKY_SPLIT_SHARE 50
+#define RPT_SKY_SPLIT_MIN_PIXELS 6000000
+long long env_integer(const char *name, long long lo, long long hi, long long otherwise) {
+    const char *e = std::getenv(name);
+    if (!e || !*e) return otherwise;
+    char *end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    return *end == 0 && v >= lo && v <= hi ? v : otherwise;
+}
+int sky_split_share_wanted() { return (int)env_integer("RPT_SKY_SPLIT_SHARE", 0, 100, RPT_SKY_SPLIT_SHARE); }
+long long sky_split_min_pixels_wanted() { return env_integer("RPT_SKY_SPLIT_MIN_PIXELS", 0, 1ll << 40, RPT_SKY_SPLIT_MIN_PIXELS); }
+static_assert(rptd::tile_origin_policy<rptd::BallotExact> && rptd::tile_origin_policy<rptd::Ballot> && rptd::tile_origin_policy<rptd::Analytic> &&
+              !rptd::tile_origin_policy<rptd::BallotFirstExact> && !rptd::tile_origin_policy<rptd::BallotFirst> && !rptd::tile_origin_policy<rptd::Unculled> &&
+              !rptd::tile_origin_policy<rptd::DopplerTwin<rptd::BallotExact>> && !rptd::tile_origin_policy<rptd::Lens<rptd::BallotExact>>,
+              "the forms sky_split_box lets through (walk, analytic, ieee) are the kernels that add tile_x0");
+bool sky_split_box(const rpt_ctx *ctx, const Choice &c, Call call, const rptd::KernelArgs &a, int tiles, int box[4]) {
+    const KernelRow *row = c.colour;
+    if (!row || !row->kernel || c.windowed || c.refine || row->camera != Camera::pinhole || row->colour != Colour::plain) return false;
+    if (!(row->form == Form::walk || row->form == Form::analytic || row->form == Form::ieee)) return false;
+    if (call.kind != CallKind::in_flight || (long long)ctx->width * ctx->height <= ctx->sky_split_min_pixels) return false;
+    if (!a.out16 || a.plane || a.debug_rgb || ctx->colour_plane || ctx->first_tile != 0 || ctx->tile_step != 1 || ctx->run_log2 != 0) return false;
+    if (ctx->msaa > 1 || ctx->doppler || ctx->env_on || ctx->v_fov != 0.0f || ctx->projection != RPT_PROJECTION_PINHOLE) return false;
+    if (ctx->object_count < 1 || ctx->object_count > 64 || ctx->rects.size() != (size_t)ctx->object_count) return false;
+    if (!rpts::object_box(ctx->rects.data(), ctx->object_count, ctx->width, ctx->height, box)) return false;      // (nothing in view: one launch of sky tiles)
+    const long long tiles_x = (ctx->width + 7) / 8, covered = (long long)(box[2] - box[0]) * (box[3] - box[1]);
+    return covered * 100 <= tiles_x * tiles * ctx->sky_split_share;
+}
+
+// box: the tiles left to the render kernel; box[0] >= box[2]: none, the whole frame is filled
+void launch_sky_fill(rpt_ctx *ctx, const rptd::KernelArgs &a, int tiles, const int box[4]) {
+    rptd::SkyFillArgs s;
+    s.out16 = a.out16;
+    s.width = ctx->width;
+    s.height = ctx->height;
+    s.bg_packed = a.bg_packed;
+    s.tx0 = box[0]; s.ty0 = box[1]; s.tx1 = box[2]; s.ty1 = box[3];
+    const int tiles_x = (ctx->width + 7) / 8;
+    hipLaunchKernelGGL(rptd::rpt_sky_fill_kernel, dim3((tiles_x + RPT_SKY_FILL_TILES - 1) / RPT_SKY_FILL_TILES, tiles), dim3(64), 0, ctx->stream, s);
+}
+
 // One colour frame on the context's stream: the choice, then buffers, arguments and the launch (pass A + pass B of an adaptive frame).
 int launch(rpt_ctx *ctx, Call call) {
     const Choice c = choose_kernels(ctx, call);
     if (call.colour_frame && ctx->scene_uploaded && ctx->params_set) ctx->last_aa_variant = 0;
     if (c.code != RPT_OK) return fail(ctx, c.code, c.text);
+    ctx->last_sky_split = false;
     if (int rc = ensure_outputs(ctx)) return rc;
     const int tiles = local_tile_count(ctx);
     if (call.colour_frame && ctx->aa_n > 1) {
@@ -1819,8 +1893,21 @@ int launch(rpt_ctx *ctx, Call call) {
     } else if (!c.colour->kernel) {
         if (rpt_launch_relaxed_kernel(relaxed_waves(c.colour->form), &a, sizeof(rptd::KernelArgs), grid1.x, grid1.y, (void *)ctx->stream)) return fail(ctx, RPT_ERR_DEVICE, "relaxed-arithmetic kernel launch failed");
     } else {
+        dim3 grid = grid1;
+        int box[4];
+        if (sky_split_box(ctx, c, call, a, tiles, box)) {
+            // The sky split: the fill first, then the frame's own kernel over the box alone, both on the context's stream (the events of
+            // render_frame bracket the two).  The box's origin: the column through tile_x0, the row through first_tile (0 here: the
+            // rule refuses a context that renders a share of the rows).
+            launch_sky_fill(ctx, a, tiles, box);
+            a.tile_x0 = box[0];
+            a.first_tile = box[1];
+            grid = dim3(box[2] - box[0], box[3] - box[1]);
+            ctx->last_sky_split = true;
+            std::memcpy(ctx->last_sky_box, box, sizeof box);
+        }
         void *args[] = {(void *)&a};
-        (void)hipLaunchKernel(c.kernel(c.launched()), grid1, dim3(64), args, 0, ctx->stream);     // (errors: below)
+        (void)hipLaunchKernel(c.kernel(c.launched()), grid, dim3(64), args, 0, ctx->stream);     // (errors: below)
     }
     RPT_HIP(ctx, hipGetLastError());
     ctx->last_variant = c.variant;
@@ -2376,6 +2463,8 @@ int rpt_create(rpt_ctx **out, int device_ordinal) {
     if (!ctx) return RPT_ERR_NOMEM;
     ctx->device = device_ordinal;
     ctx->tile_triangles = tile_triangles_wanted();
+    ctx->sky_split_share = sky_split_share_wanted();
+    ctx->sky_split_min_pixels = sky_split_min_pixels_wanted();
     (void)rpth::Workers::instance();       // the helper pool exists from the first context on, not from the first animated frame (rpt_workers.hpp: fork())
     {
         static std::atomic<int> created{0};
@@ -3111,6 +3200,12 @@ int rpt_set_variant(rpt_ctx *ctx, int variant) {
 
 int rpt_last_variant(const rpt_ctx *ctx) { return ctx ? ctx->last_variant : 0; }
 int rpt_last_exact_rcp(const rpt_ctx *ctx) { return ctx && ctx->last_exact_rcp ? 1 : 0; }
+int rpt_last_sky_split(const rpt_ctx *ctx, int rect[4]) {
+    const bool split = ctx && ctx->last_sky_split;
+    if (rect)
+        for (int k = 0; k < 4; k++) rect[k] = split ? ctx->last_sky_box[k] : 0;
+    return split ? 1 : 0;
+}
 
 // The domain of the triangle test's exact reciprocal (rcp_exact, intersect_triangle_edges<true>): |det| <= |e1| |e2| (1 + 2^-20) for
 // a normalised direction, and rcp_exact equals 1 / det for 1e-7 <= |det| <= 2^125.  Asked here: |e1| |e2| <= 2^60 for every triangle a
@@ -3166,6 +3261,7 @@ int rpt_verify_frame(rpt_ctx *ctx, unsigned long long *differing_pixels) {
     ctx->external_plane = plane_a;
     rc = launch(ctx, Call{CallKind::in_flight, false});
     const int verified_variant = ctx->last_variant;      // what rpt_last_variant reports afterwards: the kernel that was CHECKED, not the un-culled one
+    // (both launches write colour planes, which are never split: rpt_last_sky_split reports "one launch" afterwards, of that same checked launch)
     if (rc == RPT_OK) {
         ctx->external_plane = plane_b;
         ctx->variant = 3;

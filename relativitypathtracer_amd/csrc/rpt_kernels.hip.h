@@ -116,9 +116,12 @@ struct KernelArgs {
     int first_tile, tile_step;      // local tile t holds global tile (t >> run_log2) * tile_step + first_tile + (t & (run - 1))
     int run_log2;                   // run = 1 << run_log2 consecutive tiles per period of tile_step tiles (rpt_set_tile_pattern)
     int interval;
-    // dispatch order (band_first kernels): the strips [first_sx, first_sx + first_w) x [first_ty, first_ty + first_h) — where the meshes
-    // are, i.e. where the frame's longest waves live — are handed out FIRST, the rest in natural order; first_w = 0: off
-    int first_sx, first_ty, first_w, first_h;
+    // tile_x0 (in the place of first_sx, which no kernel ever read): the column of 8x8 tiles that workgroup 0 of a row renders, for the
+    // kernels a sky split launches over the object box alone (tile_origin_policy below; launch() leaves it 0 everywhere else).  The
+    // box's first tile row goes through first_tile, as a rank's share of the rows does.
+    // dispatch order (band_first kernels, never split): the tile rows [first_ty, first_ty + first_h) — where the meshes are, i.e. where
+    // the frame's longest waves live — are handed out FIRST, the rest in natural order; first_h = 0: off (first_w: never read)
+    int tile_x0, first_ty, first_w, first_h;
     int msaa;                       // MSAASAMPLES of opencl_kernel.cl:7 when it is not 1 (rpt_set_msaa; the kernels of render_pixel_body_msaa only)
     float bg_mapped[3];      // min(hable(background)/hable(white_point), 1): what every miss pixel maps to
     float ambient;
@@ -789,6 +792,16 @@ template <class P> struct Raymap : P { static constexpr Camera camera = Camera::
 // family) or the sky.  2000 + the wrapped row's variant.  DESIGN.md "Time windows".
 template <class P> struct Windowed : P { static constexpr bool windowed = true; };                                              // 2xxx
 
+// The kernels a sky split may launch over the object box alone (rpt_api.hip: launch): the plain pinhole colour kernels
+// with the wave's object mask in natural tile order — 41, 44 and the IEEE form 48.  They add KernelArgs::tile_x0 to the workgroup's
+// column; every other kernel's code stays what it was: the band-first kernels 43 / 49, which serve the blocking call and small frames,
+// where a split loses (§6.2d), and the relaxed build's two (variants 50 / 51).
+#ifdef RPT_RELAXED_FP
+template <class P> constexpr bool tile_origin_policy = false;
+#else
+template <class P> constexpr bool tile_origin_policy = P::one_wave && P::culled && P::object_mask && P::camera == Camera::pinhole && !P::doppler && !P::environment && !P::windowed && !P::band_first && P::diag == 0;
+#endif
+
 // in(W, t) of DESIGN.md "Time windows": written with two negated compares so that a NaN time, and the default (-inf, +inf), accept
 RPT_DEV bool window_accepts(const DObj &pre, float t) { return !(t < pre.win_t0) && !(t >= pre.win_t1); }
 
@@ -1427,8 +1440,10 @@ RPT_DEV void render_pixel_body(const KernelArgs &a) {
     // The product kernels are launched ONE WAVE per workgroup (blockDim 64, grid.x = tiles per row): a wave slot is handed back when
     // its wave ends, not when the longest of four neighbours does — next to a tile that walks for 70 us sit tiles that only store
     // (profiles/r03_one_wave_workgroups_ab.txt: bunny 4K in flight -8 %, one at a time -3 %).  The measurement arms keep 4 x 64.
-    const int wave = P::one_wave ? ((int)blockIdx.x & 3) : (int)(threadIdx.x >> 6);
-    const int strip = P::one_wave ? ((int)blockIdx.x >> 2) : (int)blockIdx.x;      // 32-pixel-wide strip of that row
+    // (a sky split's launch covers the object box alone: its workgroup 0 of a row renders tile column tile_x0, 0 in every other launch)
+    const int column = tile_origin_policy<P> ? (int)blockIdx.x + a.tile_x0 : (int)blockIdx.x;
+    const int wave = P::one_wave ? (column & 3) : (int)(threadIdx.x >> 6);
+    const int strip = P::one_wave ? (column >> 2) : (int)blockIdx.x;      // 32-pixel-wide strip of that row
 #ifdef RPT_DIAGNOSTICS
     const DiagWaveClock diag_clock0 = diag_wave_begin<P::diag>();
 #endif
@@ -1727,6 +1742,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 // without the octree walk compiled in, for frames whose Object[] holds no mesh: 61 VGPRs, no scratch, EIGHT waves per SIMD
 // (arch 1080p 0.0370 -> 0.0301 ms per frame in flight, cubes.txt 4K 0.0898 -> 0.0725)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_render_kernel_analytic_w8(const KernelArgs a) { render_pixel_body<Analytic>(a); }        // 44
+
+// The sky fill of a split frame (rpt_api.hip: launch): every pixel of the frame OUTSIDE the object box, written as the
+// render kernels write a pixel whose wave's object mask is empty — {(float)x, (float)y, bg_packed, 0}, store_pixel's non-temporal
+// 16-byte store — by a kernel that reads no scene memory (its arguments are all it knows) and needs a dozen registers, so that its waves
+// fit into the registers and the wave slots five walkers leave free on a SIMD.  The render kernels then run over the box alone.
+// One wave per row of RPT_SKY_FILL_TILES 8x8 tiles: lane -> pixel of a tile row by row, as in the render kernels, so each store
+// instruction of a wave is eight full 128-byte lines, and a wave's stores run along 64 x 16 B = 1 KB of each of its eight pixel rows.
+// The box is whole tiles and every test of it is wave-uniform; a pixel beyond the frame's right or lower edge is never written.
+#define RPT_SKY_FILL_TILES 8
+struct SkyFillArgs {
+    rpt_pixel *out16;               // the 16 B/pixel framebuffer, full-frame addressing
+    int width, height;
+    uint32_t bg_packed;             // KernelArgs::bg_packed
+    int tx0, ty0, tx1, ty1;         // the object box [tx0, tx1) x [ty0, ty1) in 8x8 tiles: not written here; tx0 >= tx1: no box, the whole frame
+};
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void rpt_sky_fill_kernel(const SkyFillArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int ty = (int)blockIdx.y, tx_first = (int)blockIdx.x * RPT_SKY_FILL_TILES;
+    const bool box_rows = ty >= a.ty0 && ty < a.ty1;
+    if (box_rows && tx_first >= a.tx0 && tx_first + RPT_SKY_FILL_TILES <= a.tx1) return;       // the whole run lies in the box
+    const int y = ty * RPT_TILE_ROWS + (lane >> 3);
+    if (y >= a.height) return;
+    const uint32_t fy = __float_as_uint((float)y);
+    const size_t row = (size_t)y * a.width;
+#pragma unroll
+    for (int k = 0; k < RPT_SKY_FILL_TILES; k++) {
+        const int tx = tx_first + k, x = tx * 8 + (lane & 7);
+        const bool in_box = box_rows && tx >= a.tx0 && tx < a.tx1;
+        if (!in_box && x < a.width) store_pixel(a.out16, row + x, __float_as_uint((float)x), fy, a.bg_packed, 0u);
+    }
+}
 
 // MSAASAMPLES > 1 (rpt_set_msaa): culled and un-culled; rpt_last_variant reports them as 46 / 47
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_msaa_w5(const KernelArgs a) { render_pixel_body_msaa<Ballot>(a); }            // 46

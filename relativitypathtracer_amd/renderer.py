@@ -365,6 +365,12 @@ class Renderer:
         """Whether the last launch's triangle test took 1 / det through the exact reciprocal (kernels 41 / 43 on a scene in its domain)."""
         return bool(self._lib.rpt_last_exact_rcp(self._h))
 
+    def last_sky_split(self) -> Optional[Tuple[int, int, int, int]]:
+        """The box of 8x8 tiles (x0, y0, x1, y1; x1 and y1 exclusive) the last launch's own kernel ran over when the frame was a sky
+        split — a fill wrote every pixel outside it (include/rpt.h, rpt_last_sky_split) — or None: one launch over the whole frame."""
+        box = (C.c_int * 4)()
+        return tuple(int(v) for v in box) if self._lib.rpt_last_sky_split(self._h, box) else None
+
     def verify_frame(self) -> int:
         """Pixels whose packed colour differs between the kernel a frame would get and the un-culled kernel (0 = the culls changed nothing)."""
         n = C.c_uint64(0)
