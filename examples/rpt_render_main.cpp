@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--rockets SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] [--rocket-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -45,6 +45,12 @@
 // writes them), each a straight worldline in the rest frame of the object it names; the options as for --particles.  The pass runs behind
 // the segments, under the overlay's lines, and the host reports the records seen and the pixels changed.  --ballistic-temperatures FILE:
 // raw float32 kelvin, one per record (rpt_set_ballistic_temperatures).
+//
+// --rockets FILE[:inverse_square][:bias=B] adds point sources under constant proper acceleration (rpt_set_rockets, rpt_set_rocket_options,
+// rpt_render_rockets; not in the reference): FILE holds raw 64-byte rpt_rocket records (relativitypathtracer_amd/rockets.py `save` writes
+// them), each a hyperbolic worldline in the rest frame of the object it names; the options as for --particles.  The pass runs behind the
+// ballistic one, under the overlay's lines, and the host reports the records seen and the pixels changed.  --rocket-temperatures FILE:
+// raw float32 kelvin, one per record (rpt_set_rocket_temperatures).
 // --particle-lighting lit[,shadows][,ambient] makes the particles of --particles dust (rpt_set_particle_lighting; not in the reference): their
 // rgb is an albedo and they show what they scatter from the scene's lights, with light delay on the way from the lamp too; shadows adds
 // the renderer's shadow ray per particle and light, ambient the scene's ambient term.  The host reports the pairs lit and shadowed.
@@ -206,7 +212,7 @@ static bool parse_particle_lighting(const char *spec, int *flags) {
     return true;
 }
 
-// --particles / --ballistics FILE[:inverse_square][:bias=B] (`noun` = particles / ballistics): the file name, the flags and the bias;
+// --particles / --ballistics / --rockets FILE[:inverse_square][:bias=B] (`noun` = particles / ballistics / rockets): the file name, the flags and the bias;
 // false (and a message) for what it cannot read
 static bool parse_particles(const char *noun, const char *spec, std::string *path, int *flags, float *bias) {
     const std::string s(spec);
@@ -289,7 +295,7 @@ int main(int argc, char **argv) {
     float ypr[3] = {0, 0, 0}, v_fov = 0;
     bool turned = false;
     const char *events_path = nullptr, *projection_spec = nullptr, *stars_path = nullptr;
-    const char *star_kelvin_path = nullptr, *particle_kelvin_path = nullptr, *ballistic_kelvin_path = nullptr;
+    const char *star_kelvin_path = nullptr, *particle_kelvin_path = nullptr, *ballistic_kelvin_path = nullptr, *rocket_kelvin_path = nullptr;
     int doppler = 0;
     std::string particles_path;
     int particle_flags = 0;
@@ -298,6 +304,9 @@ int main(int argc, char **argv) {
     std::string ballistics_path;                                 // --ballistics
     int ballistic_flags = 0;
     float ballistic_bias = 0.0f;
+    std::string rockets_path;                                    // --rockets
+    int rocket_flags = 0;
+    float rocket_bias = 0.0f;
     std::string segments_path;
     int segment_flags = 0, segment_pieces = 16;
     float segment_bias = 0.0f;
@@ -319,7 +328,9 @@ int main(int argc, char **argv) {
             else if (has_value && !std::strcmp(argv[i], "--star-temperatures")) star_kelvin_path = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--particle-temperatures")) particle_kelvin_path = argv[++i];
             else if (has_value && !std::strcmp(argv[i], "--ballistic-temperatures")) ballistic_kelvin_path = argv[++i];
-            else if (!std::strcmp(argv[i], "--star-temperatures") || !std::strcmp(argv[i], "--particle-temperatures") || !std::strcmp(argv[i], "--ballistic-temperatures")) {
+            else if (has_value && !std::strcmp(argv[i], "--rocket-temperatures")) rocket_kelvin_path = argv[++i];
+            else if (!std::strcmp(argv[i], "--star-temperatures") || !std::strcmp(argv[i], "--particle-temperatures") || !std::strcmp(argv[i], "--ballistic-temperatures") ||
+                     !std::strcmp(argv[i], "--rocket-temperatures")) {
                 std::fprintf(stderr, "%s needs a file name (raw float32 kelvin, one per record)\n", argv[i]);
                 return 2;
             }
@@ -355,6 +366,12 @@ int main(int argc, char **argv) {
                 if (!parse_particles("ballistics", argv[++i], &ballistics_path, &ballistic_flags, &ballistic_bias)) return 2;
             } else if (!std::strcmp(argv[i], "--ballistics")) {
                 std::fprintf(stderr, "--ballistics needs a value: FILE[:inverse_square][:bias=B] (raw 48-byte rpt_ballistic records)\n");
+                return 2;
+            }
+            else if (has_value && !std::strcmp(argv[i], "--rockets")) {
+                if (!parse_particles("rockets", argv[++i], &rockets_path, &rocket_flags, &rocket_bias)) return 2;
+            } else if (!std::strcmp(argv[i], "--rockets")) {
+                std::fprintf(stderr, "--rockets needs a value: FILE[:inverse_square][:bias=B] (raw 64-byte rpt_rocket records)\n");
                 return 2;
             }
             else if (has_value && !std::strcmp(argv[i], "--particles")) {
@@ -396,7 +413,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--rockets SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] [--rocket-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -450,19 +467,31 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    std::vector<rpt_rocket> rocket_set;                          // --rockets: the raw records
+    if (!rockets_path.empty()) {
+        std::FILE *f = std::fopen(rockets_path.c_str(), "rb");
+        rpt_rocket b;
+        while (f && std::fread(&b, sizeof b, 1, f) == 1) rocket_set.push_back(b);
+        const bool whole = f && std::feof(f) && std::ftell(f) == (long)(rocket_set.size() * sizeof(rpt_rocket));
+        if (f) std::fclose(f);
+        if (!whole || rocket_set.empty()) {
+            std::fprintf(stderr, "--rockets: %s does not hold a whole number (> 0) of 64-byte rpt_rocket records\n", rockets_path.c_str());
+            return 2;
+        }
+    }
     if (particle_lighting && particle_set.empty()) {
         std::fprintf(stderr, "--particle-lighting needs --particles\n");
         return 2;
     }
-    std::vector<float> star_kelvin, particle_kelvin, ballistic_kelvin;      // --star-, --particle-, --ballistic-temperatures: raw float32, one per record
-    for (int k = 0; k < 3; k++) {
-        const char *path = k == 0 ? star_kelvin_path : k == 1 ? particle_kelvin_path : ballistic_kelvin_path;
-        const char *flag = k == 0 ? "--star-temperatures" : k == 1 ? "--particle-temperatures" : "--ballistic-temperatures";
-        std::vector<float> &kelvin = k == 0 ? star_kelvin : k == 1 ? particle_kelvin : ballistic_kelvin;
-        const size_t records = k == 0 ? catalogue.size() : k == 1 ? particle_set.size() : ballistic_set.size();
+    std::vector<float> star_kelvin, particle_kelvin, ballistic_kelvin, rocket_kelvin;      // --star-, --particle-, --ballistic-, --rocket-temperatures: raw float32, one per record
+    for (int k = 0; k < 4; k++) {
+        const char *path = k == 0 ? star_kelvin_path : k == 1 ? particle_kelvin_path : k == 2 ? ballistic_kelvin_path : rocket_kelvin_path;
+        const char *flag = k == 0 ? "--star-temperatures" : k == 1 ? "--particle-temperatures" : k == 2 ? "--ballistic-temperatures" : "--rocket-temperatures";
+        std::vector<float> &kelvin = k == 0 ? star_kelvin : k == 1 ? particle_kelvin : k == 2 ? ballistic_kelvin : rocket_kelvin;
+        const size_t records = k == 0 ? catalogue.size() : k == 1 ? particle_set.size() : k == 2 ? ballistic_set.size() : rocket_set.size();
         if (!path) continue;
         if (records == 0) {
-            std::fprintf(stderr, "%s needs %s\n", flag, k == 0 ? "--stars" : k == 1 ? "--particles" : "--ballistics");
+            std::fprintf(stderr, "%s needs %s\n", flag, k == 0 ? "--stars" : k == 1 ? "--particles" : k == 2 ? "--ballistics" : "--rockets");
             return 2;
         }
         std::FILE *f = std::fopen(path, "rb");
@@ -642,6 +671,21 @@ int main(int argc, char **argv) {
             return 1;
         }
         std::fprintf(stderr, "ballistics: %llu of %zu seen, %llu of %lld pixels changed\n", counts[0], ballistic_set.size(), counts[1], (long long)width * height);
+    }
+    if (!rocket_set.empty()) {                                   // point sources under constant proper acceleration, depth-tested against the event frame
+        unsigned long long counts[2] = {0, 0};
+        rc = events_rendered ? 0 : rpt_render_events(last);
+        events_rendered = !rc;
+        if (!rc) rc = rpt_set_rockets(last, rocket_set.data(), (int)rocket_set.size());
+        if (!rc) rc = rpt_set_rocket_options(last, rocket_flags, rocket_bias);
+        if (!rc && !rocket_kelvin.empty()) rc = rpt_set_rocket_temperatures(last, rocket_kelvin.data(), (int)rocket_kelvin.size());
+        if (!rc) rc = rpt_render_rockets(last);
+        if (!rc) rc = rpt_last_rockets(last, counts);
+        if (rc) {
+            std::fprintf(stderr, "rockets: %s\n", rpt_last_error(last));
+            return 1;
+        }
+        std::fprintf(stderr, "rockets: %llu of %zu seen, %llu of %lld pixels changed\n", counts[0], rocket_set.size(), counts[1], (long long)width * height);
     }
     if (overlay.layers) {                                        // lines on that frame, from an event frame of the same view
         unsigned long long changed = 0;

@@ -873,6 +873,54 @@ int rpt_last_ballistics(rpt_ctx *ctx, unsigned long long out[2]);   /* records s
 int rpt_set_ballistics_measurement(rpt_ctx *ctx, int timed);
 int rpt_last_ballistics_ms(rpt_ctx *ctx, float ms[2]);
 
+/* The rocket pass (not in the reference; DESIGN.md §25 "Accelerated particles" gives every rule operation by operation): point sources
+ * under constant proper acceleration — the relativistic rocket, Bell's spaceships, a Born-rigid fleet, the Rindler horizon.  A record is
+ * a hyperbolic worldline written in the rest frame of one entry of Object[], and the window of that frame's time in which the source
+ * shines; the pass finds the event of the worldline on the camera's past light cone in closed form (+ - * / and sqrt only), and from
+ * there on is the ballistic pass: the same projection, depth test, point-source Doppler law, accumulator and resolve.  A seventh sibling
+ * of the overlay, readout, star, particle, segment and ballistic passes with the same discipline: opt-in, per context, not shared by
+ * rpt_share_scene; after a colour frame and an event frame of the same view; in place into the R, G, B bytes.  Rockets light nothing,
+ * cast no shadow and hide nothing: they add.
+ *
+ *   pos, object, rgb, u, t0, t1   exactly as in rpt_ballistic: the place at time 0 of the clock of Object[object], the frame the
+ *           worldline is written in (its own time window is not applied), the colour at rest in the rocket's own frame, the proper
+ *           velocity gamma * beta at that moment, and the window [t0, t1) held against the emission time on that clock.
+ *   acc     the proper acceleration 3-vector in the rocket's own instantaneous rest frame at that moment — what the crew feels — in
+ *           units where c = 1.  Every finite acc is legal; alpha^2 = acc.acc is formed from it directly, never by cancellation.
+ *   reserved  must be 0.
+ *
+ * In short (L = Object[object], (T, C) = L.stationaryCam, I = L.InvLorentz, al2 = acc.acc): g = sqrt(1 + u.u), a0 = u.acc,
+ * a = acc + u (a0 / (g + 1)): the 4-velocity (g, u) and the 4-acceleration (a0, a) at time 0.  With z = (2 / alpha) tanh(alpha s / 2)
+ * and d = 1 - al2 z^2 / 4 the worldline is rational in z: X = (0, pos) + (g, u) z / d + (a0, a) z^2 / (2 d).  The state is advanced to
+ * the camera's time T (G = sqrt(g^2 + 2 a0 T + al2 T^2) is gamma there), then w0 = p - C, n = u1.w0, m = a1.w0,
+ * Aq = (m - 1) - (w0.w0) al2 / 4 and r' = sqrt(n^2 - Aq (w0.w0)) — the discriminant of the light-cone quadratic Aq z^2 + 2 n z + w0.w0
+ * = 0 and, exactly, the camera's distance in the rocket's rest frame at emission.  Skipped unless 0 < r' <= FLT_MAX; the past root is
+ * z = -(w0.w0) / (n + r') where n > 0, (r' - n) / Aq where n <= 0 and Aq < 0, and none elsewhere; skipped unless d > 0: the camera is
+ * beyond the rocket's horizon.  Then tau, w, the window, k = I (tau, w), D = dist / r' and the ballistic pass's rules 5-7.  With
+ * acc = 0 the rules are the ballistic pass's up to rounding (another operation order; not bit for bit).
+ *
+ * rpt_set_rockets copies the set and writes it to the device once, in stream order; NULL or count 0 switches the pass off.
+ * RPT_ERR_ARG, message "rpt_set_rockets: entry i: ...", the previous set kept: what rpt_set_ballistics refuses, a component of acc that
+ * is not finite, |acc_k| > 1000, reserved != 0.  rpt_set_rocket_options: as rpt_set_ballistic_options, kept apart from it (flags =
+ * RPT_PARTICLES_INVERSE_SQUARE or 0; depth_bias >= 0).  rpt_set_rocket_temperatures: one temperature per record (the splat is then
+ * kernel 1162 for 1160).  rpt_render_rockets[_async] refuses what rpt_render_ballistics refuses, with messages that start
+ * "rpt_render_rockets:"; the context stays usable.  With no set the call launches nothing and reports zeros.  Calling it twice adds the
+ * rockets twice.  rpt_last_rockets: of the last FINISHED pass, out[0] = records that were not skipped and have at least one tap inside
+ * the frame that passes the depth test, out[1] = pixels whose bytes changed.
+ *
+ * Limits: constant proper acceleration only (a trip is several records with abutting windows); no rotation; the sources are not lit by
+ * the scene's lights; the ray-map camera is refused. */
+/* rpt_rocket: include/rpt_layout.h (64 B) */
+int rpt_set_rockets(rpt_ctx *ctx, const rpt_rocket *records_or_null, int count);
+int rpt_set_rocket_options(rpt_ctx *ctx, int flags, float depth_bias);   /* defaults 0, 0.0f */
+int rpt_set_rocket_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count);
+int rpt_render_rockets(rpt_ctx *ctx);        /* enqueue and wait */
+int rpt_render_rockets_async(rpt_ctx *ctx);  /* enqueue; rpt_sync waits */
+int rpt_last_rockets(rpt_ctx *ctx, unsigned long long out[2]);   /* records seen, pixels changed */
+/* Measurement only (tools/rockets_cost.py): as rpt_set_ballistics_measurement / rpt_last_ballistics_ms, for the rocket pass's two kernels. */
+int rpt_set_rockets_measurement(rpt_ctx *ctx, int timed);
+int rpt_last_rockets_ms(rpt_ctx *ctx, float ms[2]);
+
 void *rpt_output_ptr(rpt_ctx *ctx);          /* device pointer of the current framebuffer */
 size_t rpt_output_bytes(rpt_ctx *ctx);
 void *rpt_colour_plane_ptr(rpt_ctx *ctx);    /* device pointer of the compact plane (rpt_set_rows) */

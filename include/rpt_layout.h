@@ -113,6 +113,18 @@ typedef struct rpt_ballistic {    /* 48 B: three aligned 16-byte loads */
     float   t1;
 } rpt_ballistic;
 
+/* One accelerated point source of the rocket pass (not in the reference; include/rpt.h, rpt_set_rockets, states the rules) */
+typedef struct rpt_rocket {       /* 64 B: four aligned 16-byte loads */
+    float   pos[3];               /* position at time 0 of Object[object]'s rest-frame clock (the clock of rpt_event.event[0]) */
+    int32_t object;               /* index into the context's Object[]: the frame the worldline is WRITTEN in; the rocket does not ride it */
+    float   rgb[3];               /* linear colour at rest in the ROCKET's own frame, on the scale of object colours */
+    float   t0;                   /* the emission window [t0, t1) on that object's clock; -inf / +inf = always */
+    float   u[3];                 /* proper velocity gamma * beta in that object's rest frame at that frame's time 0 */
+    float   t1;
+    float   acc[3];               /* proper acceleration in the rocket's own instantaneous rest frame at that moment (what the crew feels), c = 1 */
+    float   reserved;             /* must be 0 */
+} rpt_rocket;
+
 /*
  * The eight read-only scene arrays the reference uploads once (main.cpp:33-55), in the
  * reference's layouts, as {pointer, element count} pairs.  Zero-length arrays are legal and
@@ -182,5 +194,14 @@ RPT_SA(offsetof(rpt_ballistic, rgb) == 16, "rgb");
 RPT_SA(offsetof(rpt_ballistic, t0) == 28, "t0");
 RPT_SA(offsetof(rpt_ballistic, u) == 32, "u");
 RPT_SA(offsetof(rpt_ballistic, t1) == 44, "t1");
+RPT_SA(sizeof(rpt_rocket) == 64, "rocket is 64 B");
+RPT_SA(offsetof(rpt_rocket, pos) == 0, "pos");
+RPT_SA(offsetof(rpt_rocket, object) == 12, "object");
+RPT_SA(offsetof(rpt_rocket, rgb) == 16, "rgb");
+RPT_SA(offsetof(rpt_rocket, t0) == 28, "t0");
+RPT_SA(offsetof(rpt_rocket, u) == 32, "u");
+RPT_SA(offsetof(rpt_rocket, t1) == 44, "t1");
+RPT_SA(offsetof(rpt_rocket, acc) == 48, "acc");
+RPT_SA(offsetof(rpt_rocket, reserved) == 60, "reserved");
 
 #endif /* RPT_LAYOUT_H */

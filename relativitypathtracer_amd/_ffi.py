@@ -76,6 +76,12 @@ class Ballistic(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("object", C.c_int32), ("rgb", C.c_float * 3), ("t0", C.c_float), ("u", C.c_float * 3), ("t1", C.c_float)]
 
 
+class Rocket(C.Structure):
+    """rpt_rocket of include/rpt_layout.h (64 B): one point source of the rocket pass, a hyperbolic worldline in the frame of Object[object]."""
+    _fields_ = [("pos", C.c_float * 3), ("object", C.c_int32), ("rgb", C.c_float * 3), ("t0", C.c_float), ("u", C.c_float * 3), ("t1", C.c_float),
+                ("acc", C.c_float * 3), ("reserved", C.c_float)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -281,6 +287,14 @@ HIP_SYMBOLS = {
     "rpt_last_ballistics": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_set_ballistics_measurement": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_last_ballistics_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_rockets": (C.c_int, [C.c_void_p, C.POINTER(Rocket), C.c_int]),
+    "rpt_set_rocket_options": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "rpt_set_rocket_temperatures": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "rpt_render_rockets": (C.c_int, [C.c_void_p]),
+    "rpt_render_rockets_async": (C.c_int, [C.c_void_p]),
+    "rpt_last_rockets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rpt_set_rockets_measurement": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_last_rockets_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rpt_version": (C.c_char_p, []),
 }
 

@@ -105,6 +105,50 @@ def _frames(objects):
     return objs["InvLorentz"].astype(np.float64).reshape(-1, 4, 4), objs["stationaryCam"].astype(np.float64).reshape(-1, 4)
 
 
+def seen_from_emission(visible, inv, tau, w, r, rgb0, camera: Mapping, W: int, H: int, interval: int, flags: int, options: Mapping, temperatures) -> dict:
+    """Rules 5-7 of the ballistic pass in float64, shared with rockets.project: the emission event (tau, w) (N,), (N, 3) from the camera
+    event in the object's frame, r (N,) the camera's distance in the source's rest frame, `visible` what is not skipped so far.  Returns
+    visible, X, Y, dist, D, k, n, rgb."""
+    with np.errstate(all="ignore"):
+        k = np.einsum("nij,nj->ni", inv, np.concatenate([tau[:, None], w], axis=1))
+        dist = np.sqrt((k[:, 1:] ** 2).sum(axis=1))
+        visible &= (dist > 0.0) & np.isfinite(dist)
+        n = k[:, 1:] / dist[:, None]
+        if flags and interval != 0:
+            D = dist / r
+            visible &= (D > 0.0) & np.isfinite(D)
+            rgb = point_source_colour(flags, D, rgb0)
+            if temperatures is not None:
+                rgb = thermal_colour(flags, D, rgb0, temperatures)
+                if flags & 2:
+                    rgb = rgb / (D ** 2)[:, None]
+        else:
+            D = dist / r if interval != 0 else np.ones(len(tau))
+            rgb = rgb0.copy()
+        if options.get("inverse_square"):
+            rgb = rgb / (r * r)[:, None]
+        mode = camera.get("mode", "pinhole")
+        if mode == "equirect":
+            h_fov, v_fov, yaw = (float(np.float32(camera.get(key, d))) for key, d in (("h_fov", 2.0 * math.pi), ("v_fov", math.pi), ("yaw", 0.0)))
+            lam = np.arctan2(n[:, 0], n[:, 2]) - yaw
+            lam = lam - 2.0 * math.pi * np.floor((lam + math.pi) / (2.0 * math.pi))
+            phi = np.arcsin(np.clip(n[:, 1], -1.0, 1.0))
+            X = W * (lam / h_fov + 0.5) - 0.5
+            Y = H * (phi / v_fov + 0.5) - 0.5
+        elif mode == "pinhole":
+            v_fov = float(camera.get("v_fov", 0.0) or 0.0)
+            lens = float(np.float32(math.tan(0.5 * float(np.float32(v_fov))))) if v_fov != 0.0 else 1.0
+            visible &= n[:, 2] > 0.0
+            X = W * (0.5 + (0.5 * n[:, 0] / n[:, 2]) / (lens * (float(W) / float(H))))
+            Y = H * (0.5 + (0.5 * n[:, 1] / n[:, 2]) / lens)
+        else:
+            raise ValueError(f"project: the camera's mode is 'pinhole' or 'equirect', not {mode!r} (a ray map has no inverse)")
+        visible &= (np.abs(X) < 1e9) & (np.abs(Y) < 1e9)
+    X = np.where(visible, X, np.nan)
+    Y = np.where(visible, Y, np.nan)
+    return {"visible": visible, "X": X, "Y": Y, "dist": dist, "D": D, "k": k, "n": n, "rgb": rgb}
+
+
 def project(ballistics, objects, camera: Mapping, W: int, H: int, interval: int = -1, flags: int = 0, options: Optional[Mapping] = None,
             temperatures=None) -> dict:
     """Rules 1-6 of the ballistic pass in float64.  ballistics: BALLISTIC_DTYPE records; objects, camera, interval, flags, options,
@@ -144,41 +188,5 @@ def project_columns(pos, idx, rgb0, u, t0, t1, objects, camera: Mapping, W: int,
         w = w0 + beta * tau[:, None]
         te = cam[:, 0] + tau
         visible &= window_accepts(t0, t1, te)
-        k = np.einsum("nij,nj->ni", inv, np.concatenate([tau[:, None], w], axis=1))
-        dist = np.sqrt((k[:, 1:] ** 2).sum(axis=1))
-        visible &= (dist > 0.0) & np.isfinite(dist)
-        n = k[:, 1:] / dist[:, None]
-        if flags and interval != 0:
-            D = dist / r
-            visible &= (D > 0.0) & np.isfinite(D)
-            rgb = point_source_colour(flags, D, rgb0)
-            if temperatures is not None:
-                rgb = thermal_colour(flags, D, rgb0, temperatures)
-                if flags & 2:
-                    rgb = rgb / (D ** 2)[:, None]
-        else:
-            D = dist / r if interval != 0 else np.ones(len(idx))
-            rgb = rgb0.copy()
-        if options.get("inverse_square"):
-            rgb = rgb / (r * r)[:, None]
-        mode = camera.get("mode", "pinhole")
-        if mode == "equirect":
-            h_fov, v_fov, yaw = (float(np.float32(camera.get(key, d))) for key, d in (("h_fov", 2.0 * math.pi), ("v_fov", math.pi), ("yaw", 0.0)))
-            lam = np.arctan2(n[:, 0], n[:, 2]) - yaw
-            lam = lam - 2.0 * math.pi * np.floor((lam + math.pi) / (2.0 * math.pi))
-            phi = np.arcsin(np.clip(n[:, 1], -1.0, 1.0))
-            X = W * (lam / h_fov + 0.5) - 0.5
-            Y = H * (phi / v_fov + 0.5) - 0.5
-        elif mode == "pinhole":
-            v_fov = float(camera.get("v_fov", 0.0) or 0.0)
-            lens = float(np.float32(math.tan(0.5 * float(np.float32(v_fov))))) if v_fov != 0.0 else 1.0
-            visible &= n[:, 2] > 0.0
-            X = W * (0.5 + (0.5 * n[:, 0] / n[:, 2]) / (lens * (float(W) / float(H))))
-            Y = H * (0.5 + (0.5 * n[:, 1] / n[:, 2]) / lens)
-        else:
-            raise ValueError(f"project: the camera's mode is 'pinhole' or 'equirect', not {mode!r} (a ray map has no inverse)")
-        visible &= (np.abs(X) < 1e9) & (np.abs(Y) < 1e9)
-    X = np.where(visible, X, np.nan)
-    Y = np.where(visible, Y, np.nan)
-    return {"visible": visible, "X": X, "Y": Y, "dist": dist, "r": r, "D": D, "te": te, "k": k, "n": n, "rgb": rgb, "a": a, "tau": tau,
-            "pos_e": w + cam[:, 1:]}
+    seen = seen_from_emission(visible, inv, tau, w, r, rgb0, camera, W, H, interval, flags, options, temperatures)
+    return dict(seen, r=r, te=te, a=a, tau=tau, pos_e=w + cam[:, 1:])

@@ -38,6 +38,8 @@
 #include "rpt_dust_host.hpp"
 #include "rpt_ballistics.hip.h"     /* behind the dust: kernels 1150 and 1152 are the translation unit's last */
 #include "rpt_ballistics_host.hpp"
+#include "rpt_rockets.hip.h"        /* behind the ballistic pass: kernels 1160 and 1162 are the translation unit's last */
+#include "rpt_rockets_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -83,14 +85,14 @@ struct Tally {
     size_t words = 1, spare = 0;                      // (as tally_ready was given them)
     bool pending = false;                             // a copy has been enqueued since `value` was read
 };
-enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_SEGMENTS, TALLY_BALLISTICS, TALLY_COUNT };     // rpt_ctx::tally
+enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_SEGMENTS, TALLY_BALLISTICS, TALLY_ROCKETS, TALLY_COUNT };     // rpt_ctx::tally
 
-// A splat pass (the stars, the particles, the segments, the ballistic particles): its records on the device, the temperatures beside them, and the marks of a
+// A splat pass (the stars, the particles, the segments, the ballistic particles, the rockets): its records on the device, the temperatures beside them, and the marks of a
 // timed pass.  What differs between the passes — their options — stays with the context.
 struct SplatPass {
     int count = 0;                                    // 0 = no catalogue, no set: the pass is off
     int largest_object = -1;                          // the largest Object[] index the set names, held against object_count at every launch; -1 for the stars, who name none
-    StagedUpload table;                               // rpt_star / rpt_particle / rpt_segment / rpt_ballistic per record, in the caller's order; written once per rpt_set_*
+    StagedUpload table;                               // rpt_star / rpt_particle / rpt_segment / rpt_ballistic / rpt_rocket per record, in the caller's order; written once per rpt_set_*
     // rpt_set_star_temperatures / rpt_set_particle_temperatures: x_G per source, parallel to the records; 0 entries =
     // none set, and the pass launches kernel 1120 / 1130 as before.  The segments have none
     int thermal_count = 0;
@@ -99,7 +101,7 @@ struct SplatPass {
     hipEvent_t marks[3] = {nullptr, nullptr, nullptr};    // timed passes: before the splat, between the kernels, after the resolve
     bool marked = false;                              // the last pass recorded them
 };
-enum { SPLAT_STARS, SPLAT_PARTICLES, SPLAT_SEGMENTS, SPLAT_BALLISTICS, SPLAT_COUNT };     // rpt_ctx::splat
+enum { SPLAT_STARS, SPLAT_PARTICLES, SPLAT_SEGMENTS, SPLAT_BALLISTICS, SPLAT_ROCKETS, SPLAT_COUNT };     // rpt_ctx::splat
 
 // What the last frame of one kind (colour, event) was enqueued for, as a pass over both asks (frames_of_this_view)
 struct FrameMark {
@@ -270,7 +272,7 @@ struct rpt_ctx {
     // what the passes report, by TALLY_*: the refined pixels of an adaptive frame (rpt_last_aa_refined); the overlay's changed pixels and,
     // as spare bytes, the bit pattern of the frame's largest delay (rpt_last_overlay_pixels); the readouts' changed pixels
     // (rpt_last_readout_pixels); {stars with a tap inside the frame, changed pixels} (rpt_last_stars); {particles seen, changed pixels}
-    // (rpt_last_particles); {pieces drawn, changed pixels} (rpt_last_segments); {records seen, changed pixels} (rpt_last_ballistics)
+    // (rpt_last_particles); {pieces drawn, changed pixels} (rpt_last_segments); {records seen, changed pixels} (rpt_last_ballistics, rpt_last_rockets)
     Tally tally[TALLY_COUNT];
     // rpt_set_readouts / rpt_render_readouts (not in the reference): the readout pass, per context, never shared
     std::vector<rpt_readout> readouts;                // one per entry of Object[]; empty = none set
@@ -285,6 +287,8 @@ struct rpt_ctx {
     float particle_depth_bias = 0.0f;
     int ballistic_flags = 0;                          // rpt_set_ballistic_options (the particle pass's flag and bias, kept apart from its)
     float ballistic_depth_bias = 0.0f;
+    int rocket_flags = 0;                             // rpt_set_rocket_options (the same flag and bias again, kept apart from both)
+    float rocket_depth_bias = 0.0f;
     int particle_lighting = 0;                        // rpt_set_particle_lighting: RPT_PARTICLES_LIT | _SHADOWED | _AMBIENT
     int segment_flags = 0;                            // rpt_set_segment_options
     float segment_depth_bias = 0.0f;
@@ -2186,7 +2190,7 @@ int enqueue_splat(rpt_ctx *ctx, int which, Tally &tally, size_t words, rpt_pixel
     return RPT_OK;
 }
 
-// rpt_render_stars, _particles, _segments, _ballistics: a pass that is off has no marks of one either; then frame_pass
+// rpt_render_stars, _particles, _segments, _ballistics, _rockets: a pass that is off has no marks of one either; then frame_pass
 int launch_splat(rpt_ctx *ctx, int which, const char *call, int tally, PassEnqueue enqueue) {
     SplatPass &p = ctx->splat[which];
     if (p.count == 0) p.marked = false;
@@ -2372,6 +2376,33 @@ int enqueue_ballistics(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_e
 
 int launch_ballistics(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_BALLISTICS, "rpt_render_ballistics", TALLY_BALLISTICS, enqueue_ballistics); }
 
+// One rocket pass on the context's stream (kernels 1160 or 1162, and 1131): enqueue_ballistics with the 64-byte record
+int enqueue_rockets(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    const SplatPass &p = ctx->splat[SPLAT_ROCKETS];
+    if (int rc = splat_refusals(ctx, p, "rpt_render_rockets", "rocket", true)) return rc;
+    if (int rc = thermal_refusal(ctx, p, "rpt_render_rockets", "rpt_set_rocket_temperatures", "set")) return rc;
+
+    rptd::ParticleArgs a;
+    object_pass_args(ctx, events, a);
+    a.dobjs = nullptr;
+    a.particles = (const rpt_particle *)p.table.device.ptr;      // rpt_rocket records, 64 B each: the kernels read them as such
+    a.count = p.count;
+    a.inverse_square = ctx->rocket_flags & RPT_PARTICLES_INVERSE_SQUARE;
+    a.depth_bias = ctx->rocket_depth_bias;
+    rptd::ParticleResolveArgs b;
+    std::memset((void *)&b, 0, sizeof b);
+    return enqueue_splat(ctx, SPLAT_ROCKETS, tally, 2, out16, (const void *)rptd::rpt_particles_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
+        a.acc = acc;
+        a.counts = counts;
+        const float *xg = (const float *)p.thermal_table.device.ptr;
+        void *splat_args[] = {(void *)&a, (void *)&xg};     // (1160 takes the first only)
+        (void)hipLaunchKernel(p.thermal_count != 0 ? (const void *)rptd::rpt_rockets_thermal_splat_kernel : (const void *)rptd::rpt_rockets_splat_kernel,
+                              dim3((unsigned)((p.count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+    });
+}
+
+int launch_rockets(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_ROCKETS, "rpt_render_rockets", TALLY_ROCKETS, enqueue_rockets); }
+
 // The event pass and what it leaves for rpt_pick, rpt_read_events and the passes over the frame
 int launch_event_frame(rpt_ctx *ctx) {
     if (!ctx->ev_events) RPT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
@@ -2395,7 +2426,7 @@ void mark_colour_frame(rpt_ctx *ctx) {
     ctx->colour_frame = FrameMark{ctx->view_generation, ctx->width, ctx->height, ctx->colour_plane ? nullptr : rpt_output_ptr(ctx)};
 }
 
-// rpt_set_stars, rpt_set_particles, rpt_set_segments, rpt_set_ballistics and the three rpt_set_*_temperatures, `call` naming the one: `count` records go to
+// rpt_set_stars, rpt_set_particles, rpt_set_segments, rpt_set_ballistics, rpt_set_rockets and the four rpt_set_*_temperatures, `call` naming the one: `count` records go to
 // the device here, once, as `prepare` writes them, in stream order (a pass in flight keeps what it was launched with).  Null or zero
 // switches off; a call refused for its arguments (`fault`: "" or what is wrong with them) has changed nothing, one that fails on the
 // device (RPT_ERR_DEVICE) leaves nothing set — the table may be gone or half written.  `largest`, for records that name objects: what
@@ -2423,14 +2454,14 @@ int set_records(rpt_ctx *ctx, const char *call, StagedUpload &table, int &table_
     return RPT_OK;
 }
 
-// rpt_set_stars_measurement, _particles_, _segments_, _ballistics_
+// rpt_set_stars_measurement, _particles_, _segments_, _ballistics_, _rockets_
 int set_splat_measurement(rpt_ctx *ctx, int which, int timed) {
     if (!ctx) return RPT_ERR_ARG;
     ctx->splat[which].timed = timed != 0;
     return RPT_OK;
 }
 
-// rpt_last_stars_ms, _particles_, _segments_, _ballistics_: `name` as those calls spell the pass, `pass` as their message does
+// rpt_last_stars_ms, _particles_, _segments_, _ballistics_, _rockets_: `name` as those calls spell the pass, `pass` as their message does
 int last_splat_ms(rpt_ctx *ctx, int which, float ms[2], const char *name, const char *pass) {
     if (!ctx || !ms) return RPT_ERR_ARG;
     const SplatPass &p = ctx->splat[which];
@@ -3618,6 +3649,33 @@ int rpt_last_ballistics(rpt_ctx *ctx, unsigned long long out[2]) { return tally_
 
 int rpt_set_ballistics_measurement(rpt_ctx *ctx, int timed) { return set_splat_measurement(ctx, SPLAT_BALLISTICS, timed); }
 int rpt_last_ballistics_ms(rpt_ctx *ctx, float ms[2]) { return last_splat_ms(ctx, SPLAT_BALLISTICS, ms, "ballistics", "ballistic"); }
+
+// The rocket pass.  The set goes to the device once, here (set_records)
+int rpt_set_rockets(rpt_ctx *ctx, const rpt_rocket *records_or_null, int count) {
+    if (!ctx) return RPT_ERR_ARG;
+    SplatPass &p = ctx->splat[SPLAT_ROCKETS];
+    return set_records(ctx, "rpt_set_rockets", p.table, p.count, p.largest_object, records_or_null, count, rptr::kMaxRockets, rptr::set_fault, rptr::prepare_set,
+                       rptr::largest_object);
+}
+
+int rpt_set_rocket_options(rpt_ctx *ctx, int flags, float depth_bias) {
+    if (!ctx) return RPT_ERR_ARG;
+    const std::string fault = rptp::options_fault(flags, depth_bias);
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_rocket_options: " + fault);
+    ctx->rocket_flags = flags;
+    ctx->rocket_depth_bias = depth_bias;
+    return RPT_OK;
+}
+
+int rpt_set_rocket_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) { return set_temperatures(ctx, "rpt_set_rocket_temperatures", SPLAT_ROCKETS, kelvin_or_null, count); }
+
+int rpt_render_rockets_async(rpt_ctx *ctx) { return render_pass(ctx, launch_rockets, false); }
+int rpt_render_rockets(rpt_ctx *ctx) { return render_pass(ctx, launch_rockets, true); }
+
+int rpt_last_rockets(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(ctx, TALLY_ROCKETS, out, 2); }
+
+int rpt_set_rockets_measurement(rpt_ctx *ctx, int timed) { return set_splat_measurement(ctx, SPLAT_ROCKETS, timed); }
+int rpt_last_rockets_ms(rpt_ctx *ctx, float ms[2]) { return last_splat_ms(ctx, SPLAT_ROCKETS, ms, "rockets", "rocket"); }
 
 // The segment pass.  The set goes to the device once, here (set_records); the count is held against the pieces first (rptg::load_fault)
 int rpt_set_segments(rpt_ctx *ctx, const rpt_segment *segments_or_null, int count) {

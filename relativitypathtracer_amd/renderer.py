@@ -704,6 +704,49 @@ class Renderer:
         """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_ballistics_measurement)."""
         return self._last_ms("rpt_last_ballistics_ms")
 
+    # -- the rocket pass (include/rpt.h, rpt_set_rockets; not in the reference) ----------------------
+    def set_rockets(self, rockets, temperatures=None):
+        """Point sources under constant proper acceleration: an array of rockets.ROCKET_DTYPE records (or anything of n x 64 bytes in
+        that layout: pos, object, rgb, t0, u, t1, acc, reserved), e.g. from rockets.from_arrays / rockets.launch / rockets.fleet /
+        rockets.trip / rockets.load; None or an empty array switches the pass off.  pos, object, rgb, u and [t0, t1) as in
+        set_ballistics; acc is the proper acceleration the crew feels, in the rocket's own rest frame at the object's time 0.  Copied by
+        the library; per context; what the library refuses raises RenderError.  temperatures: if given, passed to
+        set_rocket_temperatures after the set."""
+        if temperatures is not None:
+            self.set_rockets(rockets)
+            self.set_rocket_temperatures(temperatures)
+            return
+        self._set_records("rpt_set_rockets", rockets, _ffi.Rocket, "a rocket set has one 64-byte record (rockets.ROCKET_DTYPE) per rocket")
+
+    def set_rocket_temperatures(self, kelvin):
+        """Thermal rockets (rpt_set_rocket_temperatures): as set_star_temperatures, one temperature per record of the set."""
+        self._set_temperatures("rpt_set_rocket_temperatures", kelvin)
+
+    def set_rocket_options(self, inverse_square: bool = False, depth_bias: float = 0.0):
+        """As set_ballistic_options, for the rocket pass alone; inverse_square divides by the squared distance of the camera in the
+        ROCKET's rest frame at emission."""
+        self._check(self._lib.rpt_set_rocket_options(self._h, 1 if inverse_square else 0, float(depth_bias)), "rpt_set_rocket_options")
+
+    def render_rockets(self, async_: bool = False):
+        """Add the rockets of set_rockets to the framebuffer, in place, each tap depth-tested against the last event frame.  The
+        context must have rendered (or enqueued) a colour frame and an event frame of the current view first; calling it twice adds them
+        twice.  Independent of the other passes.  async_=True enqueues only (sync waits)."""
+        self._run_pass("rpt_render_rockets", async_)
+
+    def last_rockets(self) -> Tuple[int, int]:
+        """(records with at least one tap inside the frame that passed the depth test, pixels whose bytes changed) of the last finished
+        rocket pass."""
+        seen, changed = self._last_counts("rpt_last_rockets", 2)
+        return seen, changed
+
+    def set_rockets_measurement(self, timed: bool = False):
+        """Measurement only (tools/rockets_cost.py): time the two kernels of every pass (last_rockets_ms)."""
+        self._set_measurement("rpt_set_rockets_measurement", timed)
+
+    def last_rockets_ms(self) -> Tuple[float, float]:
+        """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_rockets_measurement)."""
+        return self._last_ms("rpt_last_rockets_ms")
+
     # -- results -------------------------------------------------------------------------------
     def local_tiles(self) -> int:
         first, step, _ = self._rows
@@ -840,7 +883,8 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  fov: float = math.pi, fit: int = 0, readouts=None, stars=None, particles=None,
                  particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None,
                  segments=None, segment_options: Optional[Mapping] = None, particle_lighting: Optional[Mapping] = None,
-                 ballistics=None, ballistic_options: Optional[Mapping] = None, ballistic_temperatures=None):
+                 ballistics=None, ballistic_options: Optional[Mapping] = None, ballistic_temperatures=None,
+                 rockets=None, rocket_options: Optional[Mapping] = None, rocket_temperatures=None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -864,7 +908,9 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     the keywords of Renderer.set_particle_lighting, e.g. dict(lit=True, shadows=True): the particles are dust that scatters the
     scene's lights.  ballistics: a set for Renderer.set_ballistics (ballistics.jet, ballistics.shell, ...), ballistic_options the
     keywords of Renderer.set_ballistic_options, ballistic_temperatures kelvin per record; it implies events=True as the particles do,
-    and the pass runs right behind the segments."""
+    and the pass runs right behind the segments.  rockets: a set for Renderer.set_rockets (rockets.launch, rockets.fleet, rockets.trip,
+    ...), rocket_options the keywords of Renderer.set_rocket_options, rocket_temperatures kelvin per record; it implies events=True too,
+    and the pass runs right behind the ballistic one."""
     r = Renderer(device)
     try:
         if adaptive_aa is not None:
@@ -890,7 +936,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
         if debug_rgb:
             r.set_debug_rgb(True)
         r.render()
-        if overlay is not None or readouts is not None or stars is not None or particles is not None or segments is not None or ballistics is not None:
+        if overlay is not None or readouts is not None or stars is not None or particles is not None or segments is not None or ballistics is not None or rockets is not None:
             records = r.render_events()
             if stars is not None:
                 r.set_stars(stars, star_temperatures)
@@ -908,6 +954,10 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                 r.set_ballistics(ballistics, ballistic_temperatures)
                 r.set_ballistic_options(**dict(ballistic_options or {}))
                 r.render_ballistics()
+            if rockets is not None:
+                r.set_rockets(rockets, rocket_temperatures)
+                r.set_rocket_options(**dict(rocket_options or {}))
+                r.render_rockets()
             if overlay is not None:
                 r.set_overlay(**overlay)
                 r.render_overlay()
