@@ -26,19 +26,19 @@
 #include "rpt_tile_bitmap.hpp"
 #include "rpt_sky_split.hpp"
 #include "rpt_workers.hpp"
-#include "rpt_stars.hip.h"          /* last: the kernels before it keep their place in the translation unit */
+#include "rpt_stars.hip.h"          /* the splat passes, behind the render kernels; each header includes the ones it builds on */
 #include "rpt_stars_host.hpp"
-#include "rpt_particles.hip.h"      /* behind the stars: kernels 1130 and 1131 are the translation unit's last */
+#include "rpt_particles.hip.h"      /* splat_taps and point_splat: the segments, the ballistic pass and the rockets use them */
 #include "rpt_particles_host.hpp"
-#include "rpt_thermal.hip.h"        /* behind the particles: the thermal probe and kernels 1122 and 1132 */
+#include "rpt_thermal.hip.h"        /* T_f, the thermal probe and kernels 1122 and 1132 */
 #include "rpt_thermal_host.hpp"
-#include "rpt_segments.hip.h"       /* behind the thermal kernels: kernel 1140 is the translation unit's last */
+#include "rpt_segments.hip.h"
 #include "rpt_segments_host.hpp"
-#include "rpt_dust.hip.h"           /* behind the segments: kernels 1134, 1135 and 1136 are the translation unit's last */
+#include "rpt_dust.hip.h"
 #include "rpt_dust_host.hpp"
-#include "rpt_ballistics.hip.h"     /* behind the dust: kernels 1150 and 1152 are the translation unit's last */
+#include "rpt_ballistics.hip.h"
 #include "rpt_ballistics_host.hpp"
-#include "rpt_rockets.hip.h"        /* behind the ballistic pass: kernels 1160 and 1162 are the translation unit's last */
+#include "rpt_rockets.hip.h"
 #include "rpt_rockets_host.hpp"
 
 #pragma clang fp contract(off)
@@ -88,9 +88,11 @@ struct Tally {
 enum { TALLY_AA, TALLY_OVERLAY, TALLY_READOUTS, TALLY_STARS, TALLY_PARTICLES, TALLY_SEGMENTS, TALLY_BALLISTICS, TALLY_ROCKETS, TALLY_COUNT };     // rpt_ctx::tally
 
 // A splat pass (the stars, the particles, the segments, the ballistic particles, the rockets): its records on the device, the temperatures beside them, and the marks of a
-// timed pass.  What differs between the passes — their options — stays with the context.
+// timed pass, and the two options every pass but the stars has.  What one pass alone has (the segments' pieces, the particles' lighting) stays with the context.
 struct SplatPass {
     int count = 0;                                    // 0 = no catalogue, no set: the pass is off
+    int flags = 0;                                    // rpt_set_particle_options, _ballistic_, _rocket_, _segment_: the inverse square (the same bit in all four)
+    float depth_bias = 0.0f;
     int largest_object = -1;                          // the largest Object[] index the set names, held against object_count at every launch; -1 for the stars, who name none
     StagedUpload table;                               // rpt_star / rpt_particle / rpt_segment / rpt_ballistic / rpt_rocket per record, in the caller's order; written once per rpt_set_*
     // rpt_set_star_temperatures / rpt_set_particle_temperatures: x_G per source, parallel to the records; 0 entries =
@@ -283,16 +285,8 @@ struct rpt_ctx {
     // one context are ordered by its stream
     SplatPass splat[SPLAT_COUNT];
     DeviceBuffer splat_acc;                           // 24 B per pixel of the largest frame so far: the fixed-point sums, all zero outside a pass
-    int particle_flags = 0;                           // rpt_set_particle_options
-    float particle_depth_bias = 0.0f;
-    int ballistic_flags = 0;                          // rpt_set_ballistic_options (the particle pass's flag and bias, kept apart from its)
-    float ballistic_depth_bias = 0.0f;
-    int rocket_flags = 0;                             // rpt_set_rocket_options (the same flag and bias again, kept apart from both)
-    float rocket_depth_bias = 0.0f;
     int particle_lighting = 0;                        // rpt_set_particle_lighting: RPT_PARTICLES_LIT | _SHADOWED | _AMBIENT
-    int segment_flags = 0;                            // rpt_set_segment_options
-    float segment_depth_bias = 0.0f;
-    int segment_pieces = rptg::kDefaultPieces;
+    int segment_pieces = rptg::kDefaultPieces;        // rpt_set_segment_options
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
     StagedUpload tile_bits;
     unsigned long long bits_still = 0;                // objects whose record was byte-identical in the last two rpt_set_objects calls
@@ -2256,16 +2250,27 @@ void probe_kernel_args(rpt_ctx *ctx, rptd::KernelArgs &a) {
     a.interval = ctx->interval;
 }
 
-// What the particle pass and the segment pass hand their splat kernels alike: the objects and their windows, the records of the view,
-// and the view.  The set, its count and its options are the caller's; the accumulator and the tally's words come with the launch.
-void object_pass_args(rpt_ctx *ctx, const rpt_event *events, rptd::ParticleArgs &a) {
+// What the passes whose records name objects hand their splat kernels alike: the objects, the records of the view, the view, and the
+// pass's count and options.  The objects' windows (`with_windows`: the particles and the segments ride their objects; a ballistic
+// record and a rocket bring their own) and the set's pointer are the caller's; the accumulator and the tally's words come with the launch.
+void object_pass_args(rpt_ctx *ctx, const SplatPass &p, const rpt_event *events, bool with_windows, rptd::ParticleArgs &a) {
     std::memset((void *)&a, 0, sizeof a);
     a.objects = (const rpt_object *)ctx->objects.ptr;
-    if (!ctx->windows.empty())          // (their count is the Object[]'s: the frames of this view were launched with them)
+    if (with_windows && !ctx->windows.empty())      // (their count is the Object[]'s: the frames of this view were launched with them)
         a.dobjs = (const rptd::DObj *)((const char *)ctx->objects.ptr + (size_t)ctx->object_count * sizeof(rpt_object));
     a.events = events;
     a.object_count = ctx->object_count;
+    a.count = p.count;
+    a.inverse_square = p.flags & RPT_PARTICLES_INVERSE_SQUARE;       // (RPT_SEGMENTS_INVERSE_SQUARE is the same bit)
+    a.depth_bias = p.depth_bias;
     splat_view(ctx, a);
+}
+
+// A point-source splat, one lane per record: `plain`, or `thermal` with the pass's x_G where temperatures are set
+void launch_point_splat(rpt_ctx *ctx, const SplatPass &p, rptd::ParticleArgs &a, const void *plain, const void *thermal) {
+    const float *xg = (const float *)p.thermal_table.device.ptr;
+    void *splat_args[] = {(void *)&a, (void *)&xg};         // (`plain` takes the first only)
+    (void)hipLaunchKernel(p.thermal_count != 0 ? thermal : plain, dim3((unsigned)((p.count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
 }
 
 // One particle pass on the context's stream (kernels 1130 or 1132, and 1131): its refusals, the launch.  With rpt_set_particle_lighting
@@ -2279,11 +2284,8 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
     if (dust_fault.code != RPT_OK) return fail(ctx, dust_fault.code, "rpt_render_particles: " + dust_fault.message);
 
     rptd::ParticleArgs a;
-    object_pass_args(ctx, events, a);
+    object_pass_args(ctx, p, events, true, a);
     a.particles = (const rpt_particle *)p.table.device.ptr;
-    a.count = p.count;
-    a.inverse_square = ctx->particle_flags & RPT_PARTICLES_INVERSE_SQUARE;
-    a.depth_bias = ctx->particle_depth_bias;
     rptd::ParticleResolveArgs b;
     std::memset((void *)&b, 0, sizeof b);
     // the tally's four words: seen, changed pixels; (particle, light) pairs lit, pairs shadowed (zero for a plain pass)
@@ -2291,12 +2293,8 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
         a.acc = acc;
         a.counts = counts;
         const int splat = rptl::splat_kernel(ctx->particle_lighting, ctx->interval, p.thermal_count, !ctx->windows.empty());
-        const dim3 splat_grid((unsigned)((p.count + 255) / 256));
-        if (splat == 1130 || splat == 1132) {
-            const float *xg = (const float *)p.thermal_table.device.ptr;
-            void *splat_args[] = {(void *)&a, (void *)&xg};     // (1130 takes the first only)
-            (void)hipLaunchKernel(splat == 1132 ? (const void *)rptd::rpt_particles_thermal_splat_kernel : (const void *)rptd::rpt_particles_splat_kernel,
-                                  splat_grid, dim3(256), splat_args, 0, ctx->stream);
+        if (splat == 1130 || splat == 1132) {                   // (1132: temperatures are set)
+            launch_point_splat(ctx, p, a, (const void *)rptd::rpt_particles_splat_kernel, (const void *)rptd::rpt_particles_thermal_splat_kernel);
         } else {                                                // lit particles: 1134, or 1135 / 1136 with the scene for the shadow ray
             rptd::DustArgs d;
             std::memset((void *)&d, 0, sizeof d);
@@ -2308,7 +2306,7 @@ int enqueue_particles(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_ev
             void *splat_args[] = {(void *)&d, (void *)&k};      // (1134 takes the first only)
             (void)hipLaunchKernel(splat == 1134 ? (const void *)rptd::rpt_dust_splat_kernel
                                   : splat == 1135 ? (const void *)rptd::rpt_dust_shadowed_splat_kernel : (const void *)rptd::rpt_dust_shadowed_windowed_splat_kernel,
-                                  splat_grid, dim3(256), splat_args, 0, ctx->stream);
+                                  dim3((unsigned)((p.count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
         }
     });
 }
@@ -2323,10 +2321,7 @@ int enqueue_segments(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_eve
 
     rptd::SegmentArgs a;
     std::memset((void *)&a, 0, sizeof a);
-    object_pass_args(ctx, events, a.p);
-    a.p.count = p.count;
-    a.p.inverse_square = ctx->segment_flags & RPT_SEGMENTS_INVERSE_SQUARE;
-    a.p.depth_bias = ctx->segment_depth_bias;
+    object_pass_args(ctx, p, events, true, a.p);
     a.segments = (const rpt_segment *)p.table.device.ptr;
     a.pieces = ctx->segment_pieces;
     while ((1 << a.shift) < a.pieces) a.shift++;
@@ -2348,59 +2343,45 @@ int enqueue_segments(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_eve
 
 int launch_segments(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_SEGMENTS, "rpt_render_segments", TALLY_SEGMENTS, enqueue_segments); }
 
-// One ballistic pass on the context's stream (kernels 1150 or 1152, and 1131): the refusals of a pass whose records name
-// objects, the launch.  The objects' time windows are not handed over (dobjs stays null): a record has its own window.
-int enqueue_ballistics(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
-    const SplatPass &p = ctx->splat[SPLAT_BALLISTICS];
-    if (int rc = splat_refusals(ctx, p, "rpt_render_ballistics", "particle", true)) return rc;
-    if (int rc = thermal_refusal(ctx, p, "rpt_render_ballistics", "rpt_set_ballistic_temperatures", "set")) return rc;
+// The passes of records with a worldline of their own, written in an object's frame: what differs between them on the host
+struct WorldlinePass {
+    int which;                          // SPLAT_*
+    const char *call, *noun;            // as the refusals name the pass and what it projects
+    const char *temperatures;           // the setter of its temperatures
+    const void *plain, *thermal;        // the splat kernel without and with them
+};
+
+// One ballistic or rocket pass on the context's stream (kernels 1150 or 1152, 1160 or 1162, and 1131): the refusals
+// of a pass whose records name objects, the launch.  The objects' time windows are not handed over: a record has its own window.  The
+// kernels read a.particles as their own records, 48 B and 64 B each.
+int enqueue_worldlines(rpt_ctx *ctx, const WorldlinePass &w, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    const SplatPass &p = ctx->splat[w.which];
+    if (int rc = splat_refusals(ctx, p, w.call, w.noun, true)) return rc;
+    if (int rc = thermal_refusal(ctx, p, w.call, w.temperatures, "set")) return rc;
 
     rptd::ParticleArgs a;
-    object_pass_args(ctx, events, a);
-    a.dobjs = nullptr;
-    a.particles = (const rpt_particle *)p.table.device.ptr;      // rpt_ballistic records, 48 B each: the kernels read them as such
-    a.count = p.count;
-    a.inverse_square = ctx->ballistic_flags & RPT_PARTICLES_INVERSE_SQUARE;
-    a.depth_bias = ctx->ballistic_depth_bias;
+    object_pass_args(ctx, p, events, false, a);
+    a.particles = (const rpt_particle *)p.table.device.ptr;
     rptd::ParticleResolveArgs b;
     std::memset((void *)&b, 0, sizeof b);
-    return enqueue_splat(ctx, SPLAT_BALLISTICS, tally, 2, out16, (const void *)rptd::rpt_particles_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
+    return enqueue_splat(ctx, w.which, tally, 2, out16, (const void *)rptd::rpt_particles_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
         a.acc = acc;
         a.counts = counts;
-        const float *xg = (const float *)p.thermal_table.device.ptr;
-        void *splat_args[] = {(void *)&a, (void *)&xg};     // (1150 takes the first only)
-        (void)hipLaunchKernel(p.thermal_count != 0 ? (const void *)rptd::rpt_ballistics_thermal_splat_kernel : (const void *)rptd::rpt_ballistics_splat_kernel,
-                              dim3((unsigned)((p.count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
+        launch_point_splat(ctx, p, a, w.plain, w.thermal);
     });
+}
+
+int enqueue_ballistics(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    return enqueue_worldlines(ctx, {SPLAT_BALLISTICS, "rpt_render_ballistics", "particle", "rpt_set_ballistic_temperatures", (const void *)rptd::rpt_ballistics_splat_kernel,
+                                    (const void *)rptd::rpt_ballistics_thermal_splat_kernel}, tally, out16, events);
+}
+
+int enqueue_rockets(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
+    return enqueue_worldlines(ctx, {SPLAT_ROCKETS, "rpt_render_rockets", "rocket", "rpt_set_rocket_temperatures", (const void *)rptd::rpt_rockets_splat_kernel,
+                                    (const void *)rptd::rpt_rockets_thermal_splat_kernel}, tally, out16, events);
 }
 
 int launch_ballistics(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_BALLISTICS, "rpt_render_ballistics", TALLY_BALLISTICS, enqueue_ballistics); }
-
-// One rocket pass on the context's stream (kernels 1160 or 1162, and 1131): enqueue_ballistics with the 64-byte record
-int enqueue_rockets(rpt_ctx *ctx, Tally &tally, rpt_pixel *out16, const rpt_event *events) {
-    const SplatPass &p = ctx->splat[SPLAT_ROCKETS];
-    if (int rc = splat_refusals(ctx, p, "rpt_render_rockets", "rocket", true)) return rc;
-    if (int rc = thermal_refusal(ctx, p, "rpt_render_rockets", "rpt_set_rocket_temperatures", "set")) return rc;
-
-    rptd::ParticleArgs a;
-    object_pass_args(ctx, events, a);
-    a.dobjs = nullptr;
-    a.particles = (const rpt_particle *)p.table.device.ptr;      // rpt_rocket records, 64 B each: the kernels read them as such
-    a.count = p.count;
-    a.inverse_square = ctx->rocket_flags & RPT_PARTICLES_INVERSE_SQUARE;
-    a.depth_bias = ctx->rocket_depth_bias;
-    rptd::ParticleResolveArgs b;
-    std::memset((void *)&b, 0, sizeof b);
-    return enqueue_splat(ctx, SPLAT_ROCKETS, tally, 2, out16, (const void *)rptd::rpt_particles_resolve_kernel, b, [&](unsigned long long *acc, unsigned long long *counts) {
-        a.acc = acc;
-        a.counts = counts;
-        const float *xg = (const float *)p.thermal_table.device.ptr;
-        void *splat_args[] = {(void *)&a, (void *)&xg};     // (1160 takes the first only)
-        (void)hipLaunchKernel(p.thermal_count != 0 ? (const void *)rptd::rpt_rockets_thermal_splat_kernel : (const void *)rptd::rpt_rockets_splat_kernel,
-                              dim3((unsigned)((p.count + 255) / 256)), dim3(256), splat_args, 0, ctx->stream);
-    });
-}
-
 int launch_rockets(rpt_ctx *ctx) { return launch_splat(ctx, SPLAT_ROCKETS, "rpt_render_rockets", TALLY_ROCKETS, enqueue_rockets); }
 
 // The event pass and what it leaves for rpt_pick, rpt_read_events and the passes over the frame
@@ -3578,14 +3559,17 @@ int rpt_set_particles(rpt_ctx *ctx, const rpt_particle *particles_or_null, int c
                        rptp::largest_object);
 }
 
-int rpt_set_particle_options(rpt_ctx *ctx, int flags, float depth_bias) {
+// rpt_set_particle_options, _ballistic_, _rocket_: one rule (rptp::options_fault), each pass's own pair
+static int set_splat_options(rpt_ctx *ctx, int which, const char *call, int flags, float depth_bias) {
     if (!ctx) return RPT_ERR_ARG;
     const std::string fault = rptp::options_fault(flags, depth_bias);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_particle_options: " + fault);
-    ctx->particle_flags = flags;
-    ctx->particle_depth_bias = depth_bias;
+    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, std::string(call) + ": " + fault);
+    ctx->splat[which].flags = flags;
+    ctx->splat[which].depth_bias = depth_bias;
     return RPT_OK;
 }
+
+int rpt_set_particle_options(rpt_ctx *ctx, int flags, float depth_bias) { return set_splat_options(ctx, SPLAT_PARTICLES, "rpt_set_particle_options", flags, depth_bias); }
 
 int rpt_set_particle_lighting(rpt_ctx *ctx, int flags) {
     if (!ctx) return RPT_ERR_ARG;
@@ -3633,14 +3617,7 @@ int rpt_set_ballistics(rpt_ctx *ctx, const rpt_ballistic *records_or_null, int c
                        rptb::largest_object);
 }
 
-int rpt_set_ballistic_options(rpt_ctx *ctx, int flags, float depth_bias) {
-    if (!ctx) return RPT_ERR_ARG;
-    const std::string fault = rptp::options_fault(flags, depth_bias);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_ballistic_options: " + fault);
-    ctx->ballistic_flags = flags;
-    ctx->ballistic_depth_bias = depth_bias;
-    return RPT_OK;
-}
+int rpt_set_ballistic_options(rpt_ctx *ctx, int flags, float depth_bias) { return set_splat_options(ctx, SPLAT_BALLISTICS, "rpt_set_ballistic_options", flags, depth_bias); }
 
 int rpt_render_ballistics_async(rpt_ctx *ctx) { return render_pass(ctx, launch_ballistics, false); }
 int rpt_render_ballistics(rpt_ctx *ctx) { return render_pass(ctx, launch_ballistics, true); }
@@ -3658,14 +3635,7 @@ int rpt_set_rockets(rpt_ctx *ctx, const rpt_rocket *records_or_null, int count) 
                        rptr::largest_object);
 }
 
-int rpt_set_rocket_options(rpt_ctx *ctx, int flags, float depth_bias) {
-    if (!ctx) return RPT_ERR_ARG;
-    const std::string fault = rptp::options_fault(flags, depth_bias);
-    if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_rocket_options: " + fault);
-    ctx->rocket_flags = flags;
-    ctx->rocket_depth_bias = depth_bias;
-    return RPT_OK;
-}
+int rpt_set_rocket_options(rpt_ctx *ctx, int flags, float depth_bias) { return set_splat_options(ctx, SPLAT_ROCKETS, "rpt_set_rocket_options", flags, depth_bias); }
 
 int rpt_set_rocket_temperatures(rpt_ctx *ctx, const float *kelvin_or_null, int count) { return set_temperatures(ctx, "rpt_set_rocket_temperatures", SPLAT_ROCKETS, kelvin_or_null, count); }
 
@@ -3691,8 +3661,8 @@ int rpt_set_segment_options(rpt_ctx *ctx, int flags, float depth_bias, int piece
     if (!ctx) return RPT_ERR_ARG;
     const std::string fault = rptg::options_fault(flags, depth_bias, pieces, ctx->splat[SPLAT_SEGMENTS].count);
     if (!fault.empty()) return fail(ctx, RPT_ERR_ARG, "rpt_set_segment_options: " + fault);
-    ctx->segment_flags = flags;
-    ctx->segment_depth_bias = depth_bias;
+    ctx->splat[SPLAT_SEGMENTS].flags = flags;
+    ctx->splat[SPLAT_SEGMENTS].depth_bias = depth_bias;
     ctx->segment_pieces = pieces;
     return RPT_OK;
 }

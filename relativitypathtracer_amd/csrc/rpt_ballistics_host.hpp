@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/rpt.h"
+#include "rpt_particles_host.hpp"
 
 namespace rptb {
 
@@ -35,13 +36,7 @@ inline std::string set_fault(const rpt_ballistic *records, int count) {
     return "";
 }
 
-// the largest object index of a set that has passed set_fault; -1 for an empty one
-inline int largest_object(const rpt_ballistic *records, int count) {
-    int largest = -1;
-    for (int i = 0; i < count; i++)
-        if (records[i].object > largest) largest = records[i].object;
-    return largest;
-}
+inline int largest_object(const rpt_ballistic *records, int count) { return rptp::largest_object_of(records, count); }
 
 // The set as the device reads it, in the caller's order: the record has no padding, every field is copied
 inline void prepare_set(const rpt_ballistic *records, int count, rpt_ballistic *out) {

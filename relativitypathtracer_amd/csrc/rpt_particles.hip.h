@@ -70,60 +70,73 @@ RPT_DEV bool particle_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam
     return project_to_frame(a, n, X, Y);                 // §19 rule 4, as star_place has it
 }
 
-// 1130: one lane per particle.  Two 16-byte loads of its record, then the five rpt_float4 of its object — InvLorentz and stationaryCam,
-// 80 consecutive bytes at byte 192 of Object[object]; neighbouring particles usually ride the same object, so a wave's loads fall on one
-// or two lines — and, with time windows, the two floats of its DObj.  The index is held against object_count before anything follows it
-// (the host has refused a set that names a larger one; this keeps the kernel inside Object[] whatever it is handed).  Rules 1-4 in
-// registers, then per tap one 8-byte read of the pixel's record (object, dist) and, where the tap passes, three 8-byte integer atomic
-// adds that return nothing.  Every tap is tested against the frame after the wrap and BEFORE its record is read, so no particle,
-// whatever its numbers, addresses a record or a word outside the frame.  The records are not written and the sums are integers: the
-// frame does not depend on the order of arrival.  Particles seen: a ballot per wave, LDS, one global atomic per workgroup, as 1120.
-// Kernel 1132 (rpt_thermal.hip.h) restates this body around particle_place<true>, as 1122 restates 1120's.
-__global__ __launch_bounds__(256) void rpt_particles_splat_kernel(const ParticleArgs a) {
-    __shared__ unsigned int block_seen;
-    const int t = (int)threadIdx.x;
-    if (t == 0) block_seen = 0u;
-    __syncthreads();
-    const int i = (int)blockIdx.x * 256 + t;
+// The four depth-tested taps of a point at (X, Y), `dist` from the camera, colour c: per tap one 8-byte read of the pixel's record
+// (object, dist) and, where the tap passes, three 8-byte integer atomic adds that return nothing.  Every tap is tested against the
+// frame after the wrap and BEFORE its record is read, so no source, whatever its numbers, addresses a record or a word outside the
+// frame.  The records are not written and the sums are integers: the frame does not depend on the order of arrival.  true = a tap
+// passed.  (The lit kernels, rpt_dust.hip.h, test the taps and add to them in two phases with the light loop between: not this.)
+RPT_DEV bool splat_taps(const ParticleArgs &a, float X, float Y, float dist, f3 c) {
+    const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
+    const int x0 = (int)xf, y0 = (int)yf;                // |X|, |Y| < 1e9 (+ a segment's 2 pi W / h_fov + 1024): in range
+    const float fx = X - xf, fy = Y - yf;
+    const float depth = dist - a.depth_bias;
     bool seen = false;
-    if (i < a.count) {
-        const float4 *record = reinterpret_cast<const float4 *>(a.particles + i);
-        const float4 lo = record[0], hi = record[1];     // pos.xyz, object | rgb.rgb, padding
-        const int object = __float_as_int(lo.w);
-        if (object >= 0 && object < a.object_count) {
-            const rpt_object *L = a.objects + object;
-            rpt_float4 inv[4];
-            for (int k = 0; k < 4; k++) inv[k] = L->InvLorentz[k];
-            const f4 cam = ld4(L->stationaryCam);
-            float X, Y, dist;
-            f3 c;
-            if (particle_place<false>(a, inv, cam, a.dobjs ? a.dobjs + object : nullptr, mk3(lo.x, lo.y, lo.z), mk3(hi.x, hi.y, hi.z), 0.0f, X, Y, dist, c)) {
-                const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
-                const int x0 = (int)xf, y0 = (int)yf;    // |X|, |Y| < 1e9: in range
-                const float fx = X - xf, fy = Y - yf;
-                const float depth = dist - a.depth_bias;
-                for (int k = 0; k < 4; k++) {
-                    int x = x0 + (k & 1);
-                    const int y = y0 + (k >> 1);
-                    if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
-                    if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
-                    const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
-                    const uint2 head = *reinterpret_cast<const uint2 *>(a.events + p);       // object, dist
-                    if (!((int)head.x < 0 || depth < __uint_as_float(head.y))) continue;
-                    seen = true;
-                    const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-                    unsigned long long *word = a.acc + p * 3;
-                    star_add(word + 0, c.x * w);
-                    star_add(word + 1, c.y * w);
-                    star_add(word + 2, c.z * w);
-                }
-            }
-        }
+    for (int k = 0; k < 4; k++) {
+        int x = x0 + (k & 1);
+        const int y = y0 + (k >> 1);
+        if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
+        if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
+        const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+        const uint2 head = *reinterpret_cast<const uint2 *>(a.events + p);       // object, dist
+        if (!((int)head.x < 0 || depth < __uint_as_float(head.y))) continue;
+        seen = true;
+        const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+        unsigned long long *word = a.acc + p * 3;
+        star_add(word + 0, c.x * w);
+        star_add(word + 1, c.y * w);
+        star_add(word + 2, c.z * w);
     }
-    const unsigned long long set = __ballot(seen);
-    if ((t & 63) == 0 && set) atomicAdd(&block_seen, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_seen) atomicAdd(a.counts, (unsigned long long)block_seen);
+    return seen;
+}
+
+// One lane of a point-source splat: source i of SOURCE's records.  kQuads 16-byte loads of its record (a.particles read as that
+// record, 16 * kQuads bytes each) and, THERMAL, four bytes of xg (the host has refused a count that is not the set's); then the five
+// rpt_float4 of the object the record names — InvLorentz and stationaryCam, 80 consecutive bytes at byte 192 of Object[object];
+// neighbouring sources usually name the same object, so a wave's loads fall on one or two lines.  The index is held against
+// object_count before anything follows it (the host has refused a set that names a larger one; this keeps the kernel inside Object[]
+// whatever it is handed).  SOURCE::place — the pass's rules, in registers — then splat_taps.  true = a tap of this source passed.
+template <class SOURCE, bool THERMAL>
+RPT_DEV bool point_splat(const ParticleArgs &a, const float *xg, int i) {
+    if (i >= a.count) return false;
+    const float4 *record = reinterpret_cast<const float4 *>(a.particles) + (size_t)i * SOURCE::kQuads;
+    float4 q[SOURCE::kQuads];
+    for (int k = 0; k < SOURCE::kQuads; k++) q[k] = record[k];
+    float x_green = 0.0f;
+    if constexpr (THERMAL) x_green = xg[i];
+    const int object = __float_as_int(q[0].w);
+    if (object < 0 || object >= a.object_count) return false;
+    const rpt_object *L = a.objects + object;
+    rpt_float4 inv[4];
+    for (int k = 0; k < 4; k++) inv[k] = L->InvLorentz[k];
+    const f4 cam = ld4(L->stationaryCam);
+    float X, Y, dist;
+    f3 c;
+    if (!SOURCE::template place<THERMAL>(a, inv, cam, object, q, x_green, X, Y, dist, c)) return false;
+    return splat_taps(a, X, Y, dist, c);
+}
+
+// The particle that rides its object: pos.xyz, object | rgb.rgb, padding; with time windows, the two floats of its object's DObj
+struct ParticleSource {
+    static constexpr int kQuads = 2;
+    template <bool THERMAL>
+    static RPT_DEV bool place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam, int object, const float4 *q, float xg, float &X, float &Y, float &dist, f3 &c) {
+        return particle_place<THERMAL>(a, inv, cam, a.dobjs ? a.dobjs + object : nullptr, mk3(q[0].x, q[0].y, q[0].z), mk3(q[1].x, q[1].y, q[1].z), xg, X, Y, dist, c);
+    }
+};
+
+// 1130: one lane per particle, rules 1-4.  Kernel 1132 (rpt_thermal.hip.h, behind T_f's definition) is the same with THERMAL.
+__global__ __launch_bounds__(256) void rpt_particles_splat_kernel(const ParticleArgs a) {
+    splat_and_count(a.counts, [&](int i) { return point_splat<ParticleSource, false>(a, nullptr, i); });
 }
 
 // 1131: kernel 1121 without the record read — one lane per pixel, pixels in memory order.  Where a pixel's three sums are all zero

@@ -30,13 +30,16 @@ inline std::string set_fault(const rpt_particle *particles, int count) {
     return "";
 }
 
-// the largest object index of a set that has passed set_fault; -1 for an empty one
-inline int largest_object(const rpt_particle *particles, int count) {
+// the largest object index of a set that has passed its set_fault; -1 for an empty one.  For every record that names an object: the
+// particles here, and the ballistic records, the rockets and the segments (rptb, rptr, rptg::largest_object)
+template <typename Record>
+int largest_object_of(const Record *records, int count) {
     int largest = -1;
     for (int i = 0; i < count; i++)
-        if (particles[i].object > largest) largest = particles[i].object;
+        if (records[i].object > largest) largest = records[i].object;
     return largest;
 }
+inline int largest_object(const rpt_particle *particles, int count) { return largest_object_of(particles, count); }
 
 // The set as the device reads it, in the caller's order: positions, indices and colours copied, padding zero
 inline void prepare_set(const rpt_particle *particles, int count, rpt_particle *out) {

@@ -6,8 +6,7 @@
 // with light delay off, on its simultaneity slice) is the root of a quadratic: + - * / and sqrt, no sinh, cosh or log.  From that event
 // on the pass is the ballistic pass (§24): InvLorentz into the camera's frame, the point-source Doppler law with the distance r' the
 // camera has in the ROCKET's rest frame at emission, project_to_frame, four depth-tested taps into the star pass's accumulator (kernels
-// 1160 and 1162, scatters), which kernel 1131 resolves.  Included by rpt_api.hip behind the ballistic pass, so that the kernels before
-// it keep their place in the translation unit.  tests/native/rockets_oracle.c restates every rule in C.
+// 1160 and 1162, scatters), which kernel 1131 resolves.  tests/native/rockets_oracle.c restates every rule in C.
 #pragma once
 
 #include "rpt_ballistics.hip.h"
@@ -98,80 +97,25 @@ RPT_DEV bool rocket_place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam, 
     return project_to_frame(a, n, X, Y);                 // §19 rule 4, as star_place has it
 }
 
-// The body of 1160 and 1162: kernel 1150's, lane for lane, with a fourth 16-byte load of the record (64 B a lane, a wave's records
-// 4 KiB in a row).  The index is held against object_count before anything follows it (the host has refused a set that names a larger
-// one; this keeps the kernel inside Object[] whatever it is handed).  The object's time window is not looked at (ParticleArgs::dobjs
-// is null and is not read).  Rules 1-6 in registers, then per tap one 8-byte read of the pixel's record (object, dist) and, where the
-// tap passes, three 8-byte integer atomic adds that return nothing.  Every tap is tested against the frame after the wrap and BEFORE
-// its record is read, so no record, whatever its numbers, addresses an event record or a word outside the frame.  true = a tap of
-// this lane's record passed.
-template <bool THERMAL>
-RPT_DEV bool rocket_splat(const ParticleArgs &a, const float *xg, int i) {
-    bool seen = false;
-    if (i < a.count) {
-        const float4 *record = reinterpret_cast<const float4 *>(reinterpret_cast<const rpt_rocket *>(a.particles) + i);
-        const float4 lo = record[0], mid = record[1], hi = record[2], top = record[3];      // pos.xyz, object | rgb.rgb, t0 | u.xyz, t1 | acc.xyz, reserved
-        float x_green = 0.0f;
-        if constexpr (THERMAL) x_green = xg[i];
-        const int object = __float_as_int(lo.w);
-        if (object >= 0 && object < a.object_count) {
-            const rpt_object *L = a.objects + object;
-            rpt_float4 inv[4];
-            for (int k = 0; k < 4; k++) inv[k] = L->InvLorentz[k];
-            const f4 cam = ld4(L->stationaryCam);
-            float X, Y, dist;
-            f3 c;
-            if (rocket_place<THERMAL>(a, inv, cam, mk3(lo.x, lo.y, lo.z), mk3(hi.x, hi.y, hi.z), mk3(top.x, top.y, top.z), mid.w, hi.w, mk3(mid.x, mid.y, mid.z), x_green,
-                                      X, Y, dist, c)) {
-                const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
-                const int x0 = (int)xf, y0 = (int)yf;    // |X|, |Y| < 1e9: in range
-                const float fx = X - xf, fy = Y - yf;
-                const float depth = dist - a.depth_bias;
-                for (int k = 0; k < 4; k++) {
-                    int x = x0 + (k & 1);
-                    const int y = y0 + (k >> 1);
-                    if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
-                    if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
-                    const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
-                    const uint2 head = *reinterpret_cast<const uint2 *>(a.events + p);       // object, dist
-                    if (!((int)head.x < 0 || depth < __uint_as_float(head.y))) continue;
-                    seen = true;
-                    const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-                    unsigned long long *word = a.acc + p * 3;
-                    star_add(word + 0, c.x * w);
-                    star_add(word + 1, c.y * w);
-                    star_add(word + 2, c.z * w);
-                }
-            }
-        }
+// The rocket's record: the ballistic record and a fourth quad, acc.xyz, reserved (64 B a lane, a wave's records 4 KiB in a row).  The
+// object's time window is not looked at (ParticleArgs::dobjs is null and is not read).
+struct RocketSource {
+    static constexpr int kQuads = 4;
+    template <bool THERMAL>
+    static RPT_DEV bool place(const ParticleArgs &a, const rpt_float4 *inv, f4 cam, int, const float4 *q, float xg, float &X, float &Y, float &dist, f3 &c) {
+        return rocket_place<THERMAL>(a, inv, cam, mk3(q[0].x, q[0].y, q[0].z), mk3(q[2].x, q[2].y, q[2].z), mk3(q[3].x, q[3].y, q[3].z), q[1].w, q[2].w, mk3(q[1].x, q[1].y, q[1].z), xg,
+                                     X, Y, dist, c);
     }
-    return seen;
-}
+};
 
-// 1160: rocket_splat<false>.  Rockets seen: a ballot per wave, LDS, one global atomic per workgroup, as 1150.
+// 1160: one lane per record (point_splat, rpt_particles.hip.h), rules 1-6
 __global__ __launch_bounds__(256) void rpt_rockets_splat_kernel(const ParticleArgs a) {
-    __shared__ unsigned int block_seen;
-    const int t = (int)threadIdx.x;
-    if (t == 0) block_seen = 0u;
-    __syncthreads();
-    const bool seen = rocket_splat<false>(a, nullptr, (int)blockIdx.x * 256 + t);
-    const unsigned long long set = __ballot(seen);
-    if ((t & 63) == 0 && set) atomicAdd(&block_seen, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_seen) atomicAdd(a.counts, (unsigned long long)block_seen);
+    splat_and_count(a.counts, [&](int i) { return point_splat<RocketSource, false>(a, nullptr, i); });
 }
 
-// 1162: rocket_splat<true>, T_f for S_f with xg[count] as 1152 reads it (the host has refused a count that is not the set's)
+// 1162: T_f for S_f with xg[count] as 1152 reads it
 __global__ __launch_bounds__(256) void rpt_rockets_thermal_splat_kernel(const ParticleArgs a, const float *xg) {
-    __shared__ unsigned int block_seen;
-    const int t = (int)threadIdx.x;
-    if (t == 0) block_seen = 0u;
-    __syncthreads();
-    const bool seen = rocket_splat<true>(a, xg, (int)blockIdx.x * 256 + t);
-    const unsigned long long set = __ballot(seen);
-    if ((t & 63) == 0 && set) atomicAdd(&block_seen, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_seen) atomicAdd(a.counts, (unsigned long long)block_seen);
+    splat_and_count(a.counts, [&](int i) { return point_splat<RocketSource, true>(a, xg, i); });
 }
 
 }  // namespace rptd

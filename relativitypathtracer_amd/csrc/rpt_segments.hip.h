@@ -2,7 +2,7 @@
 // rest in the rest frame of one object, drawn as a continuum of particles.  A rod is cut into P = pieces equal parts; its P + 1 nodes are
 // placed by the particle pass's rules 1-4 (particle_place<false>, as it stands); between two placed nodes the image is the chord, sampled
 // about once per pixel, every sample splatted as a particle is (kernel 1140, a scatter into the star pass's accumulator), and kernel
-// 1131 resolves.  Included by rpt_api.hip last, behind rpt_thermal.hip.h.  tests/native/segments_oracle.c restates every rule in C.
+// 1131 resolves.  tests/native/segments_oracle.c restates every rule in C.
 #pragma once
 
 #include "rpt_particles.hip.h"
@@ -50,35 +50,14 @@ RPT_DEV void segment_piece(const SegmentArgs &a, float len, float X0, float Y0, 
     o.q = len / (float)o.m;
 }
 
-// Rules S3 and S4 for sample s of a piece: true = at least one tap is inside the frame and passes the depth test.  Every tap is
-// tested against the frame after the wrap and BEFORE its record or its words are addressed (as kernel 1130).
+// Rules S3 and S4 for sample s of a piece: true = at least one tap is inside the frame and passes the depth test (splat_taps)
 RPT_DEV bool segment_sample(const ParticleArgs &a, const SegmentPiece &e, int s) {
     const float u = ((float)s + 0.5f) / (float)e.m;
     const float X = e.X0 + e.dX * u;
     const float Y = e.Y0 + e.dY * u;
     const float dist = e.dist0 + e.ddist * u;
     const f3 c = mk3((e.c0.x + e.dc.x * u) * e.q, (e.c0.y + e.dc.y * u) * e.q, (e.c0.z + e.dc.z * u) * e.q);
-    const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
-    const int x0 = (int)xf, y0 = (int)yf;                // |X|, |Y| < 1e9 + 2 pi W / h_fov + 1024: in range
-    const float fx = X - xf, fy = Y - yf;
-    const float depth = dist - a.depth_bias;
-    bool seen = false;
-    for (int k = 0; k < 4; k++) {
-        int x = x0 + (k & 1);
-        const int y = y0 + (k >> 1);
-        if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
-        if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
-        const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
-        const uint2 head = *reinterpret_cast<const uint2 *>(a.events + p);       // object, dist
-        if (!((int)head.x < 0 || depth < __uint_as_float(head.y))) continue;
-        seen = true;
-        const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-        unsigned long long *word = a.acc + p * 3;
-        star_add(word + 0, c.x * w);
-        star_add(word + 1, c.y * w);
-        star_add(word + 2, c.z * w);
-    }
-    return seen;
+    return splat_taps(a, X, Y, dist, c);
 }
 
 // Rules S0-S2 for global lane g = segment g / P, piece g % P: the three 16-byte loads of the record, the 80 bytes of InvLorentz and
@@ -198,18 +177,13 @@ __global__ __launch_bounds__(256) void rpt_segments_splat_kernel(const SegmentAr
 // The measurement arm of 1140 (librpt_hip_diag.so only; rpt_set_variant 1141): the plain loop, every lane its own piece's m samples.
 // Same rules, same integer sums: the same frame and the same counts, bit for bit (tests/test_gpu_segments.py).
 __global__ __launch_bounds__(256) void rpt_segments_splat_loop_kernel(const SegmentArgs a) {
-    __shared__ unsigned int block_seen;
-    const int t = (int)threadIdx.x;
-    if (t == 0) block_seen = 0u;
-    __syncthreads();
-    SegmentPiece e;
-    segment_lane_piece(a, (int)blockIdx.x * 256 + t, e);
-    bool seen = false;
-    for (int s = 0; s < e.m; s++) seen |= segment_sample(a.p, e, s);
-    const unsigned long long set = __ballot(seen);
-    if ((t & 63) == 0 && set) atomicAdd(&block_seen, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_seen) atomicAdd(a.p.counts, (unsigned long long)block_seen);
+    splat_and_count(a.p.counts, [&](int g) {
+        SegmentPiece e;
+        segment_lane_piece(a, g, e);                     // (every lane: the frame calls the lane function for all of them)
+        bool seen = false;
+        for (int s = 0; s < e.m; s++) seen |= segment_sample(a.p, e, s);
+        return seen;
+    });
 }
 #endif
 

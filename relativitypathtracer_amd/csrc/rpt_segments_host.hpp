@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/rpt.h"
+#include "rpt_particles_host.hpp"
 
 namespace rptg {
 
@@ -44,13 +45,7 @@ inline std::string set_fault(const rpt_segment *segments, int count, int pieces)
     return "";
 }
 
-// the largest object index of a set that has passed set_fault; -1 for an empty one
-inline int largest_object(const rpt_segment *segments, int count) {
-    int largest = -1;
-    for (int i = 0; i < count; i++)
-        if (segments[i].object > largest) largest = segments[i].object;
-    return largest;
-}
+inline int largest_object(const rpt_segment *segments, int count) { return rptp::largest_object_of(segments, count); }
 
 // The set as the device reads it, in the caller's order: ends, indices and colours copied, padding zero
 inline void prepare_set(const rpt_segment *segments, int count, rpt_segment *out) {

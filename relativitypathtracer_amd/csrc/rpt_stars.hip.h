@@ -40,7 +40,7 @@ struct StarResolveArgs {
     float hable_wp[3];
 };
 
-// T_f of rpt_thermal.hip.h, which rpt_api.hip includes last: S_f where xg == 0, Planck's law elsewhere
+// T_f of rpt_thermal.hip.h, which rpt_api.hip includes behind this header: S_f where xg == 0, Planck's law elsewhere
 RPT_DEV f3 thermal_colour(int flags, float D, f3 c, float xg);
 
 // Rule 4 for a unit direction n in the camera's frame, for StarArgs and ParticleArgs alike (the view's fields have the same names in
@@ -89,47 +89,61 @@ RPT_DEV void star_add(unsigned long long *word, float p) {
     if (q != 0ull) (void)__hip_atomic_fetch_add(word, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// 1120: one lane per star.  Two 16-byte loads of its record, rules 1-4 in registers (G and the camera are kernel arguments: scalar
-// loads), then up to twelve 8-byte integer atomic adds that return nothing — the four pixels around (X, Y), three channels each, a pixel's
-// three words 24 consecutive bytes and a row's two pixels 48.  Every tap is tested against the frame after the wrap, so no star, whatever
-// its numbers, addresses a word outside the width * height * 3 of `acc`.  Integer sums do not depend on the order of arrival.
-// Stars with a tap inside the frame: a ballot per wave, the four waves' counts added in LDS, one global atomic per workgroup.
-// Kernel 1122 (rpt_thermal.hip.h) restates this body around star_place<true>: wrapping the body itself in a function template changed
-// this kernel's machine code, templating star_place alone does not (profiles/r22_thermal_kernel_code_diff.txt).
-__global__ __launch_bounds__(256) void rpt_stars_splat_kernel(const StarArgs a) {
-    __shared__ unsigned int block_inside;
+// A splat kernel's frame: `lane` is handed this lane's global index and says whether its source left a tap; the lanes that did are
+// counted by a ballot per wave, the four waves' counts added in LDS, one global atomic per workgroup that has any.  Every lane reaches
+// both barriers: a lane function returns early, the frame does not.
+template <typename Lane>
+RPT_DEV void splat_and_count(unsigned long long *counts, Lane lane) {
+    __shared__ unsigned int block_seen;
     const int t = (int)threadIdx.x;
-    if (t == 0) block_inside = 0u;
+    if (t == 0) block_seen = 0u;
     __syncthreads();
-    const int i = (int)blockIdx.x * 256 + t;
+    const bool seen = lane((int)blockIdx.x * 256 + t);
+    const unsigned long long set = __ballot(seen);
+    if ((t & 63) == 0 && set) atomicAdd(&block_seen, (unsigned int)__popcll(set));
+    __syncthreads();
+    if (t == 0 && block_seen) atomicAdd(counts, (unsigned long long)block_seen);
+}
+
+// One lane of 1120 and 1122: one star.  Two 16-byte loads of its record and, THERMAL, xg[i] — one float per star in the catalogue's
+// order, a wave 256 consecutive bytes; the host launches 1122 only with an array of exactly a.count entries (enqueue_stars refuses
+// another), so i < a.count keeps the load inside it.  Rules 1-4 in registers (G and the camera are kernel arguments: scalar loads), then
+// up to twelve 8-byte integer atomic adds that return nothing — the four pixels around (X, Y), three channels each, a pixel's three
+// words 24 consecutive bytes and a row's two pixels 48.  Every tap is tested against the frame after the wrap, so no star, whatever its
+// numbers, addresses a word outside the width * height * 3 of `acc`.  Integer sums do not depend on the order of arrival.  The taps
+// have no depth test and read no record: they are not splat_taps (rpt_particles.hip.h).  true = a tap is inside the frame.
+template <bool THERMAL>
+RPT_DEV bool star_splat(const StarArgs &a, const float *xg, int i) {
+    if (i >= a.count) return false;
+    const float4 *record = reinterpret_cast<const float4 *>(a.stars + i);
+    const float4 lo = record[0], hi = record[1];         // dir.xyz, rgb.r | rgb.g, rgb.b, padding
+    float x_green = 0.0f;
+    if constexpr (THERMAL) x_green = xg[i];
+    float X, Y;
+    f3 c;
+    if (!star_place<THERMAL>(a, mk3(lo.x, lo.y, lo.z), mk3(lo.w, hi.x, hi.y), x_green, X, Y, c)) return false;
+    const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
+    const int x0 = (int)xf, y0 = (int)yf;                // |X|, |Y| < 1e9: in range
+    const float fx = X - xf, fy = Y - yf;
     bool inside = false;
-    if (i < a.count) {
-        const float4 *record = reinterpret_cast<const float4 *>(a.stars + i);
-        const float4 lo = record[0], hi = record[1];     // dir.xyz, rgb.r | rgb.g, rgb.b, padding
-        float X, Y;
-        f3 c;
-        if (star_place<false>(a, mk3(lo.x, lo.y, lo.z), mk3(lo.w, hi.x, hi.y), 0.0f, X, Y, c)) {
-            const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
-            const int x0 = (int)xf, y0 = (int)yf;        // |X|, |Y| < 1e9: in range
-            const float fx = X - xf, fy = Y - yf;
-            for (int k = 0; k < 4; k++) {
-                int x = x0 + (k & 1);
-                const int y = y0 + (k >> 1);
-                if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
-                if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
-                inside = true;
-                const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-                unsigned long long *word = a.acc + ((size_t)y * (size_t)a.width + (size_t)x) * 3;
-                star_add(word + 0, c.x * w);
-                star_add(word + 1, c.y * w);
-                star_add(word + 2, c.z * w);
-            }
-        }
+    for (int k = 0; k < 4; k++) {
+        int x = x0 + (k & 1);
+        const int y = y0 + (k >> 1);
+        if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
+        if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
+        inside = true;
+        const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+        unsigned long long *word = a.acc + ((size_t)y * (size_t)a.width + (size_t)x) * 3;
+        star_add(word + 0, c.x * w);
+        star_add(word + 1, c.y * w);
+        star_add(word + 2, c.z * w);
     }
-    const unsigned long long set = __ballot(inside);
-    if ((t & 63) == 0 && set) atomicAdd(&block_inside, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_inside) atomicAdd(a.counts, (unsigned long long)block_inside);
+    return inside;
+}
+
+// 1120: star_splat<false> under the frame.  Kernel 1122 (rpt_thermal.hip.h, behind T_f's definition) is star_splat<true>.
+__global__ __launch_bounds__(256) void rpt_stars_splat_kernel(const StarArgs a) {
+    splat_and_count(a.counts, [&](int i) { return star_splat<false>(a, nullptr, i); });
 }
 
 // 1121: one lane per pixel, pixels in memory order (a wave reads 1536 consecutive bytes of the accumulator).  Where a pixel's three sums

@@ -3,9 +3,8 @@
 // follow Planck's law instead of S_f's piecewise-linear spectrum, which is zero beyond its outer knots.  The operator T_f, its exponential
 // and its 1 - e^-z (only + - * /, compares and integer bit operations: no libm, no ocml, contraction off; tests/thermal_cases.py
 // restates them in numpy float32 and rpt_probe which = 8 must match that restatement bit for bit), the probe's kernel, and kernels 1122
-// and 1132: the splats of 1120 and 1130 (rpt_stars.hip.h, rpt_particles.hip.h) around star_place<true> and particle_place<true>, the
-// place functions' thermal instantiations, with one more kernel argument, x_G per source.  Included by rpt_api.hip last, so every kernel
-// before it keeps its place.
+// and 1132: the lanes of 1120 and 1130 (star_splat, rpt_stars.hip.h; point_splat, rpt_particles.hip.h) around star_place<true> and
+// particle_place<true>, the place functions' thermal instantiations, with one more kernel argument, x_G per source.
 #pragma once
 
 #include "rpt_particles.hip.h"
@@ -84,95 +83,14 @@ __global__ __launch_bounds__(256) void rpt_probe_thermal_kernel(const float *in,
     out[3 * (size_t)i + 2] = o.z;
 }
 
-// 1122: kernel 1120 with T_f for S_f — its body line for line around star_place<true>, and one more coalesced load: xg[count], one float
-// per star in the catalogue's order, lane i reads xg[i], a wave 256 consecutive bytes.  The host launches it only with an array of
-// exactly a.count entries (enqueue_stars refuses another), so i < a.count keeps the load inside it.  Taps, clamp, fixed point, atomics
-// and the count are 1120's; kernel 1121 resolves.
+// 1122: kernel 1120 with T_f for S_f and one more coalesced load, xg[i] (star_splat, rpt_stars.hip.h); kernel 1121 resolves
 __global__ __launch_bounds__(256) void rpt_stars_thermal_splat_kernel(const StarArgs a, const float *xg) {
-    __shared__ unsigned int block_inside;
-    const int t = (int)threadIdx.x;
-    if (t == 0) block_inside = 0u;
-    __syncthreads();
-    const int i = (int)blockIdx.x * 256 + t;
-    bool inside = false;
-    if (i < a.count) {
-        const float4 *record = reinterpret_cast<const float4 *>(a.stars + i);
-        const float4 lo = record[0], hi = record[1];     // dir.xyz, rgb.r | rgb.g, rgb.b, padding
-        const float x_green = xg[i];
-        float X, Y;
-        f3 c;
-        if (star_place<true>(a, mk3(lo.x, lo.y, lo.z), mk3(lo.w, hi.x, hi.y), x_green, X, Y, c)) {
-            const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
-            const int x0 = (int)xf, y0 = (int)yf;        // |X|, |Y| < 1e9: in range
-            const float fx = X - xf, fy = Y - yf;
-            for (int k = 0; k < 4; k++) {
-                int x = x0 + (k & 1);
-                const int y = y0 + (k >> 1);
-                if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
-                if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
-                inside = true;
-                const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-                unsigned long long *word = a.acc + ((size_t)y * (size_t)a.width + (size_t)x) * 3;
-                star_add(word + 0, c.x * w);
-                star_add(word + 1, c.y * w);
-                star_add(word + 2, c.z * w);
-            }
-        }
-    }
-    const unsigned long long set = __ballot(inside);
-    if ((t & 63) == 0 && set) atomicAdd(&block_inside, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_inside) atomicAdd(a.counts, (unsigned long long)block_inside);
+    splat_and_count(a.counts, [&](int i) { return star_splat<true>(a, xg, i); });
 }
 
-// 1132: kernel 1130 with T_f for S_f — its body line for line around particle_place<true>, xg[count] as 1122 reads it.  The object
-// index is held against object_count, every tap against the frame before its record is read, as in 1130; kernel 1131 resolves.
+// 1132: kernel 1130 with T_f for S_f, xg[count] as 1122 reads it (point_splat, rpt_particles.hip.h); kernel 1131 resolves
 __global__ __launch_bounds__(256) void rpt_particles_thermal_splat_kernel(const ParticleArgs a, const float *xg) {
-    __shared__ unsigned int block_seen;
-    const int t = (int)threadIdx.x;
-    if (t == 0) block_seen = 0u;
-    __syncthreads();
-    const int i = (int)blockIdx.x * 256 + t;
-    bool seen = false;
-    if (i < a.count) {
-        const float4 *record = reinterpret_cast<const float4 *>(a.particles + i);
-        const float4 lo = record[0], hi = record[1];     // pos.xyz, object | rgb.rgb, padding
-        const float x_green = xg[i];
-        const int object = __float_as_int(lo.w);
-        if (object >= 0 && object < a.object_count) {
-            const rpt_object *L = a.objects + object;
-            rpt_float4 inv[4];
-            for (int k = 0; k < 4; k++) inv[k] = L->InvLorentz[k];
-            const f4 cam = ld4(L->stationaryCam);
-            float X, Y, dist;
-            f3 c;
-            if (particle_place<true>(a, inv, cam, a.dobjs ? a.dobjs + object : nullptr, mk3(lo.x, lo.y, lo.z), mk3(hi.x, hi.y, hi.z), x_green, X, Y, dist, c)) {
-                const float xf = __builtin_floorf(X), yf = __builtin_floorf(Y);
-                const int x0 = (int)xf, y0 = (int)yf;    // |X|, |Y| < 1e9: in range
-                const float fx = X - xf, fy = Y - yf;
-                const float depth = dist - a.depth_bias;
-                for (int k = 0; k < 4; k++) {
-                    int x = x0 + (k & 1);
-                    const int y = y0 + (k >> 1);
-                    if (a.wrap) x = x < 0 ? x + a.width : (x >= a.width ? x - a.width : x);
-                    if (x < 0 || x >= a.width || y < 0 || y >= a.height) continue;
-                    const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
-                    const uint2 head = *reinterpret_cast<const uint2 *>(a.events + p);       // object, dist
-                    if (!((int)head.x < 0 || depth < __uint_as_float(head.y))) continue;
-                    seen = true;
-                    const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-                    unsigned long long *word = a.acc + p * 3;
-                    star_add(word + 0, c.x * w);
-                    star_add(word + 1, c.y * w);
-                    star_add(word + 2, c.z * w);
-                }
-            }
-        }
-    }
-    const unsigned long long set = __ballot(seen);
-    if ((t & 63) == 0 && set) atomicAdd(&block_seen, (unsigned int)__popcll(set));
-    __syncthreads();
-    if (t == 0 && block_seen) atomicAdd(a.counts, (unsigned long long)block_seen);
+    splat_and_count(a.counts, [&](int i) { return point_splat<ParticleSource, true>(a, xg, i); });
 }
 
 }  // namespace rptd

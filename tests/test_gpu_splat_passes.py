@@ -2,7 +2,8 @@
 accumulator and share one host skeleton (csrc/rpt_api.hip), so what is checked here is what only shows with all three together — the
 frame and the tallies are the same whether each call blocks or all are in flight behind one sync; the measurement switches and
 rpt_last_*_ms are each pass's own; a refused launch leaves the accumulator clean and the other passes' tallies alone; lit particles
-change the particle pass and nothing else.  The per-pass files hold each pass's bytes to its C oracle; nothing here restates a rule.
+change the particle pass and nothing else; the options (inverse square, depth bias) of the particles, the segments, the ballistic
+records and the rockets are each pass's own.  The per-pass files hold each pass's bytes to its C oracle; nothing here restates a rule.
 The case is tests/pass_tallies_case.py — the cube of tests/readout_cases.py, pinhole, 67 x 41, which is no multiple of any tile, and
 its 4096 stars — with the particles just in front of surfaces and the lattice of tests/particles_cases.py's crafted set and the rods
 just in front of surfaces, in the frame and in the lattice of tests/segments_cases.py's, built from the device's own records; star and particle temperatures set."""
@@ -11,16 +12,19 @@ import math
 import numpy as np
 import pytest
 
+import ballistics_cases as bc
 import particles_cases as pc
 import pass_tallies_case as case
 import segments_cases as gc
 import stars_cases as sc
+from relativitypathtracer_amd import rockets
 from relativitypathtracer_amd.renderer import RenderError, Renderer
 
 pytestmark = pytest.mark.gpu
 
 W, H = case.SIZE
 PASSES = ("stars", "particles", "segments")
+BIAS = {}                                                # the crafted sets' depth biases, by pass: the fixture fills it
 NOT_TIMED = r"failed \(2\): rpt_last_{0}_ms: the last .* pass was not timed \(rpt_set_{0}_measurement\)"      # RPT_ERR_STATE
 
 
@@ -81,9 +85,9 @@ def blocking():
     bare = r.read_framebuffer().tobytes()
     records = r.render_events().copy()
     objects = pc.scene_objects(scene, case.CAMERA)
-    ps, groups, _ = pc.crafted(records, objects, case.CAMERA, W, H, -1)
+    ps, groups, BIAS["particles"] = pc.crafted(records, objects, case.CAMERA, W, H, -1)
     ps = np.concatenate([ps[groups["near"]], ps[groups["lattice"]]])
-    rods, groups, _ = gc.crafted(records, objects, case.CAMERA, W, H, -1)
+    rods, groups, BIAS["segments"] = gc.crafted(records, objects, case.CAMERA, W, H, -1)
     rods = np.concatenate([rods[groups["near"]][::2], rods[groups["in frame"]], rods[groups["lattice"]]])
     print(f"{len(ps)} particles, {len(rods)} rods")
     assert 200 <= len(ps) <= 1000 and 20 <= len(rods) <= 100
@@ -241,3 +245,56 @@ def test_lighting_changes_the_particle_words_only(blocking):
             assert alone(name, in_flight) == shares[name]
     r.set_particle_lighting()
     assert _run(r) == (plain_frame, plain)
+
+
+OPTION_SETTERS = {"particles": "set_particle_options", "segments": "set_segment_options", "ballistics": "set_ballistic_options", "rockets": "set_rocket_options"}
+
+
+def test_the_options_are_each_passes_own(blocking):
+    """The four passes with options (inverse square, depth bias) keep them in one array of the context: a pass's pair moves its own
+    frame and no other's.  The ballistic records are the fixture's particles at rest in their objects' frames, the rockets those without
+    an acceleration; every pass is rendered alone on a fresh pair of frames, so its bytes and its tally are its share."""
+    r, sets, _, (frame, tallies) = blocking
+    _switch_on(r, sets)
+    records = bc.from_particles(sets[1])
+    r.set_ballistics(records)
+    r.set_rockets(rockets.from_ballistics(records))
+    names = tuple(OPTION_SETTERS)
+    default = (False, 0.0)
+    crafted = {name: (True, BIAS["segments" if name == "segments" else "particles"]) for name in names}
+    assert all(bias > 0.0 for _, bias in crafted.values())
+
+    def set_options(pairs):
+        for name in names:
+            getattr(r, OPTION_SETTERS[name])(*pairs[name])
+
+    def alone(name):
+        _frames(r)
+        getattr(r, f"render_{name}")()
+        return r.read_framebuffer().tobytes(), getattr(r, f"last_{name}")()
+
+    set_options(dict.fromkeys(names, default))
+    plain = {name: alone(name) for name in names}
+    kept = {}
+    for name in names:                                   # one pass with the crafted pair, the other three at their defaults
+        set_options({**dict.fromkeys(names, default), name: crafted[name]})
+        kept[name] = alone(name)
+        print(name, crafted[name], plain[name][1], kept[name][1])
+        assert plain[name][1][0] > 0 and kept[name][0] != plain[name][0]      # (not a dead option)
+    for turn, name in enumerate(names):                  # four different pairs at once, this pass's the crafted one
+        bias = crafted[name][1]
+        others = [(False, 2.0 * bias), (True, 0.0), (False, 0.5 * bias)]
+        rest = [n for n in names if n != name]
+        set_options({name: crafted[name], **{n: others[(k + turn) % 3] for k, n in enumerate(rest)}})
+        assert alone(name) == kept[name]
+    set_options(crafted)                                 # every pass its crafted pair: each as it was with the others at their defaults
+    for name in names:
+        assert alone(name) == kept[name]
+    for name in names:                                   # one pass back to its default: its default frame, the other three unmoved
+        set_options({**crafted, name: default})
+        for other in names:
+            assert alone(other) == (plain if other == name else kept)[other], (name, other)
+    set_options(dict.fromkeys(names, default))
+    r.set_ballistics(None)
+    r.set_rockets(None)
+    assert _run(r) == (frame, tallies)
