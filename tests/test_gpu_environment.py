@@ -176,7 +176,8 @@ def test_helper_hit_pixels_are_the_oracle(env_oracle):
 
 
 def test_helper_lookup_known_answers(env_oracle):
-    """Texel (x, y) is returned unfiltered at u = x / W, v = 1 - y / H; the column neighbour wraps, the row neighbour clamps."""
+    """Texel (x, y) is returned unfiltered at u = x / W, v = 1 - y / H; the column neighbour wraps, the row neighbour clamps; u = 1/2 is +x
+    and u = 3/4 is +z."""
     W, H = 8, 4
     img = sky_image(W, H)
     out = np.zeros((4, 5), dtype=np.float32)
@@ -188,6 +189,14 @@ def test_helper_lookup_known_answers(env_oracle):
     assert np.array_equal(out[1, 2:], (img[2, 4] / np.float32(255)).astype(np.float32))
     assert out[2, 1] == 1.0 and np.array_equal(out[2, 2:], (img[0, 4] / np.float32(255)).astype(np.float32))      # +y: the top row
     assert abs(out[3, 1]) < 1e-7 and np.array_equal(out[3, 2:], (img[3, 4] / np.float32(255)).astype(np.float32))      # -y ((float)(pi/2) / pi > 1/2 by 1.4e-8): v = H clamps to the last row
+    # +-z, which tell the image from its mirror: u = 3/4 is +z (column 6 of 8), u = 1/4 is -z (column 2), each texel unfiltered
+    out = np.zeros((2, 5), dtype=np.float32)
+    d = np.array([[0, 0, 1], [0, 0, -1]], dtype=np.float32)
+    assert env_oracle.rpt_environment_oracle_lookup(d.ctypes.data, 2, img.ctypes.data, W, H, out.ctypes.data) == 0
+    assert out[0, 0] == 0.75 and out[0, 1] == 0.5 and out[1, 0] == 0.25 and out[1, 1] == 0.5
+    assert np.array_equal(out[0, 2:], (img[2, 6] / np.float32(255)).astype(np.float32))
+    assert np.array_equal(out[1, 2:], (img[2, 2] / np.float32(255)).astype(np.float32))
+    assert not np.array_equal(img[2, 6], img[2, 2])
 
 
 # ---- 1. the lookup, bit for bit ----------------------------------------------------------------------------------------------
