@@ -311,7 +311,7 @@ int rpt_orient_matrix(const float lorentz_in[16], const float ypr[3], float lore
  *   3   derived layouts, every object tested for every pixel, 5 waves per SIMD: the NO-CULL escape hatch, and the frame
  *       rpt_verify_frame compares the culled kernels with
  *   41  every wavefront builds its own object mask from per-object image-plane rectangles (computed on the host in
- *       rpt_set_objects) with one lane-parallel test + __ballot, 5 waves per SIMD: what rpt_render_async launches
+ *       rpt_set_objects) with one lane-parallel test + __ballot, 6 waves per SIMD: what rpt_render_async launches
  *   43  41 with the band of tile rows that holds the meshes dispatched first (whole-frame contexts) and the latency form of
  *       the walk: triangle records asked for one iteration ahead, a leaf's first record together with its node record
  *       (a second copy of it, addressable by node index): what the blocking rpt_render launches

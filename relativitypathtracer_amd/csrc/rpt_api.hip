@@ -1084,7 +1084,10 @@ int launch_diagnostic(rpt_ctx *ctx, rptd::KernelArgs &a, dim3 grid, int tiles, i
         break;
     }
     case 40: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_w4, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;      // (kernel 41's body: one wave per workgroup)
-    case 42: hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_w6, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a); break;
+    case 42:      // (kernel 41 as the compiler fits it into six waves: no parking, scratch)
+        if (ctx->geo->exact_rcp_ok) hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_w6, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(rptd::rpt_render_kernel_ballot_ieee_w6, dim3(grid.x * 4, grid.y), dim3(64), 0, ctx->stream, a);
+        break;
     case 141: hipLaunchKernelGGL(rptd::rpt_render_kernel_r02walk_w5, grid, dim3(256), 0, ctx->stream, a); break;
     case 143: hipLaunchKernelGGL(rptd::rpt_render_kernel_r02walk_first_w5, grid, dim3(256), 0, ctx->stream, a); break;
     case 60: case 62: case 63: {

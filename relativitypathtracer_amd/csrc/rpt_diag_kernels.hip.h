@@ -98,7 +98,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 __global__ __launch_bounds__(256) void rpt_render_kernel_primary_only(const KernelArgs a) { render_pixel_body<DiagPolicy<5>>(a); }                                                 // 8
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_v1_masked_w5(const KernelArgs a) { render_pixel_body<DiagPolicy<10>>(a); }    // 26
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void rpt_render_kernel_ballot_w4(const KernelArgs a) { render_pixel_body<Ballot>(a); }        // 40
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_ballot_w6(const KernelArgs a) { render_pixel_body<Ballot>(a); }        // 42
+// 42: kernel 41's policy WITHOUT the parking at the six waves per SIMD kernel 41 runs at — the compiler spills what does not fit (72 B of
+// scratch, 20 dwords) — so that an A/B tells the sixth wave apart from the parking; _ieee: for scenes outside rcp_exact's domain
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_ballot_w6(const KernelArgs a) { render_pixel_body<BallotExact>(a); }   // 42
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_ballot_ieee_w6(const KernelArgs a) { render_pixel_body<Ballot>(a); }   // (42)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_r02walk_w5(const KernelArgs a) { render_pixel_body<DiagPolicy<120>>(a); }      // 141: round 2's walk, natural order
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_r02walk_first_w5(const KernelArgs a) { render_pixel_body<DiagPolicy<123>>(a); } // 143: round 2's walk, mesh band first
 #define RPT_X_KERNEL(N) __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_x##N(const KernelArgs a) { render_pixel_body<DiagPolicy<N>>(a); }

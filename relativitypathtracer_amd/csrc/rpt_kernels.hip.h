@@ -322,6 +322,38 @@ RPT_DEV ExitPlan makeExitPlan(f3 scaledDir) {
     return p;
 }
 
+// The same step for a walk that cannot afford the plan's hoisted face ids (KernelPolicy::park_bystanders: 3 - sx, 5 - sy and 1 - sz are
+// loop invariants, and what a compiler keeps of them across the leaf loop at 80 registers it keeps in scratch).  The three far-plane
+// bits 1 - s travel in ONE register, and the id is formed in the branch that picks it: 2 + bit, 4 + bit, bit — the integers above.
+struct ExitPlanBits { f3 scaledDir, inv_dir; int far_bits; };      // far_bits = (1 - sx) | (1 - sy) << 1 | (1 - sz) << 2
+
+RPT_DEV ExitPlanBits makeExitPlanBits(f3 scaledDir) {
+    const ExitPlan q = makeExitPlan(scaledDir);
+    ExitPlanBits p;
+    p.scaledDir = q.scaledDir;
+    p.inv_dir = q.inv_dir;
+    p.far_bits = (1 - q.sx) | ((1 - q.sy) << 1) | ((1 - q.sz) << 2);
+    return p;
+}
+
+RPT_DEV int getOppositeBoxSide(const ExitPlanBits &p, f3 &uv) {
+    const int bx = p.far_bits & 1, by = (p.far_bits >> 1) & 1, bz = p.far_bits >> 2;
+    const float dx = ((float)bx - uv.x) * p.inv_dir.x;
+    const float dy = ((float)by - uv.y) * p.inv_dir.y;
+    const float dz = ((float)bz - uv.z) * p.inv_dir.z;
+    // (the branches pick two immediates, the axis' first id and its bit's place; 2 + bx written in the branch would be a loop invariant
+    // again and be hoisted like the ids of the form below)
+    float t;
+    int first, place;
+    if (dx < dy) {
+        if (dx < dz) { t = dx; first = 2; place = 0; } else { t = dz; first = 0; place = 2; }
+    } else {
+        if (dy < dz) { t = dy; first = 4; place = 1; } else { t = dz; first = 0; place = 2; }
+    }
+    uv = uv + p.scaledDir * t;
+    return first + ((p.far_bits >> place) & 1);
+}
+
 RPT_DEV int getOppositeBoxSide(const ExitPlan &p, f3 &uv) {
     const float dx = ((float)(1 - p.sx) - uv.x) * p.inv_dir.x;
     const float dy = ((float)(1 - p.sy) - uv.y) * p.inv_dir.y;
@@ -637,10 +669,12 @@ RPT_DEV int descend_to_leaf(const KernelArgs &a, int link, f3 &uv) {
 // after the triangle loop) instead of nb[] and then the neighbour's node record; the "no neighbour" break moves behind that load.
 // The throughput walk takes it; the latency walk does not: there the record arrives a hop before first_tris can be asked for, and
 // kernel 43 lost 10 % on bunny 1080p in flight with it (profiles/r16_exit_hit_ab.txt).
-template <bool LATENCY, bool EXACT_RCP, bool EXITS = (RPT_EXIT_RECORDS != 0) && !LATENCY>
+// FACE_BITS: the exit plan without hoisted face ids (ExitPlanBits above); kernel 41's throughput walk only.
+template <bool LATENCY, bool EXACT_RCP, bool FACE_BITS = false, bool EXITS = (RPT_EXIT_RECORDS != 0) && !LATENCY>
 RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, const Ray &newRay, f3 world_origin,
                          float world_dirlen, Hit &hit) {
     static_assert(!(EXITS && LATENCY), "exit records: the throughput walk only");
+    static_assert(!(FACE_BITS && LATENCY), "the latency walk keeps its plan");
     int curr = root;
     NodeRec rec = load_node_rec<!LATENCY>(a, curr);
     f2 d;
@@ -659,7 +693,8 @@ RPT_DEV bool octree_walk(const KernelArgs &a, const rpt_object &obj, int root, c
         if (!intersect_AABB(nmin, nmax, newRay, d, closeSide, farSide)) return false;
         uv = newRay.origin + newRay.dir * d.x;
     }
-    const ExitPlan plan = makeExitPlan(normalize(newRay.dir / (nmax - nmin)));
+    const f3 planDir = normalize(newRay.dir / (nmax - nmin));
+    const auto plan = [&] { if constexpr (FACE_BITS) return makeExitPlanBits(planDir); else return makeExitPlan(planDir); }();
     bool didHit = false;
     int hitTri = 0;
     TriRec first;
@@ -754,13 +789,16 @@ struct KernelPolicy {
     static constexpr bool doppler = false;       // the Doppler twin (rpt_set_doppler; the arguments are a DopplerArgs)
     static constexpr bool drec = false;          // ... that also writes the per-pixel Doppler record (the debug kernel only)
     static constexpr bool environment = false;   // a pixel that hits nothing looks the sky image up (rpt_set_environment; the arguments are an EnvironmentArgs)
+    static constexpr bool park_bystanders = false;   // kernels 41 and 48 alone: what is live across a shadow walk and not read by it waits in LDS (park_put / park_get), the exit plan keeps no face ids
     static constexpr bool windowed = false;      // every hit, occluder and light is held against its object's time window (rpt_set_object_windows; DObj::win_t0, win_t1)
     static constexpr int diag = 0;               // the measurement arm's number (diagnostics build only); 0 in every product policy
 };
 struct RefLayout : KernelPolicy { static constexpr Walk walk = Walk::reference; static constexpr bool culled = false; };        // 1
 struct Unculled : KernelPolicy { static constexpr bool culled = false; };                                                       // 3, 47
 struct Ballot : KernelPolicy {};                                                                                                // 48, 46, 50, 51
-struct BallotExact : Ballot { static constexpr bool exact_rcp = true; };                                                        // 41
+struct BallotExact : Ballot { static constexpr bool exact_rcp = true; };                                                        // (41's policy but for the parking: 241, 341, 941, ...)
+struct BallotExactParked : BallotExact { static constexpr bool park_bystanders = true; };                                       // 41
+struct BallotParked : Ballot { static constexpr bool park_bystanders = true; };                                                 // 48
 struct BallotFirst : KernelPolicy { static constexpr Walk walk = Walk::latency; static constexpr bool band_first = true; };     // 49
 struct BallotFirstExact : BallotFirst { static constexpr bool exact_rcp = true; };                                              // 43
 struct Analytic : KernelPolicy { static constexpr Walk walk = Walk::none; static constexpr bool tile_bits = false; };           // 44 (no mesh, no bitmap)
@@ -811,7 +849,7 @@ RPT_DEV bool mesh_walk(const KernelArgs &a, const rpt_object &obj, int i, const 
     if constexpr (P::diag != 0) return diag_walk<P::diag>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
 #endif
     if (P::walk == Walk::reference) return octree_core_ref(a, obj, newRay, world_origin, world_dirlen, hit);
-    return octree_walk<P::walk == Walk::latency, P::exact_rcp>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
+    return octree_walk<P::walk == Walk::latency, P::exact_rcp, P::park_bystanders && P::walk == Walk::throughput>(a, obj, a.dobjs[i].root, newRay, world_origin, world_dirlen, hit);
 }
 
 RPT_DEV float max3(f3 v) { return cl_max(cl_max(v.x, v.y), v.z); }   // opencl_kernel.cl:310
@@ -1070,6 +1108,38 @@ RPT_DEV f3 sample_texture(const KernelArgs &a, const rpt_object &ho, f2 huv) {
     return result + result2;
 }
 
+// ---- parking (KernelPolicy::park_bystanders) ---------------------------------------------------------------------
+// A shadow walk reads the shadow ray and the octree; the shading state around it — the hit, its colour, the sum so far, the camera
+// ray — only waits, and at six waves per SIMD (80 registers) it would wait in scratch.  It waits here instead: slot k of lane l is
+// park_lds[k][l], so a wave's 64 lanes touch 64 consecutive words (ds_write_b32 / ds_read_b32 without a bank conflict).  A product
+// workgroup is ONE wave and a lane reads only what it wrote itself: no barrier.  volatile: the values must not be forwarded from store
+// to load in registers, which is the very thing this is for.  Lanes outside the frame have returned before anything is parked.
+// How many: with these 17 the compiler spills nothing; any ONE group below (object, direction, normal + distance, surface colour) may
+// stay in registers and it still spills nothing, any two and it spills a dword — they all wait here, for a margin of one group.  The
+// shadow ray itself (sample_light_occluded's origin, direction and length, live across its occluders) needs no slot.
+// LDS: RPT_PARK_SLOTS x 256 B = 4352 B per workgroup; six waves on each of a CU's four SIMDs are 24 workgroups, 104 448 B of the CU's
+// 163 840 B (160 KB): the registers stay the limit, not the LDS (the occupancy remark reads 6).
+#define RPT_PARK_SLOTS 17
+enum ParkSlot {
+    PARK_HCOLOR = 0,         // 3: the hit's surface colour                                           (trace: across the light loop)
+    PARK_COLOR = 3,          // 3: the sum so far
+    PARK_NORMAL = 6,         // 3: hit.normal
+    PARK_DIST = 9,           // 1: hit.dist
+    PARK_ND = 10,            // 3: the camera ray's unit direction
+    PARK_OBJECT = 13,        // 1: hit.object (its bits)
+    PARK_L3 = 14,            // 3: lightDir3_ObjFrame of the light being sampled                       (trace: across one shadow ray)
+};
+// (the accesses name the LDS address space themselves: a volatile access through a generic pointer stays a flat instruction with a
+// 64-bit address per slot)
+// ONE-WAVE WORKGROUPS ONLY: a slot is indexed by the lane, threadIdx.x & 63, so in a workgroup of several waves the waves would share
+// each other's slots, with no barrier between them.  Every function that parks static_asserts P::one_wave; call these from nowhere else.
+__shared__ float park_lds[RPT_PARK_SLOTS][64];
+typedef volatile __attribute__((address_space(3))) float park_word;
+RPT_DEV void park_put(int k, float v) { *(park_word *)&park_lds[k][threadIdx.x & 63] = v; }
+RPT_DEV float park_get(int k) { return *(park_word *)&park_lds[k][threadIdx.x & 63]; }
+RPT_DEV void park_put3(int k, f3 v) { park_put(k, v.x); park_put(k + 1, v.y); park_put(k + 2, v.z); }
+RPT_DEV f3 park_get3(int k) { const float x = park_get(k), y = park_get(k + 1), z = park_get(k + 2); return mk3(x, y, z); }
+
 // opencl_kernel.cl:488-545: true when something other than the light blocks the segment
 template <class P>
 RPT_DEV bool sample_light_occluded(const KernelArgs &a, f4 origin4, f4 dir4, float lightDist, int lightIndex) {
@@ -1192,6 +1262,55 @@ struct DopplerRecord {
     f3 ref, lit;             // the reference's colour (no Doppler); the colour after the light factors, before S(D_cam)
 };
 
+// trace()'s light loop for KernelPolicy::park_bystanders: the same operations on the same inputs in the same order, with every value
+// that outlives a shadow ray kept in LDS.  What is a pure function of parked values — ndotl, the unit light direction, the falloff's
+// length and self-dot — is formed again after the shadow ray from the parked lightDir3_ObjFrame and normal: the same bits.
+template <class P>
+RPT_DEV f3 trace_lights_parked(const KernelArgs &a, f3 nd, const Hit &hit, f3 hcolor, f3 color) {
+    static_assert(!P::doppler && !P::windowed && !P::drec && P::one_wave, "parking: kernel 41's policy only");
+    park_put3(PARK_HCOLOR, hcolor);
+    park_put3(PARK_COLOR, color);
+    park_put3(PARK_NORMAL, hit.normal);
+    park_put(PARK_DIST, hit.dist);
+    park_put3(PARK_ND, nd);
+    park_put(PARK_OBJECT, __int_as_float(hit.object));
+    for (int i = 0; i < a.object_count; i++) {
+        const int object = __float_as_int(park_get(PARK_OBJECT));
+        if (i != object && a.objects[i].light) {
+            const rpt_object &ho = a.objects[object];
+            const rpt_object &lo = a.objects[i];
+            const f3 normal = park_get3(PARK_NORMAL), d3 = park_get3(PARK_ND);
+            const f4 rayDir = mk4((float)a.interval, d3.x, d3.y, d3.z);
+            const f4 cameraPos_ObjFrame = ld4(ho.stationaryCam);
+            const f4 rayDir_ObjFrame = transformPoint4D(ho.Lorentz, rayDir);
+            f4 hitPos_ObjFrame = cameraPos_ObjFrame + rayDir_ObjFrame * park_get(PARK_DIST);
+            hitPos_ObjFrame = hitPos_ObjFrame + mk4(0, normal.x * 0.001f, normal.y * 0.001f, normal.z * 0.001f);
+            const f4 hitPos = transformPoint4D(ho.InvLorentz, hitPos_ObjFrame);
+            const f4 hitPos_LightFrame = transformPoint4D(lo.Lorentz, hitPos);
+            const f3 lightPos3_LightFrame = mk3(lo.M[0].w, lo.M[1].w, lo.M[2].w);
+            const f3 lightDir3_LightFrame = lightPos3_LightFrame - yzw(hitPos_LightFrame);
+            const f4 lightDir_LightFrame = mk4(a.interval * length(lightDir3_LightFrame), lightDir3_LightFrame.x,
+                                               lightDir3_LightFrame.y, lightDir3_LightFrame.z);
+            const f4 lightDir = transformPoint4D(lo.InvLorentz, lightDir_LightFrame);
+            const f4 lightDir_ObjFrame = transformPoint4D(ho.Lorentz, lightDir);
+            const f3 lightDir3_ObjFrame = yzw(lightDir_ObjFrame);
+            if (dot(normal, normalize(lightDir3_ObjFrame)) > 0) {
+                park_put3(PARK_L3, lightDir3_ObjFrame);
+                const f3 ld = normalize(yzw(lightDir));
+                const f4 shadowDir = mk4((float)a.interval, ld.x, ld.y, ld.z);
+                if (!sample_light_occluded<P>(a, hitPos, shadowDir, length(yzw(lightDir)), i)) {
+                    const f3 l3 = park_get3(PARK_L3);
+                    const float ndotl = dot(park_get3(PARK_NORMAL), normalize(l3));
+                    const float k = ndotl / (1.0f + 0.1f * length(l3) + 0.01f * dot(l3, l3));
+                    const f3 sum = park_get3(PARK_COLOR) + park_get3(PARK_HCOLOR) * k * ld3(lo.color);
+                    park_put3(PARK_COLOR, sum);
+                }
+            }
+        }
+    }
+    return park_get3(PARK_COLOR);
+}
+
 // opencl_kernel.cl:361-486 + 548-604: closest hit over the object list, surface colour, lights
 // Returns false (and leaves `color` untouched) when the ray hits nothing: the caller then uses the
 // per-frame background constants instead of tonemapping (0.15,0.15,0.25) again for every pixel.
@@ -1249,7 +1368,9 @@ RPT_DEV bool trace(const KernelArgs &a, f3 camdir, unsigned long long object_mas
     [[maybe_unused]] f3 color_ref = color;       // (P::drec only) the same sum with the reference's light colours
     [[maybe_unused]] float dlight = 1.0f;
     [[maybe_unused]] bool lit_any = false;
-    if (a.interval != 0) {
+    if constexpr (P::park_bystanders) {
+        if (a.interval != 0) color = trace_lights_parked<P>(a, nd, hit, hcolor, color);
+    } else if (a.interval != 0) {
         for (int i = 0; i < a.object_count; i++) {
             if (i != hit.object && a.objects[i].light) {
                 const rpt_object &lo = a.objects[i];
@@ -1731,13 +1852,16 @@ RPT_DEV void events_pixel_body(const EventArgs &a) {
 // Product kernels (rpt_set_variant; the number in the comment is the variant).
 __global__ __launch_bounds__(64) void rpt_render_kernel_v0(const KernelArgs a) { render_pixel_body<RefLayout>(a); }                                                              // 1: any valid octree
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_unculled_w5(const KernelArgs a) { render_pixel_body<Unculled>(a); }         // 3: no cull (rpt_verify_frame; the escape hatch)
-// the wave's object mask from the per-object screen rectangles by lane-parallel test + __ballot, 5 waves per SIMD (96 VGPRs, 8 B of scratch outside the loops)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_w5(const KernelArgs a) { render_pixel_body<BallotExact>(a); }          // 41 = rpt_render_async
+// the wave's object mask from the per-object screen rectangles by lane-parallel test + __ballot; SIX waves per SIMD without scratch: the
+// shading state waits in LDS across the shadow walks (BallotExactParked).  The name's suffix is history: bench.py and
+// the counter summaries are keyed by it.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_ballot_w5(const KernelArgs a) { render_pixel_body<BallotExactParked>(a); }    // 41 = rpt_render_async
 // the same with the tile rows that hold the meshes dispatched first and the latency walk (44 B of scratch): latency, not throughput
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_w5(const KernelArgs a) { render_pixel_body<BallotFirstExact>(a); }    // 43 = the blocking rpt_render; rpt_render_async below RPT_LATENCY_KERNEL_MAX_PIXELS
 // 41 and 43 above take the triangle test's 1 / det through rcp_exact (BallotExact / BallotFirstExact); these two keep the IEEE division, for scenes
 // outside rcp_exact's domain (rpt_scene_exact_rcp) and as variants 48 / 49
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_ieee_w5(const KernelArgs a) { render_pixel_body<Ballot>(a); }        // 48 (and 41 outside the domain)
+// (48 goes with 41: six waves per SIMD and the parking, 80 registers and no scratch where five waves had 12 B; 49 stays what it was)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void rpt_render_kernel_ballot_ieee_w5(const KernelArgs a) { render_pixel_body<BallotParked>(a); }  // 48 (and 41 outside the domain)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rpt_render_kernel_ballot_first_ieee_w5(const KernelArgs a) { render_pixel_body<BallotFirst>(a); }  // 49 (and 43 outside the domain)
 // without the octree walk compiled in, for frames whose Object[] holds no mesh: 61 VGPRs, no scratch, EIGHT waves per SIMD
 // (arch 1080p 0.0370 -> 0.0301 ms per frame in flight, cubes.txt 4K 0.0898 -> 0.0725)
@@ -1746,7 +1870,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 // The sky fill of a split frame (rpt_api.hip: launch): every pixel of the frame OUTSIDE the object box, written as the
 // render kernels write a pixel whose wave's object mask is empty — {(float)x, (float)y, bg_packed, 0}, store_pixel's non-temporal
 // 16-byte store — by a kernel that reads no scene memory (its arguments are all it knows) and needs a dozen registers, so that its waves
-// fit into the registers and the wave slots five walkers leave free on a SIMD.  The render kernels then run over the box alone.
+// fit into the registers and the wave slots the walkers leave free on a SIMD (six walkers at 80 registers: 32 registers and two slots,
+// two waves of the fill's 16; five at 96 left 32 and three).  The render kernels then run over the box alone.
 // One wave per row of RPT_SKY_FILL_TILES 8x8 tiles: lane -> pixel of a tile row by row, as in the render kernels, so each store
 // instruction of a wave is eight full 128-byte lines, and a wave's stores run along 64 x 16 B = 1 KB of each of its eight pixel rows.
 // The box is whole tiles and every test of it is wave-uniform; a pixel beyond the frame's right or lower edge is never written.
