@@ -3,7 +3,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/rpt_render_main.cpp -o rpt_render \
 //       -Lrelativitypathtracer_amd -lrpt_hip -lrpt_scene -Wl,-rpath,$PWD/relativitypathtracer_amd
-//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--rockets SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] [--rocket-temperatures FILE] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
+//   ./rpt_render [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--rockets SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] [--rocket-temperatures FILE] [--glare SPEC] 1920 1080 out.ppm [vx vy vz t [frames in_flight]] < assets/reference/Scenes/shadows.txt
 //
 // --yaw / --pitch / --roll turn the camera and --fov sets the pinhole's vertical field of view, all in degrees (rpt_set_orientation,
 // rpt_set_field_of_view; not in the reference, whose camera looks down +z through a 90-degree lens).  Both are settings of the render
@@ -68,6 +68,10 @@
 // thermal sources (rpt_set_star_temperatures, rpt_set_particle_temperatures; not in the reference): FILE holds raw float32 kelvin, one per
 // record of the other file in its order, 0 for a source that is none; under --doppler shift or both such a source is shifted as a
 // blackbody and is never moved out of the visible band.
+//
+// --glare W:SIGMA[,W:SIGMA[,W:SIGMA]] gives every point-source pass above a point-spread function (rpt_set_glare; not in the reference):
+// up to three Gaussian layers, each carrying the share W (> 0; together at most 1) of a source's flux over SIGMA pixels (0.5 .. 32/3),
+// so that a brighter source looks bigger.  Without a pass it spreads it does nothing.
 //
 // A scene with `dRATE,OFFSET,DIGITS,DECIMALS[,U0,V0,U1,V1]` commands gets its displays drawn too (rpt_set_readouts, rpt_render_readouts;
 // not in the reference): seven-segment digits on those objects that show their own time, after the overlay, before the picture is written.
@@ -246,6 +250,48 @@ static bool parse_particles(const char *noun, const char *spec, std::string *pat
     return true;
 }
 
+// --glare W:SIGMA[,W:SIGMA[,W:SIGMA]]: the layers; false (and a message) for what it cannot read or rpt_set_glare would refuse
+static bool parse_glare(const char *spec, rpt_glare *glare) {
+    std::memset(glare, 0, sizeof *glare);
+    const std::string s(spec);
+    double total = 0.0;
+    size_t at = 0;
+    while (true) {
+        const size_t next = s.find(',', at);
+        const std::string layer = s.substr(at, next == std::string::npos ? std::string::npos : next - at);
+        if (glare->layers == RPT_GLARE_LAYERS_MAX) {
+            std::fprintf(stderr, "--glare: '%s' has more than %d layers\n", spec, RPT_GLARE_LAYERS_MAX);
+            return false;
+        }
+        char *end = nullptr;
+        const double w = std::strtod(layer.c_str(), &end);
+        if (end == layer.c_str() || *end != ':' || !(w > 0.0) || !(w <= 1.0)) {
+            std::fprintf(stderr, "--glare: '%s' in '%s' is not W:SIGMA with a weight in (0, 1]\n", layer.c_str(), spec);
+            return false;
+        }
+        const char *sigma_text = end + 1;
+        const double sigma = std::strtod(sigma_text, &end);
+        if (end == sigma_text || *end != '\0' || !(sigma >= 0.5) || !(sigma <= 32.0 / 3.0)) {
+            std::fprintf(stderr, "--glare: '%s' in '%s' is not W:SIGMA with a sigma in [0.5, 32/3] pixels\n", layer.c_str(), spec);
+            return false;
+        }
+        glare->weight[glare->layers] = w;
+        glare->sigma[glare->layers] = sigma;
+        glare->layers++;
+        total += std::floor(w * 65536.0 + 0.5);
+        if (next == std::string::npos) break;
+        at = next + 1;
+    }
+    if (total > 65536.0) {
+        std::fprintf(stderr, "--glare: the weights of '%s' sum to more than 1\n", spec);
+        return false;
+    }
+    std::fprintf(stderr, "glare: %d layers", glare->layers);
+    for (int k = 0; k < glare->layers; k++) std::fprintf(stderr, "%s weight %g sigma %g", k ? ";" : ",", glare->weight[k], glare->sigma[k]);
+    std::fprintf(stderr, "\n");
+    return true;
+}
+
 // --segments FILE[:inverse_square][:bias=B][:pieces=N]: the file name, the flags, the bias and the pieces; false (and a message) for
 // what it cannot read
 static bool parse_segments(const char *spec, std::string *path, int *flags, float *bias, int *pieces) {
@@ -311,6 +357,8 @@ int main(int argc, char **argv) {
     int segment_flags = 0, segment_pieces = 16;
     float segment_bias = 0.0f;
     int aa_n = 1, aa_threshold = 8;
+    rpt_glare glare;                                             // --glare
+    std::memset(&glare, 0, sizeof glare);
     rpt_overlay_desc overlay;
     std::memset(&overlay, 0, sizeof overlay);
     {
@@ -374,6 +422,12 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "--rockets needs a value: FILE[:inverse_square][:bias=B] (raw 64-byte rpt_rocket records)\n");
                 return 2;
             }
+            else if (has_value && !std::strcmp(argv[i], "--glare")) {
+                if (!parse_glare(argv[++i], &glare)) return 2;
+            } else if (!std::strcmp(argv[i], "--glare")) {
+                std::fprintf(stderr, "--glare needs a value: W:SIGMA[,W:SIGMA[,W:SIGMA]] (weights > 0 that sum to at most 1, sigmas of 0.5 .. 32/3 pixels)\n");
+                return 2;
+            }
             else if (has_value && !std::strcmp(argv[i], "--particles")) {
                 if (!parse_particles("particles", argv[++i], &particles_path, &particle_flags, &particle_bias)) return 2;
             } else if (!std::strcmp(argv[i], "--particles")) {
@@ -413,7 +467,7 @@ int main(int argc, char **argv) {
         argc = kept;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--rockets SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] [--rocket-temperatures FILE] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--yaw D] [--pitch D] [--roll D] [--fov D] [--projection SPEC] [--aa N[:T]] [--events FILE] [--overlay SPEC] [--stars FILE] [--particles SPEC] [--segments SPEC] [--ballistics SPEC] [--rockets SPEC] [--particle-lighting SPEC] [--doppler SPEC] [--star-temperatures FILE] [--particle-temperatures FILE] [--ballistic-temperatures FILE] [--rocket-temperatures FILE] [--glare SPEC] width height out.ppm [vx vy vz t [frames in_flight]] < scene.txt\n", argv[0]);
         return 2;
     }
     const int width = std::atoi(argv[1]), height = std::atoi(argv[2]);
@@ -605,6 +659,10 @@ int main(int argc, char **argv) {
         last = ring.newest();
         std::fprintf(stderr, "%d frames, %d in flight: %.4f ms/frame, %.0f Mrays/s (%d presented while rendering)\n", frames,
                      ring.frames_in_flight(), sec / frames * 1e3, (double)width * height * frames / sec / 1e6, presented);
+    }
+    if (glare.layers != 0 && rpt_set_glare(last, &glare) != RPT_OK) {       // every pass below spreads its sources
+        std::fprintf(stderr, "glare: %s\n", rpt_last_error(last));
+        return 1;
     }
     bool events_rendered = false;
     if (!catalogue.empty()) {                                    // stars on that frame's sky, at rest in the scene's frame

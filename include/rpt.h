@@ -982,6 +982,29 @@ int rpt_read_counters(rpt_ctx *ctx, unsigned long long out[16]);
  * wave w = (blockIdx.y*gridDim.x + blockIdx.x)*4 + wave-in-block. */
 int rpt_read_wave_times(rpt_ctx *ctx, unsigned long long *out, size_t max_words, size_t *words);
 
+/* Opt-in glare (not in the reference): a linear point-spread function for the point-source passes.  While a descriptor
+ * is set, rpt_render_stars, _particles, _segments, _ballistics and _rockets convolve their fixed-point accumulator with it, in exact
+ * integer arithmetic, between the splat and the resolve (kernels 1170 and 1171 in place of 1121 / 1131), so that a brighter source
+ * looks bigger: more of its tail clears the display's floor.  Up to RPT_GLARE_LAYERS_MAX separable Gaussian layers (weight, sigma);
+ * sigma in pixels, in [0.5, 32/3]; every weight > 0; the weights become w_k = floor(weight_k 65536 + 0.5) and the core — the source's own
+ * pixel — keeps w_0 = 65536 - sum w_k, which must not be negative.  rpt_set_glare refuses a NaN, a weight <= 0, a sigma out of range, a
+ * negative core and a layer count outside 0 .. RPT_GLARE_LAYERS_MAX; a null descriptor or 0 layers switches glare off (the default), and
+ * a context without glare launches exactly the kernels it launched before and gives the same bytes.  Glare acts at each pass's own
+ * resolve on that pass's sources only, in pixel space (in a panorama it is stretched towards the poles and does not cross them; across
+ * the seam of a full circle it wraps), and flux that falls outside the frame is lost.  It adds no refusal at a launch.
+ * rpt_glare_taps is host code and touches no device: the 2 radius + 1 integer taps of one layer, radius = min(32, ceil(3 sigma)),
+ * t[j] = floor(65536 g_j / sum g + 0.5) off the centre with g_j = exp(-j^2 / (2 sigma^2)) in double, the centre tap what is left of 65536.
+ * taps65_out[RPT_GLARE_RADIUS_MAX + j] is t[j] for |j| <= radius, 0 beyond.  RPT_ERR_ARG for a sigma outside [0.5, 32/3] or a null. */
+#define RPT_GLARE_LAYERS_MAX 3
+#define RPT_GLARE_RADIUS_MAX 32
+typedef struct rpt_glare {
+    int layers;                                 /* 0 .. RPT_GLARE_LAYERS_MAX; 0 = off */
+    double weight[RPT_GLARE_LAYERS_MAX];        /* doubles: the integers of rules G0 and G1 are formed from exactly what the caller wrote */
+    double sigma[RPT_GLARE_LAYERS_MAX];
+} rpt_glare;
+int rpt_set_glare(rpt_ctx *ctx, const rpt_glare *desc_or_null);
+int rpt_glare_taps(double sigma, unsigned int taps65_out[2 * RPT_GLARE_RADIUS_MAX + 1], int *radius_out);
+
 /* GPU octree build (replaces Mesh::GenerateOctree, Mesh.cpp:5-28, and Subdivide, Octree.cpp:171-248): builds the
  * octree of the mesh whose triangles start at word `first_triangle_word` of `triangles` (the root lists every
  * triangle imported so far, as the reference's does).  All levels run on the device in one submission on the context's

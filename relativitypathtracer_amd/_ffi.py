@@ -82,6 +82,11 @@ class Rocket(C.Structure):
                 ("acc", C.c_float * 3), ("reserved", C.c_float)]
 
 
+class Glare(C.Structure):
+    """rpt_glare of include/rpt.h (56 B): the layers of the point-source passes' glare, (weight, sigma) in doubles."""
+    _fields_ = [("layers", C.c_int), ("weight", C.c_double * 3), ("sigma", C.c_double * 3)]
+
+
 class SceneDesc(C.Structure):
     """rpt_scene_desc — the eight scene arrays as {pointer, count} pairs."""
     _fields_ = [
@@ -295,6 +300,8 @@ HIP_SYMBOLS = {
     "rpt_last_rockets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rpt_set_rockets_measurement": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_last_rockets_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rpt_set_glare": (C.c_int, [C.c_void_p, C.POINTER(Glare)]),
+    "rpt_glare_taps": (C.c_int, [C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "rpt_version": (C.c_char_p, []),
 }
 

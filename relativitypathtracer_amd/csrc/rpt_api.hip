@@ -40,6 +40,7 @@
 #include "rpt_ballistics_host.hpp"
 #include "rpt_rockets.hip.h"
 #include "rpt_rockets_host.hpp"
+#include "rpt_glare.hip.h"          /* the opt-in glare stage between a splat pass's splat and its resolve: kernels 1170 and 1171 */
 
 #pragma clang fp contract(off)
 
@@ -285,6 +286,13 @@ struct rpt_ctx {
     // one context are ordered by its stream
     SplatPass splat[SPLAT_COUNT];
     DeviceBuffer splat_acc;                           // 24 B per pixel of the largest frame so far: the fixed-point sums, all zero outside a pass
+    // rpt_set_glare (not in the reference): the integers of rules G0 and G1 as kernels 1170 and 1171 take them, and the
+    // planes of h_k beside splat_acc, reserved at the first glared pass.  Per context, never shared
+    int glare_layers = 0;                             // 0: off, and a splat pass launches its own resolve kernel
+    unsigned int glare_weight[1 + RPT_GLARE_LAYERS_MAX] = {65536u, 0u, 0u, 0u};
+    int glare_radius[RPT_GLARE_LAYERS_MAX] = {0, 0, 0};
+    unsigned int glare_taps[RPT_GLARE_LAYERS_MAX][RPT_GLARE_RADIUS_MAX + 1] = {};
+    DeviceBuffer glare_planes;                        // layers x 24 B per pixel of the largest glared frame so far; 1170 writes every word 1171 reads
     int particle_lighting = 0;                        // rpt_set_particle_lighting: RPT_PARTICLES_LIT | _SHADOWED | _AMBIENT
     int segment_pieces = rptg::kDefaultPieces;        // rpt_set_segment_options
     // the tile bitmaps of the still meshes (rpt_tile_bitmap.hpp): slot i = object i, bitmap_words() dwords each; per context, never shared
@@ -2113,6 +2121,17 @@ int accumulator_ready(rpt_ctx *ctx, size_t pixels) {
     return RPT_OK;
 }
 
+// The planes of a glared pass, `layers` of 24 B per pixel.  They need no zeroing: kernel 1170 writes every word of the frame's planes
+// before kernel 1171 reads any
+int glare_planes_ready(rpt_ctx *ctx, size_t pixels) {
+    const size_t bytes = pixels * 3 * sizeof(unsigned long long) * (size_t)ctx->glare_layers;
+    if (bytes > ctx->glare_planes.capacity || !ctx->glare_planes.ptr) {
+        RPT_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (a pass in flight may still use the old ones)
+        if (int rc = reserve(ctx, ctx->glare_planes, bytes)) return rc;
+    }
+    return RPT_OK;
+}
+
 // The refusals the splat passes share, `call` naming the pass and `noun` what it projects: a caller's ray map (all three); and for a
 // pass whose records ride objects an interval the light cone has no closed form for, and a set that names an object beyond Object[] —
 // what keeps every index the splat follows inside it.  Like all of a pass's refusals they come before anything touches the device.
@@ -2157,12 +2176,16 @@ void splat_view(const rpt_ctx *ctx, Args &a) {
 
 // What follows a splat pass's refusals, once for the three: the accumulator, the tally's `words`, the marks of a timed pass, the tally
 // zeroed, `splat` — the pass's own launch, handed the accumulator and the tally's words for its arguments — and the resolve, kernel
-// `resolve` with `b`: the caller has set what is its kernel's alone (1121's records), the rest is filled here.
+// `resolve` with `b`: the caller has set what is its kernel's alone (1121's records), the rest is filled here.  With rpt_set_glare the
+// planes are made ready behind the accumulator, and kernels 1170 and 1171 (rpt_glare.hip.h) stand in the resolve's place, between the
+// same two marks: `wrap` is the splat's, and the star pass's records are the mask of rule G2.
 template <typename ResolveArgs, typename Splat>
 int enqueue_splat(rpt_ctx *ctx, int which, Tally &tally, size_t words, rpt_pixel *out16, const void *resolve, ResolveArgs &b, Splat splat) {
     SplatPass &p = ctx->splat[which];
     const size_t pixels = (size_t)ctx->width * (size_t)ctx->height;
     if (int rc = accumulator_ready(ctx, pixels)) return rc;
+    if (ctx->glare_layers != 0)
+        if (int rc = glare_planes_ready(ctx, pixels)) return rc;
     if (int rc = tally_ready(ctx, tally, words)) return rc;
     if (p.timed)
         for (hipEvent_t &m : p.marks)
@@ -2179,8 +2202,33 @@ int enqueue_splat(rpt_ctx *ctx, int which, Tally &tally, size_t words, rpt_pixel
     splat(b.acc, b.counts);
     RPT_HIP(ctx, hipGetLastError());
     if (p.timed) RPT_HIP(ctx, hipEventRecord(p.marks[1], ctx->stream));
-    void *resolve_args[] = {(void *)&b};
-    (void)hipLaunchKernel(resolve, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
+    if (ctx->glare_layers != 0) {
+        rptd::GlareArgs g;
+        std::memset((void *)&g, 0, sizeof g);
+        g.acc = b.acc;
+        g.planes = (unsigned long long *)ctx->glare_planes.ptr;
+        if constexpr (std::is_same<ResolveArgs, rptd::StarResolveArgs>::value) g.events = b.events;
+        g.out16 = out16;
+        g.counts = b.counts;
+        g.pixels = pixels;
+        g.width = ctx->width;
+        g.height = ctx->height;
+        g.wrap = ctx->projection == RPT_PROJECTION_EQUIRECT && ctx->projection_params[0] == (float)(2.0 * RPT_PI_D) ? 1 : 0;     // (splat_view's)
+        g.layers = ctx->glare_layers;
+        std::memcpy(g.hable_wp, b.hable_wp, sizeof g.hable_wp);
+        std::memcpy(g.weight, ctx->glare_weight, sizeof g.weight);
+        std::memcpy(g.radius, ctx->glare_radius, sizeof g.radius);
+        std::memcpy(g.taps, ctx->glare_taps, sizeof g.taps);
+        void *glare_args[] = {(void *)&g};
+        const dim3 segments((unsigned)((ctx->width + RPT_GLARE_SEGMENT - 1) / RPT_GLARE_SEGMENT), (unsigned)ctx->height);
+        (void)hipLaunchKernel((const void *)rptd::rpt_glare_rows_kernel, segments, dim3(RPT_GLARE_SEGMENT), glare_args, 0, ctx->stream);
+        RPT_HIP(ctx, hipGetLastError());
+        const dim3 tiles((unsigned)((ctx->width + RPT_GLARE_TILE - 1) / RPT_GLARE_TILE), (unsigned)((ctx->height + RPT_GLARE_TILE - 1) / RPT_GLARE_TILE));
+        (void)hipLaunchKernel((const void *)rptd::rpt_glare_columns_kernel, tiles, dim3(RPT_GLARE_TILE * RPT_GLARE_TILE), glare_args, 0, ctx->stream);
+    } else {
+        void *resolve_args[] = {(void *)&b};
+        (void)hipLaunchKernel(resolve, dim3((unsigned)((pixels + 255) / 256)), dim3(256), resolve_args, 0, ctx->stream);
+    }
     RPT_HIP(ctx, hipGetLastError());
     if (p.timed) RPT_HIP(ctx, hipEventRecord(p.marks[2], ctx->stream));
     p.marked = p.timed;
@@ -2525,7 +2573,7 @@ void rpt_destroy(rpt_ctx *ctx) {
                 ctx->host_us[4] / ctx->host_calls, ctx->host_us[5] / ctx->host_calls);
 #endif
     ctx->geo.reset();
-    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->splat_acc})
+    for (DeviceBuffer *b : {&ctx->objects, &ctx->dobjs, &ctx->counters, &ctx->wave_times, &ctx->tile_masks, &ctx->claim_counters, &ctx->verify_planes, &ctx->owned_out, &ctx->owned_plane, &ctx->owned_rgb, &ctx->owned_doppler, &ctx->owned_events, &ctx->aa_plane, &ctx->splat_acc, &ctx->glare_planes})
         release(*b);
     if (ctx->pinned_objects) (void)hipHostFree(ctx->pinned_objects);
     for (StagedUpload *u : {&ctx->pano.upload, &ctx->aa_pano.upload, &ctx->env, &ctx->tile_bits, &ctx->raymap, &ctx->readout_table}) release(*u);
@@ -3553,6 +3601,59 @@ int rpt_last_stars(rpt_ctx *ctx, unsigned long long out[2]) { return tally_read(
 
 int rpt_set_stars_measurement(rpt_ctx *ctx, int timed) { return set_splat_measurement(ctx, SPLAT_STARS, timed); }
 int rpt_last_stars_ms(rpt_ctx *ctx, float ms[2]) { return last_splat_ms(ctx, SPLAT_STARS, ms, "stars", "star-field"); }
+
+// Glare.  rpt_glare_taps: rule G1, host code, no device.  The off-centre taps are rounded from the normalised Gaussian
+// in double; the centre tap is what is left of 65536, so the taps sum to it exactly.
+int rpt_glare_taps(double sigma, unsigned int taps65_out[2 * RPT_GLARE_RADIUS_MAX + 1], int *radius_out) {
+    if (!taps65_out || !radius_out || !(sigma >= 0.5) || !(sigma <= 32.0 / 3.0)) return RPT_ERR_ARG;
+    const double r = std::ceil(3.0 * sigma);
+    const int R = r < (double)RPT_GLARE_RADIUS_MAX ? (int)r : RPT_GLARE_RADIUS_MAX;
+    double g[RPT_GLARE_RADIUS_MAX + 1], sum = 0.0;
+    for (int j = 0; j <= R; j++) g[j] = std::exp(-(double)(j * j) / (2.0 * sigma * sigma));
+    for (int j = -R; j <= R; j++) sum += g[j < 0 ? -j : j];
+    for (int k = 0; k < 2 * RPT_GLARE_RADIUS_MAX + 1; k++) taps65_out[k] = 0u;
+    unsigned int off_centre = 0u;
+    for (int j = 1; j <= R; j++) {
+        const unsigned int t = (unsigned int)std::floor(65536.0 * g[j] / sum + 0.5);
+        taps65_out[RPT_GLARE_RADIUS_MAX + j] = taps65_out[RPT_GLARE_RADIUS_MAX - j] = t;
+        off_centre += 2u * t;
+    }
+    taps65_out[RPT_GLARE_RADIUS_MAX] = 65536u - off_centre;      // (no underflow: the off-centre taps sum to less than 65536 (1 - g_0 / sum) + R)
+    *radius_out = R;
+    return RPT_OK;
+}
+
+// Rule G0.  Nothing touches the device: the integers ride in the arguments of kernels 1170 and 1171 from the next pass on
+int rpt_set_glare(rpt_ctx *ctx, const rpt_glare *desc_or_null) {
+    if (!ctx) return RPT_ERR_ARG;
+    if (!desc_or_null || desc_or_null->layers == 0) {
+        ctx->glare_layers = 0;
+        return RPT_OK;
+    }
+    const rpt_glare &d = *desc_or_null;
+    if (d.layers < 0 || d.layers > RPT_GLARE_LAYERS_MAX)
+        return fail(ctx, RPT_ERR_ARG, "rpt_set_glare: " + std::to_string(d.layers) + " layers; there are 0 .. " + std::to_string(RPT_GLARE_LAYERS_MAX));
+    unsigned int weight[1 + RPT_GLARE_LAYERS_MAX] = {0u, 0u, 0u, 0u}, taps[RPT_GLARE_LAYERS_MAX][2 * RPT_GLARE_RADIUS_MAX + 1];
+    int radius[RPT_GLARE_LAYERS_MAX] = {0, 0, 0};
+    long long core = 65536;
+    for (int k = 0; k < d.layers; k++) {
+        const std::string layer = "rpt_set_glare: layer " + std::to_string(k);
+        if (!(d.weight[k] > 0.0) || !(d.weight[k] <= 1.0)) return fail(ctx, RPT_ERR_ARG, layer + ": the weight is " + std::to_string(d.weight[k]) + ", not in (0, 1]");
+        if (rpt_glare_taps(d.sigma[k], taps[k], &radius[k]) != RPT_OK)
+            return fail(ctx, RPT_ERR_ARG, layer + ": sigma is " + std::to_string(d.sigma[k]) + ", not in [0.5, 32/3]");
+        weight[1 + k] = (unsigned int)std::floor(d.weight[k] * 65536.0 + 0.5);
+        core -= (long long)weight[1 + k];
+    }
+    if (core < 0) return fail(ctx, RPT_ERR_ARG, "rpt_set_glare: the weights sum to more than 1 (the core would keep " + std::to_string(core) + " / 65536)");
+    weight[0] = (unsigned int)core;
+    ctx->glare_layers = d.layers;
+    std::memcpy(ctx->glare_weight, weight, sizeof weight);
+    std::memcpy(ctx->glare_radius, radius, sizeof radius);
+    std::memset(ctx->glare_taps, 0, sizeof ctx->glare_taps);
+    for (int k = 0; k < d.layers; k++)
+        for (int j = 0; j <= radius[k]; j++) ctx->glare_taps[k][j] = taps[k][RPT_GLARE_RADIUS_MAX + j];
+    return RPT_OK;
+}
 
 // The particle pass.  The set goes to the device once, here (set_records)
 int rpt_set_particles(rpt_ctx *ctx, const rpt_particle *particles_or_null, int count) {

@@ -704,6 +704,22 @@ class Renderer:
         """(splat, resolve) device milliseconds of the last pass, which must have been timed (set_ballistics_measurement)."""
         return self._last_ms("rpt_last_ballistics_ms")
 
+    # -- glare for the point-source passes (include/rpt.h, rpt_set_glare; not in the reference) ------
+    def set_glare(self, layers=None):
+        """A point-spread function for the stars, the particles, the segments, the ballistic records and the rockets:
+        a list of up to three (weight, sigma) layers, e.g. glare.preset("soft"); sigma in pixels, in [0.5, 32/3], every weight > 0 and
+        their sum <= 1 (the rest stays in the source's own pixel).  From the next pass on, each of those passes spreads what it has
+        summed before it tonemaps, so a brighter source looks bigger.  None or [] switches glare off, which is the default: the passes
+        then launch the kernels they always did.  glare.apply is the same arithmetic on the host."""
+        layers = [] if layers is None else [(float(w), float(s)) for w, s in layers]
+        if len(layers) > 3:
+            raise ValueError(f"glare has at most 3 layers, {len(layers)} were given")
+        desc = _ffi.Glare()
+        desc.layers = len(layers)
+        for k, (w, s) in enumerate(layers):
+            desc.weight[k], desc.sigma[k] = w, s
+        self._check(self._lib.rpt_set_glare(self._h, C.byref(desc) if layers else None), "rpt_set_glare")
+
     # -- the rocket pass (include/rpt.h, rpt_set_rockets; not in the reference) ----------------------
     def set_rockets(self, rockets, temperatures=None):
         """Point sources under constant proper acceleration: an array of rockets.ROCKET_DTYPE records (or anything of n x 64 bytes in
@@ -884,7 +900,7 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
                  particle_options: Optional[Mapping] = None, star_temperatures=None, particle_temperatures=None,
                  segments=None, segment_options: Optional[Mapping] = None, particle_lighting: Optional[Mapping] = None,
                  ballistics=None, ballistic_options: Optional[Mapping] = None, ballistic_temperatures=None,
-                 rockets=None, rocket_options: Optional[Mapping] = None, rocket_temperatures=None):
+                 rockets=None, rocket_options: Optional[Mapping] = None, rocket_temperatures=None, glare=None):
     """Convenience: upload, render one frame, read back. Returns (pixels, rgb-or-None), and with events=True (pixels, rgb-or-None,
     records): the (H, W) event records of the same view (Renderer.render_events).  projection: None (the pinhole), a mode name
     for Renderer.set_projection, or a mapping of its keyword arguments, e.g. {"mode": "equirect", "yaw": 1.0}; or a ray-map camera:
@@ -910,9 +926,11 @@ def render_scene(scene: Scene, width: int, height: int, device: int = 0, debug_r
     keywords of Renderer.set_ballistic_options, ballistic_temperatures kelvin per record; it implies events=True as the particles do,
     and the pass runs right behind the segments.  rockets: a set for Renderer.set_rockets (rockets.launch, rockets.fleet, rockets.trip,
     ...), rocket_options the keywords of Renderer.set_rocket_options, rocket_temperatures kelvin per record; it implies events=True too,
-    and the pass runs right behind the ballistic one."""
+    and the pass runs right behind the ballistic one.  glare: the layers of Renderer.set_glare, e.g. glare.preset("soft"): every
+    point-source pass asked for spreads its sources by that point-spread function."""
     r = Renderer(device)
     try:
+        r.set_glare(glare)
         if adaptive_aa is not None:
             r.set_adaptive_aa(*adaptive_aa)
         if orientation is not None:
